@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X feature frontend.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the fused hot path (STFT -> magnitude -> mel -> per-sample
 min-max -> log, data resident in HBM) over BASELINE.json configs[1]: a batch of
@@ -9,10 +9,18 @@ min-max -> log, data resident in HBM) over BASELINE.json configs[1]: a batch of
 rotate through ROTATE distinct batches (inputs AND outputs, > 256 MiB touched per cycle),
 so that every step's waveform comes from HBM and not from the 256 MiB Infinity Cache.
 
-Order of a run: an untimed pre-conditioning burst (clock / cache state of a busy GPU), the W
-warm-up steps, the K timed steps (no event pairs, nothing but the steps on the stream), then -
-untimed and separate - the kernel-timing pass: KERNEL_PASS more rotating steps with a HIP
-event pair around each kernel on the launch stream, from which `roofline` is computed.
+Order of a plain run: an untimed pre-conditioning burst (clock / cache state of a busy GPU), the W
+warm-up steps, the K timed steps (no event pairs, nothing but the steps on the stream), then the
+JSON line.  --dump-outputs DIR writes what the last timed step computed (rank 0's log-mel batch) to
+DIR/logmel.npy; the inputs are seeded, so two builds run with the same arguments can be compared
+output for output.
+
+--full adds, untimed and after the K steps, everything beside the headline: the kernel-timing pass
+(KERNEL_PASS more rotating steps with a HIP event pair around each kernel on the launch stream, from
+which `roofline.achieved` is computed) and the two-kernel form, the CPU baseline and the parity leg
+against the oracle, and the side measurements (c3 / c4, batch sweep, per-config rooflines, c5,
+stream pipeline, graph replay, cache-resident replay).  --no-kernel-events, --no-cpu-baseline,
+--no-extras and --only-sweep select among these.
 
 With N > 1 there is one process per GPU: launched by the driver through
 torch.distributed.run, or - when WORLD_SIZE is unset - by this script itself, which starts
@@ -683,22 +691,36 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the kernel-timing pass, the CPU baseline + parity leg and the side "
+                         "measurements (off: the run times the headline steps and prints the line, nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's log-mel batch, float32) to DIR/logmel.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity leg")
     ap.add_argument("--no-kernel-events", action="store_true",
-                    help="skip the kernel-timing pass (roofline.achieved = null)")
+                    help="with --full: skip the kernel-timing pass (roofline.achieved = null)")
     ap.add_argument("--no-precondition", action="store_true", help="skip the untimed pre-conditioning burst")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the side measurements (batch sweep, cache-resident replay, c3 forward, c4 training step)")
+                    help="with --full: skip the side measurements (batch sweep, cache-resident replay, c3 forward, c4 training step)")
     ap.add_argument("--extra-steps", type=int, default=20)
     ap.add_argument("--extras-limit", type=float, default=300.0,
                     help="seconds the side measurements may take before the line is printed without them")
-    ap.add_argument("--only-sweep", action="store_true", help="of the side measurements, run only the K1 batch sweep (A/B runs)")
+    ap.add_argument("--only-sweep", action="store_true",
+                    help="with --full: of the side measurements, run only the K1 batch sweep (A/B runs)")
     ap.add_argument("--resident", action="store_true",
                     help="replay ONE batch every step (Infinity-Cache resident, as round 1 measured) instead of rotating")
     ap.add_argument("--strong", action="store_true",
                     help=f"strong scaling: a fixed global batch ({STRONG_GLOBAL_BATCH} c2 clips; {STRONG_GLOBAL_TRAIN_BATCH} for "
                          "the c4 training step) split over the ranks instead of a fixed batch per GPU")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.only_sweep and not args.full:
+        ap.error("--only-sweep is a side measurement: it needs --full")
+    # what runs beside the headline: nothing, unless --full
+    kernel_events = args.full and not args.no_kernel_events
+    cpu_leg = args.full and not args.no_cpu_baseline
+    extras_on = args.full and not args.no_extras
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -797,9 +819,15 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    # what the last timed step wrote, before anything else launches again (rank 0: one caller's batch)
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        last = outs[(cursor[0] - 1) % n_rot].cpu().numpy()
+        np.save(os.path.join(args.dump_outputs, "logmel.npy"), last.astype(np.float32, copy=False))
+
     # kernel-timing pass: separate from the timed region, independent of --steps
     k1 = k2 = np.zeros(0, np.float32)
-    if not args.no_kernel_events:
+    if kernel_events:
         plan.timing_enable(1)  # every call; the library never samples the first 4 calls after enabling
         for _ in range(KERNEL_PASS + 4):
             step()
@@ -810,7 +838,7 @@ def main():
     # the same step in its two-kernel form (round-2 structure: fused kernel without the epilogue + min-max / log kernel),
     # event-timed the same way: like-for-like continuity of the per-kernel figures
     two = None
-    if not args.no_kernel_events and rank == 0:
+    if kernel_events and rank == 0:
         plan2 = FrontendPlan(N_FFT, HOP, N_MEL, SR, 1, batch, length, dev)
         plan2.set_epilogue("two_kernels")
         plan2.timing_enable(1)
@@ -871,7 +899,7 @@ def main():
     done_lock, done = threading.Lock(), []
     # what the final line needs from the device is fetched now: finish() may run while the GPU is stuck
     kernel_name = plan.fused_kernel_name()
-    cpu_input = wavs[0].cpu().numpy() if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None
+    cpu_input = wavs[0].cpu().numpy() if (rank == 0 and world == 1 and cpu_leg) else None
     gpu_logmel = gpu_mel = None
     if cpu_input is not None:  # parity leg: batch 0 as the timed kernel wrote it + its mel magnitudes (one extra launch)
         gpu_logmel = outs[0].cpu().numpy()
@@ -957,12 +985,12 @@ def main():
         os._exit(0 if all(parity_ok) else 3)
     timer = threading.Timer(args.extras_limit, abandon)
     timer.daemon = True
-    if not args.no_extras:
+    if extras_on:
         timer.start()
     extras = None
     if args.only_sweep and world == 1:
         extras = {"k1_batch_sweep": batch_sweep(dev, fence, max(args.extra_steps, 20))}
-    elif not args.no_extras:
+    elif extras_on:
         try:
             extras = side_measurements(dev, rank, world, args.extra_steps, fence, args.strong)
         except Exception as exc:  # the side measurements must never take the headline line down (all ranks raise alike)

@@ -4,7 +4,7 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof
 rm -rf $OUT; mkdir -p $OUT
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o bench -- python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline > $OUT/bench_stdout.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o bench -- python3 bench.py --full --steps 200 --warmup 20 --no-cpu-baseline > $OUT/bench_stdout.log 2>&1
 tail -2 $OUT/bench_stdout.log
 find $OUT -name "*.csv" | head
 for f in $(find $OUT -name "*kernel_stats.csv"); do cat $f; done

@@ -8,7 +8,7 @@ IRIS_LIB=$L/libiris_frontend_c20.so timeout -k 10 600 python3 -m pytest tests/te
 for i in 1 2 3; do
   for n in prod b16 c20 d16; do
     LIB=$L/libiris_frontend_$n.so; [ "$n" = prod ] && LIB=$L/libiris_frontend.so
-    IRIS_LIB=$LIB timeout -k 10 300 python3 bench.py --steps 300 --warmup 30 --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "
+    IRIS_LIB=$LIB timeout -k 10 300 python3 bench.py --full --steps 300 --warmup 30 --no-cpu-baseline --no-extras 2>/dev/null | python3 -c "
 import sys,json
 r=json.loads(sys.stdin.readline()); ro=r['roofline']; print('$n', ro['kernel'], 'k1_us', round(1e3*ro['kernel_ms'],2), 'median', round(1e3*ro['kernel_ms_median'],2), 'k2_us', round(1e3*(ro['second_kernel_ms'] or 0),2), 'step_us', round(1e3*r['ms_per_step'],2))"
   done
@@ -16,7 +16,7 @@ done
 # large batch: the frame loop dominates (B = 512)
 for n in prod b16 c20 d16; do
   LIB=$L/libiris_frontend_$n.so; [ "$n" = prod ] && LIB=$L/libiris_frontend.so
-  IRIS_LIB=$LIB timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --only-sweep --no-cpu-baseline --no-kernel-events 2>/dev/null | python3 -c "
+  IRIS_LIB=$LIB timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --only-sweep --no-cpu-baseline --no-kernel-events 2>/dev/null | python3 -c "
 import sys,json
 r=json.loads(sys.stdin.readline()); print('$n', ' | '.join(f\"B {x['batch']}: k1 {x['k1_us']} step {x['step_us']}\" for x in r['extra']['k1_batch_sweep']))"
 done

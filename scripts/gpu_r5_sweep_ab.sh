@@ -6,7 +6,7 @@ mkdir -p $OUT
 for rep in 1 2; do
 for mode in default 1 2; do
   if [ $mode = default ]; then unset IRIS_EPILOGUE; else export IRIS_EPILOGUE=$mode; fi
-  timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --only-sweep --no-cpu-baseline --no-kernel-events > $OUT/sweep_${mode}_$rep.json 2> $OUT/sweep_${mode}_$rep.err || { echo "sweep $mode failed"; tail -3 $OUT/sweep_${mode}_$rep.err; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --only-sweep --no-cpu-baseline --no-kernel-events > $OUT/sweep_${mode}_$rep.json 2> $OUT/sweep_${mode}_$rep.err || { echo "sweep $mode failed"; tail -3 $OUT/sweep_${mode}_$rep.err; exit 1; }
   python3 - <<PY
 import json
 d = json.load(open('$OUT/sweep_${mode}_$rep.json'))

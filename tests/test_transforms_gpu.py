@@ -1619,7 +1619,7 @@ def test_bench_self_launch_two_ranks(dev):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["IRIS_BENCH_SHARE_GPU"] = "1"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-                        "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True, env=env, timeout=600)
+                        "--full", "--no-cpu-baseline", "--no-extras"], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
     res = json.loads(line)
@@ -1646,7 +1646,7 @@ def test_bench_two_ranks_lift_the_training_step_to_the_top_level(dev):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["IRIS_BENCH_SHARE_GPU"] = "1"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-                        "--no-cpu-baseline", "--no-kernel-events", "--extra-steps", "3"], capture_output=True, text=True, env=env,
+                        "--full", "--no-cpu-baseline", "--no-kernel-events", "--extra-steps", "3"], capture_output=True, text=True, env=env,
                        timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -1671,7 +1671,7 @@ def test_bench_line_survives_stuck_side_measurements(dev):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["IRIS_BENCH_SHARE_GPU"] = "1"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-                        "--no-cpu-baseline", "--extras-limit", "0.2"], capture_output=True, text=True, env=env, timeout=600)
+                        "--full", "--no-cpu-baseline", "--extras-limit", "0.2"], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -1693,6 +1693,36 @@ def test_bench_strong_scaling_two_ranks(dev):
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert res["scaling"] == "strong" and res["n_gpus"] == 2 and res["config"]["global_batch"] == 256
     assert "batch 128" in res["config"]["workload"] and res["value"] > 0 and res["rccl_world"] == 2
+
+
+def test_bench_plain_run_dumps_what_the_last_timed_step_computed(dev, tmp_path):
+    """A plain `bench.py` run (no --full) times --steps steps and prints the line without anything beside the headline;
+    --dump-outputs writes the log-mel batch of the last timed step: the same from run to run (seeded inputs), and another
+    batch of the rotation when --steps moves the last step."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "IRIS_BENCH_SHARE_GPU")}
+    dumps = []
+    for i, steps in enumerate((7, 7, 8)):
+        out = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "2",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, env=env, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        res = json.loads(lines[0])
+        assert res["steps"] == steps and res["warmup"] == 2 and res["unit"] == "audio-s/s" and res["higher_is_better"] is True
+        assert res["dtype"] == "f32" and res["ms_per_step"] > 0
+        assert abs(res["value"] - 32 * 10 * 1e3 / res["ms_per_step"]) <= 1e-3 * res["value"]   # one batch of 32 x 10 s per step
+        assert not ({"extra", "cpu_baseline", "parity"} & set(res)) and res["roofline"]["achieved"] is None
+        assert res["roofline"]["two_kernel_form"] is None and "launches_timed" not in res["roofline"]
+        assert sorted(os.listdir(out)) == ["logmel.npy"]
+        a = np.load(out / "logmel.npy")
+        assert a.dtype == np.float32 and a.shape == (32, 64, 626, 1) and np.isfinite(a).all()
+        dumps.append(a)
+    assert np.array_equal(dumps[0], dumps[1])
+    assert not np.array_equal(dumps[0], dumps[2])
 
 
 @pytest.mark.parametrize("orig,new,chan,length", [(44100, 16000, 2, 441000), (48000, 16000, 1, 48001), (8000, 16000, 2, 12345),
