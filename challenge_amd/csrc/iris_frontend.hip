@@ -22,6 +22,7 @@
 //                    step's forward and backward-data passes)
 //   k_conv_wino_b3.h   the same convolution on the BF16 matrix cores at fp32 accuracy: three-term split of both operands (opt-in)
 //   k_conv_wino_wrw.h  the same layers' weight gradient as Winograd F(2x2, 3x3) on the fp32 matrix cores (training)
+//   k_metrics.h      the training metrics er_score / cos_sim / F1 counts of a batch in one launch
 //   host_plan.h      mel matrix, constant tables, plan create / destroy
 //   host_ops.h       the operators' C-ABI entry points
 #include "common.h"
@@ -44,3 +45,4 @@
 #include "k_conv_wino_wrw.h"
 #include "k_resample.h"
 #include "k_agc_adam.h"
+#include "k_metrics.h"

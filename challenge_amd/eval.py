@@ -1,0 +1,81 @@
+"""Drop-in counterpart of the reference's eval.py: score a trained model against sample_answer.json.
+
+    python -m challenge_amd.eval --name <run name> [--p] [--path DIR] [--verbose True]
+
+loads <path>/<name>.pt (this package's checkpoint) - or, for a model trained with the reference, its Keras weights as
+<path>/<name>.npz (scripts/dump_keras_weights.py) - and runs metrics.evaluate on the *.wav files of the working directory.
+`--p` parses model / v / n_mels / n_chan / n_frame out of the run name as eval.py:51-62 does."""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+import torch
+
+from .data_utils import minmax_log_on_mel  # noqa: F401  (eval.py:13-27: the same batch-wise min-max + log)
+from .metrics import Challenge_Metric, evaluate, get_er, output_to_metric  # noqa: F401
+
+
+def second2frame(seconds: list, frame_num, resolution):
+    """eval.py:30-38: [[class, start s, end s], ...] -> frame labels [frame_num, 3] (overlaps add up)."""
+    frames = np.zeros([frame_num, 3], dtype=np.float32)
+    for second in seconds:
+        class_num = second[0]
+        start = int(np.round(second[1] * resolution))
+        end = int(np.round(second[2] * resolution))
+        frames[start:end, class_num] += 1
+    return torch.from_numpy(frames)
+
+
+def parse_name(config):
+    """eval.py:51-62: the run name's fields -> model_type / model / v / n_mels / n_chan / n_frame."""
+    parsed = config.name.split('_')
+    if parsed[0][0] not in ('B', 'v'):
+        parsed = parsed[1:]
+    if parsed[0] == 'vad':
+        config.model_type = 'vad'
+        config.model = 1
+    else:
+        config.model = int(parsed[0][-1])
+    config.v = int(parsed[1][-1])
+    config.n_mels = int(parsed[6][3:])
+    config.n_chan = int(parsed[7][-1])
+    config.n_frame = int(parsed[9].split('framelen')[-1])
+    return config
+
+
+def load_model(config, path: str = '', device=None):
+    from .model import get_model, load_keras_weights
+    if device is None:
+        device = torch.device('cuda', 0) if torch.cuda.is_available() else torch.device('cpu')
+    model = get_model(config).to(device)
+    if device.type == 'cuda':
+        model = model.to(memory_format=torch.channels_last)
+    base = os.path.join(path, config.name)
+    if base.endswith('.h5'):
+        base = base[:-3]
+    if os.path.exists(base + '.pt'):
+        model.load_state_dict(torch.load(base + '.pt', map_location=device))
+    elif os.path.exists(base + '.npz'):
+        load_keras_weights(model, base + '.npz')
+    else:
+        raise FileNotFoundError(f"neither {base}.pt nor {base}.npz")
+    model.eval()
+    return model
+
+
+def main(argv=None):
+    from .sj_train import ARGS
+    config = ARGS()
+    config.args.add_argument('--verbose', help='verbose', type=bool, default=True)
+    config.args.add_argument('--p', help='parsing name', action='store_true')
+    config.args.add_argument('--path', type=str, default='')
+    config = config.get(argv)
+    if config.p:
+        parse_name(config)
+    model = load_model(config, config.path)
+    return evaluate(config, model, verbose=config.verbose)
+
+
+if __name__ == "__main__":
+    main()

@@ -177,11 +177,14 @@ class GraphedTrainStep:
         self.model, self.x, self.y = model, x.clone(), y.clone()
         dev = x.device
         saved = None
+        self.metrics = model._metrics   # compiled metrics: one captured iris_event_metrics launch per replay
+        self.metric_out, self.y_pred = {}, None
         if preserve_state:
             tensors = list(model.parameters()) + list(model.buffers())
             saved = ([t.detach().clone() for t in tensors], tensors,
                      {id(p): {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in opt.state.get(p, {}).items()}
-                      for g in opt.param_groups for p in g['params']})
+                      for g in opt.param_groups for p in g['params']},
+                     {id(t): t.clone() for t in (self.metrics.state_tensors() if self.metrics is not None else [])})
 
         def restore():
             opt.zero_grad(set_to_none=True)
@@ -196,6 +199,9 @@ class GraphedTrainStep:
                         for k, v in now.items():
                             if torch.is_tensor(v):   # moments and the step count: back to their old values, or to a fresh 0
                                 v.copy_(before[k]) if k in before else v.zero_()
+                if self.metrics is not None:   # F1 counts and epoch accumulators: the warm-up steps counted nothing
+                    for t in self.metrics.state_tensors():
+                        t.copy_(saved[3][id(t)]) if id(t) in saved[3] else t.zero_()
             model.bump_generation()
             torch.cuda.synchronize(dev)
 
@@ -312,6 +318,9 @@ class GraphedTrainStep:
             else:   # the plain module on the aliases: DDP's reducer stays out of the capture
                 out = torch.func.functional_call(model, aliases, (self.x,))
             loss = model.loss_fn(self.y, out)
+            if self.metrics is not None:   # (before backward: from the same predictions the loss used, into preallocated outputs)
+                self.y_pred = out.detach()
+                self.metric_out = self.metrics(self.y, self.y_pred, 'train')
             loss.backward()
         finally:
             _IN_STEP[0] = was_in_step
@@ -345,6 +354,8 @@ class GraphedTrainStep:
         if self._pool_marks:
             _ZERO_POOL.mark_dirty(self._pool_marks)   # the replay has written into the zero pool behind its back
         self.model.bump_generation()  # a replay moves parameters and BatchNorm statistics behind ATen's back
+        if self.metric_out:
+            return {'loss': self.loss, **self.metric_out}
         return {'loss': self.loss}
 
     def set_lr(self, value: float) -> None:
@@ -364,15 +375,31 @@ def graph_step_possible(model: "CustomModel") -> bool:
 
 def fit(model: CustomModel, train_set, epochs, steps_per_epoch, validation_data=None, validation_steps=16,
         scheduler=None, csv_path=None, checkpoint_path=None, patience=None, rank=0, world=1, verbose=True,
-        swa=None, graph: Optional[bool] = None):
+        swa=None, graph: Optional[bool] = None, checkpoint_monitor: Optional[str] = None, callbacks=()):
     """Minimal Keras-fit equivalent for this path: per-epoch LR schedule, CSV log,
     best-val-loss checkpoint, early stopping, TerminateOnNaN (sj_train.py:489-519).
+    Compiled metrics (`model.compile(metrics=...)`) are accumulated on the device and read once per epoch: rows gain their names
+    and 'val_' twins, Keras' means (per-clip metrics weighted by clips, f1_score by batches).  `checkpoint_monitor` (e.g.
+    'val_er', mode min as Keras' 'auto' for these names): the checkpoint follows that row entry while early stopping keeps
+    val_loss / loss; None: one monitor for both, as before.  `callbacks`: further objects with on_epoch_end(epoch, model),
+    called after the checkpoint is written (metrics.eval_callback).
     `graph` (default: on, IRIS_GRAPH_STEP=0 switches it off): run the training step as ONE replayed hipGraph (GraphedTrainStep) - a
     capturable optimiser (make_optimizer(..., capturable=True)), batches of one shape, under DDP the RCCL backend; a batch of
     another shape (a ragged last one) takes the eager step.  The step then costs what its kernels cost (10 ms per batch of 64)
     however slow the host is at launching ~260 kernels.  A capture that fails is reported ONCE (warnings.warn, every rank) and
     the run goes on eagerly - on every rank alike, from the state the model had before the attempt."""
     best, bad, history = math.inf, 0, []
+    best_ckpt = math.inf
+    ms = model._metrics
+
+    def metric_sums(phase, dev):
+        """The phase's metric accumulator (sums and counts), all-reduced over the ranks - every rank logs and decides alike.
+        Still on the device: the caller reads it together with the loss, in one transfer."""
+        acc = ms.accum(dev, phase)
+        if coll:
+            acc = acc.clone()
+            torch.distributed.all_reduce(acc)
+        return acc
     coll = collectives_on(world)  # world > 1, or a forced process group at world 1 (IRIS_FORCE_PG=1)
     it = iter(train_set)
     graph = SW.GRAPH_STEP if graph is None else bool(graph)
@@ -405,6 +432,8 @@ def fit(model: CustomModel, train_set, epochs, steps_per_epoch, validation_data=
                 else:
                     g['lr'] = lr
         t0, losses = time.time(), []
+        if ms is not None:
+            ms.reset()   # (a device fill, outside any graph)
         for _ in range(steps_per_epoch):
             losses.append(one_step(next(it))['loss'].clone() if graph else one_step(next(it))['loss'])
         loss = torch.stack(losses).mean()
@@ -418,17 +447,27 @@ def fit(model: CustomModel, train_set, epochs, steps_per_epoch, validation_data=
                 _fe.check_plans(loss.device)
             except _fe.N.EpilogueTimeout as exc:
                 plan_failure = exc
+        host = None   # with compiled metrics: [loss, (failed ranks,) 5 metric sums] read in ONE transfer
         if coll:
             pack = torch.stack([loss, loss.new_tensor(1.0 if plan_failure is not None else 0.0)])
             torch.distributed.all_reduce(pack)  # two scalars per epoch
-            loss, failed_ranks = pack[0] / world, int(round(float(pack[1])))
+            if ms is None:
+                loss, failed_ranks = pack[0] / world, int(round(float(pack[1])))
+            else:
+                loss = pack[0] / world
+                host = torch.cat([torch.stack([loss, pack[1]]).double(), metric_sums('train', loss.device)]).tolist()
+                failed_ranks = int(round(host.pop(1)))
             if failed_ranks and plan_failure is None:
                 plan_failure = _fe.N.EpilogueTimeout(f"{failed_ranks} other rank(s) of this job reported a failed fused min-max / "
                                                      "log epilogue (NaN features); stopping with them")
         if plan_failure is not None:
             raise plan_failure
-        row = {'epoch': epoch, 'loss': float(loss), 'lr': float(model.optimizer.param_groups[0]['lr']),
+        if ms is not None and host is None:
+            host = torch.cat([loss.double().view(1), metric_sums('train', loss.device)]).tolist()
+        row = {'epoch': epoch, 'loss': float(loss) if host is None else host[0], 'lr': float(model.optimizer.param_groups[0]['lr']),
                'time': time.time() - t0}
+        if ms is not None:
+            row.update(ms.epoch_values(host[1:]))
         if coll:
             average_bn_statistics(model, world)
         if not math.isfinite(row['loss']):
@@ -441,7 +480,12 @@ def fit(model: CustomModel, train_set, epochs, steps_per_epoch, validation_data=
             if coll:  # every rank validates its own shard: the monitored value is the mean over ranks
                 torch.distributed.all_reduce(vl)
                 vl = vl / world
-            row['val_loss'] = float(vl)
+            if ms is None:
+                row['val_loss'] = float(vl)
+            else:
+                host = torch.cat([vl.double().view(1), metric_sums('val', vl.device)]).tolist()
+                row['val_loss'] = host[0]
+                row.update(ms.epoch_values(host[1:], 'val_'))
         history.append(row)
         if swa is not None:
             swa.on_epoch_end(epoch, model)
@@ -453,6 +497,12 @@ def fit(model: CustomModel, train_set, epochs, steps_per_epoch, validation_data=
             best, bad = monitor, 0
         else:
             bad += 1
+        save = improved
+        if checkpoint_monitor is not None:   # Keras ModelCheckpoint(save_best_only=True): strictly better, mode min
+            cm = row.get(checkpoint_monitor)
+            save = cm is not None and cm < best_ckpt
+            if save:
+                best_ckpt = cm
         if rank == 0:
             if verbose:
                 print(row)
@@ -463,8 +513,10 @@ def fit(model: CustomModel, train_set, epochs, steps_per_epoch, validation_data=
                     if new:
                         w.writeheader()
                     w.writerow(row)
-            if improved and checkpoint_path:
+            if save and checkpoint_path:
                 torch.save(model.state_dict(), checkpoint_path)
+        for cb in callbacks:
+            cb.on_epoch_end(epoch, model)
         stop = patience is not None and not improved and bad >= patience  # Keras EarlyStopping: wait >= patience, tested on a non-improving epoch
         if coll:  # belt and braces: one int per epoch, rank 0's decision wins
             flag = torch.tensor([1 if stop else 0], dtype=torch.int32, device=loss.device)

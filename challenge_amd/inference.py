@@ -1,7 +1,7 @@
 """Sliding-window inference chain of the reference's `metrics.evaluate` (metrics.py:40-81)
 up to the thresholded frame predictions -- the one place where the reference runs
-STFT -> mel -> forward in a single call.  Scoring (event extraction, error rate) stays in
-the reference's untouched metrics.py.
+STFT -> mel -> forward in a single call.  Scoring (event extraction, error rate) is
+challenge_amd.metrics (`evaluate`, `get_er`, ...), which calls `predict_frames`.
 
     wav -> load_wav (normalize + STFT, HIP) -> channel transform -> stft_filter(16)
         -> |.| -> mel -> minmax (per mel row: the tensor is unbatched here) -> log  (HIP)

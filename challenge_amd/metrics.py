@@ -1,0 +1,430 @@
+"""Drop-in counterpart of the reference's metrics.py: the training metrics `er_score`, `f1_score`, `cos_sim`
+(metrics.py:217-299), the scoring helpers `Challenge_Metric`, `extract_middle`, `output_to_metric`, `get_er` (:95-214) and
+`evaluate` / `eval_callback` (:14-87).
+
+On GPU tensors the training metrics are ONE HIP launch (iris_event_metrics, challenge_amd/csrc/k_metrics.h): no host sync,
+capturable into the training step's hipGraph.  On CPU tensors they take a vectorised torch path with the same arithmetic
+(`er` bitwise equal).  `MetricSet` serves a compiled metric list with one launch per batch and keeps the epoch accumulators
+`fit` reads once per epoch.
+
+Reference semantics kept on purpose:
+  * er_score(smoothing=True) pools the predictions with AveragePooling1D(31, padding='same') - stride 31, Keras' default -
+    and compares the pooled run middles, as indices, with full-rate label frames.
+  * f1_score() wraps ONE stateful F1Score: its counts are never reset, so the value logged per batch is the F1 of everything
+    counted since the callable was made, training and validation batches alike; Keras then averages those values over the
+    epoch's batches.
+The scoring helpers run on the host, once per file."""
+from __future__ import annotations
+
+import json
+import os
+from glob import glob
+from typing import Dict, List, Optional
+
+import numpy as np
+import torch
+
+from . import _native as N
+from .trainer import cos_sim  # noqa: F401  (metrics.py:277-288; the CPU path of the `cos_sim` metric)
+
+SMOOTHING_POOL = int(0.5 * 16000) // 256   # metrics.py:222: 31 frames
+
+
+def _first(x):
+    return x[0] if isinstance(x, tuple) else x
+
+
+def _pool_same_strided(y: torch.Tensor, k: int) -> torch.Tensor:
+    """Keras AveragePooling1D(k, padding='same') (stride = k) on [B, T, K]: ceil(T / k) windows, the padding split floor /
+    ceil before / after, each window the mean of its in-range frames summed in frame order (as the kernel sums)."""
+    b, t, c = y.shape
+    n = -(-t // k)
+    pad0 = (n * k - t) // 2
+    yp = y.new_zeros(b, n * k, c)
+    yp[:, pad0:pad0 + t] = y
+    yr = yp.view(b, n, k, c)
+    acc = torch.zeros_like(yr[:, :, 0])
+    for j in range(k):   # sequential fp32 sum (the zero padding adds exactly nothing)
+        acc = acc + yr[:, :, j]
+    lo = (torch.arange(n) * k - pad0).clamp(min=0)
+    hi = (torch.arange(n) * k - pad0 + k).clamp(max=t)
+    return acc / (hi - lo).to(y.dtype)[None, :, None]
+
+
+def _runs(x: torch.Tensor):
+    """x bool [B, K, T] -> (starts, ends) as index rows (b, k, t) in (clip, class, time) order."""
+    xi = x.to(torch.int8)
+    prev = torch.nn.functional.pad(xi, (1, 0))[..., :-1]
+    nxt = torch.nn.functional.pad(xi, (0, 1))[..., 1:]
+    return (x & (prev == 0)).nonzero(), (x & (nxt == 0)).nonzero()
+
+
+def er_host(y_true: torch.Tensor, y_pred: torch.Tensor, threshold: float = 0.5, pool: int = 0) -> torch.Tensor:
+    """The reference's er_score on CPU tensors [B, T, K] / [B, T', K] -> [B] fp32 (see k_metrics.h for the restatement)."""
+    y_true = y_true.to(torch.float32)
+    y_pred = y_pred.to(torch.float32)
+    if pool > 1:
+        y_pred = _pool_same_strided(y_pred, pool)
+    thr = torch.tensor(threshold, dtype=torch.float32)
+    yt = (y_true >= thr).transpose(1, 2)
+    yp = (y_pred >= thr).transpose(1, 2)
+    b, k, t = yt.shape
+    ts, te = _runs(yt)
+    ps, pe = _runs(yp)
+    mid = (ps[:, 2] + pe[:, 2]) // 2
+    keep = mid < t
+    hit = torch.zeros(b, k, t, dtype=torch.int32)
+    hit[ps[keep, 0], ps[keep, 1], mid[keep]] = 1
+    cum = torch.nn.functional.pad(hit.cumsum(-1), (1, 0))   # cum[..., i] = middles in [0, i)
+    correct = (cum[ts[:, 0], ts[:, 1], te[:, 2] + 1] - cum[ts[:, 0], ts[:, 1], ts[:, 2]]) > 0
+    n_true = torch.bincount(ts[:, 0], minlength=b).to(torch.float32)
+    n_pred = torch.bincount(ps[:, 0], minlength=b).to(torch.float32)
+    n_corr = torch.bincount(ts[:, 0], weights=correct.to(torch.float64), minlength=b).to(torch.float32)
+    return (n_true + n_pred - 2 * n_corr) / torch.clamp(n_true, min=1)
+
+
+def f1_counts_host(y_true: torch.Tensor, y_pred: torch.Tensor, threshold: float = 0.5) -> torch.Tensor:
+    p = (y_pred > threshold).to(torch.float64)
+    y = y_true.to(torch.float64)
+    return torch.stack([(p * y).sum(), (p * (1 - y)).sum(), ((1 - p) * y).sum()])
+
+
+def f1_from_counts(c: torch.Tensor) -> torch.Tensor:
+    """Micro F1 of fp64 (tp, fp, fn) with div-no-nan precision / recall (tfa FBetaScore.result, beta 1) -> fp32 scalar."""
+    tp, fp, fn = c[0], c[1], c[2]
+    zero = torch.zeros((), dtype=torch.float64, device=c.device)
+    prec = torch.where(tp + fp != 0, tp / torch.where(tp + fp != 0, tp + fp, 1.0), zero)
+    rec = torch.where(tp + fn != 0, tp / torch.where(tp + fn != 0, tp + fn, 1.0), zero)
+    ps = prec + rec
+    return (torch.where(ps != 0, prec * rec / torch.where(ps != 0, ps, 1.0), zero) * 2.0).to(torch.float32)
+
+
+class _Workspace:
+    """Slab + ticket of iris_event_metrics, one pair per (device, batch size); never freed while this object lives (a
+    captured graph holds the addresses).  Made by an eager call: a capture needs its warm-up call first (torch's recipe)."""
+
+    def __init__(self):
+        self._ws = {}
+
+    def get(self, device, batch):
+        key = (device, batch)
+        if key not in self._ws:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("event_metrics: the first call for a batch size must be eager (warm up before the capture)")
+            self._ws[key] = (torch.zeros(3 * batch, dtype=torch.float64, device=device),
+                             torch.zeros(1, dtype=torch.int32, device=device))
+        return self._ws[key]
+
+
+def event_metrics(y_true: torch.Tensor, y_pred: torch.Tensor, threshold: float = 0.5, pool: int = 0, want_cos: bool = False,
+                  f1_state: Optional[torch.Tensor] = None, f1_threshold: float = 0.5, accum: Optional[torch.Tensor] = None,
+                  workspace: Optional[_Workspace] = None) -> Dict[str, torch.Tensor]:
+    """One iris_event_metrics launch on the current stream: {'er': [B], 'cos_sim': [B] (want_cos), 'f1_score': [] (f1_state)}.
+    `f1_state` (fp64 [3], cumulative) and `accum` (fp64 [5]: sum er, sum cos, sum f1, clips, batches) are updated in place."""
+    if y_true.dim() != 3 or y_pred.dim() != 3 or y_true.shape[0] != y_pred.shape[0] or y_true.shape[2] != y_pred.shape[2]:
+        raise ValueError(f"event_metrics: y_true [B, T, K] and y_pred [B, T', K], got {tuple(y_true.shape)} / {tuple(y_pred.shape)}")
+    if not (y_true.is_cuda and y_pred.is_cuda):
+        raise ValueError("event_metrics: GPU tensors (the CPU path is er_host / f1_counts_host / cos_sim)")
+    dev = y_true.device
+    yt = y_true.detach().to(torch.float32).contiguous()
+    yp = y_pred.detach().to(torch.float32).contiguous()
+    b, t, k = yt.shape
+    er = torch.empty(b, dtype=torch.float32, device=dev)
+    cos = torch.empty(b, dtype=torch.float32, device=dev) if want_cos else None
+    f1 = torch.empty((), dtype=torch.float32, device=dev) if f1_state is not None else None
+    for name, s, n in (("f1_state", f1_state, 3), ("accum", accum, 5)):
+        if s is not None and (s.dtype != torch.float64 or s.device != dev or s.numel() != n or not s.is_contiguous()):
+            raise ValueError(f"event_metrics: {name} must be a contiguous fp64 [{n}] tensor on {dev}")
+    slab = ticket = None
+    if f1_state is not None or accum is not None:
+        slab, ticket = (workspace or _WS).get(dev, b)
+
+    def ptr(x):
+        return x.data_ptr() if x is not None else None
+    N.check(N.lib().iris_event_metrics(ptr(yt), ptr(yp), b, t, yp.shape[1], k, float(threshold), int(pool), float(f1_threshold),
+                                       ptr(er), ptr(cos), ptr(f1_state), ptr(f1), ptr(accum), ptr(slab), ptr(ticket),
+                                       torch.cuda.current_stream(dev).cuda_stream), "iris_event_metrics")
+    out = {'er': er}
+    if cos is not None:
+        out['cos_sim'] = cos
+    if f1 is not None:
+        out['f1_score'] = f1
+    return out
+
+
+_WS = _Workspace()
+
+
+class _ErScore:
+    def __init__(self, threshold=0.5, smoothing=True):
+        self.threshold, self.smoothing = float(threshold), bool(smoothing)
+        self.pool = SMOOTHING_POOL if smoothing else 0
+        self.__name__ = 'er'   # Keras logs the inner function's name (metrics.py:220)
+
+    def __call__(self, y_true, y_pred):
+        y_true, y_pred = _first(y_true), _first(y_pred)
+        if y_pred.is_cuda:
+            return event_metrics(y_true, y_pred, self.threshold, self.pool)['er']
+        return er_host(y_true, y_pred, self.threshold, self.pool)
+
+
+def er_score(threshold=0.5, smoothing=True):
+    """metrics.py:217-274: per-clip error rate [B] of the thresholded frame predictions."""
+    return _ErScore(threshold, smoothing)
+
+
+class _F1Score:
+    """tfa F1Score(num_classes=3, threshold=0.5, average='micro') behind a plain function (metrics.py:291-299): the counts
+    (fp64 tp, fp, fn) live as long as this object, one state per device."""
+
+    def __init__(self, threshold=0.5):
+        self.threshold = float(threshold)
+        self.states: Dict[torch.device, torch.Tensor] = {}
+        self.__name__ = 'f1_score'
+
+    def state(self, device) -> torch.Tensor:
+        device = torch.device(device)
+        if device not in self.states:
+            self.states[device] = torch.zeros(3, dtype=torch.float64, device=device)
+        return self.states[device]
+
+    def __call__(self, y_true, y_pred):
+        y_true, y_pred = _first(y_true), _first(y_pred)
+        st = self.state(y_pred.device)
+        if y_pred.is_cuda:
+            return event_metrics(y_true, y_pred, f1_state=st, f1_threshold=self.threshold)['f1_score']
+        st += f1_counts_host(y_true, y_pred, self.threshold)
+        return f1_from_counts(st)
+
+
+def f1_score():
+    return _F1Score(0.5)
+
+
+def _cos_sim_metric(y_true, y_pred):
+    """metrics.py:277-288 (== trainer.cos_sim); one launch on GPU tensors."""
+    y_true, y_pred = _first(y_true), _first(y_pred)
+    if y_pred.is_cuda:
+        return event_metrics(y_true, y_pred, want_cos=True)['cos_sim']
+    return cos_sim(y_true, y_pred)
+
+
+_cos_sim_metric.__name__ = 'cos_sim'
+
+
+def _is_cos(m):
+    return m is cos_sim or m is _cos_sim_metric
+
+
+def metric_name(m) -> str:
+    return 'cos_sim' if _is_cos(m) else getattr(m, '__name__', type(m).__name__)
+
+
+class MetricSet:
+    """A compiled metric list (`CustomModel.compile(metrics=...)`).  Any of er_score / f1_score / cos_sim are served by ONE
+    iris_event_metrics launch per batch on a GPU (at most one of each kind; other callables are called as they are).  Each call
+    adds to the epoch accumulator of its phase ('train' / 'val'): fp64 [5] = sum er, sum cos, sum f1, clips, batches - zeroed by
+    `reset`, read once per epoch by `fit` (Keras' means: per-clip metrics weighted by clips, the scalar F1 by batches)."""
+
+    def __init__(self, metrics):
+        self.metrics = list(metrics)
+        self.er = next((m for m in self.metrics if isinstance(m, _ErScore)), None)
+        self.f1 = next((m for m in self.metrics if isinstance(m, _F1Score)), None)
+        self.cos = any(_is_cos(m) for m in self.metrics)
+        fused = {id(self.er), id(self.f1)}
+        self.others = [m for m in self.metrics if id(m) not in fused and not _is_cos(m)]
+        self.names = [metric_name(m) for m in self.metrics]
+        dup = sorted({n for n in self.names if self.names.count(n) > 1})
+        if dup:   # (one result per name: a second er_score or f1_score would overwrite the first in the step's outputs)
+            raise ValueError(f"MetricSet: metric names must be unique, {dup} appear more than once")
+        self.accums: Dict[tuple, torch.Tensor] = {}
+        self.workspace = _Workspace()
+
+    def accum(self, device, phase: str) -> torch.Tensor:
+        key = (torch.device(device), phase)
+        if key not in self.accums:
+            self.accums[key] = torch.zeros(5, dtype=torch.float64, device=key[0])
+        return self.accums[key]
+
+    def state_tensors(self) -> List[torch.Tensor]:
+        """Everything a call advances (F1 counts, accumulators): GraphedTrainStep saves / restores them around its warm-up."""
+        return list(self.accums.values()) + (list(self.f1.states.values()) if self.f1 is not None else [])
+
+    def reset(self, phase: Optional[str] = None) -> None:
+        for (_, ph), a in self.accums.items():
+            if phase is None or ph == phase:
+                a.zero_()
+
+    @torch.no_grad()
+    def __call__(self, y_true, y_pred, phase: str = 'train') -> Dict[str, torch.Tensor]:
+        y_true, y_pred = _first(y_true), _first(y_pred).detach()
+        dev = y_pred.device
+        acc = self.accum(dev, phase)
+        fused = self.er is not None or self.f1 is not None or self.cos
+        res: Dict[str, torch.Tensor] = {}
+        if fused and y_pred.is_cuda:
+            er = self.er or _ErScore(0.5, False)
+            r = event_metrics(y_true, y_pred, er.threshold, er.pool, want_cos=self.cos,
+                              f1_state=self.f1.state(dev) if self.f1 is not None else None,
+                              f1_threshold=self.f1.threshold if self.f1 is not None else 0.5, accum=acc,
+                              workspace=self.workspace)
+            if self.er is not None:
+                res['er'] = r['er']
+            for key in ('cos_sim', 'f1_score'):
+                if key in r:
+                    res[key] = r[key]
+        elif fused:
+            er = cs = f1 = None
+            if self.er is not None:
+                er = res['er'] = self.er(y_true, y_pred)
+            if self.cos:
+                cs = res['cos_sim'] = cos_sim(y_true, y_pred)
+            if self.f1 is not None:
+                f1 = res['f1_score'] = self.f1(y_true, y_pred)
+            b = y_pred.shape[0]
+            acc += torch.stack([er.double().sum() if er is not None else acc.new_zeros(()),
+                                cs.double().sum() if cs is not None else acc.new_zeros(()),
+                                f1.double() if f1 is not None else acc.new_zeros(()),
+                                acc.new_tensor(float(b)), acc.new_tensor(1.0)])
+        for m in self.others:
+            res[metric_name(m)] = m(y_true, y_pred)
+        return {n: res[n] for n in self.names if n in res}
+
+    def epoch_values(self, sums: torch.Tensor, prefix: str = '') -> Dict[str, float]:
+        """Row entries from an accumulator's (possibly all-reduced) host values."""
+        s = [float(v) for v in sums]
+        out = {}
+        for n in self.names:
+            if n == 'er' and self.er is not None:
+                out[prefix + n] = s[0] / s[3] if s[3] else float('nan')
+            elif n == 'cos_sim' and self.cos:
+                out[prefix + n] = s[1] / s[3] if s[3] else float('nan')
+            elif n == 'f1_score' and self.f1 is not None:
+                out[prefix + n] = s[2] / s[4] if s[4] else float('nan')
+        return out
+
+
+# ---------------------------------------------------------------------------
+# scoring helpers (host; once per file)                        metrics.py:95-214
+# ---------------------------------------------------------------------------
+class Challenge_Metric:
+    def __init__(self, sr=16000, hop=256) -> None:
+        self.sr = sr
+        self.hop = hop
+
+    def get_start_end_time(self, data):
+        out = []
+        for cls in self.get_start_end_frame(data):
+            sec = np.round(cls * self.hop / self.sr).astype(np.int32)   # tf.round: half to even, as np.round
+            out.append(np.unique(sec, axis=0) if len(sec) else sec)    # gather(unique(..., True)[1]): sorted unique rows
+        return tuple(out)
+
+    def get_start_end_frame(self, data):
+        """[T, 3] frame decisions -> per class [n, 2] (first, last frame) of each event; an event still open at the end
+        closes at the last frame (metrics.py:111-137)."""
+        data = np.asarray(data.detach().cpu() if torch.is_tensor(data) else data)
+        prev = np.concatenate([np.zeros([1, 3], data.dtype), data[:-1, :]], 0)
+        diff = np.argwhere(prev != data)
+        out = []
+        for c in range(3):
+            idx = diff[diff[:, 1] == c][:, 0].astype(np.int64)
+            if idx.shape[0] % 2 != 0:
+                idx = np.concatenate([idx, np.array([len(data)], np.int64)])
+            idx = idx.reshape(-1, 2)
+            out.append(np.stack([idx[:, 0], idx[:, 1] - 1], 1))
+        return tuple(out)
+
+
+def extract_middle(y_pred):
+    """metrics.py:165-179: [B, T, K] binary -> [N, 3] int64 (clip, middle frame, class) in (clip, class, time) order."""
+    y = np.asarray(y_pred.detach().cpu() if torch.is_tensor(y_pred) else y_pred)
+    prev = np.pad(y, [[0, 0], [1, 0], [0, 0]])[:, :-1]
+    nxt = np.pad(y, [[0, 0], [0, 1], [0, 0]])[:, 1:]
+    starts = np.argwhere(np.clip(y - prev, 0, 1))
+    ends = np.argwhere(np.clip(y - nxt, 0, 1))
+
+    def order(a):
+        a = a[np.argsort(a[:, -1], kind='stable')]
+        return a[np.argsort(a[:, 0], kind='stable')]
+    return ((order(starts) + order(ends)) / 2).astype(np.int64)
+
+
+def get_er(gt, predict):
+    """metrics.py:182-198: greedy matching - ground-truth events by start time, each takes the first remaining prediction of
+    its class (by time) inside [start, end]; (N - 2 matched) / len(gt).  An empty gt raises ZeroDivisionError, as there."""
+    gt = np.asarray(gt).reshape(-1, 3)
+    pred = np.asarray(predict).reshape(-1, 2)
+    pred = pred[np.argsort(pred[:, 1], kind='stable')]
+    gt = gt[np.argsort(gt[:, 1], kind='stable')]
+    n = len(pred) + len(gt)
+    answer = 0
+    for g in gt:
+        for i, p in enumerate(pred):
+            if g[1] <= p[1] <= g[2] and g[0] == p[0]:
+                answer += 2
+                pred = np.concatenate([pred[:i], pred[i + 1:]], 0)
+                break
+    return (n - answer) / len(gt)
+
+
+def output_to_metric(hop, sr):
+    """metrics.py:201-214: per class [n, 2] frame events -> [N, 2] int32 (class, int(((s + e) / 2) * hop / sr))."""
+    def output_to_metric_(cls0, cls1, cls2):
+        rows = []
+        for c, cls in enumerate((cls0, cls1, cls2)):
+            for item in np.asarray(cls).reshape(-1, 2):
+                rows.append([c, int(((int(item[0]) + int(item[1])) / 2) * hop / sr)])
+        return np.asarray(rows, dtype=np.int32).reshape(-1, 2)
+    return output_to_metric_
+
+
+# ---------------------------------------------------------------------------
+# challenge score                                              metrics.py:14-87
+# ---------------------------------------------------------------------------
+def evaluate(config, model, overlap_hop=512, verbose: bool = False, *, wav_dir: str = '.',
+             answer_path: str = 'sample_answer.json', device=None):
+    """Per-file ER of `model` on sorted(glob(wav_dir/*.wav)) against answer_path's 'task2_answer' (metrics.py:31-87): the
+    frame decisions of inference.predict_frames (smoothed, >= 0.5), then get_start_end_frame -> output_to_metric -> get_er."""
+    from . import data_utils as D
+    from .inference import features_for_eval, predict_frames
+    with open(answer_path) as f:
+        answer_gt = json.load(f)['task2_answer']
+    sr, hop = 16000, 256
+    metric = Challenge_Metric()
+    if device is None:
+        device = next(model.parameters()).device if hasattr(model, 'parameters') else None
+    final_score = []
+    for path in sorted(glob(os.path.join(wav_dir, '*.wav'))):
+        spec = D.load_wav(path, device)
+        preds = predict_frames(model, features_for_eval(spec, config), config, overlap_hop)
+        cls0, cls1, cls2 = metric.get_start_end_frame(preds.cpu().numpy())
+        predict = output_to_metric(hop, sr)(cls0, cls1, cls2)
+        final_score.append(get_er(answer_gt[os.path.basename(path)[:-4]], predict))
+    if verbose:
+        print('FINAL SCORE:', np.mean(final_score))
+    return final_score
+
+
+class eval_callback:
+    """metrics.py:14-28: on epochs with epoch % 5 == 2, a copy of the model loaded from the checkpoint `name` is scored with
+    `evaluate`; when its mean ER is not worse than the best so far the copy is saved as <name>_sample.pt.  Same
+    `on_epoch_end(epoch, model)` shape as swa.SWA."""
+
+    def __init__(self, config, name, **evaluate_kwargs):
+        self.config, self.name, self.score = config, name, np.inf
+        self.kwargs = evaluate_kwargs
+
+    def on_epoch_end(self, epoch, model):
+        if epoch % 5 != 2:
+            return
+        from .model import get_model
+        ckpt = os.path.splitext(self.name)[0] + '.pt'
+        dev = next(model.parameters()).device
+        clone = get_model(self.config).to(dev)   # (tf.keras.models.clone_model + load_weights(NAME))
+        if dev.type == 'cuda':
+            clone = clone.to(memory_format=torch.channels_last)
+        clone.load_state_dict(torch.load(ckpt, map_location=dev) if os.path.exists(ckpt) else model.state_dict())
+        score = float(np.mean(evaluate(self.config, clone, verbose=True, **self.kwargs)))
+        if score <= self.score:
+            self.score = score
+            torch.save(clone.state_dict(), os.path.splitext(self.name)[0] + '_sample.pt')

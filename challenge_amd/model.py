@@ -194,6 +194,7 @@ class CustomModel(nn.Module):
         self.use_agc = True
         object.__setattr__(self, '_ddp', None)  # not a submodule: DDP wraps this very module
         object.__setattr__(self, '_fused_agc', None)
+        object.__setattr__(self, '_metrics', None)   # compile(metrics=...): a metrics.MetricSet
         # bumped by everything that changes parameters or buffers WITHOUT going through ATen's version counters: the raw-
         # pointer BatchNorm / AGC kernels, hipGraph replays (GraphedTrainStep), load_state_dict; `predict` keys its cached
         # InferenceEngine on it
@@ -231,9 +232,15 @@ class CustomModel(nn.Module):
         return self.head(self.fc_post(x))
 
     # ---- Keras-like training surface ------------------------------------
-    def compile(self, optimizer, loss, clipvalue: Optional[float] = None, use_agc: bool = True, ddp=None):
+    def compile(self, optimizer, loss, clipvalue: Optional[float] = None, use_agc: bool = True, ddp=None, metrics=None):
+        """`metrics`: the reference's list (metrics.py: er_score(...), f1_score(), cos_sim); train_step / test_step then
+        return them beside 'loss', from the same (detached) predictions - one HIP launch per step on a GPU."""
         self.optimizer, self.loss_fn, self.clipvalue, self.use_agc = optimizer, loss, clipvalue, use_agc
         object.__setattr__(self, '_ddp', ddp)
+        if metrics:
+            from .metrics import MetricSet
+            metrics = MetricSet(metrics)
+        object.__setattr__(self, '_metrics', metrics or None)
 
     def _call(self, x):
         return self._ddp(x) if self._ddp is not None else self(x)
@@ -284,13 +291,18 @@ class CustomModel(nn.Module):
         if not stepped:
             self.optimizer.step()
         mark('optimizer')
-        return {'loss': loss.detach()}
+        if self._metrics is None:
+            return {'loss': loss.detach()}
+        return {'loss': loss.detach(), **self._metrics(y, y_pred.detach(), 'train')}
 
     @torch.no_grad()
     def test_step(self, data):
         x, y = data
         self.eval()
-        return {'loss': self.loss_fn(y, self(x))}
+        if self._metrics is None:
+            return {'loss': self.loss_fn(y, self(x))}
+        y_pred = self(x)
+        return {'loss': self.loss_fn(y, y_pred), **self._metrics(y, y_pred, 'val')}
 
     def bump_generation(self) -> None:
         """Tell `predict` that parameters / buffers have changed (see `_generation`)."""

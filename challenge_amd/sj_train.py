@@ -9,7 +9,8 @@ buckets overlapped with backward; AGC and clipvalue then act on the averaged gra
 identically on every rank.
 
 Out of scope here: model_type 'eff' / 'se' branches
-(sj_train.py:258-401), metrics/er_score (metrics.py stays untouched)."""
+(sj_train.py:258-401).  The training metrics and the challenge score are challenge_amd.metrics
+(`--metrics reference` compiles the reference's list, sj_train.py:454-457)."""
 from __future__ import annotations
 
 import argparse
@@ -96,6 +97,10 @@ class ARGS:
         a('--no_clipvalue_after_agc', action='store_true',
           help="skip Adam's element-wise clipvalue (TF < 2.4 behaviour of the custom train_step)")
         a('--validation_steps', type=int, default=16)
+        a('--metrics', type=str, default='none', choices=['none', 'reference'],
+          help="'reference': compile cos_sim, f1_score() and (v != 5) er_score(smoothing=False) as sj_train.py:454-457 does, "
+               "checkpoint on val_er and score the checkpoint every 5 epochs against ./sample_answer.json and ./*.wav "
+               "(metrics.eval_callback; the file must exist); 'none': loss only")
 
     def get(self, argv=None):
         return self.args.parse_args(argv)
@@ -468,8 +473,22 @@ def main(argv=None):
                          capturable=SW.GRAPH_STEP and device.type == 'cuda' and config.optimizer == 'adam')
     loss = binary_crossentropy if config.loss == 'BCE' else \
         (lambda yt, yp: sigmoid_focal_crossentropy(yt, yp).mean())
+    metrics, callbacks, monitor = None, [], None
+    if config.metrics == 'reference':   # sj_train.py:454-457, :475-495
+        from .metrics import cos_sim, er_score, eval_callback, f1_score
+        if not os.path.exists('sample_answer.json'):
+            # eval_callback scores against ./sample_answer.json and ./*.wav from epoch 2 on, on rank 0 only: checked here, on
+            # every rank alike, instead of one rank failing mid-run while the others wait in fit's collectives
+            raise FileNotFoundError("--metrics reference: sample_answer.json is missing from the working directory (the "
+                                    "checkpoint is scored against it and the *.wav files beside it every 5 epochs)")
+        metrics = [cos_sim, f1_score()]
+        if config.v != 5:
+            metrics.append(er_score(smoothing=False))
+        monitor = 'val_er'
+        if rank == 0:
+            callbacks.append(eval_callback(config, NAME.replace('.h5', '.pt')))
     model.compile(opt, loss, clipvalue=None if config.no_clipvalue_after_agc else config.clipvalue,
-                  ddp=wrap_ddp(model, device, world))
+                  ddp=wrap_ddp(model, device, world), metrics=metrics)
     if rank == 0:
         print(NAME, sum(p.numel() for p in model.parameters()), 'parameters')
     if config.pretrain:
@@ -502,7 +521,7 @@ def main(argv=None):
     fit(model, train_set, config.epochs, config.steps_per_epoch, test_set, config.validation_steps,
         scheduler=custom_scheduler(4096, config.epochs / 12, config.lr_div),
         csv_path=NAME.replace('.h5', '.csv'), checkpoint_path=NAME.replace('.h5', '.pt'),
-        patience=config.patience, rank=rank, world=world, swa=swa)
+        patience=config.patience, rank=rank, world=world, swa=swa, checkpoint_monitor=monitor, callbacks=callbacks)
     try:
         swa.finalize(model)
         if rank == 0:

@@ -299,6 +299,26 @@ int iris_agc_clip_adam(const iris_agc_adam_row* rows_dev, size_t n_rows, float c
                        const float* step_dev, void* stream);
 
 /*
+ * The reference's training metrics of one batch (metrics.py:217-299) in ONE launch, capturable:
+ *   y_true [B, T, K], y_pred [B, T', K] fp32 contiguous; 1 <= K <= 16, 1 <= T, T' <= 8192, B >= 1.
+ *   er_out   [B]  er_score per clip: yt = y_true >= threshold, yp = y_pred >= threshold (after AveragePooling1D(pool,
+ *                 padding='same', stride = pool) when pool > 1: T' -> ceil(T' / pool) windows, each the mean of its in-range
+ *                 frames); runs are maximal 1-runs per (clip, class); a true run [ts, te] is correct iff a predicted run of the
+ *                 same clip and class has its middle (s + e) / 2 in [ts, te] (middles compared as indices with label frames);
+ *                 er = (n_true + n_pred - 2 correct) / max(n_true, 1) in fp32.
+ *   cos_out  [B]  nullable; cos_sim per clip (Keras' negative cosine over time, classes weighted by the mask sum_t y_true > 0).
+ *   f1_state [3]  nullable, DEVICE fp64 (tp, fp, fn), CUMULATIVE: the batch's sum p y, p (1 - y), (1 - p) y with p = y_pred >
+ *                 f1_threshold is added; f1_out [1] (with f1_state) = micro F1 of the cumulative counts (div-no-nan).
+ *   accum    [5]  nullable, DEVICE fp64: += (sum er, sum cos, f1_out, B, 1) - an epoch accumulator the caller zeroes.
+ *   cos_out and f1_state need T' == T.  With f1_state or accum: slab [3 B] fp64 workspace and ticket [1] uint32, zero before
+ *   the first launch (the kernel leaves it zero); one (slab, ticket) pair per stream.  Deterministic: the same inputs give the
+ *   same bits, no float atomics.
+ */
+int iris_event_metrics(const float* y_true, const float* y_pred, int batch, int n_time, int n_time_pred, int n_classes,
+                       float threshold, int pool, float f1_threshold, float* er_out, float* cos_out, double* f1_state,
+                       float* f1_out, double* accum, double* slab, unsigned int* ticket, void* stream);
+
+/*
  * Inference epilogue of ConvMPBlock's Conv2D + BatchNormalization + ReLU (+ MaxPool2D 2x2 'same'), sj_train.py:191-201,
  * once the eval-mode BatchNorm is folded into the convolution (sj_train.fold_batchnorm): the convolution itself stays
  * MIOpen (PyTorch-ROCm, per north_star); these replace the separate bias-add, ReLU and pooling passes over its output.
