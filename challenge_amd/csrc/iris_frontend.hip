@@ -23,6 +23,7 @@
 //   k_conv_wino_b3.h   the same convolution on the BF16 matrix cores at fp32 accuracy: three-term split of both operands (opt-in)
 //   k_conv_wino_wrw.h  the same layers' weight gradient as Winograd F(2x2, 3x3) on the fp32 matrix cores (training)
 //   k_metrics.h      the training metrics er_score / cos_sim / F1 counts of a batch in one launch
+//   k_detect.h       window predictions of many files -> smoothed, thresholded event lists (two launches)
 //   host_plan.h      mel matrix, constant tables, plan create / destroy
 //   host_ops.h       the operators' C-ABI entry points
 #include "common.h"
@@ -46,3 +47,4 @@
 #include "k_resample.h"
 #include "k_agc_adam.h"
 #include "k_metrics.h"
+#include "k_detect.h"

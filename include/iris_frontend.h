@@ -319,6 +319,34 @@ int iris_event_metrics(const float* y_true, const float* y_pred, int batch, int 
                        float* f1_out, double* accum, double* slab, unsigned int* ticket, void* stream);
 
 /*
+ * Window predictions of F files -> event lists (metrics.py:56-81 from the model's outputs on, then get_start_end_frame,
+ * metrics.py:111-137), two launches, capturable:
+ *   preds      [W_total, n_out, K] fp32, DEVICE: the model's outputs for every window of every file, file after file
+ *   win_off    [F + 1] int32, DEVICE: file f owns windows win_off[f] .. win_off[f + 1] - 1
+ *   frame_len  [F] int32, DEVICE: T_f, the file's STFT frames
+ *   win_off_host, frame_len_host: the same values in host memory (checked here; they size the grid)
+ * For file f, class k, frame t < T_f, with up = n_frame / n_out and 'same' pads al = (avg_pool - 1) / 2, ar = avg_pool - 1 - al
+ * (ml, mr likewise for max_pool):
+ *   p[t] = fp32 sum from 0, in ascending w over the windows with w * hop <= t < w * hop + n_frame, of
+ *          preds[win_off[f] + w, (t - w * hop) / up, k], divided by (float) their count
+ *   a[t] = fp32 sum from 0 of p[u], u in [t - al, t + ar] ∩ [0, T_f) ascending, divided by (float) the frames in range
+ *   d[t] = some u in [t - ml, t + mr] ∩ [0, T_f) has a[u] >= threshold and none of them has a NaN a[u]
+ *   events: the maximal runs of d as (first, last) frame pairs
+ * Outputs (DEVICE):
+ *   n_ev  [F, K] int32 event counts
+ *   ev    int32 (first, last) pairs; (file f, class k) owns cap_f = ceil(T_f / 2) + 1 pairs starting at pair
+ *         K * sum_{g < f} cap_g + k * cap_f, of which the first n_ev[f, k] are written, in time order
+ *   bits  workspace of K * sum_f ceil(T_f / 64) uint64 words
+ * 1 <= K <= 16, 1 <= avg_pool <= 127, 1 <= max_pool <= 256 (IRIS_E_UNSUPPORTED otherwise); IRIS_E_INVALID for
+ * overlap_hop > n_frame, n_frame % n_out != 0, negative T_f, or T_f > (windows_f - 1) * overlap_hop + n_frame (frames no window
+ * covers).  Deterministic: plain stores, no atomics; the same inputs give the same bits.
+ */
+int iris_decode_events(const float* preds, const int* win_off, const int* frame_len, const int* win_off_host,
+                       const int* frame_len_host, int n_files, int n_frame, int overlap_hop, int n_out, int n_classes,
+                       int avg_pool, int max_pool, float threshold, unsigned long long* bits, int* ev, int* n_ev,
+                       void* stream);
+
+/*
  * Inference epilogue of ConvMPBlock's Conv2D + BatchNormalization + ReLU (+ MaxPool2D 2x2 'same'), sj_train.py:191-201,
  * once the eval-mode BatchNorm is folded into the convolution (sj_train.fold_batchnorm): the convolution itself stays
  * MIOpen (PyTorch-ROCm, per north_star); these replace the separate bias-add, ReLU and pooling passes over its output.
