@@ -13,6 +13,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <type_traits>
 #include <vector>
 
@@ -61,6 +62,31 @@ static int fail(int code, const char* fmt, ...) {
             return fail((int)e_, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_),   \
                         __FILE__, __LINE__);                                              \
     } while (0)
+
+// ---------------------------------------------------------------------------
+// launch helpers
+// ---------------------------------------------------------------------------
+// CUs of device `dev` (256 when the query fails): what the persistent grids are sized by
+static int device_cu_count(int dev) {
+    int n_cu = 256;
+    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n_cu = 256;
+    return n_cu;
+}
+
+// Raises the dynamic-LDS limit of every kernel in `kernels` to `bytes`, once per device: the attribute belongs to the function
+// object of the current device, so setting it twice is harmless and skipping it on a second GPU is not.  `done` is the call
+// site's own flag per device ordinal (0 .. 63; higher ordinals set the attribute on every call), raised only once every call has
+// succeeded - safe from several threads.  Returns the first failure.
+template <typename... Kernels>
+static hipError_t set_max_lds_once(std::atomic<unsigned> (&done)[64], int dev, size_t bytes, Kernels... kernels) {
+    if (dev >= 0 && dev < 64 && done[dev].load(std::memory_order_acquire)) return hipSuccess;
+    for (const void* k : {reinterpret_cast<const void*>(kernels)...}) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) return e;
+    }
+    if (dev >= 0 && dev < 64) done[dev].store(1u, std::memory_order_release);
+    return hipSuccess;
+}
 
 // ---------------------------------------------------------------------------
 // plan

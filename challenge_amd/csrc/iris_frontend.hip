@@ -21,6 +21,7 @@
 //   k_conv_wino.h    blocks 2-5 (64 ... 512 channels) as Winograd F(2x2, 3x3) on the fp32 matrix cores (inference; the training
 //                    step's forward and backward-data passes)
 //   k_conv_wino_b3.h   the same convolution on the BF16 matrix cores at fp32 accuracy: three-term split of both operands (opt-in)
+//   host_wino.h        the host side of both: the device packers' entry points and one launch path over the two kernel families
 //   k_conv_wino_wrw.h  the same layers' weight gradient as Winograd F(2x2, 3x3) on the fp32 matrix cores (training)
 //   k_metrics.h      the training metrics er_score / cos_sim / F1 counts of a batch in one launch
 //   k_detect.h       window predictions of many files -> smoothed, thresholded event lists (two launches)
@@ -43,6 +44,7 @@
 #include "k_conv_c32.h"
 #include "k_conv_wino.h"
 #include "k_conv_wino_b3.h"
+#include "host_wino.h"
 #include "k_conv_wino_wrw.h"
 #include "k_resample.h"
 #include "k_agc_adam.h"

@@ -189,27 +189,32 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_c32(const float* __restrict_
     }
 }
 
+// What both entry points share: the argument checks, the LDS limit of the instantiations the entry point launches (`kernels`,
+// once per device; `lds_set`: its flags) and the persistent grid - two workgroups per CU walk the tiles.  `name`: the entry point.
+template <typename... Kernels>
+static int c32_prepare(const char* name, std::atomic<unsigned> (&lds_set)[64], const float* x, const float* weight, const float* y,
+                       int batch, int height, int width, unsigned* grid, Kernels... kernels) {
+    if (!x || !weight || !y) return fail(IRIS_E_INVALID, "%s: NULL argument", name);
+    if (batch <= 0 || height <= 0 || width <= 0) return fail(IRIS_E_INVALID, "%s: empty tensor", name);
+    if ((reinterpret_cast<uintptr_t>(x) & 15)) return fail(IRIS_E_INVALID, "%s: x must be 16-byte aligned", name);
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(set_max_lds_once(lds_set, dev, kC32LdsBytes, kernels...));
+    const long long n_tiles = (long long)((width + kC32TileW - 1) / kC32TileW) * ((height + kC32TileH - 1) / kC32TileH) * batch;
+    if (n_tiles >= 2147483647LL) return fail(IRIS_E_UNSUPPORTED, "%s: too many tiles", name);
+    *grid = (unsigned)std::min<long long>(n_tiles, 2LL * device_cu_count(dev));
+    return IRIS_OK;
+}
+
 // The bare 32 -> 32 convolution for the training step (forward: transposed = 0; backward-data on dz: transposed = 1), y and x
 // channels-last [B, H, W, 32], the weight [32, 32, 3, 3] with element strides
 static int conv3x3_c32_impl(const float* x, const float* weight, long stride_o, long stride_i, long stride_h, long stride_w,
                             int transposed, float* y, int batch, int height, int width, double* bn_sums, void* stream) {
-    if (!x || !weight || !y) return fail(IRIS_E_INVALID, "iris_conv3x3_c32: NULL argument");
-    if (batch <= 0 || height <= 0 || width <= 0) return fail(IRIS_E_INVALID, "iris_conv3x3_c32: empty tensor");
-    if ((reinterpret_cast<uintptr_t>(x) & 15)) return fail(IRIS_E_INVALID, "iris_conv3x3_c32: x must be 16-byte aligned");
-    int dev = 0, n_cu = 256;
-    HIP_TRY(hipGetDevice(&dev));
-    static std::atomic<unsigned> attr_set[64];
-    if (dev < 0 || dev >= 64 || !attr_set[dev].load(std::memory_order_acquire)) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3x3_c32<false, false, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kC32LdsBytes));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3x3_c32<false, false, true, true>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)kC32LdsBytes));
-        if (dev >= 0 && dev < 64) attr_set[dev].store(1u, std::memory_order_release);
-    }
-    const long long n_tiles = (long long)((width + kC32TileW - 1) / kC32TileW) * ((height + kC32TileH - 1) / kC32TileH) * batch;
-    if (n_tiles >= 2147483647LL) return fail(IRIS_E_UNSUPPORTED, "iris_conv3x3_c32: too many tiles");
-    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n_cu = 256;
-    const unsigned grid = (unsigned)std::min<long long>(n_tiles, 2LL * n_cu);
+    static std::atomic<unsigned> lds_set[64];
+    unsigned grid = 0;
+    if (const int rc = c32_prepare("iris_conv3x3_c32", lds_set, x, weight, y, batch, height, width, &grid, k_conv3x3_c32<false, false, true>,
+                                   k_conv3x3_c32<false, false, true, true>))
+        return rc;
     if (bn_sums)
         k_conv3x3_c32<false, false, true, true><<<grid, 256, kC32LdsBytes, (hipStream_t)stream>>>(x, weight, nullptr, y, batch, height, width,
                                                                                                    stride_o, stride_i, stride_h, stride_w, transposed, bn_sums);
@@ -234,29 +239,12 @@ extern "C" int iris_conv3x3_c32_bn(const float* x, const float* weight, long str
 
 extern "C" int iris_conv3x3_c32_bias_relu(const float* x, const float* weight, const float* bias, float* y, int batch, int height,
                                           int width, int pool, int out_chunked, void* stream) {
-    if (!x || !weight || !bias || !y) return fail(IRIS_E_INVALID, "iris_conv3x3_c32_bias_relu: NULL argument");
-    if (batch <= 0 || height <= 0 || width <= 0) return fail(IRIS_E_INVALID, "iris_conv3x3_c32_bias_relu: empty tensor");
-    if ((reinterpret_cast<uintptr_t>(x) & 15)) return fail(IRIS_E_INVALID, "iris_conv3x3_c32_bias_relu: x must be 16-byte aligned");
-    // per DEVICE (the attribute belongs to the function object of the current device) and safe from several threads: one
-    // atomic flag per device ordinal; setting the attribute twice is harmless, skipping it on a second GPU is not
-    int dev = 0, n_cu = 256;
-    HIP_TRY(hipGetDevice(&dev));
-    static std::atomic<unsigned> attr_set[64];
-    if (dev < 0 || dev >= 64 || !attr_set[dev].load(std::memory_order_acquire)) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3x3_c32<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)kC32LdsBytes));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3x3_c32<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)kC32LdsBytes));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3x3_c32<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)kC32LdsBytes));
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_conv3x3_c32<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)kC32LdsBytes));
-        if (dev >= 0 && dev < 64) attr_set[dev].store(1u, std::memory_order_release);
-    }
-    const long long n_tiles = (long long)((width + kC32TileW - 1) / kC32TileW) * ((height + kC32TileH - 1) / kC32TileH) * batch;
-    if (n_tiles >= 2147483647LL) return fail(IRIS_E_UNSUPPORTED, "iris_conv3x3_c32_bias_relu: too many tiles");
-    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n_cu = 256;
-    const unsigned grid = (unsigned)std::min<long long>(n_tiles, 2LL * n_cu);  // persistent: two workgroups per CU walk the tiles
+    if (!bias) return fail(IRIS_E_INVALID, "iris_conv3x3_c32_bias_relu: NULL argument");
+    static std::atomic<unsigned> lds_set[64];
+    unsigned grid = 0;
+    if (const int rc = c32_prepare("iris_conv3x3_c32_bias_relu", lds_set, x, weight, y, batch, height, width, &grid, k_conv3x3_c32<false>,
+                                   k_conv3x3_c32<true>, k_conv3x3_c32<false, true>, k_conv3x3_c32<true, true>))
+        return rc;
     hipStream_t s = (hipStream_t)stream;
     if (pool && out_chunked) k_conv3x3_c32<true, true><<<grid, 256, kC32LdsBytes, s>>>(x, weight, bias, y, batch, height, width);
     else if (pool) k_conv3x3_c32<true><<<grid, 256, kC32LdsBytes, s>>>(x, weight, bias, y, batch, height, width);

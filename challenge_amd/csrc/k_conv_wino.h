@@ -509,94 +509,11 @@ __global__ __launch_bounds__(512) void k_wino_pack_multi(const WinoPackJobs jobs
                     jb.transposed, jb.packed);
 }
 
-extern "C" int iris_wino_pack_weights_device(const float* weight, long stride_o, long stride_i, long stride_h, long stride_w, int cin,
-                                             int cout, int transposed, float* packed, void* stream) {
-    if (!weight || !packed) return fail(IRIS_E_INVALID, "iris_wino_pack_weights_device: NULL argument");
-    if (cin <= 0 || cout <= 0 || (cin % kWinoKC) || (cout % kWinoTN))
-        return fail(IRIS_E_UNSUPPORTED, "iris_wino_pack_weights_device: cin %d must be a multiple of %d, cout %d of %d", cin, kWinoKC, cout, kWinoTN);
-    if (reinterpret_cast<uintptr_t>(packed) & 15) return fail(IRIS_E_INVALID, "iris_wino_pack_weights_device: packed must be 16-byte aligned");
-    k_wino_pack<<<(unsigned)((cout / kWinoTN) * (cin / kWinoKC)), 512, 0, (hipStream_t)stream>>>(weight, stride_o, stride_i, stride_h, stride_w,
-                                                                                                 cin, cout, transposed, packed);
-    HIP_TRY(hipGetLastError());
-    return IRIS_OK;
-}
-
-template <bool POOL, bool IN_NHWC, bool BN = false>
-static hipError_t wino_launch(int tc, unsigned grid, hipStream_t s, const float* x, const float* packed, const float* bias,
-                              float* y, int batch, int height, int width, int cin, int cout, int out_nhwc, int relu, double* bn_sums) {
-    if (tc >= 64) k_conv3x3_wino<POOL, 64, IN_NHWC, BN><<<grid, 256, kWinoLdsBytes, s>>>(x, packed, bias, y, batch, height, width, cin, cout, out_nhwc, relu, bn_sums);
-    else if (tc >= 32) k_conv3x3_wino<POOL, 32, IN_NHWC, BN><<<grid, 256, kWinoLdsBytes, s>>>(x, packed, bias, y, batch, height, width, cin, cout, out_nhwc, relu, bn_sums);
-    else k_conv3x3_wino<POOL, 16, IN_NHWC, BN><<<grid, 256, kWinoLdsBytes, s>>>(x, packed, bias, y, batch, height, width, cin, cout, out_nhwc, relu, bn_sums);
-    return hipGetLastError();
-}
-
-template <bool POOL, bool IN_NHWC, bool BN = false>
-static hipError_t wino_set_lds_limit() {
-    const void* ks[3] = {(const void*)k_conv3x3_wino<POOL, 64, IN_NHWC, BN>, (const void*)k_conv3x3_wino<POOL, 32, IN_NHWC, BN>,
-                         (const void*)k_conv3x3_wino<POOL, 16, IN_NHWC, BN>};
-    for (const void* k : ks) {
-        hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWinoLdsBytes);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-// x: channel-chunked [B][cin / 8][H][W][8] (IRIS_WINO_IN_NHWC: channels-last [B][H][W][cin]); packed: iris_wino_pack_weights[_device];
-// bias: nullable; y: chunked [B][cout / 8][Ho][Wo][8] (IRIS_WINO_OUT_NHWC: channels-last [B][Ho][Wo][cout]); flags = IRIS_WINO_*
-static int conv3x3_wino_impl(const float* x, const float* packed, const float* bias, float* y, int batch, int height, int width,
-                             int cin, int cout, int flags, double* bn_sums, void* stream) {
-    if (!x || !packed || !y) return fail(IRIS_E_INVALID, "iris_conv3x3_wino: NULL argument");
-    if (bn_sums && (bias || (flags & (IRIS_WINO_POOL | IRIS_WINO_RELU)) || !(flags & IRIS_WINO_OUT_NHWC)))
-        return fail(IRIS_E_INVALID, "iris_conv3x3_wino_bn: the statistics are those of the bare convolution, channels-last out (no bias / ReLU / pooling)");
-    if (batch <= 0 || height <= 0 || width <= 0) return fail(IRIS_E_INVALID, "iris_conv3x3_wino: empty tensor");
-    if (flags & ~(IRIS_WINO_POOL | IRIS_WINO_OUT_NHWC | IRIS_WINO_IN_NHWC | IRIS_WINO_RELU)) return fail(IRIS_E_INVALID, "iris_conv3x3_wino: flags 0x%x", flags);
-    if (cin <= 0 || cout <= 0 || (cin % kWinoKC) || (cout % kWinoTN))
-        return fail(IRIS_E_UNSUPPORTED, "iris_conv3x3_wino: cin %d must be a multiple of %d, cout %d of %d", cin, kWinoKC, cout, kWinoTN);
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(packed)) & 15)
-        return fail(IRIS_E_INVALID, "iris_conv3x3_wino: x and the packed weights must be 16-byte aligned");
-    if ((long long)batch * height * width * cin >= 1073741824LL)
-        return fail(IRIS_E_UNSUPPORTED, "iris_conv3x3_wino: tensor too large for 32-bit byte offsets (>= 2^30 elements)");
-    int dev = 0, n_cu = 256;
-    HIP_TRY(hipGetDevice(&dev));
-    static std::atomic<unsigned> attr_set[64];
-    if (dev < 0 || dev >= 64 || !attr_set[dev].load(std::memory_order_acquire)) {
-        HIP_TRY((wino_set_lds_limit<false, false>()));
-        HIP_TRY((wino_set_lds_limit<false, true>()));
-        HIP_TRY((wino_set_lds_limit<true, false>()));
-        HIP_TRY((wino_set_lds_limit<true, true>()));
-        HIP_TRY((wino_set_lds_limit<false, false, true>()));
-        HIP_TRY((wino_set_lds_limit<false, true, true>()));
-        if (dev >= 0 && dev < 64) attr_set[dev].store(1u, std::memory_order_release);
-    }
-    const int pool = (flags & IRIS_WINO_POOL) != 0, out_nhwc = (flags & IRIS_WINO_OUT_NHWC) != 0;
-    const int in_nhwc = (flags & IRIS_WINO_IN_NHWC) != 0, relu = (flags & IRIS_WINO_RELU) != 0;
-    const int th = (height + 1) / 2, tw = (width + 1) / 2;
-    const int tc = tw > 32 ? 64 : (tw > 16 ? 32 : 16), tr = kWinoTM / tc;
-    const long long n_work = (((long long)batch * th + tr - 1) / tr) * ((tw + tc - 1) / tc) * (cout / kWinoTN);
-    if (n_work >= 2147483647LL) return fail(IRIS_E_UNSUPPORTED, "iris_conv3x3_wino: too many tiles");
-    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n_cu = 256;
-    const unsigned grid = (unsigned)std::min<long long>(n_work, n_cu);  // persistent: one workgroup (4 waves, 156 KiB of LDS) per CU
-    const hipStream_t st = (hipStream_t)stream;
-    hipError_t e;
-    if (pool) e = in_nhwc ? wino_launch<true, true>(tc, grid, st, x, packed, bias, y, batch, height, width, cin, cout, out_nhwc, relu, nullptr)
-                          : wino_launch<true, false>(tc, grid, st, x, packed, bias, y, batch, height, width, cin, cout, out_nhwc, relu, nullptr);
-    else if (bn_sums) e = in_nhwc ? wino_launch<false, true, true>(tc, grid, st, x, packed, bias, y, batch, height, width, cin, cout, out_nhwc, relu, bn_sums)
-                                  : wino_launch<false, false, true>(tc, grid, st, x, packed, bias, y, batch, height, width, cin, cout, out_nhwc, relu, bn_sums);
-    else e = in_nhwc ? wino_launch<false, true>(tc, grid, st, x, packed, bias, y, batch, height, width, cin, cout, out_nhwc, relu, nullptr)
-                     : wino_launch<false, false>(tc, grid, st, x, packed, bias, y, batch, height, width, cin, cout, out_nhwc, relu, nullptr);
-    HIP_TRY(e);
-    return IRIS_OK;
-}
-
-extern "C" int iris_conv3x3_wino(const float* x, const float* packed, const float* bias, float* y, int batch, int height, int width,
-                                 int cin, int cout, int flags, void* stream) {
-    return conv3x3_wino_impl(x, packed, bias, y, batch, height, width, cin, cout, flags, nullptr, stream);
-}
-// The training form (bare convolution, flags = IRIS_WINO_OUT_NHWC [| IRIS_WINO_IN_NHWC]) that ALSO accumulates the statistics of
-// the BatchNorm behind it: bn_sums_zeroed = DEVICE double [iris_bn_sums_len(cout)], zero on entry, consumed by
-// iris_bn_relu_apply_sums0 / iris_bn_relu_pool_apply_sums0 (no iris_bn_stats pass over z)
-extern "C" int iris_conv3x3_wino_bn(const float* x, const float* packed, float* y, int batch, int height, int width, int cin, int cout,
-                                    int flags, double* bn_sums_zeroed, void* stream) {
-    if (!bn_sums_zeroed) return fail(IRIS_E_INVALID, "iris_conv3x3_wino_bn: NULL argument");
-    return conv3x3_wino_impl(x, packed, nullptr, y, batch, height, width, cin, cout, flags, bn_sums_zeroed, stream);
-}
+// Traits of this kernel family for the launch path both Winograd kernels share (host_wino.h)
+struct WinoF32 {
+    template <bool POOL, int TC, bool IN_NHWC, bool BN>
+    static constexpr auto kernel = k_conv3x3_wino<POOL, TC, IN_NHWC, BN>;
+    static constexpr size_t kLdsBytes = kWinoLdsBytes;
+    static constexpr int kKC = kWinoKC;
+    using Packed = const float*;
+};

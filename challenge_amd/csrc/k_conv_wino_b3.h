@@ -148,48 +148,7 @@ __global__ __launch_bounds__(128) void k_wino_pack_b3_multi(const WinoPackJobs j
                        jb.transposed, reinterpret_cast<uint4*>(jb.packed));
 }
 
-extern "C" int iris_wino_pack_weights_device_multi(iris_pack_job* jobs_host, int n_jobs, int split_bf16, void* stream) {
-    if (!jobs_host || n_jobs <= 0) return fail(IRIS_E_INVALID, "iris_wino_pack_weights_device_multi: no jobs");
-    const int kc = split_bf16 ? kB3KC : kWinoKC;
-    for (int i = 0; i < n_jobs; ++i) {
-        const iris_pack_job& jb = jobs_host[i];
-        if (!jb.weight || !jb.packed) return fail(IRIS_E_INVALID, "iris_wino_pack_weights_device_multi: job %d: NULL pointer", i);
-        if (jb.cin <= 0 || jb.cout <= 0 || (jb.cin % kc) || (jb.cout % 64))
-            return fail(IRIS_E_UNSUPPORTED, "iris_wino_pack_weights_device_multi: job %d: cin %d must be a multiple of %d, cout %d of 64", i, jb.cin, kc, jb.cout);
-        if (reinterpret_cast<uintptr_t>(jb.packed) & 15) return fail(IRIS_E_INVALID, "iris_wino_pack_weights_device_multi: job %d: packed must be 16-byte aligned", i);
-    }
-    for (int base = 0; base < n_jobs; base += kWinoPackMaxJobs) {
-        WinoPackJobs jobs;
-        jobs.n = std::min(kWinoPackMaxJobs, n_jobs - base);
-        jobs.pad = 0;
-        long long blocks = 0;
-        for (int i = 0; i < jobs.n; ++i) {
-            iris_pack_job& jb = jobs_host[base + i];
-            jb.first_block = (int)blocks;
-            jobs.j[i] = jb;
-            blocks += (long long)(jb.cout / 64) * (jb.cin / kc);
-        }
-        if (blocks >= 2147483647LL) return fail(IRIS_E_UNSUPPORTED, "iris_wino_pack_weights_device_multi: too many blocks");
-        if (split_bf16) k_wino_pack_b3_multi<<<(unsigned)blocks, 128, 0, (hipStream_t)stream>>>(jobs);
-        else k_wino_pack_multi<<<(unsigned)blocks, 512, 0, (hipStream_t)stream>>>(jobs);
-        HIP_TRY(hipGetLastError());
-    }
-    return IRIS_OK;
-}
-
 extern "C" size_t iris_wino_b3_packed_len(int cin, int cout) { return (cin > 0 && cout > 0) ? wino_b3_packed_bytes(cin, cout) / 4 : 0; }  // in floats
-
-extern "C" int iris_wino_b3_pack_weights_device(const float* weight, long stride_o, long stride_i, long stride_h, long stride_w, int cin,
-                                                int cout, int transposed, float* packed, void* stream) {
-    if (!weight || !packed) return fail(IRIS_E_INVALID, "iris_wino_b3_pack_weights_device: NULL argument");
-    if (cin <= 0 || cout <= 0 || (cin % kB3KC) || (cout % 64))
-        return fail(IRIS_E_UNSUPPORTED, "iris_wino_b3_pack_weights_device: cin %d must be a multiple of %d, cout %d of 64", cin, kB3KC, cout);
-    if (reinterpret_cast<uintptr_t>(packed) & 15) return fail(IRIS_E_INVALID, "iris_wino_b3_pack_weights_device: packed must be 16-byte aligned");
-    k_wino_pack_b3<<<(unsigned)((cout / 64) * (cin / kB3KC)), 128, 0, (hipStream_t)stream>>>(weight, stride_o, stride_i, stride_h, stride_w, cin,
-                                                                                             cout, transposed, reinterpret_cast<uint4*>(packed));
-    HIP_TRY(hipGetLastError());
-    return IRIS_OK;
-}
 
 #ifdef IRIS_B3_STAMPS
 // timing experiments only: wave 0 of every workgroup records (s_memrealtime [100 MHz], s_memtime [shader clock]) at six points of its
@@ -594,80 +553,12 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino_b3(const float* __restr
     }
 }
 
-template <bool POOL, bool IN_NHWC, bool BN = false>
-static hipError_t wino_b3_launch(int tc, unsigned grid, hipStream_t s, const float* x, const uint4* packed, const float* bias, float* y,
-                                 int batch, int height, int width, int cin, int cout, int out_nhwc, int relu, double* bn_sums) {
-    if (tc >= 64) k_conv3x3_wino_b3<POOL, 64, IN_NHWC, BN><<<grid, 256, kB3LdsBytes, s>>>(x, packed, bias, y, batch, height, width, cin, cout, out_nhwc, relu, bn_sums);
-    else if (tc >= 32) k_conv3x3_wino_b3<POOL, 32, IN_NHWC, BN><<<grid, 256, kB3LdsBytes, s>>>(x, packed, bias, y, batch, height, width, cin, cout, out_nhwc, relu, bn_sums);
-    else k_conv3x3_wino_b3<POOL, 16, IN_NHWC, BN><<<grid, 256, kB3LdsBytes, s>>>(x, packed, bias, y, batch, height, width, cin, cout, out_nhwc, relu, bn_sums);
-    return hipGetLastError();
-}
 
-template <bool POOL, bool IN_NHWC, bool BN = false>
-static hipError_t wino_b3_set_lds_limit() {
-    const void* ks[3] = {(const void*)k_conv3x3_wino_b3<POOL, 64, IN_NHWC, BN>, (const void*)k_conv3x3_wino_b3<POOL, 32, IN_NHWC, BN>,
-                         (const void*)k_conv3x3_wino_b3<POOL, 16, IN_NHWC, BN>};
-    for (const void* k : ks) {
-        hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kB3LdsBytes);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-// Same contract as iris_conv3x3_wino (k_conv_wino.h) with `packed` from iris_wino_b3_pack_weights_device and cin % 16 == 0.
-static int conv3x3_wino_b3_impl(const float* x, const float* packed, const float* bias, float* y, int batch, int height, int width,
-                                int cin, int cout, int flags, double* bn_sums, void* stream) {
-    if (!x || !packed || !y) return fail(IRIS_E_INVALID, "iris_conv3x3_wino_b3: NULL argument");
-    if (bn_sums && (bias || (flags & (IRIS_WINO_POOL | IRIS_WINO_RELU)) || !(flags & IRIS_WINO_OUT_NHWC)))
-        return fail(IRIS_E_INVALID, "iris_conv3x3_wino_b3_bn: the statistics are those of the bare convolution, channels-last out (no bias / ReLU / pooling)");
-    if (batch <= 0 || height <= 0 || width <= 0) return fail(IRIS_E_INVALID, "iris_conv3x3_wino_b3: empty tensor");
-    if (flags & ~(IRIS_WINO_POOL | IRIS_WINO_OUT_NHWC | IRIS_WINO_IN_NHWC | IRIS_WINO_RELU)) return fail(IRIS_E_INVALID, "iris_conv3x3_wino_b3: flags 0x%x", flags);
-    if (cin <= 0 || cout <= 0 || (cin % kB3KC) || (cout % 64))
-        return fail(IRIS_E_UNSUPPORTED, "iris_conv3x3_wino_b3: cin %d must be a multiple of %d, cout %d of 64", cin, kB3KC, cout);
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(packed)) & 15)
-        return fail(IRIS_E_INVALID, "iris_conv3x3_wino_b3: x and the packed weights must be 16-byte aligned");
-    if ((long long)batch * height * width * cin >= 1073741824LL)
-        return fail(IRIS_E_UNSUPPORTED, "iris_conv3x3_wino_b3: tensor too large for 32-bit byte offsets (>= 2^30 elements)");
-    int dev = 0, n_cu = 256;
-    HIP_TRY(hipGetDevice(&dev));
-    static std::atomic<unsigned> attr_set[64];
-    if (dev < 0 || dev >= 64 || !attr_set[dev].load(std::memory_order_acquire)) {
-        HIP_TRY((wino_b3_set_lds_limit<false, false>()));
-        HIP_TRY((wino_b3_set_lds_limit<false, true>()));
-        HIP_TRY((wino_b3_set_lds_limit<true, false>()));
-        HIP_TRY((wino_b3_set_lds_limit<true, true>()));
-        HIP_TRY((wino_b3_set_lds_limit<false, false, true>()));
-        HIP_TRY((wino_b3_set_lds_limit<false, true, true>()));
-        if (dev >= 0 && dev < 64) attr_set[dev].store(1u, std::memory_order_release);
-    }
-    const int pool = (flags & IRIS_WINO_POOL) != 0, out_nhwc = (flags & IRIS_WINO_OUT_NHWC) != 0;
-    const int in_nhwc = (flags & IRIS_WINO_IN_NHWC) != 0, relu = (flags & IRIS_WINO_RELU) != 0;
-    const int th = (height + 1) / 2, tw = (width + 1) / 2;
-    const int tc = tw > 32 ? 64 : (tw > 16 ? 32 : 16), tr = 64 / tc;
-    const long long n_work = (((long long)batch * th + tr - 1) / tr) * ((tw + tc - 1) / tc) * (cout / 64);
-    if (n_work >= 2147483647LL) return fail(IRIS_E_UNSUPPORTED, "iris_conv3x3_wino_b3: too many tiles");
-    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n_cu = 256;
-    const unsigned grid = (unsigned)std::min<long long>(n_work, n_cu);
-    const hipStream_t st = (hipStream_t)stream;
-    const uint4* pk = reinterpret_cast<const uint4*>(packed);
-    hipError_t e;
-    if (pool) e = in_nhwc ? wino_b3_launch<true, true>(tc, grid, st, x, pk, bias, y, batch, height, width, cin, cout, out_nhwc, relu, nullptr)
-                          : wino_b3_launch<true, false>(tc, grid, st, x, pk, bias, y, batch, height, width, cin, cout, out_nhwc, relu, nullptr);
-    else if (bn_sums) e = in_nhwc ? wino_b3_launch<false, true, true>(tc, grid, st, x, pk, bias, y, batch, height, width, cin, cout, out_nhwc, relu, bn_sums)
-                                  : wino_b3_launch<false, false, true>(tc, grid, st, x, pk, bias, y, batch, height, width, cin, cout, out_nhwc, relu, bn_sums);
-    else e = in_nhwc ? wino_b3_launch<false, true>(tc, grid, st, x, pk, bias, y, batch, height, width, cin, cout, out_nhwc, relu, nullptr)
-                     : wino_b3_launch<false, false>(tc, grid, st, x, pk, bias, y, batch, height, width, cin, cout, out_nhwc, relu, nullptr);
-    HIP_TRY(e);
-    return IRIS_OK;
-}
-
-extern "C" int iris_conv3x3_wino_b3(const float* x, const float* packed, const float* bias, float* y, int batch, int height, int width,
-                                    int cin, int cout, int flags, void* stream) {
-    return conv3x3_wino_b3_impl(x, packed, bias, y, batch, height, width, cin, cout, flags, nullptr, stream);
-}
-// as iris_conv3x3_wino_bn: the bare convolution + the statistics of the BatchNorm behind it
-extern "C" int iris_conv3x3_wino_b3_bn(const float* x, const float* packed, float* y, int batch, int height, int width, int cin, int cout,
-                                       int flags, double* bn_sums_zeroed, void* stream) {
-    if (!bn_sums_zeroed) return fail(IRIS_E_INVALID, "iris_conv3x3_wino_b3_bn: NULL argument");
-    return conv3x3_wino_b3_impl(x, packed, nullptr, y, batch, height, width, cin, cout, flags, bn_sums_zeroed, stream);
-}
+// Traits of this kernel family for the launch path both Winograd kernels share (host_wino.h)
+struct WinoB3 {
+    template <bool POOL, int TC, bool IN_NHWC, bool BN>
+    static constexpr auto kernel = k_conv3x3_wino_b3<POOL, TC, IN_NHWC, BN>;
+    static constexpr size_t kLdsBytes = kB3LdsBytes;
+    static constexpr int kKC = kB3KC;
+    using Packed = const uint4*;
+};

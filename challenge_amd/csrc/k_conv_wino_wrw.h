@@ -333,8 +333,8 @@ static size_t wino_wrw_splits(int batch, int height, int cin, int cout, int n_cu
 extern "C" size_t iris_wino_wrw_workspace_len(int batch, int height, int width, int cin, int cout) {
     (void)width;
     if (batch <= 0 || height <= 0 || cin <= 0 || cout <= 0 || (cin % 32) || (cout % 32)) return 0;
-    int dev = 0, n_cu = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n_cu = 256;
+    int dev = 0;
+    const int n_cu = hipGetDevice(&dev) == hipSuccess ? device_cu_count(dev) : 256;
     return wino_wrw_splits(batch, height, cin, cout, n_cu) * 16 * (size_t)cin * cout;
 }
 
@@ -350,10 +350,9 @@ extern "C" int iris_conv3x3_wino_wrw(const float* x, const float* dy, float* dw,
         return fail(IRIS_E_UNSUPPORTED, "iris_conv3x3_wino_wrw: cin %d and cout %d must be multiples of 32", cin, cout);
     if ((long long)batch * height * width * std::max(cin, cout) * 4 >= 2147483648LL)
         return fail(IRIS_E_UNSUPPORTED, "iris_conv3x3_wino_wrw: tensor of 2^31 bytes or more");
-    int dev = 0, n_cu = 256;
+    int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
-    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n_cu = 256;
-    const size_t n_split = wino_wrw_splits(batch, height, cin, cout, n_cu);
+    const size_t n_split = wino_wrw_splits(batch, height, cin, cout, device_cu_count(dev));
     const int cbk = wino_wrw_cin_block(cin), obk = wino_wrw_cout_block(cout), n_bp = (cin / cbk) * (cout / obk);
     if (workspace_len < n_split * 16 * (size_t)cin * cout)
         return fail(IRIS_E_INVALID, "iris_conv3x3_wino_wrw: workspace of %zu floats, %zu needed", workspace_len, n_split * 16 * (size_t)cin * cout);

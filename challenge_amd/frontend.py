@@ -524,32 +524,44 @@ def to_chunked(x: torch.Tensor) -> torch.Tensor:
     return x.permute(0, 2, 3, 1).reshape(b, h, w, c // 8, 8).permute(0, 3, 1, 2, 4).contiguous()
 
 
+# The library functions of the two Winograd kernel families, by `split_bf16`: the exact-fp32 kernel and the one on the BF16 matrix
+# cores at fp32 accuracy.  Their packings differ in format and size: a packing goes only to the kernel of its own family.
+_WINO_FNS = {
+    False: {"packed_len": "iris_wino_packed_len", "pack": "iris_wino_pack_weights_device",
+            "conv": "iris_conv3x3_wino", "conv_bn": "iris_conv3x3_wino_bn"},
+    True: {"packed_len": "iris_wino_b3_packed_len", "pack": "iris_wino_b3_pack_weights_device",
+           "conv": "iris_conv3x3_wino_b3", "conv_bn": "iris_conv3x3_wino_b3_bn"},
+}
+
+
 def wino_pack_weights_device(weight: torch.Tensor, transposed: bool = False, out: Optional[torch.Tensor] = None,
                              split_bf16: bool = False) -> torch.Tensor:
     """The same packing on the device, on the current stream, from the weight as it lies in memory (any strides: a
     channels_last parameter needs no copy) - what a training step does every step.  `transposed`: the weights of the
     backward-data pass (dx = conv(dz, W'), W'[ci][co][i][j] = W[co][ci][2 - i][2 - j]).  `split_bf16`: U split into three bf16
-    terms in the operand order of iris_conv3x3_wino_b3 (the convolution on the BF16 matrix cores at fp32 accuracy)."""
+    terms in the operand order of iris_conv3x3_wino_b3 (the convolution on the BF16 matrix cores at fp32 accuracy).
+    `out`: a float32 tensor of at least wino_packed_len floats on the weight's device."""
     if not (weight.is_cuda and weight.dtype == torch.float32 and weight.dim() == 4 and tuple(weight.shape[2:]) == (3, 3)):
         raise ValueError("wino_pack_weights_device: a float32 device weight [Cout, Cin, 3, 3] is expected (no CPU fallback)")
     co, ci = int(weight.shape[0]), int(weight.shape[1])
     cin, cout = (co, ci) if transposed else (ci, co)
-    lib = N.lib()
-    n = int((lib.iris_wino_b3_packed_len if split_bf16 else lib.iris_wino_packed_len)(cin, cout))
+    n = wino_packed_len(cin, cout, split_bf16)
     if out is None:
         out = torch.empty(n, dtype=torch.float32, device=weight.device)
+    elif not (out.dtype == torch.float32 and out.device == weight.device and out.numel() >= n):
+        raise ValueError(f"wino_pack_weights_device: out must be a float32 tensor of at least {n} elements on {weight.device}")
     so, si, sh, sw = (int(v) for v in weight.stride())
-    pack = lib.iris_wino_b3_pack_weights_device if split_bf16 else lib.iris_wino_pack_weights_device
+    name = _WINO_FNS[bool(split_bf16)]["pack"]
     with torch.cuda.device(weight.device):
-        rc = pack(weight.data_ptr(), so, si, sh, sw, cin, cout, 1 if transposed else 0, out.data_ptr(), _stream_ptr(weight.device))
-    N.check(rc, "iris_wino_b3_pack_weights_device" if split_bf16 else "iris_wino_pack_weights_device")
+        rc = getattr(N.lib(), name)(weight.data_ptr(), so, si, sh, sw, cin, cout, 1 if transposed else 0, out.data_ptr(),
+                                    _stream_ptr(weight.device))
+    N.check(rc, name)
     return out
 
 
 def wino_packed_len(cin: int, cout: int, split_bf16: bool = False) -> int:
     """floats of the packed weights of a cin -> cout layer (iris_wino_packed_len / iris_wino_b3_packed_len)."""
-    lib = N.lib()
-    return int((lib.iris_wino_b3_packed_len if split_bf16 else lib.iris_wino_packed_len)(int(cin), int(cout)))
+    return int(getattr(N.lib(), _WINO_FNS[bool(split_bf16)]["packed_len"])(int(cin), int(cout)))
 
 
 def wino_pack_weights_device_multi(jobs, split_bf16: bool = False) -> None:
@@ -579,8 +591,9 @@ def conv3x3_wino(x: torch.Tensor, packed: torch.Tensor, bias: Optional[torch.Ten
                  out_nhwc: bool = False, relu: bool = True, split_bf16: bool = False, bn_sums: Optional[torch.Tensor] = None) -> torch.Tensor:
     """conv2d(x, weight, padding=1) (+ bias, + ReLU, + MaxPool 2x2 'same') as Winograd F(2x2, 3x3) on the fp32 matrix cores
     (iris_conv3x3_wino).  x: channel-chunked [B, Cin / 8, H, W, 8], or a channels_last [B, Cin, H, W] tensor (read where it
-    lies: IRIS_WINO_IN_NHWC); packed: `wino_pack_weights[_device]`; returns the chunked [B, cout / 8, Ho, Wo, 8] or, with
-    `out_nhwc`, a channels_last [B, cout, Ho, Wo] tensor."""
+    lies: IRIS_WINO_IN_NHWC); packed: `wino_pack_weights[_device]` with the same `split_bf16`, on x's device (a shorter packing is
+    refused; a split-bf16 packing given to the fp32 kernel is long enough and cannot be told apart); returns the chunked
+    [B, cout / 8, Ho, Wo, 8] or, with `out_nhwc`, a channels_last [B, cout, Ho, Wo] tensor."""
     if not (x.is_cuda and x.dtype == torch.float32):
         raise ValueError("conv3x3_wino: x must be a float32 device tensor (no CPU fallback)")
     if x.dim() == 5 and x.shape[4] == 8 and x.is_contiguous():
@@ -591,6 +604,10 @@ def conv3x3_wino(x: torch.Tensor, packed: torch.Tensor, bias: Optional[torch.Ten
         in_nhwc = True
     else:
         raise ValueError("conv3x3_wino: x must be contiguous [B, Cin / 8, H, W, 8] or channels_last [B, Cin, H, W]")
+    need = wino_packed_len(cin, int(cout), split_bf16)   # what the kernel reads
+    if not (packed.dtype == torch.float32 and packed.device == x.device and packed.is_contiguous() and packed.numel() >= need):
+        raise ValueError(f"conv3x3_wino: packed must be a contiguous float32 tensor of at least {need} elements on {x.device} "
+                         f"(wino_pack_weights_device(..., split_bf16={bool(split_bf16)}))")
     ho, wo = ((h + 1) // 2, (w + 1) // 2) if pool else (h, w)
     if out_nhwc:
         y = torch.empty((b, cout, ho, wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
@@ -598,18 +615,17 @@ def conv3x3_wino(x: torch.Tensor, packed: torch.Tensor, bias: Optional[torch.Ten
         y = torch.empty((b, cout // 8, ho, wo, 8), dtype=torch.float32, device=x.device)
     flags = (N.IRIS_WINO_POOL if pool else 0) | (N.IRIS_WINO_OUT_NHWC if out_nhwc else 0) | \
         (N.IRIS_WINO_IN_NHWC if in_nhwc else 0) | (N.IRIS_WINO_RELU if relu else 0)
-    lib = N.lib()
+    lib, fns = N.lib(), _WINO_FNS[bool(split_bf16)]
     with torch.cuda.device(x.device):
         if bn_sums is not None:   # the bare convolution + the statistics of the BatchNorm behind it (zeroed float64 [iris_bn_sums_len(cout)])
             if bias is not None or bn_sums.dtype != torch.float64 or bn_sums.numel() < int(lib.iris_bn_sums_len(int(cout))):
                 raise ValueError("conv3x3_wino: bn_sums goes with the bare convolution (no bias) and must be float64 [iris_bn_sums_len(cout)]")
-            fn = lib.iris_conv3x3_wino_b3_bn if split_bf16 else lib.iris_conv3x3_wino_bn
-            rc = fn(x.data_ptr(), packed.data_ptr(), y.data_ptr(), b, h, w, cin, int(cout), flags, bn_sums.data_ptr(), _stream_ptr(x.device))
+            rc = getattr(lib, fns["conv_bn"])(x.data_ptr(), packed.data_ptr(), y.data_ptr(), b, h, w, cin, int(cout), flags, bn_sums.data_ptr(),
+                                              _stream_ptr(x.device))
         else:
-            fn = lib.iris_conv3x3_wino_b3 if split_bf16 else lib.iris_conv3x3_wino   # `packed` must come from the matching packer
-            rc = fn(x.data_ptr(), packed.data_ptr(), bias.data_ptr() if bias is not None else None, y.data_ptr(),
-                    b, h, w, cin, int(cout), flags, _stream_ptr(x.device))
-    N.check(rc, "iris_conv3x3_wino_b3" if split_bf16 else "iris_conv3x3_wino")
+            rc = getattr(lib, fns["conv"])(x.data_ptr(), packed.data_ptr(), bias.data_ptr() if bias is not None else None, y.data_ptr(),
+                                           b, h, w, cin, int(cout), flags, _stream_ptr(x.device))
+    N.check(rc, fns["conv"])
     return y
 
 

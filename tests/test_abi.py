@@ -143,6 +143,93 @@ def test_round3_entry_points_validate_before_any_launch():
     assert b"" != lib.iris_last_error()
 
 
+def test_convolution_training_forms_validate_before_any_launch():
+    """The split-bf16 Winograd convolution, the BatchNorm-statistics forms of both Winograd kernels, the device packers and the
+    c32 training forms refuse NULL, misaligned, empty and unsupported arguments before any HIP call; the error names the entry
+    point that was called.  (The `_bn` entry points take no bias, so their "no bias with the statistics" rule is only reachable
+    through frontend.conv3x3_wino.)"""
+    lib = N.lib()
+    p16, p8 = C.c_void_p(16), C.c_void_p(8)
+    INVALID, UNSUPPORTED = -1, -2
+    POOL, OUT_NHWC, RELU = N.IRIS_WINO_POOL, N.IRIS_WINO_OUT_NHWC, N.IRIS_WINO_RELU
+
+    def refused(rc, code, name):
+        assert rc == code, (name, rc)
+        assert lib.iris_last_error().startswith(name.encode() + b":"), (name, lib.iris_last_error())
+
+    b3 = "iris_conv3x3_wino_b3"
+    refused(lib.iris_conv3x3_wino_b3(None, p16, p16, p16, 1, 8, 8, 64, 64, 0, None), INVALID, b3)
+    refused(lib.iris_conv3x3_wino_b3(p16, None, p16, p16, 1, 8, 8, 64, 64, 0, None), INVALID, b3)
+    refused(lib.iris_conv3x3_wino_b3(p16, p16, p16, None, 1, 8, 8, 64, 64, 0, None), INVALID, b3)
+    refused(lib.iris_conv3x3_wino_b3(p16, p16, p16, p16, 1, 8, 8, 24, 64, 0, None), UNSUPPORTED, b3)    # cin % 16 (a multiple of 8)
+    refused(lib.iris_conv3x3_wino_b3(p16, p16, p16, p16, 1, 8, 8, 64, 96, 0, None), UNSUPPORTED, b3)    # cout % 64
+    refused(lib.iris_conv3x3_wino_b3(p8, p16, p16, p16, 1, 8, 8, 64, 64, 0, None), INVALID, b3)         # x alignment
+    refused(lib.iris_conv3x3_wino_b3(p16, p8, p16, p16, 1, 8, 8, 64, 64, 0, None), INVALID, b3)         # packed alignment
+    refused(lib.iris_conv3x3_wino_b3(p16, p16, p16, p16, 0, 8, 8, 64, 64, 0, None), INVALID, b3)        # empty
+    refused(lib.iris_conv3x3_wino_b3(p16, p16, p16, p16, 1, 8, 0, 64, 64, 0, None), INVALID, b3)
+    refused(lib.iris_conv3x3_wino_b3(p16, p16, None, p16, 1, 8, 8, 64, 64, 16, None), INVALID, b3)      # unknown flag
+    refused(lib.iris_conv3x3_wino(p16, p8, p16, p16, 1, 8, 8, 64, 64, 0, None), INVALID, "iris_conv3x3_wino")
+
+    for bn in ("iris_conv3x3_wino_bn", "iris_conv3x3_wino_b3_bn"):
+        fn = getattr(lib, bn)
+        refused(fn(p16, p16, p16, 1, 8, 8, 64, 64, OUT_NHWC, None, None), INVALID, bn)                # NULL sums
+        refused(fn(p16, p16, p16, 1, 8, 8, 64, 64, OUT_NHWC | POOL, p16, None), INVALID, bn)          # sums with pooling
+        refused(fn(p16, p16, p16, 1, 8, 8, 64, 64, OUT_NHWC | RELU, p16, None), INVALID, bn)          # sums with ReLU
+        refused(fn(p16, p16, p16, 1, 8, 8, 64, 64, 0, p16, None), INVALID, bn)                        # sums need channels-last out
+        refused(fn(None, p16, p16, 1, 8, 8, 64, 64, OUT_NHWC, p16, None), INVALID, bn[:-3])           # then the plain form's checks
+        refused(fn(p16, p16, p16, 1, 8, 8, 64, 96, OUT_NHWC, p16, None), UNSUPPORTED, bn[:-3])
+
+    for name, kc in (("iris_wino_pack_weights_device", 8), ("iris_wino_b3_pack_weights_device", 16)):
+        fn = getattr(lib, name)
+        refused(fn(None, 9, 1, 3, 1, kc, 64, 0, p16, None), INVALID, name)
+        refused(fn(p16, 9, 1, 3, 1, kc, 64, 0, None, None), INVALID, name)
+        refused(fn(p16, 9, 1, 3, 1, kc + 4, 64, 0, p16, None), UNSUPPORTED, name)                     # cin % granularity
+        refused(fn(p16, 9, 1, 3, 1, kc, 48, 0, p16, None), UNSUPPORTED, name)                         # cout % 64
+        refused(fn(p16, 9, 1, 3, 1, 0, 64, 0, p16, None), UNSUPPORTED, name)
+        refused(fn(p16, 9, 1, 3, 1, kc, 64, 0, p8, None), INVALID, name)                              # packed alignment
+    refused(lib.iris_wino_b3_pack_weights_device(p16, 9, 1, 3, 1, 8, 64, 0, p16, None), UNSUPPORTED, "iris_wino_b3_pack_weights_device")
+
+    multi = "iris_wino_pack_weights_device_multi"
+
+    def jobs(*spec):
+        arr = (N.PackJob * len(spec))()
+        for k, (weight, packed, cin, cout) in enumerate(spec):
+            arr[k] = N.PackJob(weight, packed, 9, 1, 3, 1, cin, cout, 0, 0)
+        return C.cast(arr, C.c_void_p)
+
+    ok8, ok16 = (16, 16, 8, 64), (16, 16, 16, 64)
+    refused(lib.iris_wino_pack_weights_device_multi(None, 1, 0, None), INVALID, multi)
+    refused(lib.iris_wino_pack_weights_device_multi(jobs(ok8), 0, 0, None), INVALID, multi)                         # no jobs
+    for split, ok in ((0, ok8), (1, ok16)):   # every job is checked before the first launch: a bad second job refuses the call
+        refused(lib.iris_wino_pack_weights_device_multi(jobs(ok, (None, 16, 16, 64)), 2, split, None), INVALID, multi)
+        assert b"job 1" in lib.iris_last_error()
+        refused(lib.iris_wino_pack_weights_device_multi(jobs(ok, (16, None, 16, 64)), 2, split, None), INVALID, multi)
+        refused(lib.iris_wino_pack_weights_device_multi(jobs(ok, (16, 8, 16, 64)), 2, split, None), INVALID, multi)  # alignment
+        refused(lib.iris_wino_pack_weights_device_multi(jobs(ok, (16, 16, 16, 48)), 2, split, None), UNSUPPORTED, multi)
+    refused(lib.iris_wino_pack_weights_device_multi(jobs((16, 16, 12, 64)), 1, 0, None), UNSUPPORTED, multi)        # 8 | cin
+    refused(lib.iris_wino_pack_weights_device_multi(jobs((16, 16, 8, 64)), 1, 1, None), UNSUPPORTED, multi)         # 16 | cin
+    refused(lib.iris_wino_pack_weights_device_multi(jobs((16, 16, 24, 64)), 1, 1, None), UNSUPPORTED, multi)
+
+    c32 = "iris_conv3x3_c32"
+    refused(lib.iris_conv3x3_c32(None, p16, 288, 9, 3, 1, 0, p16, 1, 8, 8, None), INVALID, c32)
+    refused(lib.iris_conv3x3_c32(p16, None, 288, 9, 3, 1, 0, p16, 1, 8, 8, None), INVALID, c32)
+    refused(lib.iris_conv3x3_c32(p16, p16, 288, 9, 3, 1, 0, None, 1, 8, 8, None), INVALID, c32)
+    refused(lib.iris_conv3x3_c32(p16, p16, 288, 9, 3, 1, 1, p16, 0, 8, 8, None), INVALID, c32)          # empty
+    refused(lib.iris_conv3x3_c32(p16, p16, 288, 9, 3, 1, 0, p16, 1, 0, 8, None), INVALID, c32)
+    refused(lib.iris_conv3x3_c32(p8, p16, 288, 9, 3, 1, 0, p16, 1, 8, 8, None), INVALID, c32)           # alignment
+    refused(lib.iris_conv3x3_c32_bn(p16, p16, 288, 9, 3, 1, p16, 1, 8, 8, None, None), INVALID, "iris_conv3x3_c32_bn")
+    refused(lib.iris_conv3x3_c32_bn(None, p16, 288, 9, 3, 1, p16, 1, 8, 8, p16, None), INVALID, c32)
+    refused(lib.iris_conv3x3_c32_bn(p16, p16, 288, 9, 3, 1, p16, 1, 8, 0, p16, None), INVALID, c32)
+    refused(lib.iris_conv3x3_c32_bn(p8, p16, 288, 9, 3, 1, p16, 1, 8, 8, p16, None), INVALID, c32)
+    relu = "iris_conv3x3_c32_bias_relu"
+    refused(lib.iris_conv3x3_c32_bias_relu(p16, p16, None, p16, 1, 8, 8, 0, 0, None), INVALID, relu)   # NULL bias
+    refused(lib.iris_conv3x3_c32_bias_relu(p16, p16, p16, None, 1, 8, 8, 1, 1, None), INVALID, relu)
+    refused(lib.iris_conv3x3_c32_bias_relu(p16, p16, p16, p16, 1, 8, 0, 0, 1, None), INVALID, relu)
+
+    assert lib.iris_wino_b3_packed_len(16, 64) == 24 * 16 * 64 == 96 * 16 * 64 // 4
+    assert lib.iris_wino_b3_packed_len(0, 64) == 0 and lib.iris_wino_b3_packed_len(16, 0) == 0 and lib.iris_wino_b3_packed_len(-16, 64) == 0
+
+
 def test_product_code_refuses_cpu_tensors():
     import torch
     from challenge_amd import frontend as FE

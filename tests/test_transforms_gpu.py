@@ -1256,6 +1256,40 @@ def test_winograd_split_bf16_convolution_matches_fp64(dev, b, h, w, cin, cout):
         FE.wino_pack_weights_device(torch.zeros(64, 8, 3, 3, device=dev), split_bf16=True)   # 16 | cin
 
 
+def test_winograd_packings_shorter_than_the_kernel_reads_are_refused(dev):
+    """The two Winograd kernels read packings of different formats and sizes (16 vs 24 cin cout floats).  conv3x3_wino refuses a
+    `packed` shorter than wino_packed_len(cin, cout, split_bf16) - an fp32 packing given to the split-bf16 kernel among them - or
+    not a contiguous float32 tensor on x's device, and wino_pack_weights_device an `out` it would write past, before anything
+    launches.  (A split-bf16 packing given to the fp32 kernel is long enough: no size check can tell it apart.)"""
+    from challenge_amd import _native as N, frontend as FE
+    b, h, w, cin, cout = 2, 6, 20, 32, 64
+    x = torch.randn(b, cin, h, w, device=dev).contiguous(memory_format=torch.channels_last)
+    wt = torch.randn(cout, cin, 3, 3, device=dev) * 0.1
+    bias = torch.randn(cout, device=dev) * 0.1
+    bn_sums = torch.zeros(int(N.lib().iris_bn_sums_len(cout)), dtype=torch.float64, device=dev)
+    packed, packed3 = FE.wino_pack_weights_device(wt), FE.wino_pack_weights_device(wt, split_bf16=True)
+    with pytest.raises(ValueError):
+        FE.conv3x3_wino(x, packed, bias, cout, out_nhwc=True, split_bf16=True)                 # fp32 packing, split-bf16 kernel
+    for split, pk in ((False, packed), (True, packed3)):
+        n = FE.wino_packed_len(cin, cout, split)
+        assert pk.numel() == n
+        for bad in (pk[:-1], torch.empty(2 * n, device=dev)[::2], pk.double(), pk.cpu()):   # short, strided, float64, host
+            with pytest.raises(ValueError):
+                FE.conv3x3_wino(x, bad, bias, cout, out_nhwc=True, split_bf16=split)
+        with pytest.raises(ValueError):
+            FE.conv3x3_wino(x, pk[:-1], None, cout, out_nhwc=True, relu=False, split_bf16=split, bn_sums=bn_sums)
+        for out in (torch.empty(n - 1, device=dev), torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n)):
+            with pytest.raises(ValueError):
+                FE.wino_pack_weights_device(wt, out=out, split_bf16=split)
+        # what the kernels get today still runs: an exact or longer `out`, a full packing
+        out = torch.full((n + 64,), -1.0, device=dev)
+        assert FE.wino_pack_weights_device(wt, out=out, split_bf16=split) is out
+        assert torch.equal(out[:n], pk) and bool((out[n:] == -1.0).all())
+        y = FE.conv3x3_wino(x, out, bias, cout, out_nhwc=True, split_bf16=split)
+        assert torch.equal(y, FE.conv3x3_wino(x, pk, bias, cout, out_nhwc=True, split_bf16=split))
+    torch.cuda.synchronize(dev)
+
+
 @pytest.mark.parametrize("b,h,w,cin,cout", [(4, 8, 64, 128, 256), (2, 4, 32, 512, 512), (3, 5, 9, 64, 128), (2, 6, 10, 32, 64)])
 def test_winograd_split_bf16_training_convolution_matches_torch(dev, b, h, w, cin, cout, monkeypatch):
     """sj_train._WinoConv3x3 with IRIS_WINO_SPLIT_BF16 on: forward and backward-data through the BF16-matrix-core kernel (weights
