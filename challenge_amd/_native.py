@@ -54,6 +54,8 @@ SIGNATURES = {
     "iris_magmel": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     "iris_minmax_log_workspace": (_sz, [_i, _sz]),
     "iris_minmax_log": (_i, [_vp, _i, _sz, _i, _i, _f, _f, _vp, _sz, _vp]),
+    "iris_pcen": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _f, _f, _f, _vp]),
+    "iris_pcen_smoother": (_i, [_vp, _vp, _i, _i, _i, _f, _vp]),
     "iris_wav_to_logmel": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     "iris_mask_apply": (_i, [_vp, _sz, _sz, _sz, _i, _vp, _i, _sz, _vp]),
     "iris_agc_clip": (_i, [_vp, _sz, _f, _f, _f, _vp]),

@@ -25,6 +25,7 @@
 //   k_conv_wino_wrw.h  the same layers' weight gradient as Winograd F(2x2, 3x3) on the fp32 matrix cores (training)
 //   k_metrics.h      the training metrics er_score / cos_sim / F1 counts of a batch in one launch
 //   k_detect.h       window predictions of many files -> smoothed, thresholded event lists (two launches)
+//   k_pcen.h         per-channel energy normalisation: a chunked scan of the IIR smoother along time, then the compression
 //   host_plan.h      mel matrix, constant tables, plan create / destroy
 //   host_ops.h       the operators' C-ABI entry points
 #include "common.h"
@@ -50,3 +51,4 @@
 #include "k_agc_adam.h"
 #include "k_metrics.h"
 #include "k_detect.h"
+#include "k_pcen.h"

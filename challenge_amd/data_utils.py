@@ -108,6 +108,30 @@ def minmax_log_on_mel(mel: torch.Tensor, labels=None):
     return mel
 
 
+def pcen_on_mel(mel: torch.Tensor, labels=None, **params):
+    """Per-channel energy normalisation (`frontend.pcen`, one HIP launch) in place of min-max + log, with the calling
+    convention of `minmax_log_on_mel` (it drops into `Dataset.map`); `params` are `frontend.pcen`'s (smooth, gain, bias,
+    power, eps, time_axis).  PCEN runs along time over whatever the tensor holds, so where it is applied matters:
+    training applies it per clip of n_frame (512) frames - the smoother starts afresh on every clip - while evaluation
+    (`inference.features_for_eval`) applies it over the whole recording before it is cut into windows, as the reference
+    does with min-max.  A window seen in evaluation therefore carries the smoother state of the audio before it; the
+    same window seen in training does not."""
+    mel = _fe.pcen(mel, **params)
+    if labels is not None:
+        return mel, labels
+    return mel
+
+
+def feature_compression(name: str) -> str:
+    """The compression a run name selects, by the tokens in it (the reference's idiom for 'filter' / 'nominmax'):
+    'pcen' (pcen_on_mel), 'log' ('nominmax': log_on_mel alone) or 'minmax_log' (the default).  A name holding both
+    'pcen' and 'nominmax' is refused: PCEN replaces the whole min-max / log stage."""
+    pcen, nominmax = 'pcen' in name, 'nominmax' in name
+    if pcen and nominmax:
+        raise ValueError(f"run name {name!r} asks for both 'pcen' and 'nominmax': PCEN replaces min-max + log, name one")
+    return 'pcen' if pcen else ('log' if nominmax else 'minmax_log')
+
+
 def augment(specs: torch.Tensor, labels, time_axis: int = -2, freq_axis: int = -3):
     """6 time masks (< 24 frames) then 1 frequency mask (< 16 linear bins) on the complex
     spectrogram (data_utils.py:58-61)."""

@@ -825,6 +825,69 @@ def minmax_log(x: torch.Tensor, do_minmax: bool = True, do_log: bool = True, eps
     return x
 
 
+# PCEN defaults (librosa.pcen's): time constant 0.4 s, gain a, bias d, power r, eps
+PCEN_TIME_CONSTANT, PCEN_GAIN, PCEN_BIAS, PCEN_POWER, PCEN_EPS = 0.4, 0.98, 2.0, 0.5, 1e-6
+
+
+def pcen_smooth(time_constant_s: float = PCEN_TIME_CONSTANT, sr: int = 16000, hop: int = 256) -> float:
+    """The smoother coefficient s of a time constant, as librosa.pcen derives it: T = time_constant_s * sr / hop frames,
+    s = (sqrt(1 + 4 T^2) - 1) / (2 T^2)."""
+    t = float(time_constant_s) * float(sr) / float(hop)
+    if not (np.isfinite(t) and t > 0):
+        raise ValueError(f"pcen_smooth: the time constant must give a positive number of frames, got {t}")
+    return float((np.sqrt(1.0 + 4.0 * t * t) - 1.0) / (2.0 * t * t))
+
+
+def _pcen_view(x: torch.Tensor, time_axis: int, out: Optional[torch.Tensor], who: str):
+    x = _require_device_f32(x, "x")
+    if x.dim() < 1:
+        raise ValueError(f"{who}: x must have a time axis")
+    ax = time_axis % x.dim() if -x.dim() <= time_axis < x.dim() else None
+    if ax is None:
+        raise ValueError(f"{who}: time_axis {time_axis} is out of range for a {x.dim()}-d tensor")
+    if out is None:
+        out = torch.empty_like(x)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+              and tuple(out.shape) == tuple(x.shape) and out.device == x.device):
+        raise ValueError(f"{who}: out must be a contiguous float32 tensor of shape {tuple(x.shape)} on {x.device}")
+    shape = tuple(int(v) for v in x.shape)
+    n_rows = int(np.prod(shape[:ax], dtype=np.int64))
+    n_inner = int(np.prod(shape[ax + 1:], dtype=np.int64))
+    return x, out, n_rows, shape[ax], n_inner
+
+
+def pcen(x: torch.Tensor, smooth: Optional[float] = None, gain: float = PCEN_GAIN, bias: float = PCEN_BIAS,
+         power: float = PCEN_POWER, eps: float = PCEN_EPS, time_axis: int = -2,
+         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per-channel energy normalisation of mel magnitudes x >= 0 along `time_axis` (iris_pcen, one HIP launch): every
+    sequence along time, i.e. every (clip, mel, channel) of a batched [B, M, T, C] or (mel, channel) of an unbatched
+    [M, T, C] tensor, runs
+        M[0] = E[0],  M[t] = (1 - s) M[t-1] + s E[t],  out = (E / (eps + M)^gain + bias)^power - bias^power
+    (evaluated as bias^power expm1(power log1p(...))).  smooth = s, default `pcen_smooth()` (0.4 s at 16 kHz, hop 256);
+    the other defaults are librosa's.  Zeros stay exactly 0; a NaN propagates forward in time.  Returns a new tensor, or
+    writes into `out` (which may be `x` itself: in place).  Out-of-range parameters raise ValueError."""
+    x, out, n_rows, n_time, n_inner = _pcen_view(x, time_axis, out, "pcen")
+    s = pcen_smooth() if smooth is None else float(smooth)
+    if x.numel():
+        with torch.cuda.device(x.device):
+            rc = N.lib().iris_pcen(x.data_ptr(), out.data_ptr(), n_rows, n_time, n_inner, s, float(gain), float(bias),
+                                   float(power), float(eps), _stream_ptr(x.device))
+        N.check(rc, "iris_pcen")
+    return out
+
+
+def pcen_smoother(x: torch.Tensor, smooth: Optional[float] = None, time_axis: int = -2,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The smoother M of `pcen` itself (iris_pcen_smoother): M[0] = E[0], M[t] = (1 - s) M[t-1] + s E[t] along time_axis."""
+    x, out, n_rows, n_time, n_inner = _pcen_view(x, time_axis, out, "pcen_smoother")
+    s = pcen_smooth() if smooth is None else float(smooth)
+    if x.numel():
+        with torch.cuda.device(x.device):
+            rc = N.lib().iris_pcen_smoother(x.data_ptr(), out.data_ptr(), n_rows, n_time, n_inner, s, _stream_ptr(x.device))
+        N.check(rc, "iris_pcen_smoother")
+    return out
+
+
 def complex_to_magphase(x: torch.Tensor) -> torch.Tensor:
     x = _require_device_f32(x, "complex_tensor")
     c2 = int(x.shape[-1])

@@ -629,13 +629,13 @@ class InferenceEngine:
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):  # warm-up: MIOpen find, geometry caches, allocator
             for _ in range(3):
-                feats = fe.plan.wav_to_logmel(self.wav, minmax=fe.do_minmax, log=True, t_bands=self._tb, f_bands=self._fb)
+                feats = fe.features(self.wav, self._tb, self._fb)
                 self.model(feats)
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-            feats = fe.plan.wav_to_logmel(self.wav, minmax=fe.do_minmax, log=True, t_bands=self._tb, f_bands=self._fb)
+            feats = fe.features(self.wav, self._tb, self._fb)
             self.out = self.model(feats)
 
     @torch.no_grad()

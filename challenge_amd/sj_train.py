@@ -182,8 +182,11 @@ def _load_sources(config, training, n_classes, sources):
 
 
 def _label_tail(pipeline, config):
-    """The stages after the mel features (sj_train.py:121-129)."""
-    if 'nominmax' not in config.name:
+    """The stages after the mel features (sj_train.py:121-129); a 'pcen' run name maps PCEN instead of min-max + log."""
+    compression = _du.feature_compression(config.name)
+    if compression == 'pcen':
+        pipeline = pipeline.map(_du.pcen_on_mel)
+    elif compression == 'minmax_log':
         pipeline = pipeline.map(_du.minmax_log_on_mel)  # :121-123 fused
     else:
         pipeline = pipeline.map(log_on_mel)
@@ -325,6 +328,7 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
     length = (config.n_frame - 1) * hop
     plan = _fe.FrontendPlan(n_fft, hop, config.n_mels, sample_rate, config.n_chan, config.batch_size, length, mixer.device)
     filter_bins = int(round(200 / (16000 / 256))) if 'filter' in config.name else 0
+    do_pcen = _du.feature_compression(config.name) == 'pcen'
     do_minmax = 'nominmax' not in config.name
     band_draw = None
     if device_draw:
@@ -346,7 +350,11 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
             if filter_bins and band_draw is None:
                 flt = np.tile(np.array([[[1, filter_bins]]], np.int32), (b, 1, 1))
                 fb = flt if fb is None else np.concatenate([fb, flt], axis=1)
-            yield plan.wav_to_logmel(wav.contiguous(), t_bands=tb, f_bands=fb, minmax=do_minmax, log=True), y
+            if do_pcen:   # the raw mel out of the fused kernel, then PCEN in place
+                mel = plan.wav_to_logmel(wav.contiguous(), t_bands=tb, f_bands=fb, minmax=False, log=False)
+                yield _fe.pcen(mel, out=mel), y
+            else:
+                yield plan.wav_to_logmel(wav.contiguous(), t_bands=tb, f_bands=fb, minmax=do_minmax, log=True), y
 
     pipeline = Dataset.from_generator(gen)
     if config.v in label_downsample_model:
@@ -362,11 +370,18 @@ class WaveFrontend:
     """MI355X-native on-line variant of the chain: waveforms [B, C, L] on the device ->
     SpecAugment bands drawn per sample -> fused HIP kernel (STFT, magnitude, masks, mel,
     min-max, log) -> [B, M, T, C].  Equivalent to load_wav + augment + complex_to_magphase
-    + magphase_to_mel + minmax + log_on_mel without materialising the spectrum."""
+    + magphase_to_mel + minmax + log_on_mel without materialising the spectrum.
+    compression='pcen': the fused kernel stops at the mel magnitudes and `frontend.pcen` follows in place (a second
+    launch) instead of min-max + log."""
 
     def __init__(self, n_fft=1024, hop=256, n_mels=64, sample_rate=16000, n_chan=1, batch=64, length=130816,
                  device=None, training=True, filter_bins: int = 0, do_minmax: bool = True,
-                 device_draw: bool = False, seed: int = 0):
+                 device_draw: bool = False, seed: int = 0, compression: str = 'log'):
+        if compression not in ('log', 'pcen'):
+            raise ValueError(f"WaveFrontend: compression must be 'log' or 'pcen', got {compression!r}")
+        if compression == 'pcen' and not do_minmax:
+            raise ValueError("WaveFrontend: compression='pcen' replaces min-max + log; do_minmax=False does not apply")
+        self.compression = compression
         self.plan = _fe.FrontendPlan(n_fft, hop, n_mels, sample_rate, n_chan, batch, length, device)
         self.training, self.filter_bins, self.do_minmax = training, filter_bins, do_minmax
         self.device_draw = device_draw
@@ -399,7 +414,15 @@ class WaveFrontend:
             else:
                 flt = np.tile(np.array([[[1, self.filter_bins]]], np.int32), (b, 1, 1))
                 fb = flt if fb is None else np.concatenate([fb, flt], axis=1)
-        return self.plan.wav_to_logmel(wav, minmax=self.do_minmax, log=True, t_bands=tb, f_bands=fb, out=out)
+        return self.features(wav, tb, fb, out=out)
+
+    def features(self, wav: torch.Tensor, t_bands=None, f_bands=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The features of `wav` with the given bands (no draws): the fused kernel with min-max + log, or with
+        compression='pcen' the raw mel followed by PCEN in place.  Capturable into a hipGraph either way."""
+        if self.compression == 'pcen':
+            mel = self.plan.wav_to_logmel(wav, minmax=False, log=False, t_bands=t_bands, f_bands=f_bands, out=out)
+            return _fe.pcen(mel, out=mel)
+        return self.plan.wav_to_logmel(wav, minmax=self.do_minmax, log=True, t_bands=t_bands, f_bands=f_bands, out=out)
 
 
 # ---------------------------------------------------------------------------

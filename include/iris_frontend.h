@@ -238,6 +238,22 @@ int iris_minmax_log(float* x, int n_rows, size_t row_len, int do_minmax, int do_
                     float eps_log, float* workspace, size_t workspace_floats, void* stream);
 
 /*
+ * Per-channel energy normalisation (PCEN; Wang et al. 2017, Lostanlen et al. 2019), an opt-in alternative to
+ * min-max + log.  mel >= 0 viewed as [n_rows, n_time, n_inner] (a row's n_time * n_inner floats contiguous): the batched
+ * [B, M, T, C] tensor is n_rows = B M, the unbatched [M, T, C] one n_rows = M.  Per (row, inner) sequence, along time:
+ *     M[0] = E[0],  M[t] = (1 - s) M[t-1] + s E[t]
+ *     out  = d^r expm1(r log1p(E exp(-a (log eps + log1p(M / eps))) / d))   = (E / (eps + M)^a + d)^r - d^r
+ * with s = smooth, a = gain, d = bias, r = power.  Accepted: 0 < s <= 1, a >= 0, d > 0, 0 < r <= 1, eps > 0, all finite
+ * (IRIS_E_INVALID otherwise, checked before any HIP call).  E == 0 gives exactly 0; a NaN propagates forward in time
+ * along its sequence only.  out == mel (in place) is allowed, any other overlap is refused.  Any n_time (no length cap),
+ * n_inner up to 65535 * 256.  One launch, no workspace, deterministic (the same inputs give the same bits), capturable.
+ * iris_pcen_smoother writes the smoother M itself.  Runs on the current HIP device.
+ */
+int iris_pcen(const float* mel, float* out, int n_rows, int n_time, int n_inner, float smooth, float gain, float bias,
+              float power, float eps, void* stream);
+int iris_pcen_smoother(const float* mel, float* m_out, int n_rows, int n_time, int n_inner, float smooth, void* stream);
+
+/*
  * The fused hot path: [normalize ->] STFT -> magnitude -> band masks -> mel
  * [-> min-max] [-> log] without materialising the spectrum
  * (load_wav data_utils.py:22-23 + sj_train.py:108-123).  flags = IRIS_F_*.
