@@ -56,6 +56,9 @@ SIGNATURES = {
     "iris_minmax_log": (_i, [_vp, _i, _sz, _i, _i, _f, _f, _vp, _sz, _vp]),
     "iris_pcen": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _f, _f, _f, _vp]),
     "iris_pcen_smoother": (_i, [_vp, _vp, _i, _i, _i, _f, _vp]),
+    "iris_pcen_banded": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _f, _vp]),
+    "iris_pcen_banded_grad_workspace": (_sz, [_i, _i, _i]),
+    "iris_pcen_banded_grad": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _f, _vp, _vp, _sz, _vp]),
     "iris_wav_to_logmel": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     "iris_mask_apply": (_i, [_vp, _sz, _sz, _sz, _i, _vp, _i, _sz, _vp]),
     "iris_agc_clip": (_i, [_vp, _sz, _f, _f, _f, _vp]),
@@ -92,6 +95,7 @@ SIGNATURES = {
     "iris_conv0_stats": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "iris_conv0_bn_relu": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     "iris_conv0_bn_relu_backward": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "iris_conv0_bn_relu_backward_dx": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "iris_conv3x3_small_bias_relu_nhwc": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "iris_conv3x3_small_bias_relu_nchw": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "iris_bilstm128_forward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),

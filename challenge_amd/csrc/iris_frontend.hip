@@ -26,6 +26,8 @@
 //   k_metrics.h      the training metrics er_score / cos_sim / F1 counts of a batch in one launch
 //   k_detect.h       window predictions of many files -> smoothed, thresholded event lists (two launches)
 //   k_pcen.h         per-channel energy normalisation: a chunked scan of the IIR smoother along time, then the compression
+//                    (host scalars, or per-band parameters from a device array: the trainable layer's forward)
+//   k_pcen_grad.h    the trainable layer's backward: gradient with respect to the per-band parameters, two launches, no atomics
 //   host_plan.h      mel matrix, constant tables, plan create / destroy
 //   host_ops.h       the operators' C-ABI entry points
 #include "common.h"
@@ -52,3 +54,4 @@
 #include "k_metrics.h"
 #include "k_detect.h"
 #include "k_pcen.h"
+#include "k_pcen_grad.h"

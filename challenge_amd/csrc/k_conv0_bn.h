@@ -194,11 +194,13 @@ __global__ __launch_bounds__(256) void k_conv0_bias_relu(const float* __restrict
 }
 
 // DW = false: sums[0][c] += g, sums[1][c] += g xhat.   DW = true: dw[co][ci][tap] += dz * tap (fp64 staging buffer).
-template <int CIN, bool DW>
+// DZ (with DW): dz is also written out, channels-last like dy, for the input gradient (k_conv0_dx) of a model whose first
+// stage is trainable (the PCEN layer of a 'pcen_learn' run); the instantiations without it are unchanged.
+template <int CIN, bool DW, bool DZ = false>
 __global__ __launch_bounds__(256) void k_conv0_bwd(const float* __restrict__ x, const float* __restrict__ w,
                                                    const float* __restrict__ dy, int B, int H, int W, int C4, float inv_m,
                                                    const float* mean, const float* rstd, const float* gamma, const float* beta,
-                                                   double* sums, double* dw, float* dgamma, float* dbeta) {
+                                                   double* sums, double* dw, float* dgamma, float* dbeta, float* dz_out = nullptr) {
     extern __shared__ float c0mem[];
     const int C = 4 * C4;
     const int tys = 256 / C4, tx = threadIdx.x % C4, ty = threadIdx.x / C4;
@@ -238,6 +240,7 @@ __global__ __launch_bounds__(256) void k_conv0_bwd(const float* __restrict__ x, 
             float z[4];
             conv0_z<CIN>(t, wreg, z);
             const float dd[4] = {d.x, d.y, d.z, d.w};
+            [[maybe_unused]] float dzv[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const float g = fmaf(z[k], a[k], hq[k]) > 0.f ? dd[k] : 0.f;
@@ -246,12 +249,15 @@ __global__ __launch_bounds__(256) void k_conv0_bwd(const float* __restrict__ x, 
                     part[4 + k] = fmaf(g, (z[k] - mu[k]) * rs[k], part[4 + k]);
                 } else {
                     const float dz = fmaf(a[k], g, fmaf(bq[k], z[k], dq[k]));
+                    if constexpr (DZ) dzv[k] = dz;
 #pragma unroll
                     for (int c = 0; c < CIN; ++c)
 #pragma unroll
                         for (int q = 0; q < 9; ++q) part[(k * CIN + c) * 9 + q] = fmaf(dz, t.v[c][q], part[(k * CIN + c) * 9 + q]);
                 }
             }
+            if constexpr (DW && DZ)
+                reinterpret_cast<float4*>(dz_out)[((size_t)row * W + wq) * C4 + tx] = make_float4(dzv[0], dzv[1], dzv[2], dzv[3]);
         }
     }
     if constexpr (!DW) {
@@ -263,6 +269,50 @@ __global__ __launch_bounds__(256) void k_conv0_bwd(const float* __restrict__ x, 
         // (kConv0DwSlots copies of dw, block % copies: the caller adds them up)
         conv0_block_reduce<NVAL>(part, c0mem, tx, ty, C4, tys, dw + (size_t)(blockIdx.x % kConv0DwSlots) * C * CIN * 9,
                                  [=](int g, int j) { return (size_t)g * 4 * CIN * 9 + j; });
+    }
+}
+
+// The layer's input gradient from dz [B, H, W, C] (channels-last, written by k_conv0_bwd<CIN, true, true>):
+//     dx[b][ci][h][w] = sum over (co, ky, kx) of weight[co][ci][ky][kx] dz[b][h + 1 - ky][w + 1 - kx][co]
+// A gather, one thread per pixel, every sum in a fixed order (no atomics: the same inputs give the same bits).  The weights sit in
+// LDS as [tap][ci][co] (all lanes read the same address: a broadcast); a thread reads the C contiguous floats of each of its nine
+// neighbouring dz pixels as float4s, neighbouring threads neighbouring pixels.
+template <int CIN>
+__global__ __launch_bounds__(256) void k_conv0_dx(const float* __restrict__ dz, const float* __restrict__ w, float* __restrict__ dx,
+                                                  int B, int H, int W, int C) {
+    extern __shared__ float c0mem[];   // [9][CIN][C]
+    for (int i = threadIdx.x; i < C * CIN * 9; i += 256) {
+        const int co = i / (CIN * 9), ci = (i / 9) % CIN, q = i % 9;   // weight [C][CIN][3][3]
+        c0mem[(q * CIN + ci) * C + co] = w[i];
+    }
+    __syncthreads();
+    const size_t n_pix = (size_t)B * H * W;
+    for (size_t pix = (size_t)blockIdx.x * 256 + threadIdx.x; pix < n_pix; pix += (size_t)gridDim.x * 256) {
+        const int wq = (int)(pix % W), h = (int)((pix / W) % H);
+        const size_t b = pix / ((size_t)W * H);
+        float acc[CIN];
+#pragma unroll
+        for (int ci = 0; ci < CIN; ++ci) acc[ci] = 0.f;
+        for (int ky = 0; ky < 3; ++ky) {
+            const int hh = h + 1 - ky;
+            if (hh < 0 || hh >= H) continue;
+            for (int kx = 0; kx < 3; ++kx) {
+                const int ww = wq + 1 - kx;
+                if (ww < 0 || ww >= W) continue;
+                const float4* src = reinterpret_cast<const float4*>(dz + ((b * H + hh) * W + ww) * C);
+                const float* wl = c0mem + (size_t)(ky * 3 + kx) * CIN * C;
+                for (int c4 = 0; c4 < C / 4; ++c4) {
+                    const float4 v = src[c4];
+#pragma unroll
+                    for (int ci = 0; ci < CIN; ++ci) {
+                        const float* wc = wl + ci * C + 4 * c4;
+                        acc[ci] = fmaf(v.x, wc[0], fmaf(v.y, wc[1], fmaf(v.z, wc[2], fmaf(v.w, wc[3], acc[ci]))));
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int ci = 0; ci < CIN; ++ci) dx[((b * CIN + ci) * H + h) * W + wq] = acc[ci];
     }
 }
 
@@ -339,14 +389,17 @@ extern "C" int iris_conv0_bn_relu(const float* x, const float* weight, float* y,
     return IRIS_OK;
 }
 
-extern "C" int iris_conv0_bn_relu_backward(const float* x, const float* weight, const float* dy, int batch, int in_channels,
-                                           int out_channels, int height, int width, const float* save_mean, const float* save_rstd,
-                                           const float* gamma, const float* beta, double* sums_zeroed, double* dweight_zeroed,
-                                           float* dgamma, float* dbeta, void* stream) {
-    int rc = conv0_check(x, weight, batch, in_channels, out_channels, height, width, "iris_conv0_bn_relu_backward");
+template <bool DZ>
+static int conv0_backward(const char* who, const float* x, const float* weight, const float* dy, int batch, int in_channels,
+                          int out_channels, int height, int width, const float* save_mean, const float* save_rstd,
+                          const float* gamma, const float* beta, double* sums_zeroed, double* dweight_zeroed, float* dgamma,
+                          float* dbeta, float* dz, float* dx, void* stream) {
+    int rc = conv0_check(x, weight, batch, in_channels, out_channels, height, width, who);
     if (rc) return rc;
     if (!dy || !save_mean || !save_rstd || !gamma || !beta || !sums_zeroed || !dweight_zeroed || !dgamma || !dbeta)
-        return fail(IRIS_E_INVALID, "iris_conv0_bn_relu_backward: NULL argument");
+        return fail(IRIS_E_INVALID, "%s: NULL argument", who);
+    if (DZ && (!dz || !dx)) return fail(IRIS_E_INVALID, "%s: %s is NULL", who, !dz ? "dz_scratch" : "dx");
+    if (DZ && (reinterpret_cast<uintptr_t>(dz) & 15)) return fail(IRIS_E_INVALID, "%s: dz_scratch must be 16-byte aligned", who);
     const int C4 = out_channels / 4;
     const size_t n_pix = (size_t)batch * height * width;
     const unsigned grid = (unsigned)std::min<size_t>((size_t)batch * height, 1024);  // blocks walk image rows
@@ -357,14 +410,36 @@ extern "C" int iris_conv0_bn_relu_backward(const float* x, const float* weight, 
     if (in_channels == 1) {
         k_conv0_bwd<1, false><<<grid, 256, lds_r, s>>>(x, weight, dy, batch, height, width, C4, inv_m, save_mean, save_rstd, gamma, beta,
                                                      sums_zeroed, nullptr, nullptr, nullptr);
-        k_conv0_bwd<1, true><<<grid, 256, lds_w, s>>>(x, weight, dy, batch, height, width, C4, inv_m, save_mean, save_rstd, gamma, beta,
-                                                    sums_zeroed, dweight_zeroed, dgamma, dbeta);
+        k_conv0_bwd<1, true, DZ><<<grid, 256, lds_w, s>>>(x, weight, dy, batch, height, width, C4, inv_m, save_mean, save_rstd, gamma, beta,
+                                                        sums_zeroed, dweight_zeroed, dgamma, dbeta, dz);
     } else {
         k_conv0_bwd<2, false><<<grid, 256, lds_r, s>>>(x, weight, dy, batch, height, width, C4, inv_m, save_mean, save_rstd, gamma, beta,
                                                      sums_zeroed, nullptr, nullptr, nullptr);
-        k_conv0_bwd<2, true><<<grid, 256, lds_w, s>>>(x, weight, dy, batch, height, width, C4, inv_m, save_mean, save_rstd, gamma, beta,
-                                                    sums_zeroed, dweight_zeroed, dgamma, dbeta);
+        k_conv0_bwd<2, true, DZ><<<grid, 256, lds_w, s>>>(x, weight, dy, batch, height, width, C4, inv_m, save_mean, save_rstd, gamma, beta,
+                                                        sums_zeroed, dweight_zeroed, dgamma, dbeta, dz);
+    }
+    if (DZ) {
+        const unsigned gx = (unsigned)std::min<size_t>((n_pix + 255) / 256, 8192);
+        const size_t lds_x = (size_t)9 * in_channels * out_channels * sizeof(float);
+        if (in_channels == 1) k_conv0_dx<1><<<gx, 256, lds_x, s>>>(dz, weight, dx, batch, height, width, out_channels);
+        else k_conv0_dx<2><<<gx, 256, lds_x, s>>>(dz, weight, dx, batch, height, width, out_channels);
     }
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
+}
+
+extern "C" int iris_conv0_bn_relu_backward(const float* x, const float* weight, const float* dy, int batch, int in_channels,
+                                           int out_channels, int height, int width, const float* save_mean, const float* save_rstd,
+                                           const float* gamma, const float* beta, double* sums_zeroed, double* dweight_zeroed,
+                                           float* dgamma, float* dbeta, void* stream) {
+    return conv0_backward<false>("iris_conv0_bn_relu_backward", x, weight, dy, batch, in_channels, out_channels, height, width,
+                                 save_mean, save_rstd, gamma, beta, sums_zeroed, dweight_zeroed, dgamma, dbeta, nullptr, nullptr, stream);
+}
+
+extern "C" int iris_conv0_bn_relu_backward_dx(const float* x, const float* weight, const float* dy, int batch, int in_channels,
+                                              int out_channels, int height, int width, const float* save_mean, const float* save_rstd,
+                                              const float* gamma, const float* beta, double* sums_zeroed, double* dweight_zeroed,
+                                              float* dgamma, float* dbeta, float* dz_scratch, float* dx, void* stream) {
+    return conv0_backward<true>("iris_conv0_bn_relu_backward_dx", x, weight, dy, batch, in_channels, out_channels, height, width,
+                                save_mean, save_rstd, gamma, beta, sums_zeroed, dweight_zeroed, dgamma, dbeta, dz_scratch, dx, stream);
 }

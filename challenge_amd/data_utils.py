@@ -124,11 +124,14 @@ def pcen_on_mel(mel: torch.Tensor, labels=None, **params):
 
 def feature_compression(name: str) -> str:
     """The compression a run name selects, by the tokens in it (the reference's idiom for 'filter' / 'nominmax'):
-    'pcen' (pcen_on_mel), 'log' ('nominmax': log_on_mel alone) or 'minmax_log' (the default).  A name holding both
-    'pcen' and 'nominmax' is refused: PCEN replaces the whole min-max / log stage."""
+    'pcen_learn' (no compression stage: the datasets yield raw mel magnitudes and the model's own trainable `model.PCEN`
+    layer follows), 'pcen' (pcen_on_mel, fixed parameters), 'log' ('nominmax': log_on_mel alone) or 'minmax_log' (the
+    default).  A name holding both 'pcen' and 'nominmax' is refused: PCEN replaces the whole min-max / log stage."""
     pcen, nominmax = 'pcen' in name, 'nominmax' in name
     if pcen and nominmax:
         raise ValueError(f"run name {name!r} asks for both 'pcen' and 'nominmax': PCEN replaces min-max + log, name one")
+    if 'pcen_learn' in name:
+        return 'pcen_learn'
     return 'pcen' if pcen else ('log' if nominmax else 'minmax_log')
 
 

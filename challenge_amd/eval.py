@@ -28,9 +28,13 @@ def second2frame(seconds: list, frame_num, resolution):
 
 
 def parse_name(config):
-    """eval.py:51-62: the run name's fields -> model_type / model / v / n_mels / n_chan / n_frame."""
+    """eval.py:51-62: the run name's fields -> model_type / model / v / n_mels / n_chan / n_frame.  The reference drops one
+    leading token in front of the model field; here every one is dropped, so a --name with an underscore of its own
+    ('pcen_learn', 'filter_pcen') round-trips through `fit.run_name` too (such names raised before; names with one leading
+    token or none parse as they did).  As in the reference, a --name token that itself starts with 'B' or 'v' is taken for the
+    model field: keep such tokens out of --name."""
     parsed = config.name.split('_')
-    if parsed[0][0] not in ('B', 'v'):
+    while len(parsed) > 1 and parsed[0][:1] not in ('B', 'v'):
         parsed = parsed[1:]
     if parsed[0] == 'vad':
         config.model_type = 'vad'

@@ -888,6 +888,59 @@ def pcen_smoother(x: torch.Tensor, smooth: Optional[float] = None, time_axis: in
     return out
 
 
+def _pcen_banded_view(x: torch.Tensor, params: torch.Tensor, time_axis: int, out: Optional[torch.Tensor], who: str):
+    """`_pcen_view` plus the band axis: the axis in front of `time_axis` holds the bands, params is [4, n_bands]."""
+    x, out, n_rows, n_time, n_inner = _pcen_view(x, time_axis, out, who)
+    ax = time_axis % x.dim()
+    if ax < 1:
+        raise ValueError(f"{who}: x needs a band axis in front of the time axis (got time_axis {time_axis} of a {x.dim()}-d tensor)")
+    n_bands = int(x.shape[ax - 1])
+    if not (isinstance(params, torch.Tensor) and params.is_cuda and params.device == x.device and params.dtype == torch.float32
+            and params.is_contiguous() and tuple(params.shape) == (4, n_bands)):
+        raise ValueError(f"{who}: params must be a contiguous float32 tensor of shape (4, {n_bands}) on {x.device} "
+                         "(rows: smooth s, gain a, bias d, power r)")
+    return x, out, n_rows, n_time, n_inner, n_bands
+
+
+def pcen_banded(x: torch.Tensor, params: torch.Tensor, eps: float = PCEN_EPS, time_axis: int = -2,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`pcen` with its own parameters for every band (iris_pcen_banded, one HIP launch): the axis in front of `time_axis`
+    is the band axis (M of a batched [B, M, T, C] or an unbatched [M, T, C] tensor) and `params` [4, n_bands] holds the
+    effective s (0 < s <= 1), a (>= 0), d (> 0), r (0 < r <= 1) of each band on the device.  Their ranges are the caller's
+    to keep (`model.PCEN` does by construction): they cannot be checked without a host synchronisation.  Zero / NaN
+    semantics, `out` and in place as `pcen`."""
+    x, out, n_rows, n_time, n_inner, n_bands = _pcen_banded_view(x, params, time_axis, out, "pcen_banded")
+    if x.numel():
+        with torch.cuda.device(x.device):
+            rc = N.lib().iris_pcen_banded(x.data_ptr(), out.data_ptr(), n_rows, n_time, n_inner, params.data_ptr(), n_bands,
+                                          float(eps), _stream_ptr(x.device))
+        N.check(rc, "iris_pcen_banded")
+    return out
+
+
+def pcen_banded_grad(x: torch.Tensor, dout: torch.Tensor, params: torch.Tensor, eps: float = PCEN_EPS,
+                     time_axis: int = -2) -> torch.Tensor:
+    """Gradient [4, n_bands] of a scalar loss with respect to `pcen_banded`'s effective parameters, given the loss's
+    gradient `dout` with respect to its output (iris_pcen_banded_grad: two HIP launches, no atomics, bitwise reproducible).
+    The smoother is recomputed from x; x is data, so no gradient with respect to it exists."""
+    x = _require_device_f32(x, "x")
+    x, _, n_rows, n_time, n_inner, n_bands = _pcen_banded_view(x, params, time_axis, x, "pcen_banded_grad")  # (no output tensor)
+    if not (isinstance(dout, torch.Tensor) and dout.is_cuda and dout.device == x.device and dout.dtype == torch.float32
+            and tuple(dout.shape) == tuple(x.shape)):
+        raise ValueError(f"pcen_banded_grad: dout must be a float32 tensor of shape {tuple(x.shape)} on {x.device}")
+    dout = dout.contiguous()
+    dparams = (torch.empty if x.numel() else torch.zeros)((4, n_bands), dtype=torch.float32, device=x.device)
+    if x.numel():
+        lib = N.lib()
+        ws = torch.empty(max(int(lib.iris_pcen_banded_grad_workspace(n_rows, n_time, n_inner)), 1), dtype=torch.float32,
+                         device=x.device)
+        with torch.cuda.device(x.device):
+            rc = lib.iris_pcen_banded_grad(x.data_ptr(), dout.data_ptr(), n_rows, n_time, n_inner, params.data_ptr(), n_bands,
+                                           float(eps), dparams.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(x.device))
+        N.check(rc, "iris_pcen_banded_grad")
+    return dparams
+
+
 def complex_to_magphase(x: torch.Tensor) -> torch.Tensor:
     x = _require_device_f32(x, "complex_tensor")
     c2 = int(x.shape[-1])

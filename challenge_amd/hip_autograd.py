@@ -442,7 +442,9 @@ class _FusedBiasBNReLU(torch.autograd.Function):
 class _FusedConv0BNReLU(torch.autograd.Function):
     """relu(batch_norm(conv2d(x, w) + conv_bias)) for the model's FIRST layer (1 or 2 input channels, 3x3 'same') in training
     mode, the convolution recomputed inside every pass (iris_conv0_*): its output - 32x the input - is never stored.
-    x gets no gradient (it is the feature tensor); the bias gradient is identically zero (BatchNorm removes the mean)."""
+    The bias gradient is identically zero (BatchNorm removes the mean).  x is the feature tensor and normally gets no
+    gradient; where it wants one (the output of the trainable PCEN layer of a 'pcen_learn' model, `_ConvBNReLU.input_grad`)
+    the backward also writes dz and gathers dx from it (iris_conv0_bn_relu_backward_dx: one more launch, no atomics)."""
 
     @staticmethod
     def forward(ctx, x, weight, conv_bias, gamma, beta, running_mean, running_var, eps, momentum):
@@ -493,18 +495,28 @@ class _FusedConv0BNReLU(torch.autograd.Function):
         dw64 = _zeros(lib.iris_conv0_dweight_len(cin, cout), torch.float64, dev)
         dgamma = torch.empty(cout, dtype=torch.float32, device=dev)
         dbeta = torch.empty(cout, dtype=torch.float32, device=dev)
+        dx = None
         with torch.cuda.device(dev):
-            N.check(lib.iris_conv0_bn_relu_backward(xc.data_ptr(), wc.data_ptr(), dy.data_ptr(), b, cin, cout, h, w,
-                                                    save_mean.data_ptr(), save_rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                                    sums.data_ptr(), dw64.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), stream),
-                    "iris_conv0_bn_relu_backward")
+            if ctx.needs_input_grad[0]:
+                dz = torch.empty((b, h, w, cout), dtype=torch.float32, device=dev)
+                dx = torch.empty((b, cin, h, w), dtype=torch.float32, device=dev)
+                N.check(lib.iris_conv0_bn_relu_backward_dx(xc.data_ptr(), wc.data_ptr(), dy.data_ptr(), b, cin, cout, h, w,
+                                                           save_mean.data_ptr(), save_rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                                           sums.data_ptr(), dw64.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
+                                                           dz.data_ptr(), dx.data_ptr(), stream),
+                        "iris_conv0_bn_relu_backward_dx")
+            else:
+                N.check(lib.iris_conv0_bn_relu_backward(xc.data_ptr(), wc.data_ptr(), dy.data_ptr(), b, cin, cout, h, w,
+                                                        save_mean.data_ptr(), save_rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                                        sums.data_ptr(), dw64.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), stream),
+                        "iris_conv0_bn_relu_backward")
         dw = dw64.view(-1, cout, cin, 3, 3).sum(0).to(torch.float32).contiguous(memory_format=ctx.weight_format)
         if cin == 1 and tuple(dw.stride()) != ctx.weight_strides:
             # one input channel: both memory formats are the same bytes, only the stride of the size-1 axis differs - hand the
             # gradient back with the parameter's own strides (DDP's bucket views follow those, and warn otherwise)
             dw = dw.as_strided(dw.shape, ctx.weight_strides)
         dbias = _zeros(cout, torch.float32, dev, "grad") if ctx.has_bias else None
-        return None, dw, dbias, dgamma, dbeta, None, None, None, None
+        return dx, dw, dbias, dgamma, dbeta, None, None, None, None
 
 
 def _is_first_layer_conv(conv, x) -> bool:
@@ -699,6 +711,34 @@ class _BiLSTM128(torch.autograd.Function):
         dg = dgx.permute(2, 3, 0, 1).reshape(2, 512, b * t)            # [d, gate row, (b, t)]
         dw_hh = torch.bmm(dg, hprev.reshape(2, b * t, 128))
         return dgx, dw_hh
+
+
+class _PCENBanded(torch.autograd.Function):
+    """out = pcen_banded(x, params) with the gradient of the effective per-band parameters [4, n_bands] from
+    iris_pcen_banded_grad.  x is saved, not M: the backward kernel recomputes the smoother beside its sensitivity."""
+
+    @staticmethod
+    def forward(ctx, x, params, eps):
+        params = params.contiguous()
+        ctx.save_for_backward(x, params)
+        ctx.eps = eps
+        return _fe.pcen_banded(x, params, eps=eps)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, params = ctx.saved_tensors
+        return None, _fe.pcen_banded_grad(x, dout, params, eps=ctx.eps), None
+
+
+def pcen_banded(x: torch.Tensor, params: torch.Tensor, eps: float) -> torch.Tensor:
+    """`frontend.pcen_banded` under autograd: differentiable in `params` only."""
+    if x.requires_grad:
+        raise RuntimeError("pcen_banded: x requires a gradient, but the PCEN layer treats its input as data - the backward "
+                           "kernel (iris_pcen_banded_grad) produces the parameters' gradient only, no reverse scan through the "
+                           "smoother exists; detach the input")
+    if torch.is_grad_enabled() and params.requires_grad:
+        return _PCENBanded.apply(x, params, eps)
+    return _fe.pcen_banded(x, params.detach().contiguous(), eps=eps)
 
 
 def _lstm_is_bilstm128(lstm) -> bool:

@@ -70,8 +70,10 @@ def smooth(preds: torch.Tensor, sr: int = 16000, hop: int = 256) -> torch.Tensor
 def features_for_eval(spec: torch.Tensor, config) -> torch.Tensor:
     """[F, T, 2C] complex spectrogram -> log-mel [M, T, C'] as metrics.py:42-54 prepares it.  A 'pcen' run name
     (data_utils.feature_compression) applies PCEN instead of min-max + log, over the whole recording before it is cut
-    into windows (training applies it per clip: see data_utils.pcen_on_mel)."""
-    pcen = D.feature_compression(getattr(config, 'name', '')) == 'pcen'
+    into windows (training applies it per clip: see data_utils.pcen_on_mel).  A 'pcen_learn' run name returns the raw mel
+    magnitudes: the trainable PCEN layer is inside the model and runs per window, which is what training saw per clip."""
+    compression = D.feature_compression(getattr(config, 'name', ''))
+    pcen = compression == 'pcen'
     inputs = spec
     if config.n_chan == 1:
         inputs = D.mono_chan(inputs)
@@ -82,6 +84,8 @@ def features_for_eval(spec: torch.Tensor, config) -> torch.Tensor:
     inputs = D.stft_filter(int(round(256 * 1000 / 16000)))(inputs)
     inputs = T.complex_to_magphase(inputs)
     inputs = T.magphase_to_mel(config.n_mels, inputs.shape[0])(inputs)
+    if compression == 'pcen_learn':
+        return inputs
     if pcen:
         return D.pcen_on_mel(inputs)
     inputs = D.minmax(inputs)       # unbatched: per-mel-row min-max (the reference's behaviour)

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 from typing import Callable, Optional
 
+import math
 import numpy as np
 import os
 import torch
@@ -15,7 +16,7 @@ import torch.nn as nn
 from . import frontend as _fe
 from . import switches as SW
 from .hip_autograd import (FusedAGC, _FusedBiasBNReLU, _FusedConv0BNReLU, _IN_STEP, _PACKS, _WinoConv3x3, _ZERO_POOL, _is_first_layer_conv,
-                           _is_pool_2x2_same, _lstm_is_bilstm128, _wino_train_conv, adaptive_clip_grad, bilstm128)
+                           _is_pool_2x2_same, _lstm_is_bilstm128, _wino_train_conv, adaptive_clip_grad, bilstm128, pcen_banded)
 
 
 # BatchNorm's num_batches_tracked counters of the layers whose fused passes ran, bumped by ONE _foreach_add_ at the end of
@@ -45,7 +46,10 @@ class _ConvBNReLU(nn.Sequential):
                 and not torch.is_autocast_enabled()):
             conv, bn = self[0], self[1]
             if x.dtype == torch.float32 and conv.out_channels % 4 == 0 and bn.track_running_stats and bn.momentum is not None:
-                if SW.FUSED_CONV0 and pool is None and _is_first_layer_conv(conv, x):
+                # (input_grad: set by CustomModel on its first layer when a trainable PCEN layer feeds it - the fused first-layer
+                # passes then also return the input gradient; any other input that wants a gradient keeps the generic passes)
+                if SW.FUSED_CONV0 and pool is None and (_is_first_layer_conv(conv, x) or (
+                        getattr(self, 'input_grad', False) and x.requires_grad and _is_first_layer_conv(conv, x.detach()))):
                     _count_batch(bn)  # the model's first layer: convolution recomputed inside the passes
                     return _FusedConv0BNReLU.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean,
                                                    bn.running_var, bn.eps, bn.momentum)
@@ -155,6 +159,64 @@ class _SmoothPool(nn.Module):  # v == 6 (sj_train.py:225-229): avg (1,k) then ma
         return self._same(self._same(x, self.k, 'avg'), 2 * self.k, 'max')
 
 
+def _pcen_torch(x, s, a, d, r, eps):
+    """PCEN with per-band parameters in plain torch ops, differentiable in s, a, d, r ([n_bands] each): x is
+    [..., n_bands, T, C]; the definition of `frontend.pcen`, frame by frame."""
+    frames = x.unbind(-2)                                        # T x [..., n_bands, C]
+    s2 = s.unsqueeze(-1)
+    m = frames[0]
+    ms = [m]
+    for e in frames[1:]:
+        m = (1.0 - s2) * m + s2 * e
+        ms.append(m)
+    m = torch.stack(ms, -2)
+    a3, d3, r3 = (p.view(-1, 1, 1) for p in (a, d, r))
+    log_m = math.log(eps) + torch.log1p(m / eps)                 # ln(eps + M)
+    log_d = torch.log(d3)
+    return torch.exp(r3 * log_d) * torch.expm1(r3 * torch.log1p(x * torch.exp(-a3 * log_m - log_d)))
+
+
+class PCEN(nn.Module):
+    """Trainable per-channel energy normalisation (Wang et al. 2017): gain, bias, power and the smoother coefficient are
+    learned per mel band with the network.  Input [B, n_bands, T, C] (or unbatched [n_bands, T, C]) mel MAGNITUDES, treated as
+    data - no gradient flows into it, and an input that requires one is refused.  Four unconstrained parameters [n_bands]:
+        a = exp(log_gain) >= 0, d = exp(log_bias) > 0, r = sigmoid(power_logit), s = sigmoid(smooth_logit) in (0, 1)
+    so the effective values are inside the kernels' domain by construction (the kernels read them from device memory and
+    cannot check them); initialised at `frontend.pcen`'s fixed defaults, so an untrained layer reproduces the 'pcen' features.
+    On a device the forward is iris_pcen_banded and the gradient of (s, a, d, r) iris_pcen_banded_grad (hip_autograd.pcen_banded;
+    the map from the raw parameters and its chain rule are torch ops on [n_bands] tensors); on CPU tensors, or with
+    IRIS_PCEN_LEARN_HIP=0, the differentiable torch restatement `_pcen_torch` runs instead.  The smoother starts afresh on
+    every item of the batch: a training clip, or one window of a recording in evaluation."""
+
+    def __init__(self, n_bands: int, eps: float = _fe.PCEN_EPS):
+        super().__init__()
+        self.n_bands, self.eps = int(n_bands), float(eps)
+        s = _fe.pcen_smooth()
+
+        def full(v):
+            return nn.Parameter(torch.full((self.n_bands,), float(v), dtype=torch.float32))
+        self.log_gain = full(math.log(_fe.PCEN_GAIN))
+        self.log_bias = full(math.log(_fe.PCEN_BIAS))
+        self.power_logit = full(math.log(_fe.PCEN_POWER / (1.0 - _fe.PCEN_POWER)))
+        self.smooth_logit = full(math.log(s / (1.0 - s)))
+
+    def effective(self):
+        """(s, a, d, r), [n_bands] each, differentiable in the raw parameters."""
+        return (torch.sigmoid(self.smooth_logit), torch.exp(self.log_gain), torch.exp(self.log_bias),
+                torch.sigmoid(self.power_logit))
+
+    def forward(self, x):
+        if x.requires_grad:
+            raise RuntimeError("PCEN: the input requires a gradient, but the layer treats its input as data: only the four "
+                               "per-band parameters are differentiated (no reverse scan through the smoother exists); detach it")
+        if x.dim() < 3 or x.shape[-3] != self.n_bands:
+            raise ValueError(f"PCEN: expected [..., {self.n_bands}, T, C], got {tuple(x.shape)}")
+        s, a, d, r = self.effective()
+        if x.is_cuda and x.dtype == torch.float32 and SW.PCEN_LEARN_HIP:
+            return pcen_banded(x, torch.stack((s, a, d, r)), self.eps)
+        return _pcen_torch(x, s, a, d, r, self.eps)
+
+
 class CustomModel(nn.Module):
     """The CRNN of define_keras_model plus the Keras-style training surface the reference
     uses: compile(), train_step(data) (sj_train.py:158-188), test_step, fit."""
@@ -163,6 +225,10 @@ class CustomModel(nn.Module):
         super().__init__()
         fsize = 48 if (config.model_type == 'vad' and config.v == 8) else 32
         self.config_v, self.model_type = config.v, config.model_type
+        # a 'pcen_learn' run name: the datasets feed raw mel magnitudes and the trainable PCEN layer is the model's first stage
+        # (registered first; models of other names have no such submodule and the state_dict keys they always had)
+        from .data_utils import feature_compression
+        self.pcen = PCEN(config.n_mels) if feature_compression(getattr(config, 'name', '') or '') == 'pcen_learn' else None
         blocks = [ConvMPBlock(config.n_chan, 2, fsize, BN=True)]
         cin, width = fsize, config.n_frame // 2
         for i in range(1, 5):
@@ -174,6 +240,8 @@ class CustomModel(nn.Module):
             blocks.append(ConvMPBlock(cin, 3, fsize * 2 ** i, BN=True))
             cin, width = fsize * 2 ** i, -(-width // 2)
         self.features = nn.Sequential(*blocks)
+        if self.pcen is not None:   # the first layer's input is the PCEN layer's output: its fused passes must hand back dx
+            blocks[0].convs[0].input_grad = True
         m_out = config.n_mels
         for _ in range(5):
             m_out = -(-m_out // 2)
@@ -218,6 +286,8 @@ class CustomModel(nn.Module):
                 torch._foreach_add_(pending, 1)
 
     def _forward(self, x):
+        if self.pcen is not None:
+            x = self.pcen(x)       # on the [B, M, T, C] input: per clip / per window
         x = x.permute(0, 3, 1, 2)  # NCHW view of the NHWC tensor (channels_last strides)
         x = self.features(x)       # [B, C, M', T']
         x = x.permute(0, 3, 2, 1).flatten(2)  # [B, T', M' * C], m' major as Keras Permute+Reshape
@@ -703,7 +773,8 @@ def load_keras_weights(model: "CustomModel", weights) -> "CustomModel":
         of [B, M', T', C] to [B, T', M' C] (m' major, :243-244) - the order `CustomModel.forward` flattens in
       Bidirectional(LSTM(128)) forward then backward layer: kernel [in, 4u], recurrent_kernel [u, 4u], bias [4u], gate order
         i, f, c, o = torch's i, f, g, o -> weight_ih [4u, in], weight_hh [4u, u], bias_ih = bias, bias_hh = 0
-    Shapes are checked entry by entry; a count or shape mismatch raises ValueError naming the layer.  v 6 / 7 / 8 / 9."""
+    Shapes are checked entry by entry; a count or shape mismatch raises ValueError naming the layer.  v 6 / 7 / 8 / 9.
+    The trainable PCEN layer of a 'pcen_learn' model has no counterpart in the reference: it is skipped and keeps its values."""
     ws = _keras_weight_list(weights)
     pos = [0]
 
@@ -772,7 +843,8 @@ def load_keras_weights(model: "CustomModel", weights) -> "CustomModel":
 
 
 def keras_weight_shapes(model: "CustomModel") -> list:
-    """Shapes of the reference model's get_weights() for this architecture, in order (what `load_keras_weights` expects)."""
+    """Shapes of the reference model's get_weights() for this architecture, in order (what `load_keras_weights` expects;
+    without the PCEN layer of a 'pcen_learn' model, which the reference does not have)."""
     probe = []
 
     def conv_bn(layer):

@@ -182,9 +182,12 @@ def _load_sources(config, training, n_classes, sources):
 
 
 def _label_tail(pipeline, config):
-    """The stages after the mel features (sj_train.py:121-129); a 'pcen' run name maps PCEN instead of min-max + log."""
+    """The stages after the mel features (sj_train.py:121-129); a 'pcen' run name maps PCEN instead of min-max + log, a
+    'pcen_learn' one maps no compression at all (the raw mel magnitudes go to the model's trainable PCEN layer)."""
     compression = _du.feature_compression(config.name)
-    if compression == 'pcen':
+    if compression == 'pcen_learn':
+        pass
+    elif compression == 'pcen':
         pipeline = pipeline.map(_du.pcen_on_mel)
     elif compression == 'minmax_log':
         pipeline = pipeline.map(_du.minmax_log_on_mel)  # :121-123 fused
@@ -328,7 +331,8 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
     length = (config.n_frame - 1) * hop
     plan = _fe.FrontendPlan(n_fft, hop, config.n_mels, sample_rate, config.n_chan, config.batch_size, length, mixer.device)
     filter_bins = int(round(200 / (16000 / 256))) if 'filter' in config.name else 0
-    do_pcen = _du.feature_compression(config.name) == 'pcen'
+    compression = _du.feature_compression(config.name)
+    do_pcen, raw_mel = compression == 'pcen', compression == 'pcen_learn'   # raw_mel: the model's PCEN layer takes the magnitudes
     do_minmax = 'nominmax' not in config.name
     band_draw = None
     if device_draw:
@@ -353,6 +357,8 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
             if do_pcen:   # the raw mel out of the fused kernel, then PCEN in place
                 mel = plan.wav_to_logmel(wav.contiguous(), t_bands=tb, f_bands=fb, minmax=False, log=False)
                 yield _fe.pcen(mel, out=mel), y
+            elif raw_mel:
+                yield plan.wav_to_logmel(wav.contiguous(), t_bands=tb, f_bands=fb, minmax=False, log=False), y
             else:
                 yield plan.wav_to_logmel(wav.contiguous(), t_bands=tb, f_bands=fb, minmax=do_minmax, log=True), y
 
@@ -372,15 +378,16 @@ class WaveFrontend:
     min-max, log) -> [B, M, T, C].  Equivalent to load_wav + augment + complex_to_magphase
     + magphase_to_mel + minmax + log_on_mel without materialising the spectrum.
     compression='pcen': the fused kernel stops at the mel magnitudes and `frontend.pcen` follows in place (a second
-    launch) instead of min-max + log."""
+    launch) instead of min-max + log; compression='mel': the mel magnitudes themselves, for a model whose first layer is the
+    trainable `PCEN` (a 'pcen_learn' run name)."""
 
     def __init__(self, n_fft=1024, hop=256, n_mels=64, sample_rate=16000, n_chan=1, batch=64, length=130816,
                  device=None, training=True, filter_bins: int = 0, do_minmax: bool = True,
                  device_draw: bool = False, seed: int = 0, compression: str = 'log'):
-        if compression not in ('log', 'pcen'):
-            raise ValueError(f"WaveFrontend: compression must be 'log' or 'pcen', got {compression!r}")
-        if compression == 'pcen' and not do_minmax:
-            raise ValueError("WaveFrontend: compression='pcen' replaces min-max + log; do_minmax=False does not apply")
+        if compression not in ('log', 'pcen', 'mel'):
+            raise ValueError(f"WaveFrontend: compression must be 'log', 'pcen' or 'mel', got {compression!r}")
+        if compression != 'log' and not do_minmax:
+            raise ValueError(f"WaveFrontend: compression={compression!r} replaces min-max + log; do_minmax=False does not apply")
         self.compression = compression
         self.plan = _fe.FrontendPlan(n_fft, hop, n_mels, sample_rate, n_chan, batch, length, device)
         self.training, self.filter_bins, self.do_minmax = training, filter_bins, do_minmax
@@ -418,7 +425,10 @@ class WaveFrontend:
 
     def features(self, wav: torch.Tensor, t_bands=None, f_bands=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The features of `wav` with the given bands (no draws): the fused kernel with min-max + log, or with
-        compression='pcen' the raw mel followed by PCEN in place.  Capturable into a hipGraph either way."""
+        compression='pcen' the raw mel followed by PCEN in place, with 'mel' the raw mel alone.  Capturable into a hipGraph
+        in every form."""
+        if self.compression == 'mel':
+            return self.plan.wav_to_logmel(wav, minmax=False, log=False, t_bands=t_bands, f_bands=f_bands, out=out)
         if self.compression == 'pcen':
             mel = self.plan.wav_to_logmel(wav, minmax=False, log=False, t_bands=t_bands, f_bands=f_bands, out=out)
             return _fe.pcen(mel, out=mel)

@@ -32,6 +32,9 @@ FUSED_CONV0 = _on("IRIS_FUSED_CONV0")        # the first layer (1-2 input channe
 FUSED_LSTM = _on("IRIS_FUSED_LSTM")          # Bidirectional(LSTM(128)): each pass through time in one launch (k_lstm.h)
 # zero-initialised scratch (BatchNorm sums, first-layer dW copies, zero bias gradients) from one pool with one fill per step
 ZERO_POOL = _on("IRIS_ZERO_POOL")
+# the trainable PCEN layer of a 'pcen_learn' run (model.PCEN) on a device: forward and parameter gradient through the HIP kernels
+# iris_pcen_banded / iris_pcen_banded_grad; IRIS_PCEN_LEARN_HIP=0 runs the layer's differentiable torch restatement there (A/B runs)
+PCEN_LEARN_HIP = _on("IRIS_PCEN_LEARN_HIP")
 
 # round 6: every Winograd weight packing of a training step (12 forward + 11 backward-data layers) in ONE launch at the top of the
 # forward pass (iris_wino_pack_weights_device_multi) instead of one launch per layer and pass; 0: per layer
@@ -81,6 +84,6 @@ DDP_BUCKET_MB = int(os.environ.get("IRIS_DDP_BUCKET_MB", "12"))
 # --- test hook ------------------------------------------------------------------------------------------------------------------------
 _PLAN_CHECK_ON_CPU = False  # tests/test_ddp_gloo.py: consult the frontend plans' status for a CPU-resident loss too
 
-NAMES = ("FUSED_BN_RELU", "FUSED_FC_BN", "FUSED_BN_POOL", "FUSED_BN_STATS", "FUSED_PACK", "FUSED_ADAM", "FUSED_CONV0", "FUSED_LSTM", "ZERO_POOL", "WINO_TRAIN",
+NAMES = ("FUSED_BN_RELU", "FUSED_FC_BN", "FUSED_BN_POOL", "FUSED_BN_STATS", "FUSED_PACK", "FUSED_ADAM", "FUSED_CONV0", "FUSED_LSTM", "ZERO_POOL", "PCEN_LEARN_HIP", "WINO_TRAIN",
          "WINO_TRAIN_MIN_C_FWD", "WINO_TRAIN_MIN_C_BWD", "WINO_TRAIN_WRW", "C32_TRAIN", "WINO_SPLIT_BF16", "WINO_CONVS", "GRAPH_STEP", "DDP_BUCKET_MB",
          "_PLAN_CHECK_ON_CPU")

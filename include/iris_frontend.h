@@ -254,6 +254,31 @@ int iris_pcen(const float* mel, float* out, int n_rows, int n_time, int n_inner,
 int iris_pcen_smoother(const float* mel, float* m_out, int n_rows, int n_time, int n_inner, float smooth, void* stream);
 
 /*
+ * PCEN with its own parameters per band, and their gradient: the two halves of the trainable PCEN layer (model.PCEN).
+ * The view [n_rows, n_time, n_inner] is iris_pcen's; row i belongs to band i % n_bands (the batched [B, M, T, C] tensor:
+ * n_rows = B M, n_bands = M; the unbatched [M, T, C] one: n_rows = n_bands = M) and params is a DEVICE array
+ * params[4][n_bands] of the EFFECTIVE values s (0 < s <= 1), a (>= 0), d (> 0), r (0 < r <= 1), in this order.  The
+ * per-band constants (1 - s, ln d, d^r) are formed on the device.  The values cannot be range-checked here without a
+ * synchronisation: the caller guarantees them (model.PCEN maps unconstrained parameters through exp / sigmoid).  eps is a
+ * host scalar as in iris_pcen.  Checked before any HIP call (IRIS_E_INVALID): NULL pointers, non-positive shape,
+ * n_bands <= 0, n_rows % n_bands != 0, eps; IRIS_E_CAPACITY: workspace too small.
+ *
+ * iris_pcen_banded: the same definition, scan, zero / NaN semantics and in-place rule as iris_pcen; one launch.
+ *
+ * iris_pcen_banded_grad: dparams[4][n_bands] = sum over a band's elements of dout * d out / d (s, a, d, r), the gradient
+ * of a scalar loss whose gradient with respect to the output is dout (same shape as mel).  The smoother and its
+ * sensitivity dM / ds are recomputed from mel by a forward scan (nothing is saved by the forward; mel is data, so no
+ * gradient with respect to it is produced).  Two launches: per-workgroup partial sums into `workspace`
+ * (iris_pcen_banded_grad_workspace(n_rows, n_time, n_inner) floats, DEVICE), then their sum per band in a fixed order.
+ * No atomics: bitwise reproducible.  Both enqueue on `stream`, allocate nothing, never synchronise: capturable.
+ */
+int iris_pcen_banded(const float* mel, float* out, int n_rows, int n_time, int n_inner, const float* params, int n_bands,
+                     float eps, void* stream);
+size_t iris_pcen_banded_grad_workspace(int n_rows, int n_time, int n_inner);
+int iris_pcen_banded_grad(const float* mel, const float* dout, int n_rows, int n_time, int n_inner, const float* params,
+                          int n_bands, float eps, float* dparams, float* workspace, size_t workspace_floats, void* stream);
+
+/*
  * The fused hot path: [normalize ->] STFT -> magnitude -> band masks -> mel
  * [-> min-max] [-> log] without materialising the spectrum
  * (load_wav data_utils.py:22-23 + sj_train.py:108-123).  flags = IRIS_F_*.
@@ -554,6 +579,10 @@ int iris_conv3x3_wino_wrw(const float* x, const float* dy, float* dw, long strid
  *             sums_zeroed [iris_bn_sums_len(out_channels)] and dweight_zeroed [iris_conv0_dweight_len(...)] DEVICE doubles,
  *             zero on entry; dweight = several partial copies [copies][out_channels][in_channels][3][3] that the caller
  *             adds up (the blocks' atomics are spread over them); dgamma, dbeta [out_channels] floats.
+ *             iris_conv0_bn_relu_backward_dx: the same two launches, and the input gradient for a model whose first stage
+ *             is trainable (the PCEN layer of a 'pcen_learn' run): the second launch also writes dz into dz_scratch
+ *             [batch, height, width, out_channels] (DEVICE floats, 16-byte aligned), a third gathers
+ *             dx [batch, in_channels, height, width] from it in a fixed order (no atomics).
  */
 size_t iris_conv0_dweight_len(int in_channels, int out_channels);
 int iris_conv0_stats(const float* x, const float* weight, int batch, int in_channels, int out_channels, int height, int width,
@@ -565,6 +594,10 @@ int iris_conv0_bn_relu_backward(const float* x, const float* weight, const float
                                 int out_channels, int height, int width, const float* save_mean, const float* save_rstd,
                                 const float* gamma, const float* beta, double* sums_zeroed, double* dweight_zeroed, float* dgamma,
                                 float* dbeta, void* stream);
+int iris_conv0_bn_relu_backward_dx(const float* x, const float* weight, const float* dy, int batch, int in_channels,
+                                   int out_channels, int height, int width, const float* save_mean, const float* save_rstd,
+                                   const float* gamma, const float* beta, double* sums_zeroed, double* dweight_zeroed, float* dgamma,
+                                   float* dbeta, float* dz_scratch, float* dx, void* stream);
 
 /*
  * First convolution of the CRNN (ConvMPBlock's Conv2D(32, 3, padding='same') on the n_chan-channel log-mel input,
