@@ -28,6 +28,8 @@
 //   k_pcen.h         per-channel energy normalisation: a chunked scan of the IIR smoother along time, then the compression
 //                    (host scalars, or per-band parameters from a device array: the trainable layer's forward)
 //   k_pcen_grad.h    the trainable layer's backward: gradient with respect to the per-band parameters, two launches, no atomics
+//   k_vocoder.h      time stretching: a batched phase vocoder over a ragged set of spectrograms, the running phase as the same
+//                    chunked scan modulo 2 pi
 //   host_plan.h      mel matrix, constant tables, plan create / destroy
 //   host_ops.h       the operators' C-ABI entry points
 #include "common.h"
@@ -55,3 +57,4 @@
 #include "k_detect.h"
 #include "k_pcen.h"
 #include "k_pcen_grad.h"
+#include "k_vocoder.h"

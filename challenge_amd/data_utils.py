@@ -135,6 +135,13 @@ def feature_compression(name: str) -> str:
     return 'pcen' if pcen else ('log' if nominmax else 'minmax_log')
 
 
+def wants_stretch(name: str) -> bool:
+    """Whether a run name asks for time-stretch augmentation of the voice corpus: the token 'stretch' in it (the same
+    idiom).  Honoured by `sj_train.make_device_dataset(training=True)` alone (`DeviceMixer.enable_stretch` / `restretch`);
+    `make_dataset` and `make_wave_dataset` refuse it.  It does not interact with `feature_compression`."""
+    return 'stretch' in name
+
+
 def augment(specs: torch.Tensor, labels, time_axis: int = -2, freq_axis: int = -3):
     """6 time masks (< 24 frames) then 1 frequency mask (< 16 linear bins) on the complex
     spectrogram (data_utils.py:58-61)."""

@@ -941,6 +941,89 @@ def pcen_banded_grad(x: torch.Tensor, dout: torch.Tensor, params: torch.Tensor, 
     return dparams
 
 
+# mirrors iris_voc_src (include/iris_frontend.h)
+VOC_SRC = np.dtype([("src", "<u8"), ("dst", "<u8"), ("n_in", "<i4"), ("n_out", "<i4"), ("rate", "<f8")])
+assert VOC_SRC.itemsize == 32
+
+
+def stretched_frames(n_frames: int, rate: float) -> int:
+    """Frames of a spectrogram of `n_frames` frames stretched by `rate`: ceil(n_frames / rate) in double, the length of
+    numpy.arange(0, n_frames, rate)."""
+    rate = float(rate)
+    if not (np.isfinite(rate) and rate > 0):
+        raise ValueError(f"stretch rate must be a positive finite number, got {rate}")
+    return int(np.ceil(float(n_frames) / rate))
+
+
+def phase_vocoder_launch(table: np.ndarray, n_bins: int, chan2: int, max_out_frames: int, device: torch.device,
+                         table_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Upload a VOC_SRC table (into `table_dev`, a long-lived uint8 device buffer, when given) and run iris_phase_vocoder over
+    it on the current stream: one launch.  Returns the device table (tied to the stream when it was allocated here)."""
+    raw = torch.from_numpy(np.ascontiguousarray(table).view(np.uint8).reshape(-1))
+    if table_dev is None:
+        dev_table = raw.to(device, non_blocking=True)
+    else:
+        dev_table = table_dev[:raw.numel()]
+        dev_table.copy_(raw)
+    with torch.cuda.device(device):
+        rc = N.lib().iris_phase_vocoder(dev_table.data_ptr(), int(table.shape[0]), int(n_bins), int(chan2), int(max_out_frames),
+                                        _stream_ptr(device))
+    N.check(rc, "iris_phase_vocoder")
+    if table_dev is None and dev_table.numel():
+        dev_table.record_stream(torch.cuda.current_stream(device))
+    return dev_table
+
+
+def phase_vocoder_batch(specs, rates, out=None):
+    """Time-stretch a ragged batch of complex spectrograms in ONE launch (iris_phase_vocoder): specs is a list of
+    [F, T_i, 2C] float32 tensors on one ROCm device (re block, im block last, equal F and 2C), rates as many positive
+    numbers.  Returns a list of [F, ceil(T_i / rate_i), 2C] tensors: the reference's `phase_vocoder` with the time grid in
+    double and the running phase kept in [-pi, pi] (|out - fp64| <= mag (1e-5 + 16 u pi (t + 1)), where the reference's own
+    fp32 form is 1e-2 of the peak off); a rate of 1 copies its source.  out: optional list of preallocated contiguous
+    float32 buffers on the same device, out[i] holding at least F * n_i * 2C floats; the result i is a view of the start of
+    out[i] and the floats beyond it are left alone.  CPU tensors raise: there is no CPU fallback."""
+    specs, rates = list(specs), [float(r) for r in rates]
+    if len(specs) != len(rates):
+        raise ValueError(f"phase_vocoder_batch: {len(specs)} spectrograms but {len(rates)} rates")
+    if out is not None and len(out) != len(specs):
+        raise ValueError(f"phase_vocoder_batch: {len(specs)} spectrograms but {len(out)} output buffers")
+    if not specs:
+        return []
+    specs = [_require_device_f32(s, f"specs[{i}]") for i, s in enumerate(specs)]
+    dev = specs[0].device
+    if specs[0].dim() != 3:
+        raise ValueError("phase_vocoder_batch: every spectrogram must be [freq, time, chan * 2]")
+    n_bins, chan2 = int(specs[0].shape[0]), int(specs[0].shape[2])
+    if n_bins < 2 or chan2 < 2 or chan2 % 2:
+        raise ValueError(f"phase_vocoder_batch: [freq = {n_bins}, time, chan2 = {chan2}] needs freq >= 2 and an even chan2")
+    table = np.zeros(len(specs), VOC_SRC)
+    results = []
+    for i, (s, r) in enumerate(zip(specs, rates)):
+        if s.dim() != 3 or int(s.shape[0]) != n_bins or int(s.shape[2]) != chan2 or s.device != dev or int(s.shape[1]) < 1:
+            raise ValueError(f"phase_vocoder_batch: specs[{i}] has shape {tuple(s.shape)} on {s.device}; expected "
+                             f"[{n_bins}, T >= 1, {chan2}] on {dev}")
+        n = stretched_frames(int(s.shape[1]), r)
+        if out is None:
+            o = torch.empty((n_bins, n, chan2), dtype=torch.float32, device=dev)
+        else:
+            buf = out[i]
+            if not (isinstance(buf, torch.Tensor) and buf.is_cuda and buf.device == dev and buf.dtype == torch.float32
+                    and buf.is_contiguous()):
+                raise ValueError(f"phase_vocoder_batch: out[{i}] must be a contiguous float32 tensor on {dev}")
+            if buf.numel() < n_bins * n * chan2:
+                raise ValueError(f"phase_vocoder_batch: out[{i}] holds {buf.numel()} floats, fewer than the {n_bins} x {n} x "
+                                 f"{chan2} of {int(s.shape[1])} frames at rate {r}")
+            if buf.data_ptr() == s.data_ptr():
+                raise ValueError(f"phase_vocoder_batch: out[{i}] is specs[{i}] itself (the stretch is not in place)")
+            o = buf.view(-1)[:n_bins * n * chan2].view(n_bins, n, chan2)
+        table[i] = (s.data_ptr(), o.data_ptr(), int(s.shape[1]), n, r)
+        results.append(o)
+    phase_vocoder_launch(table, n_bins, chan2, int(table["n_out"].max()), dev)
+    for s in specs:   # (a contiguous copy made above must outlive the kernel)
+        s.record_stream(torch.cuda.current_stream(dev))
+    return results
+
+
 def complex_to_magphase(x: torch.Tensor) -> torch.Tensor:
     x = _require_device_f32(x, "complex_tensor")
     c2 = int(x.shape[-1])

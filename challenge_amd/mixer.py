@@ -56,6 +56,19 @@ class _Stream:
         return out
 
 
+def check_stretch_range(lo: float, hi: float) -> None:
+    """The rate range of `DeviceMixer.enable_stretch`: finite, 0 < lo <= hi."""
+    lo, hi = float(lo), float(hi)
+    if not (np.isfinite(lo) and np.isfinite(hi) and 0 < lo <= hi):
+        raise ValueError(f"stretch rates must satisfy 0 < lo <= hi (finite), got lo = {lo}, hi = {hi}")
+
+
+def stretch_rates(rng: np.random.Generator, n: int, lo: float = 0.8, hi: float = 1.2) -> np.ndarray:
+    """The random half of `DeviceMixer.restretch`: n rates ~ U[lo, hi) (float64) from `rng`."""
+    check_stretch_range(lo, hi)
+    return rng.uniform(float(lo), float(hi), size=int(n))
+
+
 class BatchDraw:
     """The random decisions of one batch as arrays (B samples, V = max_voices, N = max_noises):
     bg [B], bg_offset [B], voices [B, V], v_len [B], n_voices [B], v_gain [B, V] f32, v_offset [B, V],
@@ -301,6 +314,81 @@ class DeviceMixer:
         self._dd["bg"] = corpus(self._bg_ptr, None, self._bg_T, self._bg_L if wave else None)
         self._dd["voice"] = corpus(self._v_ptr, self._v_act, self._v_T, self._v_L if wave else None)
         self._dd["noise"] = corpus(self._n_ptr, None, self._n_T, self._n_L if wave else None) if self.noises is not None else None
+        self._dd["voice_arrays"] = self._dd["keep"][1]   # `restretch` rewrites the voices' T (and, once, src / act) in place
+
+    # -- time-stretch augmentation of the voice corpus ----------------------------------
+    def enable_stretch(self, lo: float = 0.8, hi: float = 1.2) -> None:
+        """Keep a time-stretched copy of every voice beside the original and mix from the copies: `restretch()` then
+        re-stretches the whole voice corpus by fresh rates ~ U[lo, hi) in one launch (`iris_phase_vocoder`, the
+        reference's `transforms.phase_vocoder` with the running phase kept in [-pi, pi]).  The defaults are the two rates of
+        the reference's own test.  One buffer per voice with room for ceil(T_i / lo) frames and its frame-activity vector
+        of the same capacity are allocated here and never move: the pointer tables (and the device-side corpus of
+        `enable_device_draw`, in either call order) are switched to them once, so a captured `mix` replayed after a
+        `restretch` reads the new contents through unchanged addresses.  Until the first `restretch` the copies hold the
+        voices at rate 1 (bit-identical).  Backgrounds and noises are not stretched: they carry no labels, and the
+        reference's function was written for voices.  No accuracy claim is made for the augmentation."""
+        check_stretch_range(lo, hi)
+        if getattr(self, "_st", None) is not None:
+            raise RuntimeError("enable_stretch was already called on this mixer")
+        from . import frontend as _fe
+        orig, orig_T = list(self.voices), self._v_T.copy()
+        cap = np.array([_fe.stretched_frames(int(t), lo) for t in orig_T], np.int64)
+        row = self.n_bins * self.chan2
+        bufs = [torch.zeros(int(c) * row, device=self.device, dtype=torch.float32) for c in cap]
+        acts = [torch.zeros(int(c), device=self.device, dtype=torch.float32) for c in cap]
+        table = np.zeros(len(orig), _fe.VOC_SRC)
+        table["src"], table["dst"] = [t.data_ptr() for t in orig], [b.data_ptr() for b in bufs]
+        table["n_in"] = orig_T
+        self._st = {"lo": float(lo), "hi": float(hi), "orig": orig, "orig_T": orig_T, "cap": cap, "bufs": bufs, "acts": acts,
+                    "table": table, "rates": None,
+                    "table_dev": torch.empty(max(table.nbytes, 1), dtype=torch.uint8, device=self.device)}
+        self.voice_active = acts
+        self._v_ptr = np.array([b.data_ptr() for b in bufs], np.uint64)
+        self._v_act = np.array([a.data_ptr() for a in acts], np.uint64)
+        dd = getattr(self, "_dd", None)
+        if dd is not None:
+            dd["voice_arrays"]["src"].copy_(torch.from_numpy(self._v_ptr.astype(np.int64)))
+            dd["voice_arrays"]["act"].copy_(torch.from_numpy(self._v_act.astype(np.int64)))
+        self.restretch(np.ones(len(orig)))
+
+    def restretch(self, rates=None) -> np.ndarray:
+        """Stretch every ORIGINAL voice anew into its buffer: rate_i ~ U[lo, hi) from the mixer's own NumPy generator
+        (or the given `rates`, one per voice, each >= lo so that the result fits its buffer), ONE `iris_phase_vocoder`
+        launch over the whole voice corpus, then every voice's frame activity recomputed from the stretched voice
+        (`iris_mix_frame_active`: the labels follow from `max(voice) > 0`, as in the reference).  The voices' frame counts
+        change to ceil(T_i / rate_i), on the host (`_v_T`) and in place in the device corpus of `enable_device_draw`.  Call
+        it outside any graph capture.  Backgrounds and noises are not stretched.  Returns the rates used."""
+        st = getattr(self, "_st", None)
+        if st is None:
+            raise RuntimeError("restretch needs enable_stretch() first")
+        from . import frontend as _fe
+        n_voice = len(st["orig"])
+        if rates is None:
+            rates = stretch_rates(self.rng, n_voice, st["lo"], st["hi"])
+        rates = np.asarray(rates, np.float64).reshape(-1)
+        if rates.shape[0] != n_voice:
+            raise ValueError(f"restretch: {rates.shape[0]} rates for {n_voice} voices")
+        n_out = np.array([_fe.stretched_frames(int(t), r) for t, r in zip(st["orig_T"], rates)], np.int64)
+        if np.any(n_out > st["cap"]):
+            i = int(np.argmax(n_out > st["cap"]))
+            raise ValueError(f"restretch: voice {i} at rate {rates[i]} needs {n_out[i]} frames but its buffer holds "
+                             f"{st['cap'][i]} (rates below lo = {st['lo']} do not fit)")
+        table = st["table"]
+        table["n_out"], table["rate"] = n_out, rates
+        _fe.phase_vocoder_launch(table, self.n_bins, self.chan2, int(st["cap"].max()), self.device, st["table_dev"])
+        with torch.cuda.device(self.device):
+            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            for buf, act, n in zip(st["bufs"], st["acts"], n_out):
+                N.check(N.lib().iris_mix_frame_active(buf.data_ptr(), self.n_bins, int(n), self.chan2, act.data_ptr(), stream),
+                        "iris_mix_frame_active")
+        self._v_T = n_out
+        self.voices = [b[:self.n_bins * int(n) * self.chan2].view(self.n_bins, int(n), self.chan2)
+                       for b, n in zip(st["bufs"], n_out)]
+        dd = getattr(self, "_dd", None)
+        if dd is not None:
+            dd["voice_arrays"]["T"].copy_(torch.from_numpy(n_out.astype(np.int32)))
+        st["rates"] = rates.copy()
+        return st["rates"]
 
     def _draw_on_device(self, batch: int):
         """(table_d [batch * stride, 48 B], first_d [batch + 1], n_srcs) written by iris_mix_draw on the current stream."""
@@ -427,6 +515,10 @@ class WaveMixer(DeviceMixer):
         self._b = _Stream(len(self.backgrounds), self.rng)
         self._v = _Stream(len(self.voices), self.rng)
         self._n = _Stream(len(self.noises), self.rng) if self.noises is not None else None
+
+    def enable_stretch(self, lo: float = 0.8, hi: float = 1.2) -> None:
+        raise NotImplementedError("WaveMixer.enable_stretch: a waveform corpus has no spectra to stretch (the phase vocoder "
+                                  "works on complex spectrograms: use DeviceMixer)")
 
     def mix(self, batch: int, draws=None):
         """One batch of (waveforms [B, C, (n_frame - 1) * hop], labels [B, max_voices, n_frame, n_classes])."""

@@ -205,6 +205,9 @@ def _label_tail(pipeline, config):
 def make_dataset(config, training=True, n_classes=3, sources=None):
     """Stage order of sj_train.py:74-130.  `sources` = (backgrounds, voices, labels, noises)
     overrides the pickle files (used with --synthetic and by the tests)."""
+    if _du.wants_stretch(config.name):
+        raise ValueError(f"run name {config.name!r} asks for 'stretch': time stretching runs on the device-resident corpus "
+                         "(make_device_dataset); the per-sample host pipeline does not stretch")
     backgrounds, voices, labels, noises = _load_sources(config, training, n_classes, sources)
 
     pipeline = make_pipeline(backgrounds, voices, labels, noises, n_frame=config.n_frame,
@@ -239,7 +242,10 @@ def make_device_dataset(config, training=True, n_classes=3, sources=None, device
     the magnitude).  Yields (x [B, n_mels, n_frame, C], y) forever, like the repeated reference graph.
     device_draw=True: the random half of a batch (sources, offsets, gains, SpecAugment bands) is drawn by two small HIP
     kernels on the device (`iris_mix_draw`, `iris_augment_draw`) instead of NumPy on the host - no table upload, the
-    host only enqueues launches."""
+    host only enqueues launches.
+    A 'stretch' token in config.name (training sets only): the voice corpus is time-stretched by rates ~ U[0.8, 1.2) at
+    creation and again every config.steps_per_epoch batches (`DeviceMixer.enable_stretch` / `restretch`, one
+    `iris_phase_vocoder` launch over the corpus); a name without the token takes no new code path."""
     from .mixer import DeviceMixer
     backgrounds, voices, labels, noises = _load_sources(config, training, n_classes, sources)
     if config.model_type == 'se' and config.v == 9:
@@ -253,6 +259,10 @@ def make_device_dataset(config, training=True, n_classes=3, sources=None, device
     if device_draw:
         mixer.enable_device_draw(0 if seed is None else seed)
         band_draw = _du.DeviceAugmentDraw(mixer.device, (0 if seed is None else seed) + 1, filter_bins) if training else None
+    stretch = training and _du.wants_stretch(config.name)
+    if stretch:   # the voice corpus is re-stretched now and once per epoch (the validation set never is)
+        mixer.enable_stretch()
+        mixer.restretch()
     to_mel = complex_to_mel(config.n_mels, mixer.n_bins)
     chan_map = None
     if config.n_chan == 1:
@@ -263,7 +273,12 @@ def make_device_dataset(config, training=True, n_classes=3, sources=None, device
         chan_map = random_merge_aug(config.n_chan)
 
     def gen():
+        n_batches = 0
         while True:
+            if stretch:
+                if n_batches and n_batches % max(int(config.steps_per_epoch), 1) == 0:
+                    mixer.restretch()
+                n_batches += 1
             x, y = to_frame_labels(*mixer.mix(config.batch_size))
             b = int(x.shape[0])
             tb = fb = None
@@ -278,7 +293,9 @@ def make_device_dataset(config, training=True, n_classes=3, sources=None, device
                 x, y = chan_map(x, y)
             yield to_mel(x, y, t_bands=tb, f_bands=fb)
 
-    return _label_tail(Dataset.from_generator(gen), config)
+    dataset = _label_tail(Dataset.from_generator(gen), config)
+    dataset.mixer = mixer   # (for inspection: the resident corpus, its draws and - 'stretch' runs - the current voice lengths)
+    return dataset
 
 
 def synthetic_wave_sources(n_chan: int = 2, n_classes: int = 3, hop: int = 256, n_bg: int = 8, n_voice: int = 24,
@@ -316,6 +333,9 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
     factors and are not available here.  device_draw=True: sources / offsets / gains / SpecAugment bands are drawn on
     the device (`iris_mix_draw`, `iris_augment_draw`), as in `make_device_dataset`."""
     from .mixer import WaveMixer
+    if _du.wants_stretch(config.name):
+        raise ValueError(f"run name {config.name!r} asks for 'stretch': a waveform corpus has no spectra to stretch "
+                         "(use make_device_dataset)")
     if sources is None:
         sources = synthetic_wave_sources(2, n_classes, hop, seed=0 if training else 1)
     backgrounds, voices, labels, noises = sources

@@ -212,7 +212,8 @@ def phase_vocoder(complex_spec: torch.Tensor, rate: float = 1.0) -> torch.Tensor
     """Time-stretch a [freq, time, chan*2] spectrogram by `rate` (transforms.py:137-195):
     hop_length = freq - 1, phase advance linspace(0, pi*hop, freq), wrapped phase
     differences accumulated with the first frame's phase prepended, magnitudes linearly
-    interpolated.  Output time length ceil(time / rate)."""
+    interpolated.  Output time length ceil(time / rate).
+    (Torch glue on any device and dtype; `time_stretch` is the batched HIP form, with the phase kept in [-pi, pi].)"""
     if rate == 1:
         return complex_spec
     spec = complex_spec
@@ -242,3 +243,11 @@ def phase_vocoder(complex_spec: torch.Tensor, rate: float = 1.0) -> torch.Tensor
     alphas = (time_steps % 1.0).reshape(1, -1, 1)
     mag = alphas * norm_1 + (1 - alphas) * norm_0
     return torch.cat([mag * torch.cos(phase_acc), mag * torch.sin(phase_acc)], dim=-1)
+
+
+def time_stretch(complex_spec: torch.Tensor, rate: float = 1.0) -> torch.Tensor:
+    """`phase_vocoder` of one [freq, time, chan*2] float32 spectrogram on a ROCm device as ONE HIP launch
+    (`frontend.phase_vocoder_batch`, iris_phase_vocoder): the same frame pairs and formulas with the time grid in double
+    and the running phase reduced to [-pi, pi], three orders of magnitude closer to a float64 evaluation than the fp32
+    torch form above.  Returns a new tensor (a copy at rate 1).  CPU tensors raise: there is no CPU fallback."""
+    return _fe.phase_vocoder_batch([complex_spec], [rate])[0]

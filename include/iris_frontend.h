@@ -734,6 +734,35 @@ int iris_augment_draw(int batch, int n_time, int n_time_masks, int max_time_mask
                       void* stream);
 
 /*
+ * Time stretching of complex spectrograms: the reference's phase_vocoder (transforms.py:137-195) for a RAGGED BATCH of
+ * sources, each with its own rate, in one launch.  Per record: src DEVICE [n_bins, n_in, chan2] fp32 (re block | im block
+ * last), rate > 0, dst DEVICE buffer whose first n_bins * n_out * chan2 floats receive the contiguous [n_bins, n_out, chan2]
+ * result (floats beyond are not written); n_out = ceil(n_in / rate), formed by the caller in double.  Output frame i sits at
+ * ts = (double)i * rate (the grid of numpy.arange(0, n_in, rate) in float64): i0 = floor(ts), alpha = (float)(ts - i0);
+ * frames >= n_in read as zeros;
+ *     mag  = alpha |X[i0 + 1]| + (1 - alpha) |X[i0]|
+ *     step = angle(X[j0 + 1]) - angle(X[j0]) - adv, reduced by 2 pi rint(step / 2 pi), + adv   (j0 = i0 of frame i - 1;
+ *            frame 0 takes angle(X[0]);  adv = pi * bin, i.e. hop_length = n_bins - 1 as in the reference)
+ *     out  = mag (cos, sin)(sum of the steps up to frame i)
+ * The running phase is kept reduced to [-pi, pi] wherever it is stored or carried (the reference lets it grow to pi * bin * i
+ * and loses ~1e-2 of the peak in fp32); against the float64 evaluation |out - ref| <= mag (1e-5 + 16 u pi (i + 1)), u = 2^-24.
+ * mag == 0 gives exactly 0.  rate == 1 copies the source bit for bit.  A record with n_in <= 0, n_out <= 0, rate <= 0 or
+ * n_out > max_out_frames is skipped (nothing written): the table lives on the device and cannot be checked here without a
+ * synchronisation.  src and dst must not overlap.
+ * Checked before any HIP call (IRIS_E_INVALID): n_src < 0, n_bins < 2, chan2 odd or <= 0, NULL table with n_src > 0,
+ * max_out_frames <= 0; IRIS_E_UNSUPPORTED: chan2 > 512, n_src > 65535.  n_src == 0 returns 0 and launches nothing.
+ * One launch on `stream`; no workspace, no atomics, no synchronisation: capturable, bitwise reproducible.  Runs on the
+ * current HIP device.
+ */
+typedef struct {
+    const float* src;
+    float* dst;
+    int32_t n_in, n_out;
+    double rate;
+} iris_voc_src;
+int iris_phase_vocoder(const void* table_dev, int n_src, int n_bins, int chan2, int max_out_frames, void* stream);
+
+/*
  * Per-kernel timing for bench.py: with enable = n > 0 every n-th call of
  * iris_wav_to_logmel carries a start/stop hipEvent pair around each of its
  * kernels on the launch stream (n = 1: every call; an event pair costs a few

@@ -1,0 +1,321 @@
+"""GPU tests of the time-stretch augmentation (iris_phase_vocoder, csrc/k_vocoder.h): parity with the fp64 oracle under the
+error rule of tests/test_stretch_host.py, ragged batches, exact zeros and untouched tails, bit reproducibility (repeat, second
+stream, graph replay), `DeviceMixer.enable_stretch` / `restretch` against the oracle's mixing, and the 'stretch' run name.
+
+Kernel's own worst ratio |out - ref| / (mag u pi (t + 1)) on one MI355X over the cases of test_single_source_meets_the_rule:
+2.49 (at the reference's KAT shape [257, 100, 6], rate 0.5), 0.078 of the rule's bound - beside the yardstick's 2.92 (DESIGN.md
+section 4, K2v; profiles/stretch/kernel_error_ratios.log).  The test prints every case."""
+import ctypes as C
+import json
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import frontend_ref as R
+from test_stretch_host import K, RATES, make_spec, oracle_and_mag, rule_ratio
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available()
+    return torch.device("cuda", 0)
+
+
+def _stretch(dev, spec, rate):
+    from challenge_amd import transforms as T
+    return T.time_stretch(torch.from_numpy(np.ascontiguousarray(spec)).to(dev), rate).cpu().numpy()
+
+
+def test_single_source_meets_the_rule(dev, golden_dir):
+    with open(os.path.join(golden_dir, "ref_kats.json")) as f:
+        k = json.load(f)["phase_vocoder_shapes"]
+    cases = [((k["n_freq"], k["time"], k["chan2"]), RATES), ((257, 600, 4), RATES), ((513, 200, 2), RATES), ((33, 50, 2), RATES),
+             ((65, 1, 4), RATES), ((65, 2, 4), RATES), ((33, 5, 4), [7.0, 5.5]), ((129, 5000, 2), RATES)]
+    worst_raw, worst_rule, where = 0.0, 0.0, None
+    for n, (shape, rates) in enumerate(cases):
+        spec = make_spec(shape, 100 + n)
+        for rate in rates:
+            ref, mag = oracle_and_mag(spec, rate)
+            out = _stretch(dev, spec, rate)
+            assert out.shape == ref.shape == (shape[0], math.ceil(shape[1] / rate), shape[2]) and out.dtype == np.float32
+            raw, rule = rule_ratio(out, ref, mag)
+            print(f"k_phase_vocoder {shape} rate {rate}: |out - ref| / (mag u pi (t + 1)) <= {raw:.3f}; over the rule's bound {rule:.3f}")
+            if raw > worst_raw:
+                worst_raw, where = raw, (shape, rate)
+            worst_rule = max(worst_rule, rule)
+            assert rule <= 1.0, (shape, rate, raw, rule)
+    assert math.ceil(5 / 7.0) == 1    # the rate larger than T gave a single frame
+    print(f"k_phase_vocoder: worst |out - ref| / (mag u pi (t + 1)) = {worst_raw:.3f} at {where}; worst over the bound (K = {K}) "
+          f"{worst_rule:.3f}")
+
+
+def test_ragged_batch_equals_single_calls(dev):
+    from challenge_amd import _native as N
+    from challenge_amd import frontend as FE
+    rng = np.random.default_rng(7)
+    lengths = [int(t) for t in rng.permutation(np.arange(30, 30 + 24 * 17, 17))]
+    rates = [float(r) for r in rng.uniform(0.5, 2.0, size=24)]
+    rates[5] = 1.0
+    assert len(set(lengths)) == 24 and len(set(rates)) == 24
+    specs = [torch.from_numpy(make_spec((65, t, 4), 200 + i)).to(dev) for i, t in enumerate(lengths)]
+    batch = FE.phase_vocoder_batch(specs, rates)
+    for s, r, b in zip(specs, rates, batch):
+        single = FE.phase_vocoder_batch([s], [r])[0]
+        assert b.shape == (65, math.ceil(s.shape[1] / r), 4) and torch.equal(b, single)
+    assert torch.equal(batch[5], specs[5]) and batch[5].data_ptr() != specs[5].data_ptr()   # rate 1: a bit-identical copy
+    # no sources: status 0, nothing launched, nothing written
+    assert FE.phase_vocoder_batch([], []) == []
+    dst = torch.full((65 * 40 * 4,), -7.0, device=dev)
+    table = np.zeros(1, FE.VOC_SRC)
+    table[0] = (specs[0].data_ptr(), dst.data_ptr(), lengths[0], 40, 1.0)
+    table_d = torch.from_numpy(table.view(np.uint8).reshape(-1)).to(dev)
+    assert N.lib().iris_phase_vocoder(table_d.data_ptr(), 0, 65, 4, 40, None) == 0
+    torch.cuda.synchronize()
+    assert bool((dst == -7.0).all())
+
+
+def test_zeros_silent_tails_and_the_floats_beyond(dev):
+    from challenge_amd import frontend as FE
+    zero = torch.zeros((33, 77, 4), device=dev)
+    for rate in (0.8, 1.2):
+        out = FE.phase_vocoder_batch([zero], [rate])[0]
+        assert out.shape[1] == math.ceil(77 / rate) and torch.count_nonzero(out) == 0
+    silent_from = 60
+    spec = make_spec((33, 90, 4), 3)
+    spec[:, silent_from:] = 0
+    for rate in (0.5, 0.8, 0.93, 1.07, 1.2, 2.0):
+        n = math.ceil(90 / rate)
+        buf = torch.full((33 * n * 4 + 1000,), -7.0, device=dev)
+        out = FE.phase_vocoder_batch([torch.from_numpy(spec).to(dev)], [rate], out=[buf])[0]
+        assert out.data_ptr() == buf.data_ptr() and out.shape == (33, n, 4)
+        assert bool((buf[33 * n * 4:] == -7.0).all())                  # the floats beyond F * n * 2C keep the sentinel
+        got = out.cpu().numpy()
+        i0 = np.floor(np.arange(n, dtype=np.float64) * rate).astype(np.int64)
+        assert np.all(got[:, i0 >= silent_from] == 0)                  # both frames of the pair are silent: exactly zero
+        edge = (i0 == silent_from - 1)                                 # the pair straddles the boundary: (1 - alpha) |X[s - 1]|
+        alpha = (np.arange(n, dtype=np.float64) * rate - i0)[edge]
+        assert np.all((np.abs(got[:, edge]).max(axis=(0, 2)) > 0) == (alpha < 1))
+        assert edge.any() == (rate < 1.2)                              # (the grids of rates 1.2 and 2 step over frame 59)
+        assert np.all(np.abs(got[:, i0 < silent_from - 1]).max(axis=(0, 2)) > 0)
+
+
+def test_repeat_second_stream_and_graph_replay_are_bitwise_equal(dev):
+    from challenge_amd import _native as N
+    from challenge_amd import frontend as FE
+    specs = [torch.from_numpy(make_spec((129, t, 4), 300 + i)).to(dev) for i, t in enumerate((700, 33, 1500))]
+    rates = [0.8, 1.2, 0.93]
+    a = FE.phase_vocoder_batch(specs, rates)
+    b = FE.phase_vocoder_batch(specs, rates)
+    assert all(torch.equal(x, y) for x, y in zip(a, b))
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        c = FE.phase_vocoder_batch(specs, rates)
+    torch.cuda.current_stream().wait_stream(side)
+    assert all(torch.equal(x, y) for x, y in zip(a, c))
+    # the launch alone (table uploaded beforehand) captured into a graph and replayed: a single-branch graph
+    outs = [torch.zeros_like(x) for x in a]
+    table = np.zeros(3, FE.VOC_SRC)
+    for i, (s, r, o) in enumerate(zip(specs, rates, outs)):
+        table[i] = (s.data_ptr(), o.data_ptr(), s.shape[1], o.shape[1], r)
+    table_d = torch.from_numpy(table.view(np.uint8).reshape(-1)).to(dev)
+    max_out = max(int(o.shape[1]) for o in outs)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, capture_error_mode="thread_local"):
+        rc = N.lib().iris_phase_vocoder(table_d.data_ptr(), 3, 129, 4, max_out, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert rc == 0
+    g.replay()
+    torch.cuda.synchronize()
+    assert all(torch.equal(x, y) for x, y in zip(a, outs))
+    specs[0].copy_(specs[0].flip(1))
+    g.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(outs[0], FE.phase_vocoder_batch([specs[0]], [rates[0]])[0]) and torch.equal(outs[2], a[2])
+
+
+def _corpus(rng, F=33, C2=4):
+    def clip(t, silent_from=None):
+        x = rng.standard_normal((F, t, C2)).astype(np.float32)
+        if silent_from is not None:
+            x[:, silent_from:] = 0     # silent tail: stays exactly zero after stretching, so those frames are inactive
+        return x
+    backgrounds = [clip(t) for t in (20, 70, 48)]
+    voices = [clip(t, s) for t, s in ((30, 20), (55, None), (41, 5), (64, 50), (25, None), (48, 30), (36, None))]
+    noises = [clip(t) for t in (18, 90, 40, 52)]
+    return backgrounds, voices, noises
+
+
+def _oracle_mix(draws, backgrounds, voices, labels, noises, n_frame, n_classes):
+    F, C2 = backgrounds[0].shape[0], backgrounds[0].shape[2]
+    out = []
+    for d in draws:
+        def padded(bank, idx, length):
+            p = np.zeros((len(idx), F, length, C2), np.float32)
+            for j, k in enumerate(idx):
+                p[j, :, :bank[k].shape[1]] = bank[k]
+            return p
+        out.append(R.merge_complex_specs_apply(backgrounds[d["bg"]], padded(voices, d["voices"], d["v_len"]), labels[d["voices"]],
+                                               padded(noises, d["noises"], d["n_len"]), d, n_frame=n_frame, n_classes=n_classes,
+                                               min_ratio=1))
+    return out
+
+
+def test_device_mixer_restretch(dev):
+    from challenge_amd import _native as N
+    from challenge_amd.mixer import DeviceMixer
+    rng = np.random.default_rng(11)
+    n_frame, n_classes, F, C2 = 48, 3, 33, 4
+    backgrounds, voices, noises = _corpus(rng)
+    labels = np.eye(n_classes, dtype=np.float32)[rng.integers(0, n_classes, len(voices))]
+    kw = dict(n_frame=n_frame, max_voices=4, max_noises=3, n_classes=n_classes, device=dev, min_ratio=1)
+    T0 = np.array([v.shape[1] for v in voices])
+    rates = np.array([0.8, 1.19, 1.0, 0.93, 1.07, 0.85, 1.1])
+
+    mixer = DeviceMixer(backgrounds, voices, labels, noises, seed=5, **kw)
+    mixer.enable_stretch()
+    assert np.array_equal(mixer._v_T, T0) and all(torch.equal(a, torch.from_numpy(b).to(dev)) for a, b in zip(mixer.voices, voices))
+    ptrs = (mixer._v_ptr.copy(), mixer._v_act.copy())
+    used = mixer.restretch(rates)
+    assert np.array_equal(used, rates)
+    want_T = np.array([math.ceil(t / r) for t, r in zip(T0, rates)])
+    assert np.array_equal(mixer._v_T, want_T) and [int(v.shape[1]) for v in mixer.voices] == list(want_T)
+    stretched = [v.cpu().numpy() for v in mixer.voices]
+    for v, s, r in zip(voices, stretched, rates):   # what the buffers hold is the kernel's stretch of the ORIGINAL voice
+        assert np.array_equal(s, v if r == 1 else _stretch(dev, v, r))
+    # frame activity == a fresh iris_mix_frame_active of the stretched voice (== max over freq, chan2 > 0)
+    for s, act, n in zip(stretched, mixer.voice_active, want_T):
+        fresh = torch.empty(int(n), device=dev)
+        N.check(N.lib().iris_mix_frame_active(torch.from_numpy(s).to(dev).data_ptr(), F, int(n), C2, fresh.data_ptr(), None), "active")
+        torch.cuda.synchronize()
+        assert torch.equal(act[:int(n)], fresh) and np.array_equal(fresh.cpu().numpy(), (s.max(axis=(0, 2)) > 0).astype(np.float32))
+    assert any(0 < float(a[:int(n)].sum()) < n for a, n in zip(mixer.voice_active, want_T))   # silent tails survived the stretch
+    # mixing from the stretched corpus == the oracle's mixing of the stretched voices, bit for bit, labels included
+    draws = mixer.draw(16)
+    spec, lab = mixer.mix(16, draws)
+    for i, (ref_spec, ref_lab) in enumerate(_oracle_mix(draws, backgrounds, stretched, labels, noises, n_frame, n_classes)):
+        assert np.array_equal(spec[i].cpu().numpy(), ref_spec) and np.array_equal(lab[i].cpu().numpy(), ref_lab), i
+    assert float(lab.sum()) > 0
+    # addresses never move: two more (random) restretches
+    r1, r2 = mixer.restretch().copy(), mixer.restretch().copy()
+    assert np.all((r1 >= 0.8) & (r1 < 1.2)) and not np.array_equal(r1, r2)
+    assert np.array_equal(mixer._v_ptr, ptrs[0]) and np.array_equal(mixer._v_act, ptrs[1])
+    assert [v.data_ptr() for v in mixer.voices] == list(ptrs[0]) and [a.data_ptr() for a in mixer.voice_active] == list(ptrs[1])
+    with pytest.raises(ValueError):
+        mixer.restretch(np.full(7, 0.5))          # below lo: would not fit the buffers
+    with pytest.raises(ValueError):
+        mixer.restretch(np.ones(6))
+    with pytest.raises(RuntimeError):
+        DeviceMixer(backgrounds, voices, labels, noises, seed=5, **kw).restretch()
+
+    # all rates 1 == a mixer on which enable_stretch was never called, same seed
+    plain = DeviceMixer(backgrounds, voices, labels, noises, seed=21, **kw)
+    ones = DeviceMixer(backgrounds, voices, labels, noises, seed=21, **kw)
+    ones.enable_stretch()
+    ones.restretch(np.ones(7))
+    for _ in range(2):
+        (sa, la), (sb, lb) = plain.mix(8), ones.mix(8)
+        assert torch.equal(sa, sb) and torch.equal(la, lb)
+
+    # with the draws on the device, in either call order: the T fields of the drawn records are the new lengths
+    for order in ("stretch_first", "draw_first"):
+        m = DeviceMixer(backgrounds, voices, labels, noises, seed=5, **kw)
+        if order == "stretch_first":
+            m.enable_stretch()
+            m.enable_device_draw(77)
+        else:
+            m.enable_device_draw(77)
+            m.enable_stretch()
+        m.restretch(rates)
+        spec, lab = m.mix(16)
+        table = m.last_table(16)
+        dd = m.table_to_draws(table)
+        bank = [v.cpu().numpy() for v in m.voices]
+        for i, d in enumerate(dd):
+            assert np.array_equal(table[i]["T"][1:5], want_T[d["voices"]]), (order, i)
+            assert np.array_equal(table[i]["src"][1:5], m._v_ptr[d["voices"]]) and np.array_equal(table[i]["active"][1:5], m._v_act[d["voices"]])
+        for i, (ref_spec, ref_lab) in enumerate(_oracle_mix(dd, backgrounds, bank, labels, noises, n_frame, n_classes)):
+            assert np.array_equal(spec[i].cpu().numpy(), ref_spec) and np.array_equal(lab[i].cpu().numpy(), ref_lab), (order, i)
+
+
+def test_stretch_run_name_in_make_device_dataset(dev):
+    from challenge_amd import data_utils as D
+    from challenge_amd import sj_train as S
+    from challenge_amd.mixer import DeviceMixer
+    args = ['--v', '9', '--n_mels', '40', '--n_frame', '64', '--n_chan', '2', '--batch_size', '6', '--max_voices', '4',
+            '--max_noises', '3', '--steps_per_epoch', '2']
+    sources = S.synthetic_sources(2, 3, freq=257, n_bg=3, n_voice=7, n_noise=4, seed=3)
+    backgrounds, voices, labels, noises = sources
+    T0 = np.array([v.shape[1] for v in voices])
+    ds = S.make_device_dataset(S.ARGS().get(args + ['--name', 'run_stretch']), training=True, sources=sources, device=dev, seed=4)
+    assert ds.mixer._st is not None and not np.array_equal(ds.mixer._v_T, T0)
+    it = iter(ds)
+    for _ in range(3):   # steps_per_epoch = 2: the third batch comes after a second restretch
+        bx, by = next(it)
+        assert bx.shape == (6, 40, 64, 2) and by.shape == (6, 2, 3)
+        assert torch.isfinite(bx).all() and float(by.min()) >= 0 and float(by.max()) <= 1
+    assert np.all(ds.mixer._v_T >= np.ceil(T0 / 1.2)) and np.all(ds.mixer._v_T <= np.ceil(T0 / 0.8))
+    # validation sets are never stretched
+    val = S.make_device_dataset(S.ARGS().get(args + ['--name', 'run_stretch']), training=False, sources=sources, device=dev, seed=4)
+    assert getattr(val.mixer, "_st", None) is None and np.array_equal(val.mixer._v_T, T0)
+    # without the token: the first batch of the code path as it was (a mixer built here, the same seeds, the same stages)
+    cfg = S.ARGS().get(args + ['--name', 'run'])
+    plain = S.make_device_dataset(cfg, training=True, sources=sources, device=dev, seed=4)
+    assert getattr(plain.mixer, "_st", None) is None
+    bx, by = next(iter(plain))
+    mixer = DeviceMixer(backgrounds, voices, np.eye(3, dtype=np.float32)[np.asarray(labels)], noises, n_frame=64, max_voices=4,
+                        max_noises=3, n_classes=3, device=dev, snr=cfg.snr, min_ratio=1, seed=4)
+    x, y = D.to_frame_labels(*mixer.mix(6))
+    tb, fb = D.augment_draw_batch(6, 64, 257, np.random.default_rng(5))
+    x, y = S.complex_to_mel(40, 257)(x, y, t_bands=tb, f_bands=fb)
+    x, y = S.label_downsample(32)(*D.minmax_log_on_mel(x, y))
+    assert torch.equal(bx, x) and torch.equal(by, y)
+
+
+def test_refusals(dev):
+    from challenge_amd import _native as N
+    from challenge_amd import frontend as FE
+    from challenge_amd import transforms as T
+    cpu = torch.zeros(33, 20, 4)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        FE.phase_vocoder_batch([cpu], [0.8])
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        T.time_stretch(cpu, 0.8)
+    spec = torch.from_numpy(make_spec((33, 20, 4), 0)).to(dev)
+    with pytest.raises(ValueError):
+        FE.phase_vocoder_batch([spec], [0.0])
+    with pytest.raises(ValueError):
+        FE.phase_vocoder_batch([spec, spec[:, :, :2].contiguous()], [0.8, 0.8])
+    with pytest.raises(ValueError, match="fewer than"):   # 25 frames at rate 0.8; room for 24
+        FE.phase_vocoder_batch([spec], [0.8], out=[torch.empty(33 * 24 * 4, device=dev)])
+    # at the ABI the table lives on the device: a record whose n_out exceeds max_out_frames is skipped, nothing is written
+    dst = torch.full((33 * 25 * 4,), -7.0, device=dev)
+    table = np.zeros(1, FE.VOC_SRC)
+    table[0] = (spec.data_ptr(), dst.data_ptr(), 20, 25, 0.8)
+    table_d = torch.from_numpy(table.view(np.uint8).reshape(-1)).to(dev)
+    assert N.lib().iris_phase_vocoder(table_d.data_ptr(), 1, 33, 4, 24, None) == 0
+    torch.cuda.synchronize()
+    assert bool((dst == -7.0).all())
+    assert N.lib().iris_phase_vocoder(table_d.data_ptr(), 1, 33, 4, 25, None) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(dst.view(33, 25, 4), T.time_stretch(spec, 0.8))
+
+
+def test_three_orders_closer_than_the_torch_fp32_form(dev):
+    """[257, 600, 4]: the kernel is within 1e-3 of the fp64 oracle's peak where the torch fp32 form of the same function (the only
+    form there was before) is 1e-2 off: it lets the phase grow to pi * bin * frame."""
+    from challenge_amd import transforms as T
+    spec = make_spec((257, 600, 4), 42)
+    sd = torch.from_numpy(spec).to(dev)
+    for rate in (0.8, 0.93, 1.07, 1.2):
+        ref, _ = oracle_and_mag(spec, rate)
+        peak = np.abs(ref).max()
+        kernel = np.abs(T.time_stretch(sd, rate).cpu().numpy() - ref).max() / peak
+        torch32 = np.abs(T.phase_vocoder(sd, rate).cpu().numpy() - ref).max() / peak
+        print(f"[257, 600, 4] rate {rate}: max|out - ref| / max|ref| kernel {kernel:.2e}, torch fp32 form {torch32:.2e}")
+        assert kernel <= 1e-3 and kernel < torch32, (rate, kernel, torch32)
