@@ -30,6 +30,8 @@
 //   k_pcen_grad.h    the trainable layer's backward: gradient with respect to the per-band parameters, two launches, no atomics
 //   k_vocoder.h      time stretching: a batched phase vocoder over a ragged set of spectrograms, the running phase as the same
 //                    chunked scan modulo 2 pi
+//   k_speed.h        speed perturbation: a batched band-limited resampler over a ragged set of waveforms, each at its own
+//                    real-valued rate, and the frame activity of the results, one launch each
 //   host_plan.h      mel matrix, constant tables, plan create / destroy
 //   host_ops.h       the operators' C-ABI entry points
 #include "common.h"
@@ -58,3 +60,4 @@
 #include "k_pcen.h"
 #include "k_pcen_grad.h"
 #include "k_vocoder.h"
+#include "k_speed.h"

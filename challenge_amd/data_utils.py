@@ -142,6 +142,13 @@ def wants_stretch(name: str) -> bool:
     return 'stretch' in name
 
 
+def wants_speed(name: str) -> bool:
+    """Whether a run name asks for speed perturbation of the voice corpus: the token 'speed' in it (the same idiom).
+    Honoured by `sj_train.make_wave_dataset(training=True)` alone (`WaveMixer.enable_speed` / `respeed`); `make_dataset` and
+    `make_device_dataset` refuse it.  It does not interact with `feature_compression`."""
+    return 'speed' in name
+
+
 def augment(specs: torch.Tensor, labels, time_axis: int = -2, freq_axis: int = -3):
     """6 time masks (< 24 frames) then 1 frequency mask (< 16 linear bins) on the complex
     spectrogram (data_utils.py:58-61)."""

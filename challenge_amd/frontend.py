@@ -1024,6 +1024,73 @@ def phase_vocoder_batch(specs, rates, out=None):
     return results
 
 
+# mirrors iris_speed_src (include/iris_frontend.h)
+SPEED_SRC = np.dtype([("src", "<u8"), ("dst", "<u8"), ("len_in", "<i4"), ("len_out", "<i4"), ("rate", "<f8")])
+assert SPEED_SRC.itemsize == 32
+
+
+def speed_len(length: int, rate: float) -> int:
+    """Samples of a waveform of `length` samples played `rate` times faster: ceil(length / rate) in double, the length of
+    numpy.arange(0, length, rate) (the law of `stretched_frames`)."""
+    rate = float(rate)
+    if not (np.isfinite(rate) and rate > 0):
+        raise ValueError(f"speed rate must be a positive finite number, got {rate}")
+    return int(np.ceil(float(length) / rate))
+
+
+def speed_perturb_launch(table: np.ndarray, channels: int, max_out_len: int, device: torch.device,
+                         table_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Upload a SPEED_SRC table (into `table_dev`, a long-lived uint8 device buffer, when given) and run iris_speed_perturb over
+    it on the current stream: one launch.  Returns the device table (tied to the stream when it was allocated here)."""
+    raw = torch.from_numpy(np.ascontiguousarray(table).view(np.uint8).reshape(-1))
+    if table_dev is None:
+        dev_table = raw.to(device, non_blocking=True)
+    else:
+        dev_table = table_dev[:raw.numel()]
+        dev_table.copy_(raw)
+    with torch.cuda.device(device):
+        rc = N.lib().iris_speed_perturb(dev_table.data_ptr(), int(table.shape[0]), int(channels), int(max_out_len),
+                                        _stream_ptr(device))
+    N.check(rc, "iris_speed_perturb")
+    if table_dev is None and dev_table.numel():
+        dev_table.record_stream(torch.cuda.current_stream(device))
+    return dev_table
+
+
+def speed_perturb_batch(waves, rates):
+    """Speed-perturb a ragged batch of waveforms in ONE launch (iris_speed_perturb): waves is a list of [C, L_i] float32
+    tensors on one ROCm device (equal C), rates as many positive numbers (rate > 1 = faster and shorter: tempo and pitch move
+    together).  Returns a list of new [C, ceil(L_i / rate_i)] tensors: the Hann-windowed sinc of torchaudio's `resample`
+    (width 6, rolloff 0.99) evaluated at the real-valued positions m * rate_i, |out - fp64| <= 8 u cut sum |x| over the
+    support; a rate of 1 copies its source.  CPU tensors raise: there is no CPU fallback."""
+    waves, rates = list(waves), [float(r) for r in rates]
+    if len(waves) != len(rates):
+        raise ValueError(f"speed_perturb_batch: {len(waves)} waveforms but {len(rates)} rates")
+    if not waves:
+        return []
+    waves = [_require_device_f32(w, f"waves[{i}]") for i, w in enumerate(waves)]
+    dev = waves[0].device
+    if waves[0].dim() != 2:
+        raise ValueError("speed_perturb_batch: every waveform must be [chan, samples]")
+    chan = int(waves[0].shape[0])
+    table = np.zeros(len(waves), SPEED_SRC)
+    results = []
+    for i, (w, r) in enumerate(zip(waves, rates)):
+        if w.dim() != 2 or int(w.shape[0]) != chan or w.device != dev or int(w.shape[1]) < 1 or chan < 1:
+            raise ValueError(f"speed_perturb_batch: waves[{i}] has shape {tuple(w.shape)} on {w.device}; expected "
+                             f"[{chan} >= 1, L >= 1] on {dev}")
+        n = speed_len(int(w.shape[1]), r)
+        if n > 2 ** 31 - 1:
+            raise ValueError(f"speed_perturb_batch: waves[{i}] at rate {r} would have {n} samples (> 2^31 - 1)")
+        o = torch.empty((chan, n), dtype=torch.float32, device=dev)
+        table[i] = (w.data_ptr(), o.data_ptr(), int(w.shape[1]), n, r)
+        results.append(o)
+    speed_perturb_launch(table, chan, int(table["len_out"].max()), dev)
+    for w in waves:   # (a contiguous copy made above must outlive the kernel)
+        w.record_stream(torch.cuda.current_stream(dev))
+    return results
+
+
 def complex_to_magphase(x: torch.Tensor) -> torch.Tensor:
     x = _require_device_f32(x, "complex_tensor")
     c2 = int(x.shape[-1])

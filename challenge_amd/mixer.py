@@ -69,6 +69,13 @@ def stretch_rates(rng: np.random.Generator, n: int, lo: float = 0.8, hi: float =
     return rng.uniform(float(lo), float(hi), size=int(n))
 
 
+def check_speed_range(lo: float, hi: float) -> None:
+    """The rate range of `WaveMixer.enable_speed`: finite, 0 < lo <= hi."""
+    lo, hi = float(lo), float(hi)
+    if not (np.isfinite(lo) and np.isfinite(hi) and 0 < lo <= hi):
+        raise ValueError(f"speed rates must satisfy 0 < lo <= hi (finite), got lo = {lo}, hi = {hi}")
+
+
 class BatchDraw:
     """The random decisions of one batch as arrays (B samples, V = max_voices, N = max_noises):
     bg [B], bg_offset [B], voices [B, V], v_len [B], n_voices [B], v_gain [B, V] f32, v_offset [B, V],
@@ -390,6 +397,10 @@ class DeviceMixer:
         st["rates"] = rates.copy()
         return st["rates"]
 
+    def enable_speed(self, lo: float = 0.9, hi: float = 1.1) -> None:
+        raise NotImplementedError("DeviceMixer.enable_speed: a spectrum corpus cannot be resampled in time (speed perturbation "
+                                  "works on waveforms: use WaveMixer; this corpus has enable_stretch)")
+
     def _draw_on_device(self, batch: int):
         """(table_d [batch * stride, 48 B], first_d [batch + 1], n_srcs) written by iris_mix_draw on the current stream."""
         dd, dev = self._dd, self.device
@@ -519,6 +530,83 @@ class WaveMixer(DeviceMixer):
     def enable_stretch(self, lo: float = 0.8, hi: float = 1.2) -> None:
         raise NotImplementedError("WaveMixer.enable_stretch: a waveform corpus has no spectra to stretch (the phase vocoder "
                                   "works on complex spectrograms: use DeviceMixer)")
+
+    # -- speed perturbation of the voice corpus ------------------------------------------
+    def enable_speed(self, lo: float = 0.9, hi: float = 1.1) -> None:
+        """Keep a speed-perturbed copy of every voice beside the original and mix from the copies: `respeed()` then resamples
+        the whole voice corpus by fresh rates ~ U[lo, hi) in one launch (`iris_speed_perturb`: tempo and pitch move together,
+        the standard 0.9 .. 1.1 of speech and sound-event training).  One buffer per voice with room for ceil(L_i / lo) samples
+        per channel and its frame-activity vector of 1 + capacity // hop frames are allocated here and never move: the pointer
+        tables (and the device-side corpus of `enable_device_draw`, in either call order) are switched to them once, so a
+        captured `mix` replayed after a `respeed` reads the new contents through unchanged addresses.  Until the first
+        `respeed` the copies hold the voices at rate 1 (bit-identical).  Backgrounds and noises are not perturbed: they carry
+        no labels.  No accuracy claim is made for the augmentation."""
+        check_speed_range(lo, hi)
+        if getattr(self, "_sp", None) is not None:
+            raise RuntimeError("enable_speed was already called on this mixer")
+        from . import frontend as _fe
+        orig, orig_L = list(self.voices), self._v_L.copy()
+        cap = np.array([_fe.speed_len(int(n), lo) for n in orig_L], np.int64)
+        if cap.max() > 2 ** 31 - 1:
+            raise ValueError(f"enable_speed: a voice at rate {lo} would have {cap.max()} samples (> 2^31 - 1)")
+        bufs = [torch.zeros(self.channels * int(c), device=self.device, dtype=torch.float32) for c in cap]
+        acts = [torch.zeros(1 + int(c) // self.hop, device=self.device, dtype=torch.float32) for c in cap]
+        table = np.zeros(len(orig), _fe.SPEED_SRC)
+        table["src"], table["dst"] = [t.data_ptr() for t in orig], [b.data_ptr() for b in bufs]
+        table["len_in"] = orig_L
+        act_ptr = np.array([a.data_ptr() for a in acts], np.uint64)
+        self._sp = {"lo": float(lo), "hi": float(hi), "orig": orig, "orig_L": orig_L, "cap": cap, "bufs": bufs, "acts": acts,
+                    "table": table, "rates": None,
+                    "table_dev": torch.empty(max(table.nbytes, 1), dtype=torch.uint8, device=self.device),
+                    "act_ptr_dev": torch.from_numpy(act_ptr.astype(np.int64)).to(self.device)}
+        self.voice_active = acts
+        self._v_ptr = np.array([b.data_ptr() for b in bufs], np.uint64)
+        self._v_act = act_ptr
+        dd = getattr(self, "_dd", None)
+        if dd is not None:
+            dd["voice_arrays"]["src"].copy_(torch.from_numpy(self._v_ptr.astype(np.int64)))
+            dd["voice_arrays"]["act"].copy_(torch.from_numpy(self._v_act.astype(np.int64)))
+        self.respeed(np.ones(len(orig)))
+
+    def respeed(self, rates=None) -> np.ndarray:
+        """Resample every ORIGINAL voice anew into its buffer: rate_i ~ U[lo, hi) from the mixer's own NumPy generator (or the
+        given `rates`, one per voice, each >= lo so that the result fits its buffer), ONE `iris_speed_perturb` launch over the
+        whole voice corpus and ONE `iris_mix_wave_frame_active_batch` launch for the frame activity of the results (the labels
+        follow the perturbed voice; a silent tail stays exactly zero).  The voices' lengths change to L' = ceil(L_i / rate_i)
+        and their frame counts to 1 + L' // hop, on the host (`_v_L`, `_v_T`, `voices`) and in place in the device corpus of
+        `enable_device_draw`.  Call it outside any graph capture.  Backgrounds and noises are not perturbed.  Returns the rates
+        used."""
+        sp = getattr(self, "_sp", None)
+        if sp is None:
+            raise RuntimeError("respeed needs enable_speed() first")
+        from . import frontend as _fe
+        n_voice = len(sp["orig"])
+        if rates is None:
+            rates = stretch_rates(self.rng, n_voice, sp["lo"], sp["hi"])
+        rates = np.asarray(rates, np.float64).reshape(-1)
+        if rates.shape[0] != n_voice:
+            raise ValueError(f"respeed: {rates.shape[0]} rates for {n_voice} voices")
+        n_out = np.array([_fe.speed_len(int(n), r) for n, r in zip(sp["orig_L"], rates)], np.int64)
+        if np.any(n_out > sp["cap"]):
+            i = int(np.argmax(n_out > sp["cap"]))
+            raise ValueError(f"respeed: voice {i} at rate {rates[i]} needs {n_out[i]} samples but its buffer holds "
+                             f"{sp['cap'][i]} (rates below lo = {sp['lo']} do not fit)")
+        table = sp["table"]
+        table["len_out"], table["rate"] = n_out, rates
+        table_dev = _fe.speed_perturb_launch(table, self.channels, int(sp["cap"].max()), self.device, sp["table_dev"])
+        with torch.cuda.device(self.device):
+            rc = N.lib().iris_mix_wave_frame_active_batch(table_dev.data_ptr(), n_voice, self.channels, self.n_fft, self.hop,
+                                                          sp["act_ptr_dev"].data_ptr(), 1 + int(sp["cap"].max()) // self.hop,
+                                                          C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        N.check(rc, "iris_mix_wave_frame_active_batch")
+        self._v_L, self._v_T = n_out, 1 + n_out // self.hop
+        self.voices = [b[:self.channels * int(n)].view(self.channels, int(n)) for b, n in zip(sp["bufs"], n_out)]
+        dd = getattr(self, "_dd", None)
+        if dd is not None:
+            dd["voice_arrays"]["T"].copy_(torch.from_numpy(self._v_T.astype(np.int32)))
+            dd["voice_arrays"]["len"].copy_(torch.from_numpy(n_out.astype(np.int32)))
+        sp["rates"] = rates.copy()
+        return sp["rates"]
 
     def mix(self, batch: int, draws=None):
         """One batch of (waveforms [B, C, (n_frame - 1) * hop], labels [B, max_voices, n_frame, n_classes])."""

@@ -208,6 +208,9 @@ def make_dataset(config, training=True, n_classes=3, sources=None):
     if _du.wants_stretch(config.name):
         raise ValueError(f"run name {config.name!r} asks for 'stretch': time stretching runs on the device-resident corpus "
                          "(make_device_dataset); the per-sample host pipeline does not stretch")
+    if _du.wants_speed(config.name):
+        raise ValueError(f"run name {config.name!r} asks for 'speed': speed perturbation runs on the resident waveform corpus "
+                         "(make_wave_dataset); the per-sample host pipeline does not resample")
     backgrounds, voices, labels, noises = _load_sources(config, training, n_classes, sources)
 
     pipeline = make_pipeline(backgrounds, voices, labels, noises, n_frame=config.n_frame,
@@ -247,6 +250,9 @@ def make_device_dataset(config, training=True, n_classes=3, sources=None, device
     creation and again every config.steps_per_epoch batches (`DeviceMixer.enable_stretch` / `restretch`, one
     `iris_phase_vocoder` launch over the corpus); a name without the token takes no new code path."""
     from .mixer import DeviceMixer
+    if _du.wants_speed(config.name):
+        raise ValueError(f"run name {config.name!r} asks for 'speed': a spectrum corpus cannot be resampled in time "
+                         "(use make_wave_dataset; this path has 'stretch')")
     backgrounds, voices, labels, noises = _load_sources(config, training, n_classes, sources)
     if config.model_type == 'se' and config.v == 9:
         raise NotImplementedError("model_type 'se' is outside the accelerated path (SURVEY.md section 2)")
@@ -331,7 +337,10 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
     and channel counts for stereo corpora at n_chan == 1; at n_chan == 2 (the reference's default) they agree up to
     the boundary frames of the waveform-domain mix.  The augmenting maps of n_chan > 2 mix spectra with per-bin
     factors and are not available here.  device_draw=True: sources / offsets / gains / SpecAugment bands are drawn on
-    the device (`iris_mix_draw`, `iris_augment_draw`), as in `make_device_dataset`."""
+    the device (`iris_mix_draw`, `iris_augment_draw`), as in `make_device_dataset`.
+    A 'speed' token in config.name (training sets only): the voice corpus is speed-perturbed by rates ~ U[0.9, 1.1) at
+    creation and again every config.steps_per_epoch batches (`WaveMixer.enable_speed` / `respeed`: one `iris_speed_perturb`
+    and one `iris_mix_wave_frame_active_batch` launch over the corpus); a name without the token takes no new code path."""
     from .mixer import WaveMixer
     if _du.wants_stretch(config.name):
         raise ValueError(f"run name {config.name!r} asks for 'stretch': a waveform corpus has no spectra to stretch "
@@ -358,9 +367,18 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
     if device_draw:
         mixer.enable_device_draw(0 if seed is None else seed)
         band_draw = _du.DeviceAugmentDraw(mixer.device, (0 if seed is None else seed) + 1, filter_bins) if training else None
+    speed = training and _du.wants_speed(config.name)
+    if speed:   # the voice corpus is perturbed anew now and once per epoch (the validation set never is)
+        mixer.enable_speed()
+        mixer.respeed()
 
     def gen():
+        n_batches = 0
         while True:
+            if speed:
+                if n_batches and n_batches % max(int(config.steps_per_epoch), 1) == 0:
+                    mixer.respeed()
+                n_batches += 1
             wav, y = mixer.mix(config.batch_size)
             _, y = to_frame_labels(None, y)
             if config.n_chan == 1 and wav.shape[1] == 2:
@@ -389,7 +407,9 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
         pipeline = pipeline.map(label_downsample(config.n_frame // (config.n_frame * 256 // 16000)))
     if config.loss.upper() in ('MSE', 'MAE'):
         pipeline = pipeline.map(multiply_label(config.mse_multiplier))
-    return pipeline.prefetch(AUTOTUNE)
+    dataset = pipeline.prefetch(AUTOTUNE)
+    dataset.mixer = mixer   # (for inspection: the resident corpus, its draws and - 'speed' runs - the current voice lengths)
+    return dataset
 
 
 class WaveFrontend:

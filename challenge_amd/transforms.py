@@ -251,3 +251,13 @@ def time_stretch(complex_spec: torch.Tensor, rate: float = 1.0) -> torch.Tensor:
     and the running phase reduced to [-pi, pi], three orders of magnitude closer to a float64 evaluation than the fp32
     torch form above.  Returns a new tensor (a copy at rate 1).  CPU tensors raise: there is no CPU fallback."""
     return _fe.phase_vocoder_batch([complex_spec], [rate])[0]
+
+
+def speed_perturb(wav: torch.Tensor, rate: float = 1.0) -> torch.Tensor:
+    """Speed perturbation of one [chan, samples] (or [samples]) float32 waveform on a ROCm device as ONE HIP launch
+    (`frontend.speed_perturb_batch`, iris_speed_perturb): resampled by `rate` with torchaudio's Hann-windowed sinc and played
+    back at the old sample rate, so tempo and pitch move together (rate > 1 = faster, shorter, higher); ceil(samples / rate)
+    samples.  Returns a new tensor (a copy at rate 1).  CPU tensors raise: there is no CPU fallback."""
+    if isinstance(wav, torch.Tensor) and wav.dim() == 1:
+        return _fe.speed_perturb_batch([wav.unsqueeze(0)], [rate])[0][0]
+    return _fe.speed_perturb_batch([wav], [rate])[0]

@@ -763,6 +763,47 @@ typedef struct {
 int iris_phase_vocoder(const void* table_dev, int n_src, int n_bins, int chan2, int max_out_frames, void* stream);
 
 /*
+ * Speed perturbation of waveforms (Ko et al., Interspeech 2015; Kaldi's 0.9 / 1.0 / 1.1): a RAGGED BATCH of waveforms, each
+ * resampled by its own real-valued rate and played back at the old sample rate (tempo and pitch move together), in one launch.
+ * Per record: src DEVICE [channels, len_in] fp32, rate > 0 (rate > 1 = faster and shorter, the convention of
+ * iris_phase_vocoder), dst DEVICE buffer whose first channels * len_out floats receive the contiguous [channels, len_out]
+ * result (floats beyond are not written); len_out = iris_speed_len(len_in, rate) = ceil(len_in / rate), formed in double.
+ * Output sample m sits at pos = (double)m * rate: i0 = floor(pos), frac = (float)(pos - i0), and
+ *     y[c, m] = sum_s x[c, s] * cut * g(cut * ((s - i0) - frac)),      cut = 0.99 * min(1, 1 / rate),
+ *     g(t)    = sinc(pi t) * cos^2(pi t / 12)  for |t| < 6, else 0,     x[c, s] = 0 outside [0, len_in)
+ * - the Hann-windowed sinc of torchaudio.functional.resample (lowpass_filter_width 6, rolloff 0.99) evaluated at a real-valued
+ * position; for a rational rate = o / n it is iris_resample(orig_freq = o, new_freq = n) with no host-built tap table.
+ * Against the float64 evaluation |y - ref| <= 8 u S, u = 2^-24, S = cut * (sum of |x[c, s]| over the support).  An output
+ * sample whose whole support is zero input is exactly 0.  rate == 1 copies the source bit for bit (it does not low-pass at
+ * 0.99).  A record with len_in <= 0, len_out <= 0, rate <= 0, len_out > max_out_len or a NULL pointer is skipped (nothing
+ * written): the table lives on the device and cannot be checked here without a synchronisation.  src and dst must not overlap.
+ * Checked before any HIP call (IRIS_E_INVALID): n_src < 0, channels <= 0, NULL table with n_src > 0, max_out_len <= 0;
+ * IRIS_E_UNSUPPORTED: n_src > 65535.  n_src == 0 returns 0 and launches nothing.
+ * One launch on `stream`; no workspace, no atomics, no synchronisation: capturable, bitwise reproducible, and a record's
+ * result does not depend on the records around it.  Runs on the current HIP device.
+ *
+ * iris_mix_wave_frame_active_batch: the frame activity (iris_mix_wave_frame_active, bit for bit) of every waveform
+ * `dst` [channels, len_out] of the same table in one launch.  Only `dst` and `len_out` of a record are read.
+ *   active_ptrs_dev  DEVICE [n_src] addresses of the DEVICE float vectors that receive the flags: record i writes
+ *                    active_ptrs[i][t] for t < 1 + len_out_i / hop (the vector must hold that many floats); entries beyond
+ *                    are not written
+ *   max_frames       the largest frame count of the table (it sizes the grid, as max_out_len does): a record with
+ *                    len_out <= 0, a NULL dst, a NULL vector or 1 + len_out / hop > max_frames is skipped
+ * Checked before any HIP call (IRIS_E_INVALID): n_src < 0, channels <= 0, n_fft <= 1, hop <= 0, NULL table or NULL
+ * active_ptrs_dev with n_src > 0, max_frames <= 0; IRIS_E_UNSUPPORTED: n_src > 65535.  n_src == 0 launches nothing.
+ */
+typedef struct {
+    const float* src;
+    float* dst;
+    int32_t len_in, len_out;
+    double rate;
+} iris_speed_src;
+long long iris_speed_len(long long len, double rate); /* ceil(len / rate); 0 for len <= 0 or a rate that is not positive and finite */
+int iris_speed_perturb(const void* table_dev, int n_src, int channels, int max_out_len, void* stream);
+int iris_mix_wave_frame_active_batch(const void* table_dev, int n_src, int channels, int n_fft, int hop,
+                                     const void* active_ptrs_dev, int max_frames, void* stream);
+
+/*
  * Per-kernel timing for bench.py: with enable = n > 0 every n-th call of
  * iris_wav_to_logmel carries a start/stop hipEvent pair around each of its
  * kernels on the launch stream (n = 1: every call; an event pair costs a few

@@ -1,0 +1,187 @@
+"""CPU tests of the speed-perturbation augmentation (iris_speed_perturb and its Python surface): the float64 definition against
+the committed resampling oracle, the fp32 yardstick that fixes the error rule's constant, the length law, the run-name token,
+the mixer's range checks and the ABI's argument checks.
+
+Error rule (asserted for the kernel in tests/test_speed_gpu.py against `speed_ref`; u = 2^-24):
+
+    |y - y_ref| <= K u S,      S[c, m] = cut * sum over the support of |x[c, s]|
+
+Every tap is at most `cut` and carries an absolute rounding error proportional to cut u (its argument pi t reaches 19, so near a
+zero of the sinc the error is not small relative to the tap itself); the products and the running sum add a few u each.
+K is not fitted to the kernel.  It comes from `speed_ref.yardstick32`, the same loop in NumPy float32: K = the smallest power of
+two at or above four times the yardstick's worst ratio |y32 - ref| / (u S) over SWEEP.  Measured over SWEEP (3 shapes x 10 seeds
+x 10 rates = 300 cases): worst ratio 1.906 (at [2, 40000], seed 8, rate 0.7509), so K = 8."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+
+from oracle import frontend_ref as R
+from speed_ref import make_wave, rule_ratio, speed_len, speed_ref, yardstick32
+
+K = 8
+SHAPES = [(2, 37), (2, 4096), (2, 40000)]
+SEEDS = list(range(10))
+RATES = [0.5, 0.8, 0.9, 0.93, 1.001, 1.07, 1.1, 1.2, 2.0]
+RATIONAL = [(11, 10), (9, 10), (6, 5), (4, 5), (2, 1), (1, 2), (441, 160)]
+
+
+def random_rate(seed):
+    """The one random rate of a seed: U[0.5, 2)."""
+    return float(np.random.default_rng(1000 + seed).uniform(0.5, 2.0))
+
+
+SWEEP = [(shape, seed, rate) for shape in SHAPES for seed in SEEDS for rate in RATES + [random_rate(seed)]]
+
+
+def test_definition_is_the_committed_resampling_oracle_at_rational_rates():
+    x = np.random.default_rng(0).standard_normal((2, 4000))
+    for o, n in RATIONAL:
+        y, _ = speed_ref(x, o / n)
+        ref = R.resample_waveform(x, o, n)
+        assert y.shape == ref.shape == (2, speed_len(4000, o / n))
+        assert np.abs(y - ref).max() <= 1e-10 * np.abs(ref).max(), (o, n)
+
+
+def test_yardstick_meets_the_rule_with_the_committed_constant():
+    worst, where = 0.0, None
+    for shape, seed, rate in SWEEP:
+        w = make_wave(shape, seed)
+        ref, s_abs = speed_ref(w, rate)
+        y = yardstick32(w, rate)
+        assert y.shape == ref.shape == (shape[0], speed_len(shape[1], rate)) and y.dtype == np.float32
+        ratio = rule_ratio(y, ref, s_abs)
+        if ratio > worst:
+            worst, where = ratio, (shape, seed, rate)
+    print(f"yardstick32 over {len(SWEEP)} cases: worst |y32 - ref| / (u S) = {worst:.3f} at {where}; K = {K}")
+    assert 4 * worst <= K
+    assert K == 2 ** math.ceil(math.log2(4 * worst)), (K, worst)   # K follows from the yardstick, by the stated recipe
+
+
+@pytest.mark.parametrize("length", [1, 2, 5, 37, 4096, 40000])
+def test_length_law(length):
+    from challenge_amd import _native as N
+    from challenge_amd.frontend import speed_len as fe_len
+    lib = N.lib()
+    for rate in RATES + [7.0, 0.25, 1.0, 1e6, random_rate(3)]:
+        n = len(np.arange(0, length, rate, dtype=np.float64))
+        assert n == speed_len(length, rate) == fe_len(length, rate) == lib.iris_speed_len(length, rate) == math.ceil(length / rate)
+        i0 = np.floor(np.arange(n, dtype=np.float64) * rate)
+        assert np.all(i0 <= length - 1)           # every output sample sits inside the source
+    for bad in (0.0, -1.0, float("nan"), float("inf")):
+        with pytest.raises(ValueError):
+            fe_len(length, bad)
+        assert lib.iris_speed_len(length, bad) == 0
+    assert lib.iris_speed_len(0, 1.1) == 0 and lib.iris_speed_len(-3, 1.1) == 0
+
+
+def test_rate_one_is_the_identity_and_silence_stays_silence():
+    w = make_wave((2, 500), 1)
+    y, s_abs = speed_ref(w, 1.0)
+    assert np.array_equal(y, w.astype(np.float64)) and np.array_equal(yardstick32(w, 1.0), w)
+    for rate in (0.9, 1.1, 2.0):
+        y, s_abs = speed_ref(w, rate)
+        y32 = yardstick32(w, rate)
+        pos = np.arange(y.shape[1]) * rate
+        h = math.ceil(6 / (0.99 * min(1.0, 1 / rate)))
+        silent = np.floor(pos) - h >= 400          # the whole support lies in the silent fifth (samples 400 ..)
+        assert silent.any() and np.all(s_abs[:, silent] == 0)
+        assert np.all(y[:, silent] == 0) and np.all(y32[:, silent] == 0)
+        assert np.all(s_abs[:, np.floor(pos) + h + 1 < 400] > 0)
+    zero = np.zeros((2, 100), np.float32)
+    assert not speed_ref(zero, 0.93)[0].any() and not yardstick32(zero, 0.93).any()
+
+
+def test_sign_convention_rate_above_one_raises_the_pitch():
+    """A sine well below the cut-off comes out as the sine at `rate` times the frequency."""
+    f0, length = 0.02, 4000
+    x = np.sin(2 * np.pi * f0 * np.arange(length))[None, :]
+    for rate in (0.9, 1.1, 1.2, 0.5, 2.0):
+        y, _ = speed_ref(x, rate)
+        m = np.arange(y.shape[1])
+        want = np.sin(2 * np.pi * f0 * rate * m)
+        mid = slice(40, y.shape[1] - 40)
+        assert np.abs(y[0, mid] - want[mid]).max() <= 1e-2, rate
+        assert np.abs(yardstick32(x.astype(np.float32), rate)[0, mid] - want[mid]).max() <= 1e-2, rate
+        other = np.sin(2 * np.pi * f0 / rate * m)
+        assert np.abs(y[0, mid] - other[mid]).max() > 0.5, rate
+
+
+def test_wants_speed_and_the_refusals():
+    from challenge_amd import data_utils as D
+    from challenge_amd import sj_train as S
+    assert D.wants_speed("run_speed") and D.wants_speed("speed") and D.wants_speed("pcen_speed_filter")
+    assert not D.wants_speed("") and not D.wants_speed("run_filter") and not D.wants_speed("run_stretch")
+    for name, want in (("", "minmax_log"), ("nominmax", "log"), ("pcen", "pcen"), ("pcen_learn", "pcen_learn")):
+        assert D.feature_compression(name) == want == D.feature_compression(name + "_speed") == D.feature_compression("speed_" + name)
+    cfg = S.ARGS().get(['--name', 'run_speed', '--n_frame', '64', '--batch_size', '2'])
+    with pytest.raises(ValueError, match="make_wave_dataset"):
+        S.make_dataset(cfg, training=True, sources=S.synthetic_sources(2, 3, freq=33, n_bg=2, n_voice=3, n_noise=2))
+    with pytest.raises(ValueError, match="make_wave_dataset"):
+        S.make_device_dataset(cfg, training=True, sources=S.synthetic_sources(2, 3, freq=33, n_bg=2, n_voice=3, n_noise=2))
+    from challenge_amd.mixer import DeviceMixer
+    with pytest.raises(NotImplementedError, match="spectrum"):
+        DeviceMixer.enable_speed(object())
+    # a name with both tokens is refused by every dataset maker
+    both = S.ARGS().get(['--name', 'run_speed_stretch', '--n_frame', '64', '--batch_size', '2'])
+    with pytest.raises(ValueError):
+        S.make_wave_dataset(both, training=True, sources=S.synthetic_wave_sources(2, 3, n_bg=2, n_voice=3, n_noise=2))
+    with pytest.raises(ValueError):
+        S.make_device_dataset(both, training=True, sources=S.synthetic_sources(2, 3, freq=33, n_bg=2, n_voice=3, n_noise=2))
+
+
+def test_mixer_range_checks_need_no_device():
+    from challenge_amd.mixer import WaveMixer, check_speed_range
+    check_speed_range(0.9, 1.1)
+    check_speed_range(1.0, 1.0)
+    for lo, hi in ((0.0, 1.1), (-0.5, 1.1), (1.2, 1.1), (float("nan"), 1.1), (0.9, float("inf"))):
+        with pytest.raises(ValueError):
+            check_speed_range(lo, hi)
+        with pytest.raises(ValueError):
+            WaveMixer.enable_speed(object(), lo, hi)
+    with pytest.raises(RuntimeError, match="enable_speed"):
+        WaveMixer.respeed(object())
+
+
+def test_argument_validation_without_gpu():
+    from challenge_amd import _native as N
+    lib = N.lib()
+    p8 = C.c_void_p(8)
+    INVALID, UNSUPPORTED = -1, -2
+
+    def refused(rc, code, who):
+        assert rc == code, rc
+        assert lib.iris_last_error().startswith(who), lib.iris_last_error()
+
+    who = b"iris_speed_perturb:"
+    refused(lib.iris_speed_perturb(None, 1, 2, 100, None), INVALID, who)       # NULL table with n_src > 0
+    refused(lib.iris_speed_perturb(p8, -1, 2, 100, None), INVALID, who)        # n_src < 0
+    refused(lib.iris_speed_perturb(p8, 1, 0, 100, None), INVALID, who)         # channels
+    refused(lib.iris_speed_perturb(p8, 1, -2, 100, None), INVALID, who)
+    refused(lib.iris_speed_perturb(p8, 1, 2, 0, None), INVALID, who)           # max_out_len
+    refused(lib.iris_speed_perturb(p8, 1, 2, -5, None), INVALID, who)
+    refused(lib.iris_speed_perturb(p8, 70000, 2, 100, None), UNSUPPORTED, who)  # more sources than the grid holds
+    assert lib.iris_speed_perturb(None, 0, 2, 100, None) == 0                  # no sources: nothing to do, no launch
+    assert lib.iris_speed_perturb(p8, 0, 2, 0, None) == 0
+    who = b"iris_mix_wave_frame_active_batch:"
+    refused(lib.iris_mix_wave_frame_active_batch(None, 1, 2, 512, 256, p8, 10, None), INVALID, who)
+    refused(lib.iris_mix_wave_frame_active_batch(p8, 1, 2, 512, 256, None, 10, None), INVALID, who)
+    refused(lib.iris_mix_wave_frame_active_batch(p8, -1, 2, 512, 256, p8, 10, None), INVALID, who)
+    refused(lib.iris_mix_wave_frame_active_batch(p8, 1, 0, 512, 256, p8, 10, None), INVALID, who)
+    refused(lib.iris_mix_wave_frame_active_batch(p8, 1, 2, 1, 256, p8, 10, None), INVALID, who)
+    refused(lib.iris_mix_wave_frame_active_batch(p8, 1, 2, 512, 0, p8, 10, None), INVALID, who)
+    refused(lib.iris_mix_wave_frame_active_batch(p8, 1, 2, 512, 256, p8, 0, None), INVALID, who)
+    refused(lib.iris_mix_wave_frame_active_batch(p8, 70000, 2, 512, 256, p8, 10, None), UNSUPPORTED, who)
+    assert lib.iris_mix_wave_frame_active_batch(None, 0, 2, 512, 256, None, 10, None) == 0
+    from challenge_amd import frontend as FE
+    from challenge_amd import transforms as T
+    assert FE.SPEED_SRC.itemsize == 32 and FE.SPEED_SRC.fields["rate"][1] == 24 and FE.SPEED_SRC.fields["len_out"][1] == 20
+    import torch
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        FE.speed_perturb_batch([torch.zeros(2, 70)], [0.9])
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        T.speed_perturb(torch.zeros(2, 70), 0.9)
+    with pytest.raises(ValueError):
+        FE.speed_perturb_batch([torch.zeros(2, 70)], [0.9, 1.1])
+    assert FE.speed_perturb_batch([], []) == []
