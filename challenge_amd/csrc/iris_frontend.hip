@@ -25,6 +25,8 @@
 //   k_conv_wino_wrw.h  the same layers' weight gradient as Winograd F(2x2, 3x3) on the fp32 matrix cores (training)
 //   k_metrics.h      the training metrics er_score / cos_sim / F1 counts of a batch in one launch
 //   k_detect.h       window predictions of many files -> smoothed, thresholded event lists (two launches)
+//   k_tune.h         the same decoder at every point of a settings grid, scored against ground truth: event and match counts
+//                    per (grid point, file, class) in two launches
 //   k_pcen.h         per-channel energy normalisation: a chunked scan of the IIR smoother along time, then the compression
 //                    (host scalars, or per-band parameters from a device array: the trainable layer's forward)
 //   k_pcen_grad.h    the trainable layer's backward: gradient with respect to the per-band parameters, two launches, no atomics
@@ -57,6 +59,7 @@
 #include "k_agc_adam.h"
 #include "k_metrics.h"
 #include "k_detect.h"
+#include "k_tune.h"
 #include "k_pcen.h"
 #include "k_pcen_grad.h"
 #include "k_vocoder.h"

@@ -2,6 +2,7 @@
 
     python -m challenge_amd.detect --name <run name> [--p] [--path DIR] [--wav_dir .] [--out answer.json]
                                    [--overlap_hop 512] [--score ANSWER.json]
+                                   [--tune ANSWER.json --decoder_out decoder.json] [--decoder decoder.json]
 
 `detect` runs a trained model over wav files (or in-memory recordings) and returns, per file, the events it finds in the
 forms of the reference's helpers: frame events (Challenge_Metric.get_start_end_frame), the (class, middle second) rows
@@ -19,14 +20,22 @@ below, which follows the kernel's arithmetic bit for bit:
   4. the maximal runs of d as (first, last) frames.
 inference.predict_frames computes the same function with torch ops whose fp32 rounding differs in the last bits (the
 overlap-add's index_add_ order, avg_pool1d's sum / 31 * 31 / n): the two agree wherever no a[t] sits within rounding of
-the threshold."""
+the threshold.
+
+The three decoder constants (threshold 0.5, average pool 31, max pool 124) are the reference's.  `tune_decoder` chooses them
+per class on labelled recordings: `sweep_decoder` runs the decoder at every point of a grid of settings and counts, per (grid
+point, file, class), the predicted events and those get_er's greedy rule matches (on GPU tensors one iris_decode_sweep call,
+csrc/k_tune.h, and one copy back); get_er is a sum of per-class terms, so `choose_settings` picks each class's setting on its
+own and that choice minimises the mean ER over every per-class combination of grid points.  `DecoderSettings` carries the
+result to `decode_events` / `detect` (`settings=`) and to the command line (`--tune`, `--decoder`).  Settings chosen on the
+recordings they are then scored on flatter the score: tune on other recordings."""
 from __future__ import annotations
 
 import json
 import os
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from glob import glob
-from typing import List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -76,12 +85,9 @@ def _pairs(frame_lens: np.ndarray) -> np.ndarray:
     return (frame_lens + 1) // 2 + 1      # event capacity of one (file, class): ceil(T / 2) + 1
 
 
-def _decode_file_host(preds: torch.Tensor, w0: int, n_win: int, t_len: int, n_frame: int, hop: int, avg_pool: int,
-                      max_pool: int, threshold: float) -> Tuple[np.ndarray, ...]:
-    """Steps 1-4 for one file on CPU fp32 tensors, in the kernel's order."""
+def _overlap_add_host(preds: torch.Tensor, w0: int, n_win: int, t_len: int, n_frame: int, hop: int) -> torch.Tensor:
+    """Step 1 for one file on CPU fp32 tensors, in the kernel's order: p [T, K] (T >= 1)."""
     n_out, k = preds.shape[1], preds.shape[2]
-    if t_len == 0:
-        return tuple(np.zeros((0, 2), np.int64) for _ in range(k))
     up = n_frame // n_out
     t = torch.arange(t_len)
     w_hi = torch.clamp(t // hop, max=n_win - 1)
@@ -93,14 +99,25 @@ def _decode_file_host(preds: torch.Tensor, w0: int, n_win: int, t_len: int, n_fr
         w = torch.where(ok, w, w_lo)
         v = preds[w0 + w, torch.div(t - w * hop, up, rounding_mode='floor')]
         s = s + torch.where(ok[:, None], v, torch.zeros((), dtype=torch.float32))   # (+0 is exact: s is never -0)
-    p = s / (w_hi - w_lo + 1).to(torch.float32)[:, None]
+    return s / (w_hi - w_lo + 1).to(torch.float32)[:, None]
+
+
+def _avg_pool_host(p: torch.Tensor, avg_pool: int) -> torch.Tensor:
+    """Step 2: a [T, K] from p [T, K]."""
+    t_len, k = p.shape
+    t = torch.arange(t_len)
     al, ar = (avg_pool - 1) // 2, avg_pool - 1 - ((avg_pool - 1) // 2)
     pp = torch.nn.functional.pad(p.t(), (al, ar)).t()
     acc = torch.zeros(t_len, k, dtype=torch.float32)
     for j in range(avg_pool):                         # frame order; the zero padding adds exactly nothing
         acc = acc + pp[j:j + t_len]
     n = (torch.clamp(t + ar, max=t_len - 1) - torch.clamp(t - al, min=0) + 1).to(torch.float32)
-    a = acc / n[:, None]
+    return acc / n[:, None]
+
+
+def _runs_host(a: torch.Tensor, max_pool: int, threshold: float) -> Tuple[np.ndarray, ...]:
+    """Steps 3-4: per class the [n, 2] int64 (first, last) runs of d."""
+    t_len, k = a.shape
     ml, mr = (max_pool - 1) // 2, max_pool - 1 - ((max_pool - 1) // 2)
     on = (a >= threshold).numpy()
     isn = torch.isnan(a).numpy()
@@ -114,6 +131,15 @@ def _decode_file_host(preds: torch.Tensor, w0: int, n_win: int, t_len: int, n_fr
         e = np.diff(np.concatenate([[0], d.astype(np.int8), [0]]))
         out.append(np.stack([np.flatnonzero(e == 1), np.flatnonzero(e == -1) - 1], 1).astype(np.int64))
     return tuple(out)
+
+
+def _decode_file_host(preds: torch.Tensor, w0: int, n_win: int, t_len: int, n_frame: int, hop: int, avg_pool: int,
+                      max_pool: int, threshold: float) -> Tuple[np.ndarray, ...]:
+    """Steps 1-4 for one file on CPU fp32 tensors, in the kernel's order."""
+    if t_len == 0:
+        return tuple(np.zeros((0, 2), np.int64) for _ in range(preds.shape[2]))
+    p = _overlap_add_host(preds, w0, n_win, t_len, n_frame, hop)
+    return _runs_host(_avg_pool_host(p, avg_pool), max_pool, threshold)
 
 
 class DecodeLayout:
@@ -176,10 +202,22 @@ def launch_decode(preds: torch.Tensor, layout: DecodeLayout, meta: torch.Tensor,
 
 
 def decode_events(preds: torch.Tensor, win_off, frame_lens, n_frame: int, overlap_hop: int, avg_pool: int = AVG_POOL,
-                  max_pool: int = MAX_POOL, threshold: float = THRESHOLD) -> List[Tuple[np.ndarray, ...]]:
+                  max_pool: int = MAX_POOL, threshold: float = THRESHOLD,
+                  settings: Optional["DecoderSettings"] = None) -> List[Tuple[np.ndarray, ...]]:
     """Window predictions [W_total, n_out, K] of F files (file f owns windows win_off[f] .. win_off[f + 1] - 1 and has
     frame_lens[f] frames) -> per file, per class [n, 2] int64 (first, last) frame events, as get_start_end_frame returns them.
-    GPU tensors: the iris_decode_events launches and one copy back; CPU tensors: the restatement of the module doc."""
+    GPU tensors: the iris_decode_events launches and one copy back; CPU tensors: the restatement of the module doc.
+    With `settings` (per-class DecoderSettings; avg_pool / max_pool / threshold are then not used) the decoder runs once per
+    distinct setting and class k's events are those of its own setting's run."""
+    if settings is not None:
+        k = int(preds.shape[2]) if preds.dim() == 3 else -1
+        if settings.n_classes != k:
+            raise ValueError(f"decode_events: settings for {settings.n_classes} classes, preds have {k}")
+        runs: Dict[Tuple[float, int, int], list] = {}
+        for key in settings.points():
+            if key not in runs:
+                runs[key] = decode_events(preds, win_off, frame_lens, n_frame, overlap_hop, key[1], key[2], key[0])
+        return [tuple(runs[key][f][c] for c, key in enumerate(settings.points())) for f in range(len(frame_lens))]
     wo = np.asarray(win_off.cpu() if torch.is_tensor(win_off) else win_off, dtype=np.int64).reshape(-1)
     fl = np.asarray(frame_lens.cpu() if torch.is_tensor(frame_lens) else frame_lens, dtype=np.int64).reshape(-1)
     _check(tuple(preds.shape), wo, fl, int(n_frame), int(overlap_hop), int(avg_pool), int(max_pool))
@@ -192,6 +230,318 @@ def decode_events(preds: torch.Tensor, win_off, frame_lens, n_frame: int, overla
     meta, bits, out = layout.buffers(p.device)
     launch_decode(p, layout, meta, bits, out, n_frame, overlap_hop, avg_pool, max_pool, threshold)
     return layout.parse(out.cpu().numpy())
+
+
+# ---------------------------------------------------------------------------
+# decoder settings per class, and the sweep that chooses them
+# ---------------------------------------------------------------------------
+MAX_GRID = 4096            # the limits of iris_decode_sweep (include/iris_frontend.h)
+MAX_GROUP_THRESHOLDS = 256
+MAX_SWEEP_WORDS = 6144
+MAX_GT_ROWS = 64
+MAX_SWEEP_FILES = 65535
+MAX_SWEEP_INDEX = 2 ** 31 - 1     # K * frames (the workspace) and G * F * K (the counts) are int32 indices
+
+GridPoint = Tuple[float, int, int]     # (threshold as the fp32 value the decoder compares with, avg_pool, max_pool)
+
+
+def _f32(x) -> float:
+    return float(np.float32(x))
+
+
+def _grid_points(grid) -> List[GridPoint]:
+    pts = [(_f32(t), int(a), int(m)) for t, a, m in grid]
+    if not pts:
+        raise ValueError("decoder grid: no points")
+    for t, a, m in pts:
+        if t != t:
+            raise ValueError("decoder grid: a NaN threshold")
+        if not (1 <= a <= 127 and 1 <= m <= 256):
+            raise ValueError(f"decoder grid: avg_pool {a} (1..127), max_pool {m} (1..256)")
+    return pts
+
+
+def decoder_grid(thresholds=None, avg_pools=(1, 15, 31, 47, 63), max_pools=(1, 31, 62, 124, 186, 248)) -> List[GridPoint]:
+    """The default grid: the reference point (0.5, 31, 124) first, then thresholds 0.1 .. 0.9 in steps of 0.05 x avg_pools x
+    max_pools (threshold slowest).  The reference point comes first so that a tie in choose_settings keeps it."""
+    if thresholds is None:
+        thresholds = [round(0.1 + 0.05 * i, 2) for i in range(17)]
+    grid = [(THRESHOLD, AVG_POOL, MAX_POOL)]
+    grid += [(t, a, m) for t in thresholds for a in avg_pools for m in max_pools]
+    return _grid_points(grid)
+
+
+@dataclass
+class DecoderSettings:
+    """One (threshold, avg_pool, max_pool) per class, with - when they were chosen by choose_settings - the grid and the
+    score table [G][K] (sum over the files of the class's ER term) they were chosen from.  Thresholds are kept as the fp32
+    values the decoder compares with."""
+    threshold: Tuple[float, ...]
+    avg_pool: Tuple[int, ...]
+    max_pool: Tuple[int, ...]
+    grid: Optional[List[GridPoint]] = field(default=None, compare=False)
+    score: Optional[List[List[float]]] = field(default=None, compare=False)
+
+    def __post_init__(self):
+        self.threshold = tuple(_f32(t) for t in self.threshold)
+        self.avg_pool = tuple(int(a) for a in self.avg_pool)
+        self.max_pool = tuple(int(m) for m in self.max_pool)
+        if not (len(self.threshold) == len(self.avg_pool) == len(self.max_pool) >= 1):
+            raise ValueError(f"DecoderSettings: {len(self.threshold)} thresholds, {len(self.avg_pool)} avg_pool, "
+                             f"{len(self.max_pool)} max_pool")
+        _grid_points(self.points())
+
+    @property
+    def n_classes(self) -> int:
+        return len(self.threshold)
+
+    def points(self) -> List[GridPoint]:
+        return list(zip(self.threshold, self.avg_pool, self.max_pool))
+
+    @classmethod
+    def default(cls, n_classes: int) -> "DecoderSettings":
+        return cls((THRESHOLD,) * n_classes, (AVG_POOL,) * n_classes, (MAX_POOL,) * n_classes)
+
+    def save(self, path: str) -> None:
+        doc = {"threshold": list(self.threshold), "avg_pool": list(self.avg_pool), "max_pool": list(self.max_pool),
+               "grid": None if self.grid is None else [list(g) for g in self.grid],
+               "score": None if self.score is None else [list(map(float, r)) for r in self.score]}
+        with open(path, 'w') as f:
+            json.dump(doc, f, indent=1)
+
+    @classmethod
+    def load(cls, path: str) -> "DecoderSettings":
+        with open(path) as f:
+            doc = json.load(f)
+        grid = doc.get("grid")
+        return cls(doc["threshold"], doc["avg_pool"], doc["max_pool"],
+                   None if grid is None else _grid_points(grid), doc.get("score"))
+
+
+def class_counts(gt_rows, metric, n_classes: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """get_er's terms class by class: (n_pred [K], matched [K], n_gt [K]) of ground-truth rows [[class, start_s, end_s], ...]
+    and prediction rows [[class, second], ...].  get_er matches a row only to predictions of its class and both of its stable
+    sorts keep the order inside a class, so its greedy rule runs here within each class on its own.  Without n_classes, K
+    covers every class either side names."""
+    gt = np.asarray(gt_rows).reshape(-1, 3)
+    pred = np.asarray(metric).reshape(-1, 2)
+    if n_classes is None:
+        n_classes = int(max([0] + gt[:, 0].tolist() + pred[:, 0].tolist())) + 1
+    n_pred, matched, n_gt = (np.zeros(n_classes, np.int64) for _ in range(3))
+    for c in range(n_classes):
+        g = gt[gt[:, 0] == c]
+        g = g[np.argsort(g[:, 1], kind='stable')]
+        sec = pred[pred[:, 0] == c][:, 1]
+        sec = sec[np.argsort(sec, kind='stable')]
+        n_pred[c], n_gt[c] = len(sec), len(g)
+        matched[c] = _greedy_matches(g[:, 1:], sec)
+    return n_pred, matched, n_gt
+
+
+def _greedy_matches(rows, seconds) -> int:
+    """Ground-truth rows (start_s, end_s) in order; each takes the first second not yet taken that lies in [start_s, end_s]."""
+    free = list(seconds)
+    n = 0
+    for s, e in rows:
+        for i, v in enumerate(free):
+            if s <= v <= e:
+                del free[i]
+                n += 1
+                break
+    return n
+
+
+def er_from_counts(n_pred, matched, n_gt) -> float:
+    """get_er's expression, (N - 2 matched) / len(gt), from one file's per-class counts (ZeroDivisionError on an empty gt)."""
+    n = int(np.sum(n_pred)) + int(np.sum(n_gt))
+    return (n - 2 * int(np.sum(matched))) / int(np.sum(n_gt))
+
+
+def _middle_second(s: int, e: int) -> int:
+    return int(((int(s) + int(e)) / 2) * HOP / SR)      # output_to_metric's expression
+
+
+def _gt_table(gt, n_files: int, k: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Per-file ground-truth rows [[class, start_s, end_s], ...] -> (rows [n, 2] int32 grouped by (file, class), each group
+    sorted by start_s (stable); gt_off [F K + 1] int32)."""
+    if len(gt) != n_files:
+        raise ValueError(f"sweep_decoder: ground truth for {len(gt)} files, {n_files} files")
+    rows, off = [], [0]
+    for f, g in enumerate(gt):
+        raw = np.asarray(g).reshape(-1, 3)
+        g = raw.astype(np.int64)
+        if raw.size and (not np.array_equal(g, raw) or np.abs(g).max() > np.iinfo(np.int32).max):
+            raise ValueError(f"sweep_decoder: file {f}: ground-truth rows must be int32 [class, start_s, end_s]")
+        if g.size and (g[:, 0].min() < 0 or g[:, 0].max() >= k):
+            raise ValueError(f"sweep_decoder: file {f}: a ground-truth class outside 0..{k - 1}")
+        for c in range(k):
+            gc = g[g[:, 0] == c][:, 1:]
+            gc = gc[np.argsort(gc[:, 0], kind='stable')]
+            if len(gc) > MAX_GT_ROWS:
+                raise ValueError(f"sweep_decoder: file {f}, class {c}: {len(gc)} ground-truth events (at most {MAX_GT_ROWS})")
+            rows.append(gc)
+            off.append(off[-1] + len(gc))
+    return np.concatenate(rows).astype(np.int32).reshape(-1, 2), np.asarray(off, np.int32)
+
+
+class SweepLayout:
+    """Host-side layout of one iris_decode_sweep call.  The grid is sorted (avg_pool, threshold bits, max_pool) as the kernel
+    needs it; `parse` returns the counts in the caller's order.  `meta` = int32 [win_off (F + 1), frame_len (F), avg_pool (G),
+    max_pool (G), threshold bits (G), gt_off (F K + 1), gt rows (2 n)], uploaded once; `out` = int32 [n_pred (G F K),
+    matched (G F K)]."""
+
+    def __init__(self, win_off, frame_lens, n_classes: int, gt, grid):
+        self.win_off = np.ascontiguousarray(np.asarray(win_off, dtype=np.int64)).astype(np.int32)
+        self.frame_lens = np.ascontiguousarray(np.asarray(frame_lens, dtype=np.int64)).astype(np.int32)
+        self.k = int(n_classes)
+        f = len(self.frame_lens)
+        pts = _grid_points(grid)
+        thr = np.asarray([p[0] for p in pts], np.float32)
+        avg = np.asarray([p[1] for p in pts], np.int32)
+        mx = np.asarray([p[2] for p in pts], np.int32)
+        self.order = np.lexsort((mx, thr.view(np.int32), avg))        # sorted position -> caller's index
+        self.thr, self.avg, self.max = (np.ascontiguousarray(x[self.order]) for x in (thr, avg, mx))
+        self.g = len(pts)
+        self.n_ws = max(int(self.k * self.frame_lens.astype(np.int64).sum()), 1)
+        self.n_out = self.g * f * self.k
+        self._check_limits()
+        self.gt_rows, self.gt_off = _gt_table(gt, f, self.k)
+        self.n_gt = np.diff(self.gt_off.astype(np.int64)).reshape(f, self.k)
+        self.parts = [self.win_off, self.frame_lens, self.avg, self.max, self.thr.view(np.int32), self.gt_off,
+                      self.gt_rows.reshape(-1)]
+        self.meta = np.concatenate(self.parts).astype(np.int32)
+
+    def _check_limits(self):
+        f = len(self.frame_lens)
+        if self.g > MAX_GRID:
+            raise ValueError(f"sweep_decoder: {self.g} grid points (at most {MAX_GRID})")
+        if f > MAX_SWEEP_FILES:
+            raise ValueError(f"sweep_decoder: {f} files in one call (at most {MAX_SWEEP_FILES})")
+        if self.n_ws > MAX_SWEEP_INDEX:
+            raise ValueError(f"sweep_decoder: {self.n_ws // self.k} frames x {self.k} classes in one call (at most {MAX_SWEEP_INDEX})")
+        if self.n_out > MAX_SWEEP_INDEX:
+            raise ValueError(f"sweep_decoder: {self.g} grid points x {f} files x {self.k} classes is too many counts "
+                             f"(at most {MAX_SWEEP_INDEX})")
+        nw = (int(self.frame_lens.max()) + 63) // 64 if f else 0
+        for a in np.unique(self.avg):
+            n_thr = len(np.unique(self.thr[self.avg == a].view(np.int32)))
+            if n_thr > MAX_GROUP_THRESHOLDS:
+                raise ValueError(f"sweep_decoder: {n_thr} distinct thresholds with avg_pool {a} (at most {MAX_GROUP_THRESHOLDS})")
+            if (n_thr + 1) * nw > MAX_SWEEP_WORDS:
+                raise ValueError(f"sweep_decoder: ({n_thr} thresholds of avg_pool {a} + 1) * {nw} words of the longest file "
+                                 f"({int(self.frame_lens.max())} frames) > {MAX_SWEEP_WORDS}")
+
+    def buffers(self, device):
+        """(meta on the device, the p workspace, the output buffer)."""
+        return (torch.from_numpy(self.meta).to(device), torch.empty(self.n_ws, dtype=torch.float32, device=device),
+                torch.empty(2 * self.n_out, dtype=torch.int32, device=device))
+
+    def parse(self, out_host: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        f = len(self.frame_lens)
+        res = []
+        for part in (out_host[:self.n_out], out_host[self.n_out:]):
+            x = np.empty((self.g, f, self.k), np.int64)
+            x[self.order] = part.reshape(self.g, f, self.k)
+            res.append(x)
+        return res[0], res[1]
+
+
+def launch_sweep(preds: torch.Tensor, layout: SweepLayout, meta: torch.Tensor, p_ws: torch.Tensor, out: torch.Tensor,
+                 n_frame: int, overlap_hop: int) -> None:
+    """The iris_decode_sweep launches on the current stream into `out` (no host sync: capturable once the buffers exist)."""
+    if not (preds.is_cuda and preds.dtype == torch.float32 and preds.is_contiguous() and preds.dim() == 3):
+        raise ValueError("launch_sweep: preds must be a contiguous fp32 GPU tensor [windows, n_out, K]")
+    if preds.shape[2] != layout.k:
+        raise ValueError(f"launch_sweep: layout for {layout.k} classes, preds have {preds.shape[2]}")
+    for name, t, n in (("meta", meta, layout.meta.size), ("out", out, 2 * layout.n_out)):
+        if t.dtype != torch.int32 or t.device != preds.device or t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"launch_sweep: {name} must be a contiguous int32 [{n}] tensor on {preds.device}")
+    if p_ws.dtype != torch.float32 or p_ws.device != preds.device or p_ws.numel() < layout.n_ws:
+        raise ValueError(f"launch_sweep: p_ws must be an fp32 tensor of >= {layout.n_ws} elements on {preds.device}")
+    dev_ptr, at = [], meta.data_ptr()
+    for part in layout.parts:
+        dev_ptr.append(at)
+        at += 4 * part.size
+    d_wo, d_fl, d_avg, d_max, d_thr, d_goff, d_gt = dev_ptr
+    N.check(N.lib().iris_decode_sweep(preds.data_ptr(), d_wo, d_fl, layout.win_off.ctypes.data, layout.frame_lens.ctypes.data,
+                                      len(layout.frame_lens), int(n_frame), int(overlap_hop), preds.shape[1], layout.k,
+                                      d_thr, d_avg, d_max, layout.thr.ctypes.data, layout.avg.ctypes.data,
+                                      layout.max.ctypes.data, layout.g, d_gt, d_goff, layout.gt_off.ctypes.data, HOP, SR,
+                                      p_ws.data_ptr(), out.data_ptr(), out.data_ptr() + 4 * layout.n_out,
+                                      torch.cuda.current_stream(preds.device).cuda_stream), "iris_decode_sweep")
+
+
+def sweep_decoder(preds: torch.Tensor, win_off, frame_lens, gt, grid, n_frame: int,
+                  overlap_hop: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The decoder at every grid point (threshold, avg_pool, max_pool), scored: (n_pred [G, F, K], matched [G, F, K],
+    n_gt [F, K]) int64, where n_pred counts the events decode_events yields with that setting, matched those get_er's greedy
+    rule pairs with one of `gt[f]`'s rows [[class, start_s, end_s], ...] of the class, and n_gt the rows.  get_er of file f
+    with one grid point per class is then sum_k (n_pred + n_gt - 2 matched) / sum_k n_gt.
+    GPU tensors: one iris_decode_sweep call and one copy back; CPU tensors: the restatement on _decode_file_host's steps."""
+    wo = np.asarray(win_off.cpu() if torch.is_tensor(win_off) else win_off, dtype=np.int64).reshape(-1)
+    fl = np.asarray(frame_lens.cpu() if torch.is_tensor(frame_lens) else frame_lens, dtype=np.int64).reshape(-1)
+    pts = _grid_points(grid)
+    _check(tuple(preds.shape), wo, fl, int(n_frame), int(overlap_hop), AVG_POOL, MAX_POOL)
+    p = preds.detach().to(torch.float32).contiguous()
+    layout = SweepLayout(wo, fl, p.shape[2], gt, pts)
+    if p.is_cuda:
+        meta, p_ws, out = layout.buffers(p.device)
+        launch_sweep(p, layout, meta, p_ws, out, n_frame, overlap_hop)
+        n_pred, matched = layout.parse(out.cpu().numpy())
+        return n_pred, matched, layout.n_gt
+    f, k = len(fl), p.shape[2]
+    n_pred, matched = (np.zeros((len(pts), f, k), np.int64) for _ in range(2))
+    for i in range(f):
+        if fl[i] == 0:
+            continue
+        ola = _overlap_add_host(p, int(wo[i]), int(wo[i + 1] - wo[i]), int(fl[i]), int(n_frame), int(overlap_hop))
+        smoothed: Dict[int, torch.Tensor] = {}
+        for g, (thr, avg, mx) in enumerate(pts):
+            if avg not in smoothed:
+                smoothed[avg] = _avg_pool_host(ola, avg)
+            for c, ev in enumerate(_runs_host(smoothed[avg], mx, thr)):
+                q = i * k + c
+                rows = layout.gt_rows[layout.gt_off[q]:layout.gt_off[q + 1]]
+                n_pred[g, i, c] = len(ev)
+                matched[g, i, c] = _greedy_matches(rows, [_middle_second(s, e) for s, e in ev])
+    return n_pred, matched, layout.n_gt
+
+
+@dataclass
+class Tuning:
+    settings: DecoderSettings
+    mean_er_reference: Optional[float]     # mean over the files of get_er at (0.5, 31, 124); None if the grid lacks that point
+    mean_er_chosen: float
+    index: Tuple[int, ...]                 # the chosen grid point of each class
+
+
+def choose_settings(n_pred, matched, n_gt, grid, names: Optional[Sequence[str]] = None) -> Tuning:
+    """Per class the grid point that minimises sum_f (n_pred + n_gt - 2 matched)[g, f, k] / len(gt_f) (float64; ties go to the
+    earliest grid point).  The mean ER over the files is the sum over the classes of these terms / F, so the independent choices
+    minimise it over every per-class combination of grid points.  A file without ground truth is refused (get_er divides by
+    its length)."""
+    pts = _grid_points(grid)
+    n_pred, matched, n_gt = (np.asarray(x, np.int64) for x in (n_pred, matched, n_gt))
+    g, f, k = n_pred.shape
+    if matched.shape != (g, f, k) or n_gt.shape != (f, k) or g != len(pts) or f < 1:
+        raise ValueError(f"choose_settings: n_pred {n_pred.shape}, matched {matched.shape}, n_gt {n_gt.shape}, {len(pts)} grid points")
+    total = n_gt.sum(1)
+    if (total == 0).any():
+        i = int(np.flatnonzero(total == 0)[0])
+        raise ValueError(f"choose_settings: file {names[i] if names is not None else i} has no ground-truth events "
+                         f"(get_er divides by their number)")
+    score = ((n_pred + n_gt[None] - 2 * matched).astype(np.float64) / total.astype(np.float64)[None, :, None]).sum(1)   # [G, K]
+    index = tuple(int(i) for i in np.argmin(score, axis=0))       # argmin: the first of equal minima
+    settings = DecoderSettings([pts[i][0] for i in index], [pts[i][1] for i in index], [pts[i][2] for i in index],
+                               grid=pts, score=score.tolist())
+
+    def mean_er(idx):
+        idx, cls = np.asarray(idx), np.arange(k)
+        return float(np.mean([er_from_counts(n_pred[idx, i, cls], matched[idx, i, cls], n_gt[i]) for i in range(f)]))
+
+    ref = (_f32(THRESHOLD), AVG_POOL, MAX_POOL)
+    er_ref = mean_er((pts.index(ref),) * k) if ref in pts else None
+    return Tuning(settings, er_ref, mean_er(index), index)
 
 
 # ---------------------------------------------------------------------------
@@ -247,24 +597,12 @@ def _predict(model, windows: torch.Tensor, batch_size: int) -> torch.Tensor:
     return torch.cat([model(windows[i:i + batch_size]) for i in range(0, windows.shape[0], batch_size)])
 
 
-@torch.no_grad()
-def detect(model, wavs_or_paths: Sequence, config, overlap_hop: int = 512, batch_size: int = 32, sample_rate: int = SR,
-           device=None, max_windows: int = 1024) -> List[Detection]:
-    """Events of `model` in each recording: a wav path, a (name, [chan, samples] array[, sample rate]) tuple or a bare array
-    (named by its position).  Files are handled in groups of at most `max_windows` windows (a longer file forms a group of
-    its own); each window's prediction does not depend on the grouping."""
+def _groups(model, wavs_or_paths: Sequence, config, overlap_hop: int, sample_rate: int, device, max_windows: int):
+    """The front end of `detect`: yields groups [(name, frames, windows [W, M, n_frame, C])] of at most `max_windows` windows
+    (a longer file forms a group of its own)."""
     dev = _model_device(model, device)
-    items = _items(wavs_or_paths, sample_rate)
-    results: List[Detection] = []
     group, n_group = [], 0
-
-    def flush():
-        nonlocal group, n_group
-        if group:
-            results.extend(_detect_group(model, group, config, overlap_hop, batch_size))
-        group, n_group = [], 0
-
-    for name, path, wav, sr in items:
+    for name, path, wav, sr in _items(wavs_or_paths, sample_rate):
         spec = D.load_wav(path, dev) if path is not None else D.load_wav_array(wav, sr, dev)
         feats = features_for_eval(spec, config)
         del spec
@@ -272,24 +610,69 @@ def detect(model, wavs_or_paths: Sequence, config, overlap_hop: int = 512, batch
         windows = frame(feats, config.n_frame, overlap_hop, pad_end=True, axis=-2)   # [M, W, n_frame, C']
         windows = windows.permute(1, 0, 2, 3)[..., :config.n_chan].contiguous()
         if group and n_group + windows.shape[0] > max_windows:
-            flush()
+            yield group
+            group, n_group = [], 0
         group.append((name, t_len, windows))
         n_group += windows.shape[0]
-    flush()
-    return results
+    if group:
+        yield group
 
 
-def _detect_group(model, group, config, overlap_hop: int, batch_size: int) -> List[Detection]:
+def _group_preds(model, group, batch_size: int) -> Tuple[torch.Tensor, np.ndarray]:
     windows = torch.cat([w for _, _, w in group]) if len(group) > 1 else group[0][2]
     preds = _predict(model, windows, batch_size)
     del windows
-    win_off = np.concatenate([[0], np.cumsum([w.shape[0] for _, _, w in group])])
-    events = decode_events(preds.to(torch.float32), win_off, [t for _, t, _ in group], config.n_frame, overlap_hop)
+    return preds.to(torch.float32), np.concatenate([[0], np.cumsum([w.shape[0] for _, _, w in group])])
+
+
+@torch.no_grad()
+def detect(model, wavs_or_paths: Sequence, config, overlap_hop: int = 512, batch_size: int = 32, sample_rate: int = SR,
+           device=None, max_windows: int = 1024, settings: Optional[DecoderSettings] = None) -> List[Detection]:
+    """Events of `model` in each recording: a wav path, a (name, [chan, samples] array[, sample rate]) tuple or a bare array
+    (named by its position).  Files are handled in groups of at most `max_windows` windows (a longer file forms a group of
+    its own); each window's prediction does not depend on the grouping.  `settings`: per-class decoder settings (default: the
+    reference's constants for every class)."""
+    results: List[Detection] = []
+    for group in _groups(model, wavs_or_paths, config, overlap_hop, sample_rate, device, max_windows):
+        results.extend(_detect_group(model, group, config, overlap_hop, batch_size, settings))
+    return results
+
+
+def _detect_group(model, group, config, overlap_hop: int, batch_size: int,
+                  settings: Optional[DecoderSettings] = None) -> List[Detection]:
+    preds, win_off = _group_preds(model, group, batch_size)
+    events = decode_events(preds, win_off, [t for _, t, _ in group], config.n_frame, overlap_hop, settings=settings)
     out = []
     for (name, t_len, _), ev in zip(group, events):
         metric = M.output_to_metric(HOP, SR)(*ev)
         out.append(Detection(name, t_len, ev, metric, _FromEvents(ev).get_start_end_time(None)))
     return out
+
+
+@torch.no_grad()
+def tune_decoder(model, wavs_or_paths: Sequence, answer, config, grid=None, overlap_hop: int = 512, batch_size: int = 32,
+                 sample_rate: int = SR, device=None, max_windows: int = 1024) -> Tuning:
+    """Per-class decoder settings for `model`, chosen on labelled recordings: the front end and the model run as in `detect`,
+    group by group; each group's window predictions go through `sweep_decoder` against `answer` ({name: [[class, start_s,
+    end_s], ...]}, or the path of a file {"task2_answer": {...}}); the count tables of all groups end in `choose_settings`.
+    Tune on recordings other than those the settings are scored on."""
+    if isinstance(answer, (str, os.PathLike)):
+        with open(answer) as f:
+            answer = json.load(f)['task2_answer']
+    pts = decoder_grid() if grid is None else _grid_points(grid)
+    names, tables = [], []
+    for group in _groups(model, wavs_or_paths, config, overlap_hop, sample_rate, device, max_windows):
+        missing = [n for n, _, _ in group if n not in answer]
+        if missing:
+            raise ValueError(f"tune_decoder: no ground truth for {missing[0]}")
+        preds, win_off = _group_preds(model, group, batch_size)
+        tables.append(sweep_decoder(preds, win_off, [t for _, t, _ in group], [answer[n] for n, _, _ in group], pts,
+                                    config.n_frame, overlap_hop))
+        names += [n for n, _, _ in group]
+    if not tables:
+        raise ValueError("tune_decoder: no recordings")
+    n_pred, matched, n_gt = (np.concatenate([t[i] for t in tables], axis=ax) for i, ax in ((0, 1), (1, 1), (2, 0)))
+    return choose_settings(n_pred, matched, n_gt, pts, names)
 
 
 def answer_rows(det: Detection) -> List[List[int]]:
@@ -315,12 +698,26 @@ def main(argv=None):
     config.args.add_argument('--out', type=str, default='answer.json')
     config.args.add_argument('--overlap_hop', type=int, default=512)
     config.args.add_argument('--score', type=str, default=None, help='sample_answer.json to print per-file ER against')
+    config.args.add_argument('--tune', type=str, default=None,
+                             help='answer file to choose per-class decoder settings on (the wavs of --wav_dir); they are then applied: the '
+                                  'front end and the model run over every recording twice, once to tune and once to detect')
+    config.args.add_argument('--decoder_out', type=str, default='decoder.json', help='where --tune writes the settings')
+    config.args.add_argument('--decoder', type=str, default=None, help='decoder settings written by --tune, to apply')
     config = config.get(argv)
     if config.p:
         parse_name(config)
+    if config.tune and config.decoder:
+        raise ValueError("--tune chooses the decoder settings and --decoder loads them: give one of the two")
     model = load_model(config, config.path)
     paths = sorted(glob(os.path.join(config.wav_dir, '*.wav')))
-    results = detect(model, paths, config, overlap_hop=config.overlap_hop)
+    settings = DecoderSettings.load(config.decoder) if config.decoder else None
+    if config.tune:
+        tuned = tune_decoder(model, paths, config.tune, config, overlap_hop=config.overlap_hop)
+        settings = tuned.settings
+        settings.save(config.decoder_out)
+        print(f"decoder settings (threshold, avg_pool, max_pool) per class {settings.points()} -> {config.decoder_out}")
+        print(f"MEAN ER reference {tuned.mean_er_reference!r} chosen {tuned.mean_er_chosen!r} (on the tuning recordings)")
+    results = detect(model, paths, config, overlap_hop=config.overlap_hop, settings=settings)
     write_answer(results, config.out)
     print(f"{len(results)} files, {sum(len(d.metric) for d in results)} events -> {config.out}")
     if config.score:
@@ -328,7 +725,7 @@ def main(argv=None):
             gt = json.load(f)['task2_answer']
         scores = []
         for d in results:
-            er = M.get_er(gt[d.name], d.metric)
+            er = er_from_counts(*class_counts(gt[d.name], d.metric))
             scores.append(er)
             print(f"ER {d.name} {er!r}")
         print('FINAL SCORE:', np.mean(scores))

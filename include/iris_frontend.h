@@ -381,11 +381,45 @@ int iris_event_metrics(const float* y_true, const float* y_pred, int batch, int 
  * 1 <= K <= 16, 1 <= avg_pool <= 127, 1 <= max_pool <= 256 (IRIS_E_UNSUPPORTED otherwise); IRIS_E_INVALID for
  * overlap_hop > n_frame, n_frame % n_out != 0, negative T_f, or T_f > (windows_f - 1) * overlap_hop + n_frame (frames no window
  * covers).  Deterministic: plain stores, no atomics; the same inputs give the same bits.
+ * iris_decode_sweep below runs this decoder at every point of a grid of settings and scores each against ground truth.
  */
 int iris_decode_events(const float* preds, const int* win_off, const int* frame_len, const int* win_off_host,
                        const int* frame_len_host, int n_files, int n_frame, int overlap_hop, int n_out, int n_classes,
                        int avg_pool, int max_pool, float threshold, unsigned long long* bits, int* ev, int* n_ev,
                        void* stream);
+
+/*
+ * The decoder above at G settings at once, scored against ground truth (metrics.output_to_metric + the per-class terms of
+ * metrics.get_er), two launches whatever G and F are, capturable:
+ *   preds, win_off, frame_len, win_off_host, frame_len_host, n_files, n_frame, overlap_hop, n_out, n_classes: as above
+ *   threshold [G] fp32, avg_pool [G] int32, max_pool [G] int32, DEVICE: the grid.  It must be SORTED so that equal avg_pool
+ *         values are adjacent and, among them, equal thresholds (compared as bit patterns) are adjacent; the *_host arrays hold
+ *         the same values in host memory (checked here, IRIS_E_INVALID if the order is not kept)
+ *   gt    [rows, 2] int32 (start_s, end_s), DEVICE: the ground-truth events grouped by (file, class); (file f, class k) owns
+ *         rows gt_off[f K + k] .. gt_off[f K + k + 1] - 1, sorted by start_s (stable).  gt_off [F K + 1] int32 DEVICE,
+ *         gt_off_host the same in host memory
+ *   metric_hop, sample_rate: an event (s, e) in frames becomes the second (int)((((double)(s + e)) / 2) * metric_hop /
+ *         sample_rate) - output_to_metric's expression, left to right in fp64
+ *   p_ws  workspace of K * sum_f T_f floats (the overlap-add average p, which no setting changes)
+ * Outputs (DEVICE, int32, every element written):
+ *   n_pred  [G, F, K]  the number of events iris_decode_events yields with setting g (the same fp32 summation orders for p and
+ *                      a, the same >= and NaN rules)
+ *   matched [G, F, K]  get_er's greedy rule within the class: the ground-truth rows in order; each takes the first prediction
+ *                      not yet taken, in time order, whose second lies in [start_s, end_s]
+ * so that get_er of file f at one setting per class is sum_k (n_pred + n_gt - 2 matched) / sum_k n_gt.
+ * Limits (IRIS_E_UNSUPPORTED, nothing is launched or written): 1 <= K <= 16; per grid point 1 <= avg_pool <= 127 and
+ * 1 <= max_pool <= 256; G <= 4096; at most 256 distinct thresholds share one avg_pool; (distinct thresholds of one avg_pool + 1)
+ * * ceil(max_f T_f / 64) <= 6144 (the threshold bit words of one (file, class, avg_pool) are held in LDS: 17 thresholds allow
+ * 21,824 frames, a file of 1,900 frames 203 thresholds); at most 64 ground-truth rows per (file, class) (one per lane); F <= 65535;
+ * K * sum_f T_f <= 2^31 - 1 (the workspace index) and G * F * K <= 2^31 - 1 (the output index).
+ * IRIS_E_INVALID as for iris_decode_events.  Deterministic: integer outputs, plain stores, no atomics.
+ */
+int iris_decode_sweep(const float* preds, const int* win_off, const int* frame_len, const int* win_off_host,
+                      const int* frame_len_host, int n_files, int n_frame, int overlap_hop, int n_out, int n_classes,
+                      const float* threshold, const int* avg_pool, const int* max_pool, const float* threshold_host,
+                      const int* avg_pool_host, const int* max_pool_host, int n_grid, const int* gt, const int* gt_off,
+                      const int* gt_off_host, int metric_hop, int sample_rate, float* p_ws, int* n_pred, int* matched,
+                      void* stream);
 
 /*
  * Inference epilogue of ConvMPBlock's Conv2D + BatchNormalization + ReLU (+ MaxPool2D 2x2 'same'), sj_train.py:191-201,

@@ -1,0 +1,168 @@
+"""GPU tests of the decoder sweep: iris_decode_sweep's counts against detect.py's CPU restatement over the whole default grid,
+against iris_decode_events' own event counts, bitwise repeatability (repeat, second stream, after another shape, graph
+replay), its limits on device buffers, and tune_decoder -> detect(settings=...) end to end."""
+import numpy as np
+import pytest
+import torch
+
+from challenge_amd import detect as DT
+from challenge_amd import metrics as M
+from test_detect_host import run_preds
+from test_tune_host import plant_info, random_gt, sweep_case
+
+pytestmark = pytest.mark.gpu
+
+
+def _dev():
+    assert torch.cuda.is_available()
+    return torch.device("cuda", 0)
+
+
+def _big_case(seed, k):
+    rng = np.random.default_rng(seed)
+    frame_lens = [int(x) for x in rng.integers(200, 3600, 18)]
+    frame_lens[0], frame_lens[2], frame_lens[5], frame_lens[9], frame_lens[12], frame_lens[17] = 1500, 12_345, 0, 1, 63, 2200
+    assert len(plant_info(frame_lens, 512, 256)[1]) == 2        # smoothed values equal to a threshold are in the inputs
+    return (*sweep_case(seed, frame_lens, hop=256, n_out=16, k=k), frame_lens)
+
+
+@pytest.mark.parametrize("k,seed", [(3, 21), (1, 22)])
+def test_sweep_kernel_equals_host_on_default_grid(k, seed):
+    preds, win_off, gt, frame_lens = _big_case(seed, k)
+    assert len(frame_lens) >= 16 and max(frame_lens) >= 12_000 and torch.isnan(preds).any()
+    grid = DT.decoder_grid()
+    want = DT.sweep_decoder(preds, win_off, frame_lens, gt, grid, 512, 256)
+    got = DT.sweep_decoder(preds.to(_dev()), win_off, frame_lens, gt, grid, 512, 256)
+    for name, g, w in zip(("n_pred", "matched", "n_gt"), got, want):
+        assert g.shape == w.shape and g.dtype == w.dtype
+        bad = np.argwhere(g != w)
+        assert bad.size == 0, (name, len(bad), bad[:5].tolist())
+    assert got[0].shape == (511, 18, k) and got[1].sum() > 0
+    assert len({tuple(x) for x in got[0].reshape(511, -1)}) > 100     # the settings do differ
+
+
+def test_sweep_counts_equal_decode_events_counts():
+    preds, win_off, gt, frame_lens = _big_case(23, 3)
+    p = preds.to(_dev())
+    grid = [(0.5, 31, 124), (0.3, 1, 1), (0.65, 63, 248), (0.2, 15, 31)]
+    n_pred, _, _ = DT.sweep_decoder(p, win_off, frame_lens, gt, grid, 512, 256)
+    for g, (thr, avg, mx) in enumerate(grid):
+        ev = DT.decode_events(p, win_off, frame_lens, 512, 256, avg, mx, thr)
+        assert n_pred[g].tolist() == [[len(c) for c in f] for f in ev]
+
+
+def _launch_setup(seed, n_files=12, grid=None):
+    dev = _dev()
+    rng = np.random.default_rng(seed)
+    frame_lens = [int(x) for x in rng.integers(1, 5000, n_files)]
+    preds, win_off = run_preds(rng, frame_lens, 512, 256, 16, noise=0.3)
+    lay = DT.SweepLayout(win_off, frame_lens, 3, random_gt(rng, frame_lens), grid or DT.decoder_grid())
+    return torch.from_numpy(preds).to(dev), lay, lay.buffers(dev)
+
+
+def test_sweep_bitwise_repeatable():
+    p, lay, (meta, p_ws, out) = _launch_setup(31)
+    out.fill_(-7)
+    DT.launch_sweep(p, lay, meta, p_ws, out, 512, 256)
+    torch.cuda.synchronize()
+    first = out.clone()
+    assert (first >= 0).all()                       # every element is written
+    out.fill_(-7)
+    p_ws.fill_(float("nan"))
+    DT.launch_sweep(p, lay, meta, p_ws, out, 512, 256)            # a repeat
+    torch.cuda.synchronize()
+    assert torch.equal(out, first)
+    p2, lay2, (meta2, ws2, out2) = _launch_setup(32, n_files=5, grid=DT.decoder_grid()[:40])
+    DT.launch_sweep(p2, lay2, meta2, ws2, out2, 512, 256)         # another shape in between
+    out.fill_(-7)
+    DT.launch_sweep(p, lay, meta, p_ws, out, 512, 256)
+    torch.cuda.synchronize()
+    assert torch.equal(out, first)
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    out.fill_(-7)
+    torch.cuda.synchronize()
+    with torch.cuda.stream(s):                                    # a second stream
+        DT.launch_sweep(p, lay, meta, p_ws, out, 512, 256)
+    s.synchronize()
+    assert torch.equal(out, first)
+
+
+def test_sweep_graph_replay_equals_eager():
+    p, lay, (meta, p_ws, out) = _launch_setup(33)
+    DT.launch_sweep(p, lay, meta, p_ws, out, 512, 256)            # warm-up (eager)
+    torch.cuda.synchronize()
+    eager = out.clone()
+    g = torch.cuda.CUDAGraph()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        with torch.cuda.graph(g, stream=s):
+            DT.launch_sweep(p, lay, meta, p_ws, out, 512, 256)
+    torch.cuda.current_stream().wait_stream(s)
+    for _ in range(2):
+        out.fill_(-7)
+        g.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(out, eager)
+    p.mul_(0.0)                                                   # the graph reads the live inputs: nothing predicted now
+    g.replay()
+    torch.cuda.synchronize()
+    n_pred, matched = lay.parse(out.cpu().numpy())
+    assert n_pred.sum() == 0 and matched.sum() == 0
+
+
+@pytest.mark.parametrize("case,msg", [
+    ("grid", "grid points"), ("thresholds", "distinct thresholds"), ("words", "words"), ("gt", "ground-truth events"),
+    ("avg", "avg_pool 128"), ("max", "max_pool 257"), ("classes", "K 17"), ("files", "65536 files")])
+def test_sweep_caps_refuse_and_write_nothing(case, msg, monkeypatch):
+    """With the Python-side checks out of the way, the C ABI's own: IRIS_E_UNSUPPORTED (a ValueError) and untouched buffers."""
+    dev = _dev()
+    for name in ("MAX_GRID", "MAX_GROUP_THRESHOLDS", "MAX_SWEEP_WORDS", "MAX_GT_ROWS", "MAX_K", "MAX_SWEEP_FILES"):
+        monkeypatch.setattr(DT, name, 10 ** 9)
+    k, frame_lens, win_off, grid, gt = 3, [900], [0, 2], [(0.5, 31, 124)], [[[0, 1, 2]]]
+    if case == "grid":
+        grid = [(0.5, 31, 1 + i % 256) for i in range(4097)]
+    elif case == "thresholds":
+        grid = [(0.001 * i, 31, 124) for i in range(257)]
+    elif case == "words":
+        frame_lens, win_off, grid = [25_000], [0, 50], DT.decoder_grid()
+    elif case == "gt":
+        gt = [[[1, i, i + 1] for i in range(65)]]
+    elif case == "classes":
+        k = 17
+    elif case == "files":                 # zero-length files, the last one owning the two windows: the count alone is refused
+        frame_lens, win_off, gt = [0] * 65536, [0] * 65536 + [2], [[]] * 65536
+    lay = DT.SweepLayout(win_off, frame_lens, k, gt, grid)
+    if case == "avg":                  # (the Python grid check refuses these two: set them behind its back)
+        lay.avg[:] = 128
+    elif case == "max":
+        lay.max[:] = 257
+    meta, p_ws, out = lay.buffers(dev)
+    out.fill_(-7)
+    p_ws.fill_(-7.0)
+    preds = torch.full((win_off[-1], 16, k), 0.9, device=dev)
+    with pytest.raises(ValueError, match=msg):
+        DT.launch_sweep(preds, lay, meta, p_ws, out, 512, 512)
+    torch.cuda.synchronize()
+    assert (out == -7).all() and (p_ws == -7.0).all()
+
+
+def test_tune_decoder_end_to_end():
+    """tune_decoder on the device, then detect with and without its settings: the two mean ERs it reports are get_er's."""
+    from test_detect_gpu import StubModel, _cfg, _wavs
+    dev = _dev()
+    cfg = _cfg()
+    model = StubModel().to(dev)
+    items = _wavs([37.3, 14.1, 21.0, 60.2, 12.5, 9.0], seed=77)
+    truth = DT.DecoderSettings([0.3, 0.5, 0.75], [15, 31, 47], [62, 124, 31])
+    answer = {d.name: DT.answer_rows(d) for d in DT.detect(model, items, cfg, settings=truth, max_windows=6)}
+    assert all(len(rows) > 0 for rows in answer.values())
+    tuned = DT.tune_decoder(model, items, answer, cfg, max_windows=6)          # several groups
+    assert DT.tune_decoder(model, items, answer, cfg).settings == tuned.settings
+    ref = [M.get_er(answer[d.name], d.metric) for d in DT.detect(model, items, cfg)]
+    new = [M.get_er(answer[d.name], d.metric) for d in DT.detect(model, items, cfg, settings=tuned.settings)]
+    assert tuned.mean_er_reference == float(np.mean(ref))
+    assert tuned.mean_er_chosen == float(np.mean(new)) <= tuned.mean_er_reference
+    with pytest.raises(ValueError, match="no ground truth for f0"):
+        DT.tune_decoder(model, items, {}, cfg)
