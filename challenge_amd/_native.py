@@ -64,6 +64,8 @@ SIGNATURES = {
     "iris_speed_len": (C.c_longlong, [C.c_longlong, C.c_double]),
     "iris_speed_perturb": (_i, [_vp, _i, _i, _i, _vp]),
     "iris_mix_wave_frame_active_batch": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),
+    "iris_istft_len": (C.c_longlong, [C.c_longlong, _i]),
+    "iris_istft": (_i, [_vp, _vp, _i, _i, _vp]),
     "iris_wav_to_logmel": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     "iris_mask_apply": (_i, [_vp, _sz, _sz, _sz, _i, _vp, _i, _sz, _vp]),
     "iris_agc_clip": (_i, [_vp, _sz, _f, _f, _f, _vp]),

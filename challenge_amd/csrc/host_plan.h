@@ -256,6 +256,8 @@ static hipError_t allow_big_lds(const iris_plan* p) {
         e = hipFuncSetAttribute((const void*)mfma_kernel(p->log2n), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
         if (e != hipSuccess) return e;
     }
+    e = hipFuncSetAttribute(istft_kernel(p->log2n), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
+    if (e != hipSuccess) return e;
     return hipFuncSetAttribute(stft_kernel(p->log2n), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
 }
 

@@ -10,6 +10,7 @@
 //   k_fused.h        K1: waveform -> mel magnitudes (the hot path)
 //   k_fused_mfma.h   K1m: the same with the mel contraction on the matrix cores (fp16 MFMA variant)
 //   k_stft.h         STFT in the reference layout
+//   k_istft.h        inverse STFT of a ragged set of spectrograms in that layout (pickled spectrum corpora -> waveforms), one launch
 //   k_magmel.h       spectrum -> mel
 //   k_elementwise.h  min-max / log, normalize, magnitude-phase, mask, adaptive gradient clipping
 //   k_mix.h          batched sample synthesis (merge_complex_specs)
@@ -41,6 +42,7 @@
 #include "k_fused.h"
 #include "k_fused_mfma.h"
 #include "k_stft.h"
+#include "k_istft.h"
 #include "k_magmel.h"
 #include "k_elementwise.h"
 #include "host_plan.h"

@@ -237,6 +237,30 @@ class FrontendPlan:
         N.check(rc, "iris_stft")
         return spec
 
+    def istft(self, spec: torch.Tensor, length: Optional[int] = None) -> torch.Tensor:
+        """spec [B,F,T,2C] -> wav [B,C,L]: the inverse of `stft` (torch.istft with the periodic Hann window, center=True),
+        L = `length` or (T - 1) hop, at most (T - 1) hop.  Each clip is one record of one `iris_istft` launch."""
+        spec = _require_device_f32(spec, "spec")
+        if spec.device != self.device:
+            raise RuntimeError(f"spec is on {spec.device}, plan is on {self.device}")
+        if spec.dim() != 4 or spec.shape[1] != self.n_bins or spec.shape[3] != 2 * self.channels or self.n_fft == 0:
+            raise ValueError(f"spec must be [B, F={self.n_bins}, T, 2C={2 * self.channels}] on a plan with an FFT, got {tuple(spec.shape)}")
+        b, t = int(spec.shape[0]), int(spec.shape[2])
+        full = istft_len(t, self.hop)
+        length = full if length is None else int(length)
+        if t < 2 or not 0 < length <= full:
+            raise ValueError(f"istft: {t} frames at hop {self.hop} give at most {full} samples, asked for {length}")
+        wav = torch.empty((b, self.channels, length), dtype=torch.float32, device=self.device)
+        if b == 0:
+            return wav
+        table = np.zeros(b, ISTFT_SRC)
+        table["src"] = spec.data_ptr() + np.arange(b, dtype=np.uint64) * np.uint64(spec.stride(0) * 4)
+        table["dst"] = wav.data_ptr() + np.arange(b, dtype=np.uint64) * np.uint64(wav.stride(0) * 4)
+        table["n_frames"], table["len_out"] = t, length
+        istft_launch(table, self, t)
+        spec.record_stream(torch.cuda.current_stream(self.device))
+        return wav
+
     def magmel(self, spec: torch.Tensor, is_magphase: bool = False, t_bands=None, f_bands=None) -> torch.Tensor:
         """spec [B,F,T,2C] -> mel [B,M,T,C] (complex_to_magphase + magphase_to_mel)."""
         spec = _require_device_f32(spec, "spec")
@@ -1088,6 +1112,67 @@ def speed_perturb_batch(waves, rates):
     speed_perturb_launch(table, chan, int(table["len_out"].max()), dev)
     for w in waves:   # (a contiguous copy made above must outlive the kernel)
         w.record_stream(torch.cuda.current_stream(dev))
+    return results
+
+
+# mirrors iris_istft_src (include/iris_frontend.h)
+ISTFT_SRC = np.dtype([("src", "<u8"), ("dst", "<u8"), ("n_frames", "<i4"), ("len_out", "<i4")])
+assert ISTFT_SRC.itemsize == 24
+
+
+def istft_len(n_frames: int, hop: int) -> int:
+    """Samples the inverse STFT of `n_frames` frames returns by default: (n_frames - 1) * hop (iris_istft_len); 0 below two
+    frames."""
+    n_frames, hop = int(n_frames), int(hop)
+    if hop <= 0:
+        raise ValueError(f"hop must be positive, got {hop}")
+    return (n_frames - 1) * hop if n_frames >= 2 else 0
+
+
+def istft_launch(table: np.ndarray, plan: "FrontendPlan", max_frames: int, table_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Upload an ISTFT_SRC table (into `table_dev`, a long-lived uint8 device buffer, when given) and run iris_istft over it on
+    the current stream of the plan's device: one launch.  Returns the device table (tied to the stream when it was allocated
+    here)."""
+    device = plan.device
+    raw = torch.from_numpy(np.ascontiguousarray(table).view(np.uint8).reshape(-1))
+    if table_dev is None:
+        dev_table = raw.to(device, non_blocking=True)
+    else:
+        dev_table = table_dev[:raw.numel()]
+        dev_table.copy_(raw)
+    with plan._lock, torch.cuda.device(device):
+        rc = N.lib().iris_istft(plan._handle, dev_table.data_ptr(), int(table.shape[0]), int(max_frames), _stream_ptr(device))
+    N.check(rc, "iris_istft")
+    if table_dev is None and dev_table.numel():
+        dev_table.record_stream(torch.cuda.current_stream(device))
+    return dev_table
+
+
+def istft_batch(plan: "FrontendPlan", specs):
+    """Invert a ragged batch of complex spectrograms in ONE launch (iris_istft): specs is a list of [F, T_i >= 2, 2C] float32
+    tensors on the plan's device (re block, im block last; F = n_fft / 2 + 1 and C of the plan).  Returns a list of new
+    [C, (T_i - 1) hop] waveforms: torch.istft with the periodic Hann window and center=True, |out - fp64| <= 128 u S (see
+    include/iris_frontend.h).  CPU tensors raise: there is no CPU fallback."""
+    specs = list(specs)
+    if not specs:
+        return []
+    specs = [_require_device_f32(s, f"specs[{i}]") for i, s in enumerate(specs)]
+    table = np.zeros(len(specs), ISTFT_SRC)
+    results = []
+    for i, s in enumerate(specs):
+        if s.dim() != 3 or int(s.shape[0]) != plan.n_bins or int(s.shape[2]) != 2 * plan.channels or s.device != plan.device \
+                or int(s.shape[1]) < 2:
+            raise ValueError(f"istft_batch: specs[{i}] has shape {tuple(s.shape)} on {s.device}; expected "
+                             f"[{plan.n_bins}, T >= 2, {2 * plan.channels}] on {plan.device}")
+        n = istft_len(int(s.shape[1]), plan.hop)
+        if n > 2 ** 31 - 1:
+            raise ValueError(f"istft_batch: specs[{i}] would have {n} samples (> 2^31 - 1)")
+        o = torch.empty((plan.channels, n), dtype=torch.float32, device=plan.device)
+        table[i] = (s.data_ptr(), o.data_ptr(), int(s.shape[1]), n)
+        results.append(o)
+    istft_launch(table, plan, int(table["n_frames"].max()))
+    for s in specs:   # (a contiguous copy made above must outlive the kernel)
+        s.record_stream(torch.cuda.current_stream(plan.device))
     return results
 
 

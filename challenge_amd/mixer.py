@@ -473,7 +473,7 @@ class WaveMixer(DeviceMixer):
                  n_classes: int = 3, device=None, min_ratio: float = 2 / 3, min_noise_ratio: float = 1 / 2,
                  snr: float = -20, seed=None):
         labels = np.asarray(labels, np.float32)
-        assert len(np.asarray(backgrounds[0]).shape) == 2, 'each waveform must be [chan, samples]'
+        assert len(backgrounds[0].shape if isinstance(backgrounds[0], torch.Tensor) else np.asarray(backgrounds[0]).shape) == 2, 'each waveform must be [chan, samples]'
         assert len(voices) == len(labels)
         assert labels.ndim == 2 and labels.shape[1] == n_classes, \
             'labels must be in the form of [n_samples, n_classes]'
@@ -491,7 +491,9 @@ class WaveMixer(DeviceMixer):
         self.rng = np.random.default_rng(seed)
 
         def upload(items):
-            out = [torch.as_tensor(np.ascontiguousarray(np.asarray(x, np.float32))).to(self.device) for x in items]
+            # (a float32 tensor - e.g. a waveform `sj_train.waves_from_specs` left on the device - is taken as it is)
+            out = [x.detach().to(self.device, torch.float32).contiguous() if isinstance(x, torch.Tensor)
+                   else torch.as_tensor(np.ascontiguousarray(np.asarray(x, np.float32))).to(self.device) for x in items]
             for t in out:
                 if t.dim() != 2 or t.shape[0] != out[0].shape[0] or t.shape[1] < 1:
                     raise ValueError("sources must be [chan, samples] with equal chan")

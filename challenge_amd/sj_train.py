@@ -87,6 +87,10 @@ class ARGS:
         a('--online_stft', action='store_true',
           help='keep (synthetic) waveform corpora on the device, mix them before the STFT (WaveMixer) and run the '
                'fused HIP frontend on line instead of mixing pre-computed spectra (make_wave_dataset)')
+        a('--wave_corpus', type=str, default='synthetic', choices=['synthetic', 'pickles'],
+          help="--online_stft only.  'synthetic' (default): synthetic waveform corpora.  'pickles': the pickled SPECTRUM corpora "
+               "(or their --synthetic stand-ins) are inverted to waveforms once at start-up (waves_from_specs: one iris_istft "
+               "launch per corpus list) and mixed from there")
         a('--per_sample_pipeline', action='store_true',
           help='build samples one at a time with the tf.data-shaped graph (make_dataset) instead of the '
                'batched on-device synthesis (make_device_dataset), which is the default on a GPU')
@@ -323,8 +327,57 @@ def synthetic_wave_sources(n_chan: int = 2, n_classes: int = 3, hop: int = 256, 
     return backgrounds, voices, labels, noises
 
 
+def waves_from_specs(sources, n_fft=512, hop=256, device=None):
+    """(background spectra, voice spectra, labels, noise spectra) -> the same tuple with WAVEFORMS: every [F, T_i, 2C] complex
+    spectrogram (re block, im block last - what `load_wav` pickles) becomes a [C, (T_i - 1) hop] float32 tensor on `device`
+    by the inverse STFT (`frontend.istft_batch`: one `iris_istft` launch per corpus list).  Labels pass through.
+    What comes back: a corpus made by `load_wav` is a consistent STFT (of the reflect-padded recording), so its inverse is the
+    recording's first (T - 1) hop samples up to rounding, the stretch under the last frames included (in float64 to 1e-12:
+    tests/test_istft_host.py); the recording's tail beyond a multiple of `hop` was never in the kept range and is not
+    recoverable.  Spectra that are not the STFT of any waveform (mixed, masked or stretched ones) are inverted in the
+    least-squares sense (Griffin & Lim 1984)."""
+    backgrounds, voices, labels, noises = sources
+    if device is None:
+        if not torch.cuda.is_available():
+            raise RuntimeError("waves_from_specs needs a ROCm device (no CPU fallback)")
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("waves_from_specs needs a ROCm device (no CPU fallback)")
+    n_bins = n_fft // 2 + 1
+    plans = {}
+
+    def convert(items, what):
+        if items is None:
+            return None
+        specs = []
+        for i, x in enumerate(items):
+            t = x.detach() if isinstance(x, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(np.asarray(x, np.float32)))
+            if t.dim() != 3 or int(t.shape[0]) != n_bins or int(t.shape[2]) < 2 or int(t.shape[2]) % 2:
+                raise ValueError(f"waves_from_specs: {what}[{i}] has shape {tuple(t.shape)}; expected [F = n_fft / 2 + 1 = "
+                                 f"{n_bins}, T, 2 * chan] at n_fft {n_fft}")
+            if int(t.shape[1]) < 2:
+                raise ValueError(f"waves_from_specs: {what}[{i}] has {int(t.shape[1])} frame(s); the inverse needs two")
+            specs.append(t.to(device, torch.float32))
+        if not specs:
+            return []
+        chan = int(specs[0].shape[2]) // 2
+        if chan not in plans:
+            plans[chan] = _fe.FrontendPlan(n_fft, hop, 64, 16000, chan, 1, n_fft, device)
+        out = []
+        for i in range(0, len(specs), 65535):   # (the launch's grid holds 65535 records)
+            out += _fe.istft_batch(plans[chan], specs[i:i + 65535])
+        return out
+
+    waves = convert(backgrounds, "backgrounds"), convert(voices, "voices"), labels, convert(noises, "noises")
+    torch.cuda.current_stream(device).synchronize()   # the spectra above are released here
+    for plan in plans.values():
+        plan.close()
+    return waves
+
+
 def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=None, seed=None, n_fft=512, hop=256,
-                      sample_rate=16000, device_draw=False):
+                      sample_rate=16000, device_draw=False, spec_sources=None):
     """`make_device_dataset` from WAVEFORMS (waveform-domain variant): the corpora
     stay resident in HBM as [chan, L_i] waveforms, `WaveMixer` mixes a batch before the STFT (which is linear), and
     the fused kernel takes it from there - STFT, SpecAugment / `stft_filter` bands, mel, min-max, log in one pass;
@@ -340,11 +393,18 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
     the device (`iris_mix_draw`, `iris_augment_draw`), as in `make_device_dataset`.
     A 'speed' token in config.name (training sets only): the voice corpus is speed-perturbed by rates ~ U[0.9, 1.1) at
     creation and again every config.steps_per_epoch batches (`WaveMixer.enable_speed` / `respeed`: one `iris_speed_perturb`
-    and one `iris_mix_wave_frame_active_batch` launch over the corpus); a name without the token takes no new code path."""
+    and one `iris_mix_wave_frame_active_batch` launch over the corpus); a name without the token takes no new code path.
+    spec_sources: the same tuple as SPECTRA ([F, T_i, 2C], integer labels), e.g. the pickled corpora - converted once here by
+    `waves_from_specs` at this n_fft / hop and used as `sources` (giving both is a ValueError)."""
     from .mixer import WaveMixer
+    if spec_sources is not None:
+        if sources is not None:
+            raise ValueError("make_wave_dataset: give `sources` (waveforms) or `spec_sources` (spectra), not both")
     if _du.wants_stretch(config.name):
         raise ValueError(f"run name {config.name!r} asks for 'stretch': a waveform corpus has no spectra to stretch "
                          "(use make_device_dataset)")
+    if spec_sources is not None:
+        sources = waves_from_specs(spec_sources, n_fft, hop, device)
     if sources is None:
         sources = synthetic_wave_sources(2, n_classes, hop, seed=0 if training else 1)
     backgrounds, voices, labels, noises = sources
@@ -576,11 +636,19 @@ def main(argv=None):
             if rank == 0:
                 print('loaded pretrained Keras weights', NAME.replace('.h5', '.npz'))
     if device.type == 'cuda' and config.online_stft:
-        # corpora resident in HBM as WAVEFORMS, mixed before the STFT, fused frontend on line (synthetic sources:
-        # the reference's pickles hold spectra, not waveforms)
+        # corpora resident in HBM as WAVEFORMS, mixed before the STFT, fused frontend on line.  Synthetic sources by default;
+        # --wave_corpus pickles: the reference's pickles hold spectra, inverted to waveforms once (waves_from_specs)
         dd = not config.host_draws
-        train_set = make_wave_dataset(config, training=True, device=device, seed=1000 + rank, device_draw=dd)
-        test_set = make_wave_dataset(config, training=False, device=device, seed=2000 + rank, device_draw=dd)
+
+        def spec_sources(training):
+            if config.wave_corpus != 'pickles':
+                return None
+            backgrounds, voices, onehot, noises = _load_sources(config, training, 3, None)
+            return backgrounds, voices, onehot.argmax(-1), noises
+        train_set = make_wave_dataset(config, training=True, device=device, seed=1000 + rank, device_draw=dd,
+                                      spec_sources=spec_sources(True))
+        test_set = make_wave_dataset(config, training=False, device=device, seed=2000 + rank, device_draw=dd,
+                                     spec_sources=spec_sources(False))
     elif device.type == 'cuda' and not config.per_sample_pipeline:
         # corpora resident in HBM, whole batches synthesised on the device (each rank draws its own stream)
         dd = not config.host_draws

@@ -838,6 +838,37 @@ int iris_mix_wave_frame_active_batch(const void* table_dev, int n_src, int chann
                                      const void* active_ptrs_dev, int max_frames, void* stream);
 
 /*
+ * Inverse STFT of a RAGGED BATCH of complex spectrograms in the reference layout, in one launch: the inverse of iris_stft /
+ * load_wav's Spectrogram(n_fft, power = None), i.e. torch.istft(n_fft, hop, window = periodic Hann, center = True, onesided,
+ * normalized = False, length = len_out).  n_fft, hop, the channel count C and the constants come from the plan.
+ * Per record: src DEVICE [F = n_fft / 2 + 1, n_frames, 2C] fp32 (re block | im block last), dst DEVICE buffer whose first
+ * C * len_out floats receive the contiguous [C, len_out] result (floats beyond are not written), len_out <= (n_frames - 1) hop
+ * = iris_istft_len(n_frames, hop).  With N = n_fft, w[i] = 0.5 - 0.5 cos(2 pi i / N) (formed in double, rounded once) and
+ * p = n + N / 2:
+ *     x_t[i]  = (1 / N) (Re S[0, t] + (-1)^i Re S[N/2, t] + 2 sum_{0 < f < N/2} (Re S[f, t] cos(2 pi f i / N) - Im S[f, t] sin(2 pi f i / N)))
+ *     y[c, n] = (sum_t w[p - t hop] x_t[p - t hop]) / (sum_t w[p - t hop]^2)     over 0 <= t < n_frames with 0 <= p - t hop < N,
+ *                                                                                  in ascending t
+ * The imaginary parts of bins 0 and N / 2 are ignored.  Against the float64 evaluation |y - ref| <= 128 u S[c, n], u = 2^-24,
+ * S = (sum_t w[p - t hop] rms_i(x_t)) / (sum_t w[p - t hop]^2).  A sample whose covering frames are all zero is exactly 0; a
+ * NaN stays inside the samples its frame covers.  A record with n_frames < 2, len_out <= 0, len_out > (n_frames - 1) hop,
+ * n_frames > max_frames (it sizes the grid) or a NULL pointer is skipped (nothing written): the table lives on the device and
+ * cannot be checked here without a synchronisation.  src and dst must not overlap.
+ * Checked before any HIP call: NULL plan, n_src < 0, NULL table with n_src > 0, max_frames < 2 -> IRIS_E_INVALID; a mel-only
+ * plan, hop > n_fft / 2 (the envelope could vanish; with hop <= n_fft / 2 it is at least 0.5 inside the kept range), more
+ * channels than the LDS holds (n_fft 512: 4), (max_frames - 1) hop near 2^31, n_src > 65535 -> IRIS_E_UNSUPPORTED.  Every
+ * n_fft a plan can have (256 ... 2048) is supported.  n_src == 0 returns 0 and launches nothing.
+ * One launch on `stream`; no workspace, no atomics, no synchronisation: capturable, bitwise reproducible, and a record's
+ * result does not depend on the records around it.  Runs on the current HIP device (the plan's).
+ */
+typedef struct {
+    const float* src;
+    float* dst;
+    int32_t n_frames, len_out;
+} iris_istft_src;
+long long iris_istft_len(long long n_frames, int hop); /* (n_frames - 1) * hop; 0 for n_frames < 2 or hop <= 0 */
+int iris_istft(iris_plan* plan, const void* table_dev, int n_src, int max_frames, void* stream);
+
+/*
  * Per-kernel timing for bench.py: with enable = n > 0 every n-th call of
  * iris_wav_to_logmel carries a start/stop hipEvent pair around each of its
  * kernels on the launch stream (n = 1: every call; an event pair costs a few
