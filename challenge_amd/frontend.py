@@ -727,10 +727,13 @@ def bilstm128_forward(gx: torch.Tensor, w_hh: torch.Tensor, save: bool = False):
 def bilstm128_backward(dout: torch.Tensor, act: torch.Tensor, w_hh: torch.Tensor) -> torch.Tensor:
     """Back-propagation through time of `bilstm128_forward` in ONE launch: dout [B, T, 256] and the saved activations ->
     the gradient of the input pre-activations, dgx [B, T, 2, 512]."""
+    # refused before .contiguous() and before any launch: a host tensor here would hand the kernel a host pointer
+    if (dout.dim() != 3 or dout.shape[2] != 256 or tuple(act.shape) != (dout.shape[0], dout.shape[1], 2, 5, 128)
+            or tuple(w_hh.shape) != (2, 512, 128) or not (dout.is_cuda and act.is_cuda and w_hh.is_cuda)
+            or act.device != dout.device or w_hh.device != dout.device
+            or dout.dtype != torch.float32 or act.dtype != torch.float32 or w_hh.dtype != torch.float32):
+        raise ValueError("bilstm128_backward: dout [B, T, 256], act [B, T, 2, 5, 128], w_hh [2, 512, 128], all float32 on one device")
     b, t = int(dout.shape[0]), int(dout.shape[1])
-    if (tuple(dout.shape) != (b, t, 256) or tuple(act.shape) != (b, t, 2, 5, 128) or tuple(w_hh.shape) != (2, 512, 128)
-            or not dout.is_cuda or dout.dtype != torch.float32 or act.dtype != torch.float32):
-        raise ValueError("bilstm128_backward: dout [B, T, 256], act [B, T, 2, 5, 128], w_hh [2, 512, 128] (float32, device)")
     dout, act, w_hh = dout.contiguous(), act.contiguous(), w_hh.contiguous()
     dgx = torch.empty((b, t, 2, 512), dtype=torch.float32, device=dout.device)
     with torch.cuda.device(dout.device):
