@@ -973,19 +973,25 @@ VOC_SRC = np.dtype([("src", "<u8"), ("dst", "<u8"), ("n_in", "<i4"), ("n_out", "
 assert VOC_SRC.itemsize == 32
 
 
+def _scaled_len(n: int, rate: float, word: str) -> int:
+    """ceil(n / rate) in double, the length of numpy.arange(0, n, rate): the one length law of `stretched_frames` and
+    `speed_len` (`word` names the caller's rate in the error)."""
+    rate = float(rate)
+    if not (np.isfinite(rate) and rate > 0):
+        raise ValueError(f"{word} rate must be a positive finite number, got {rate}")
+    return int(np.ceil(float(n) / rate))
+
+
 def stretched_frames(n_frames: int, rate: float) -> int:
     """Frames of a spectrogram of `n_frames` frames stretched by `rate`: ceil(n_frames / rate) in double, the length of
     numpy.arange(0, n_frames, rate)."""
-    rate = float(rate)
-    if not (np.isfinite(rate) and rate > 0):
-        raise ValueError(f"stretch rate must be a positive finite number, got {rate}")
-    return int(np.ceil(float(n_frames) / rate))
+    return _scaled_len(n_frames, rate, "stretch")
 
 
-def phase_vocoder_launch(table: np.ndarray, n_bins: int, chan2: int, max_out_frames: int, device: torch.device,
-                         table_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Upload a VOC_SRC table (into `table_dev`, a long-lived uint8 device buffer, when given) and run iris_phase_vocoder over
-    it on the current stream: one launch.  Returns the device table (tied to the stream when it was allocated here)."""
+def _launch_records(table: np.ndarray, device: torch.device, table_dev: Optional[torch.Tensor], name: str, call) -> torch.Tensor:
+    """Upload a table of records (into `table_dev`, a long-lived uint8 device buffer, when given) and run
+    `call(device table pointer, record count, stream)` - the C entry point `name` - on the current stream of `device`.
+    Returns the device table (tied to the stream when it was allocated here)."""
     raw = torch.from_numpy(np.ascontiguousarray(table).view(np.uint8).reshape(-1))
     if table_dev is None:
         dev_table = raw.to(device, non_blocking=True)
@@ -993,12 +999,19 @@ def phase_vocoder_launch(table: np.ndarray, n_bins: int, chan2: int, max_out_fra
         dev_table = table_dev[:raw.numel()]
         dev_table.copy_(raw)
     with torch.cuda.device(device):
-        rc = N.lib().iris_phase_vocoder(dev_table.data_ptr(), int(table.shape[0]), int(n_bins), int(chan2), int(max_out_frames),
-                                        _stream_ptr(device))
-    N.check(rc, "iris_phase_vocoder")
+        rc = call(dev_table.data_ptr(), int(table.shape[0]), _stream_ptr(device))
+    N.check(rc, name)
     if table_dev is None and dev_table.numel():
         dev_table.record_stream(torch.cuda.current_stream(device))
     return dev_table
+
+
+def phase_vocoder_launch(table: np.ndarray, n_bins: int, chan2: int, max_out_frames: int, device: torch.device,
+                         table_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Upload a VOC_SRC table (into `table_dev`, a long-lived uint8 device buffer, when given) and run iris_phase_vocoder over
+    it on the current stream: one launch.  Returns the device table (tied to the stream when it was allocated here)."""
+    return _launch_records(table, device, table_dev, "iris_phase_vocoder", lambda ptr, n, stream: N.lib().iris_phase_vocoder(
+        ptr, n, int(n_bins), int(chan2), int(max_out_frames), stream))
 
 
 def phase_vocoder_batch(specs, rates, out=None):
@@ -1059,29 +1072,15 @@ assert SPEED_SRC.itemsize == 32
 def speed_len(length: int, rate: float) -> int:
     """Samples of a waveform of `length` samples played `rate` times faster: ceil(length / rate) in double, the length of
     numpy.arange(0, length, rate) (the law of `stretched_frames`)."""
-    rate = float(rate)
-    if not (np.isfinite(rate) and rate > 0):
-        raise ValueError(f"speed rate must be a positive finite number, got {rate}")
-    return int(np.ceil(float(length) / rate))
+    return _scaled_len(length, rate, "speed")
 
 
 def speed_perturb_launch(table: np.ndarray, channels: int, max_out_len: int, device: torch.device,
                          table_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Upload a SPEED_SRC table (into `table_dev`, a long-lived uint8 device buffer, when given) and run iris_speed_perturb over
     it on the current stream: one launch.  Returns the device table (tied to the stream when it was allocated here)."""
-    raw = torch.from_numpy(np.ascontiguousarray(table).view(np.uint8).reshape(-1))
-    if table_dev is None:
-        dev_table = raw.to(device, non_blocking=True)
-    else:
-        dev_table = table_dev[:raw.numel()]
-        dev_table.copy_(raw)
-    with torch.cuda.device(device):
-        rc = N.lib().iris_speed_perturb(dev_table.data_ptr(), int(table.shape[0]), int(channels), int(max_out_len),
-                                        _stream_ptr(device))
-    N.check(rc, "iris_speed_perturb")
-    if table_dev is None and dev_table.numel():
-        dev_table.record_stream(torch.cuda.current_stream(device))
-    return dev_table
+    return _launch_records(table, device, table_dev, "iris_speed_perturb", lambda ptr, n, stream: N.lib().iris_speed_perturb(
+        ptr, n, int(channels), int(max_out_len), stream))
 
 
 def speed_perturb_batch(waves, rates):
@@ -1136,19 +1135,10 @@ def istft_launch(table: np.ndarray, plan: "FrontendPlan", max_frames: int, table
     """Upload an ISTFT_SRC table (into `table_dev`, a long-lived uint8 device buffer, when given) and run iris_istft over it on
     the current stream of the plan's device: one launch.  Returns the device table (tied to the stream when it was allocated
     here)."""
-    device = plan.device
-    raw = torch.from_numpy(np.ascontiguousarray(table).view(np.uint8).reshape(-1))
-    if table_dev is None:
-        dev_table = raw.to(device, non_blocking=True)
-    else:
-        dev_table = table_dev[:raw.numel()]
-        dev_table.copy_(raw)
-    with plan._lock, torch.cuda.device(device):
-        rc = N.lib().iris_istft(plan._handle, dev_table.data_ptr(), int(table.shape[0]), int(max_frames), _stream_ptr(device))
-    N.check(rc, "iris_istft")
-    if table_dev is None and dev_table.numel():
-        dev_table.record_stream(torch.cuda.current_stream(device))
-    return dev_table
+    def call(ptr, n, stream):
+        with plan._lock:
+            return N.lib().iris_istft(plan._handle, ptr, n, int(max_frames), stream)
+    return _launch_records(table, plan.device, table_dev, "iris_istft", call)
 
 
 def istft_batch(plan: "FrontendPlan", specs):

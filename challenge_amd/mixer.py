@@ -14,12 +14,14 @@ drop-in (`pipeline.make_pipeline`) stays available for code that wants the tf.da
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _native as N
+from . import frontend as _fe
 from . import pipeline as _pl
 
 # mirrors iris_mix_src (include/iris_frontend.h)
@@ -56,11 +58,20 @@ class _Stream:
         return out
 
 
-def check_stretch_range(lo: float, hi: float) -> None:
-    """The rate range of `DeviceMixer.enable_stretch`: finite, 0 < lo <= hi."""
+def _check_rate_range(word: str, lo: float, hi: float) -> None:
     lo, hi = float(lo), float(hi)
     if not (np.isfinite(lo) and np.isfinite(hi) and 0 < lo <= hi):
-        raise ValueError(f"stretch rates must satisfy 0 < lo <= hi (finite), got lo = {lo}, hi = {hi}")
+        raise ValueError(f"{word} rates must satisfy 0 < lo <= hi (finite), got lo = {lo}, hi = {hi}")
+
+
+def check_stretch_range(lo: float, hi: float) -> None:
+    """The rate range of `DeviceMixer.enable_stretch`: finite, 0 < lo <= hi."""
+    _check_rate_range("stretch", lo, hi)
+
+
+def check_speed_range(lo: float, hi: float) -> None:
+    """The rate range of `WaveMixer.enable_speed`: finite, 0 < lo <= hi."""
+    _check_rate_range("speed", lo, hi)
 
 
 def stretch_rates(rng: np.random.Generator, n: int, lo: float = 0.8, hi: float = 1.2) -> np.ndarray:
@@ -69,11 +80,79 @@ def stretch_rates(rng: np.random.Generator, n: int, lo: float = 0.8, hi: float =
     return rng.uniform(float(lo), float(hi), size=int(n))
 
 
-def check_speed_range(lo: float, hi: float) -> None:
-    """The rate range of `WaveMixer.enable_speed`: finite, 0 < lo <= hi."""
-    lo, hi = float(lo), float(hi)
-    if not (np.isfinite(lo) and np.isfinite(hi) and 0 < lo <= hi):
-        raise ValueError(f"speed rates must satisfy 0 < lo <= hi (finite), got lo = {lo}, hi = {hi}")
+@dataclass
+class _VoiceAug:
+    """The voice corpus under `enable_stretch` / `enable_speed`: the originals, their never-moving copies and the launch table.
+    Lengths (`orig_n`, `cap`) are frames for the spectrum mixer and samples per channel for the waveform mixer."""
+    lo: float
+    hi: float
+    orig: list                      # the voices as given (device tensors)
+    orig_n: np.ndarray              # their lengths
+    cap: np.ndarray                 # ceil(orig_n / lo): what each buffer holds
+    bufs: list                      # one flat float32 buffer per voice
+    acts: list                      # its frame-activity vector
+    table: np.ndarray               # VOC_SRC / SPEED_SRC records, src / dst / input length filled once
+    table_dev: torch.Tensor         # long-lived device copy of `table`
+    act_ptr_dev: Optional[torch.Tensor] = None   # device array of the `acts` addresses (waveform mixer: one batched launch)
+    rates: Optional[np.ndarray] = None           # the rates of the latest re-augmentation
+
+
+def _enable_voice_aug(mixer, word: str, lo: float, hi: float) -> None:
+    """`enable_stretch` / `enable_speed` (word = 'stretch' / 'speed'): allocate the copies, switch the pointer tables to them
+    and fill them at rate 1.  The range is checked before `mixer` is touched."""
+    _check_rate_range(word, lo, hi)
+    if mixer._aug is not None:
+        raise RuntimeError(f"enable_{word} was already called on this mixer")
+    dev = mixer.device
+    dtype, f_in, _ = mixer._aug_record
+    orig = list(mixer.voices)
+    orig_n = (mixer._v_T if mixer._v_L is None else mixer._v_L).copy()
+    cap = np.array([_fe._scaled_len(int(n), lo, word) for n in orig_n], np.int64)
+    buf_floats, act_len = mixer._aug_sizes(cap, lo)
+    bufs = [torch.zeros(int(n), device=dev, dtype=torch.float32) for n in buf_floats]
+    acts = [torch.zeros(int(n), device=dev, dtype=torch.float32) for n in act_len]
+    table = np.zeros(len(orig), dtype)
+    table["src"], table["dst"] = [t.data_ptr() for t in orig], [b.data_ptr() for b in bufs]
+    table[f_in] = orig_n
+    mixer._aug = aug = _VoiceAug(float(lo), float(hi), orig, orig_n, cap, bufs, acts, table,
+                                 torch.empty(max(table.nbytes, 1), dtype=torch.uint8, device=dev))
+    mixer.voice_active = acts
+    mixer._v_ptr = np.array([b.data_ptr() for b in bufs], np.uint64)
+    mixer._v_act = np.array([a.data_ptr() for a in acts], np.uint64)
+    if mixer._v_L is not None:
+        aug.act_ptr_dev = torch.from_numpy(mixer._v_act.astype(np.int64)).to(dev)
+    if mixer._dd is not None:
+        mixer._dd["voice_arrays"]["src"].copy_(torch.from_numpy(mixer._v_ptr.astype(np.int64)))
+        mixer._dd["voice_arrays"]["act"].copy_(torch.from_numpy(mixer._v_act.astype(np.int64)))
+    _reaugment(mixer, word, np.ones(len(orig)))
+
+
+def _reaugment(mixer, word: str, rates) -> np.ndarray:
+    """`restretch` / `respeed`: draw the rates (unless given), check that every result fits its buffer, run the class's launch
+    and activity pass, then move the voices' lengths on the host and in the device corpus of `enable_device_draw`."""
+    aug = mixer._aug if isinstance(mixer, DeviceMixer) else None   # (called unbound on something that is no mixer: not enabled)
+    if aug is None:
+        raise RuntimeError(f"re{word} needs enable_{word}() first")
+    n_voice = len(aug.orig)
+    if rates is None:
+        rates = stretch_rates(mixer.rng, n_voice, aug.lo, aug.hi)
+    rates = np.asarray(rates, np.float64).reshape(-1)
+    if rates.shape[0] != n_voice:
+        raise ValueError(f"re{word}: {rates.shape[0]} rates for {n_voice} voices")
+    n_out = np.array([_fe._scaled_len(int(n), r, word) for n, r in zip(aug.orig_n, rates)], np.int64)
+    if np.any(n_out > aug.cap):
+        i = int(np.argmax(n_out > aug.cap))
+        raise ValueError(f"re{word}: voice {i} at rate {rates[i]} needs {n_out[i]} {mixer._aug_unit} but its buffer holds "
+                         f"{aug.cap[i]} (rates below lo = {aug.lo} do not fit)")
+    aug.table[mixer._aug_record[2]], aug.table["rate"] = n_out, rates
+    mixer._aug_launch(aug, n_out)
+    mixer._aug_adopt(aug, n_out)
+    if mixer._dd is not None:
+        mixer._dd["voice_arrays"]["T"].copy_(torch.from_numpy(mixer._v_T.astype(np.int32)))
+        if mixer._v_L is not None:
+            mixer._dd["voice_arrays"]["len"].copy_(torch.from_numpy(mixer._v_L.astype(np.int32)))
+    aug.rates = rates.copy()
+    return aug.rates
 
 
 class BatchDraw:
@@ -137,40 +216,55 @@ class DeviceMixer:
     (no per-sample Python loop): ~0.1 ms for a batch of 64.
     """
 
+    # what the constructor asks the class (`WaveMixer` differs in these): the values below and the methods `_source_ok`,
+    # `_set_dims`, `_frames` and `_frame_active`
+    _no_device = "DeviceMixer needs a ROCm device (no CPU fallback); use pipeline.make_pipeline"
+    _rank, _rank_error = 3, 'each spec must be a 3D-tensor'
+    _takes_tensors = False          # sources that already are torch tensors are taken as they are
+    _in_samples = False             # a source's second axis counts samples (not frames): keep the `_L` tables
+    _shape_errors = ("sources must be [freq, time, chan2] with equal freq and chan2",
+                     "voices / noises must share the backgrounds' freq and chan2 sizes")
+
     def __init__(self, backgrounds: Sequence, voices: Sequence, labels, noises: Optional[Sequence] = None,
                  n_frame: int = 300, max_voices: int = 10, max_noises: int = 10, n_classes: int = 3, device=None,
                  min_ratio: float = 2 / 3, min_noise_ratio: float = 1 / 2, snr: float = -20, seed=None):
         labels = np.asarray(labels, np.float32)
-        assert len(np.asarray(backgrounds[0]).shape) == 3, 'each spec must be a 3D-tensor'
+        as_tensor = lambda x: self._takes_tensors and isinstance(x, torch.Tensor)  # noqa: E731
+        first = backgrounds[0]
+        assert len(first.shape if as_tensor(first) else np.asarray(first).shape) == self._rank, self._rank_error
         assert len(voices) == len(labels)
         assert labels.ndim == 2 and labels.shape[1] == n_classes, \
             'labels must be in the form of [n_samples, n_classes]'
         if device is None:
             if not torch.cuda.is_available():
-                raise RuntimeError("DeviceMixer needs a ROCm device (no CPU fallback); use pipeline.make_pipeline")
+                raise RuntimeError(self._no_device)
             device = torch.device("cuda", torch.cuda.current_device())
         self.device = torch.device(device)
         if self.device.type != "cuda":
-            raise RuntimeError("DeviceMixer needs a ROCm device (no CPU fallback); use pipeline.make_pipeline")
+            raise RuntimeError(self._no_device)
         N.lib()  # fail loudly when the HIP library is missing
         self.n_frame, self.max_voices, self.max_noises, self.n_classes = n_frame, max_voices, max_noises, n_classes
         self.min_ratio, self.min_noise_ratio, self.snr = min_ratio, min_noise_ratio, snr
         self.rng = np.random.default_rng(seed)
+        self._dd = None    # the device-side corpus and draw state of `enable_device_draw`
+        self._aug = None   # the `_VoiceAug` of `enable_stretch` / `enable_speed`
 
         def upload(items):
-            out = [torch.as_tensor(np.ascontiguousarray(np.asarray(x, np.float32))).to(self.device) for x in items]
+            # (a float32 tensor - e.g. a waveform `sj_train.waves_from_specs` left on the device - is taken as it is)
+            out = [x.detach().to(self.device, torch.float32).contiguous() if as_tensor(x)
+                   else torch.as_tensor(np.ascontiguousarray(np.asarray(x, np.float32))).to(self.device) for x in items]
             for t in out:
-                if t.dim() != 3 or t.shape[0] != out[0].shape[0] or t.shape[2] != out[0].shape[2]:
-                    raise ValueError("sources must be [freq, time, chan2] with equal freq and chan2")
+                if not self._source_ok(t, out[0]):
+                    raise ValueError(self._shape_errors[0])
             return out
 
         self.backgrounds, self.voices = upload(backgrounds), upload(voices)
         self.noises = upload(noises) if noises is not None else None
-        self.n_bins, self.chan2 = int(self.backgrounds[0].shape[0]), int(self.backgrounds[0].shape[2])
+        self._set_dims(self.backgrounds[0])
         for group in (self.voices, self.noises or []):
             for t in group:
-                if t.shape[0] != self.n_bins or t.shape[2] != self.chan2:
-                    raise ValueError("voices / noises must share the backgrounds' freq and chan2 sizes")
+                if not self._source_ok(t, self.backgrounds[0]):
+                    raise ValueError(self._shape_errors[1])
         self.label_vecs = torch.from_numpy(labels).to(self.device)
         # which frames of a voice are active (max over freq, chan2 > 0; pipeline.py:57) is a property of
         # the source: one pass over the corpus now instead of one per use
@@ -178,21 +272,40 @@ class DeviceMixer:
         with torch.cuda.device(self.device):
             stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
             for v in self.voices:
-                act = torch.empty(int(v.shape[1]), device=self.device, dtype=torch.float32)
-                N.check(N.lib().iris_mix_frame_active(v.data_ptr(), self.n_bins, int(v.shape[1]), self.chan2,
-                                                      act.data_ptr(), stream), "iris_mix_frame_active")
+                act = torch.empty(int(self._frames(int(v.shape[1]))), device=self.device, dtype=torch.float32)
+                self._frame_active(v, int(v.shape[1]), act, stream)
                 self.voice_active.append(act)
-        # pointer / frame-count lookup tables of every source, indexed per batch when its table is built
-        self._bg_ptr = np.array([t.data_ptr() for t in self.backgrounds], np.uint64)
-        self._bg_T = np.array([int(t.shape[1]) for t in self.backgrounds], np.int64)
-        self._v_ptr = np.array([t.data_ptr() for t in self.voices], np.uint64)
-        self._v_act = np.array([a.data_ptr() for a in self.voice_active], np.uint64)
-        self._v_T = np.array([int(t.shape[1]) for t in self.voices], np.int64)
-        self._n_ptr = np.array([t.data_ptr() for t in self.noises], np.uint64) if self.noises is not None else None
-        self._n_T = np.array([int(t.shape[1]) for t in self.noises], np.int64) if self.noises is not None else None
+        # pointer / length / frame-count lookup tables of every source, indexed per batch when its table is built
+        ptrs = lambda ts: np.array([t.data_ptr() for t in ts], np.uint64)  # noqa: E731
+        lens = lambda ts: np.array([int(t.shape[1]) for t in ts], np.int64)  # noqa: E731
+        self._bg_ptr, self._v_ptr, self._v_act = ptrs(self.backgrounds), ptrs(self.voices), ptrs(self.voice_active)
+        self._n_ptr = ptrs(self.noises) if self.noises is not None else None
+        bg_len, v_len = lens(self.backgrounds), lens(self.voices)
+        n_len = lens(self.noises) if self.noises is not None else None
+        self._bg_T, self._v_T = self._frames(bg_len), self._frames(v_len)
+        self._n_T = self._frames(n_len) if n_len is not None else None
+        self._bg_L = self._v_L = self._n_L = None   # samples per channel: waveform sources only
+        if self._in_samples:
+            self._bg_L, self._v_L, self._n_L = bg_len, v_len, n_len
         self._b = _Stream(len(self.backgrounds), self.rng)
         self._v = _Stream(len(self.voices), self.rng)
         self._n = _Stream(len(self.noises), self.rng) if self.noises is not None else None
+
+    def _source_ok(self, t: torch.Tensor, ref: torch.Tensor) -> bool:
+        """The shape rule: `t` is [freq, time, chan2] with the freq and chan2 of `ref`."""
+        return t.dim() == 3 and t.shape[0] == ref.shape[0] and t.shape[2] == ref.shape[2]
+
+    def _set_dims(self, ref: torch.Tensor) -> None:
+        self.n_bins, self.chan2 = int(ref.shape[0]), int(ref.shape[2])
+
+    def _frames(self, n):
+        """Frames of a source whose second axis has `n` entries (an int or an array of them)."""
+        return n
+
+    def _frame_active(self, src: torch.Tensor, n: int, act: torch.Tensor, stream) -> None:
+        """Launch the frame-activity pass of a source of `n` frames (`WaveMixer`: samples) into `act`."""
+        N.check(N.lib().iris_mix_frame_active(src.data_ptr(), self.n_bins, n, self.chan2, act.data_ptr(), stream),
+                "iris_mix_frame_active")
 
     # -- random half ------------------------------------------------------------------
     @staticmethod
@@ -261,7 +374,7 @@ class DeviceMixer:
             n = full[:, 1 + V:]
             n["src"], n["T"] = self._n_ptr[d.noises], self._n_T[d.noises]
             n["pad"], n["off"], n["gain"], n["kind"] = np.maximum(pad_n, 0)[:, None], d.n_offset, d.n_gain, KIND_NOISE
-        if getattr(self, "_bg_L", None) is not None:  # waveform sources (WaveMixer): samples per channel
+        if self._bg_L is not None:  # waveform sources (WaveMixer): samples per channel
             full["reserved"][:, 0] = self._bg_L[d.bg]
             full["reserved"][:, 1:1 + V] = self._v_L[d.voices]
             if Nn:
@@ -269,34 +382,39 @@ class DeviceMixer:
         first = np.concatenate([[0], np.cumsum(use.sum(axis=1))]).astype(np.int32)
         return np.ascontiguousarray(full[use]), first
 
+    def _batch_table(self, batch: int, draws):
+        """(table_d, first_d, n_srcs, batch, keep) of one batch: drawn and written on the device after `enable_device_draw`
+        (unless `draws` are given), else drawn on the host and uploaded.  keep: what must be tied to the stream."""
+        if draws is None and self._dd is not None:
+            return (*self._draw_on_device(batch), batch, ())
+        draws = self.draw_arrays(batch) if draws is None else draws
+        table, first = self.table(draws)
+        table_d = torch.from_numpy(table.view(np.uint8).reshape(-1)).to(self.device, non_blocking=True)
+        first_d = torch.from_numpy(first).to(self.device, non_blocking=True)
+        return table_d, first_d, int(table.shape[0]), len(draws), (table_d, first_d)
+
+    def _launch_mix(self, name: str, n_srcs: int, keep, call) -> None:
+        """Allocate the workspace, run `call(workspace pointer, its floats, stream)` - the C entry point `name` - and tie the
+        workspace and `keep` to the stream: they must outlive the kernels."""
+        dev = self.device
+        ws_floats = int(N.lib().iris_mix_workspace(n_srcs, self.n_frame))
+        ws = torch.empty(max(ws_floats, 1), device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            rc = call(ws.data_ptr(), ws_floats, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        N.check(rc, name)
+        for t in (*keep, ws):
+            t.record_stream(torch.cuda.current_stream(dev))
+
     def mix(self, batch: int, draws=None):
         """One batch of (complex spectrogram [B, F, n_frame, 2C], labels [B, max_voices, n_frame,
         n_classes]) - `merge_complex_specs` (pipeline.py:6-110) for every sample, two launches.
         draws: a BatchDraw or a list of per-sample dicts (default: a fresh `draw_arrays(batch)`)."""
-        dev = self.device
-        on_device = draws is None and getattr(self, "_dd", None) is not None
-        if on_device:
-            table_d, first_d, n_srcs = self._draw_on_device(batch)
-        else:
-            draws = self.draw_arrays(batch) if draws is None else draws
-            batch = len(draws)
-            table, first = self.table(draws)
-            n_srcs = int(table.shape[0])
-            table_d = torch.from_numpy(table.view(np.uint8).reshape(-1)).to(dev, non_blocking=True)
-            first_d = torch.from_numpy(first).to(dev, non_blocking=True)
-        spec = torch.empty((batch, self.n_bins, self.n_frame, self.chan2), device=dev, dtype=torch.float32)
-        label = torch.empty((batch, self.max_voices, self.n_frame, self.n_classes), device=dev, dtype=torch.float32)
-        ws_floats = int(N.lib().iris_mix_workspace(n_srcs, self.n_frame))
-        ws = torch.empty(max(ws_floats, 1), device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev):
-            rc = N.lib().iris_mix_specs(table_d.data_ptr(), n_srcs, first_d.data_ptr(), self.label_vecs.data_ptr(),
-                                        spec.data_ptr(), label.data_ptr(), batch, self.n_bins, self.n_frame,
-                                        self.chan2, self.max_voices, self.n_classes, ws.data_ptr(), ws_floats,
-                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        N.check(rc, "iris_mix_specs")
-        # the table, ranges and workspace must outlive the kernels: tie them to the stream
-        for t in ((ws,) if on_device else (table_d, first_d, ws)):
-            t.record_stream(torch.cuda.current_stream(dev))
+        table_d, first_d, n_srcs, batch, keep = self._batch_table(batch, draws)
+        spec = torch.empty((batch, self.n_bins, self.n_frame, self.chan2), device=self.device, dtype=torch.float32)
+        label = torch.empty((batch, self.max_voices, self.n_frame, self.n_classes), device=self.device, dtype=torch.float32)
+        self._launch_mix("iris_mix_specs", n_srcs, keep, lambda ws, ws_floats, stream: N.lib().iris_mix_specs(
+            table_d.data_ptr(), n_srcs, first_d.data_ptr(), self.label_vecs.data_ptr(), spec.data_ptr(), label.data_ptr(), batch,
+            self.n_bins, self.n_frame, self.chan2, self.max_voices, self.n_classes, ws, ws_floats, stream))
         return spec, label
 
     # -- random half on the device ----------------------------------------------------
@@ -317,11 +435,10 @@ class DeviceMixer:
             self._dd["keep"].append(t)
             return _Corpus(t["src"].data_ptr(), 0 if t["act"] is None else t["act"].data_ptr(), t["T"].data_ptr(),
                            0 if t["len"] is None else t["len"].data_ptr(), int(len(ptr)))
-        wave = getattr(self, "_bg_L", None) is not None
-        self._dd["bg"] = corpus(self._bg_ptr, None, self._bg_T, self._bg_L if wave else None)
-        self._dd["voice"] = corpus(self._v_ptr, self._v_act, self._v_T, self._v_L if wave else None)
-        self._dd["noise"] = corpus(self._n_ptr, None, self._n_T, self._n_L if wave else None) if self.noises is not None else None
-        self._dd["voice_arrays"] = self._dd["keep"][1]   # `restretch` rewrites the voices' T (and, once, src / act) in place
+        self._dd["bg"] = corpus(self._bg_ptr, None, self._bg_T, self._bg_L)
+        self._dd["voice"] = corpus(self._v_ptr, self._v_act, self._v_T, self._v_L)
+        self._dd["noise"] = corpus(self._n_ptr, None, self._n_T, self._n_L) if self.noises is not None else None
+        self._dd["voice_arrays"] = self._dd["keep"][1]   # `_reaugment` rewrites the voices' T / len (and, once, src / act) in place
 
     # -- time-stretch augmentation of the voice corpus ----------------------------------
     def enable_stretch(self, lo: float = 0.8, hi: float = 1.2) -> None:
@@ -334,29 +451,7 @@ class DeviceMixer:
         `restretch` reads the new contents through unchanged addresses.  Until the first `restretch` the copies hold the
         voices at rate 1 (bit-identical).  Backgrounds and noises are not stretched: they carry no labels, and the
         reference's function was written for voices.  No accuracy claim is made for the augmentation."""
-        check_stretch_range(lo, hi)
-        if getattr(self, "_st", None) is not None:
-            raise RuntimeError("enable_stretch was already called on this mixer")
-        from . import frontend as _fe
-        orig, orig_T = list(self.voices), self._v_T.copy()
-        cap = np.array([_fe.stretched_frames(int(t), lo) for t in orig_T], np.int64)
-        row = self.n_bins * self.chan2
-        bufs = [torch.zeros(int(c) * row, device=self.device, dtype=torch.float32) for c in cap]
-        acts = [torch.zeros(int(c), device=self.device, dtype=torch.float32) for c in cap]
-        table = np.zeros(len(orig), _fe.VOC_SRC)
-        table["src"], table["dst"] = [t.data_ptr() for t in orig], [b.data_ptr() for b in bufs]
-        table["n_in"] = orig_T
-        self._st = {"lo": float(lo), "hi": float(hi), "orig": orig, "orig_T": orig_T, "cap": cap, "bufs": bufs, "acts": acts,
-                    "table": table, "rates": None,
-                    "table_dev": torch.empty(max(table.nbytes, 1), dtype=torch.uint8, device=self.device)}
-        self.voice_active = acts
-        self._v_ptr = np.array([b.data_ptr() for b in bufs], np.uint64)
-        self._v_act = np.array([a.data_ptr() for a in acts], np.uint64)
-        dd = getattr(self, "_dd", None)
-        if dd is not None:
-            dd["voice_arrays"]["src"].copy_(torch.from_numpy(self._v_ptr.astype(np.int64)))
-            dd["voice_arrays"]["act"].copy_(torch.from_numpy(self._v_act.astype(np.int64)))
-        self.restretch(np.ones(len(orig)))
+        _enable_voice_aug(self, "stretch", lo, hi)
 
     def restretch(self, rates=None) -> np.ndarray:
         """Stretch every ORIGINAL voice anew into its buffer: rate_i ~ U[lo, hi) from the mixer's own NumPy generator
@@ -365,37 +460,27 @@ class DeviceMixer:
         (`iris_mix_frame_active`: the labels follow from `max(voice) > 0`, as in the reference).  The voices' frame counts
         change to ceil(T_i / rate_i), on the host (`_v_T`) and in place in the device corpus of `enable_device_draw`.  Call
         it outside any graph capture.  Backgrounds and noises are not stretched.  Returns the rates used."""
-        st = getattr(self, "_st", None)
-        if st is None:
-            raise RuntimeError("restretch needs enable_stretch() first")
-        from . import frontend as _fe
-        n_voice = len(st["orig"])
-        if rates is None:
-            rates = stretch_rates(self.rng, n_voice, st["lo"], st["hi"])
-        rates = np.asarray(rates, np.float64).reshape(-1)
-        if rates.shape[0] != n_voice:
-            raise ValueError(f"restretch: {rates.shape[0]} rates for {n_voice} voices")
-        n_out = np.array([_fe.stretched_frames(int(t), r) for t, r in zip(st["orig_T"], rates)], np.int64)
-        if np.any(n_out > st["cap"]):
-            i = int(np.argmax(n_out > st["cap"]))
-            raise ValueError(f"restretch: voice {i} at rate {rates[i]} needs {n_out[i]} frames but its buffer holds "
-                             f"{st['cap'][i]} (rates below lo = {st['lo']} do not fit)")
-        table = st["table"]
-        table["n_out"], table["rate"] = n_out, rates
-        _fe.phase_vocoder_launch(table, self.n_bins, self.chan2, int(st["cap"].max()), self.device, st["table_dev"])
+        return _reaugment(self, "stretch", rates)
+
+    # what differs between `restretch` and `WaveMixer.respeed` (`_enable_voice_aug`, `_reaugment`)
+    _aug_record = (_fe.VOC_SRC, "n_in", "n_out")   # the launch table's dtype and its input / output length fields
+    _aug_unit = "frames"
+
+    def _aug_sizes(self, cap: np.ndarray, lo: float):
+        """(floats of each voice's buffer, length of its activity vector) for capacities `cap`."""
+        return cap * (self.n_bins * self.chan2), cap
+
+    def _aug_launch(self, aug: _VoiceAug, n_out: np.ndarray) -> None:
+        _fe.phase_vocoder_launch(aug.table, self.n_bins, self.chan2, int(aug.cap.max()), self.device, aug.table_dev)
         with torch.cuda.device(self.device):
             stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            for buf, act, n in zip(st["bufs"], st["acts"], n_out):
-                N.check(N.lib().iris_mix_frame_active(buf.data_ptr(), self.n_bins, int(n), self.chan2, act.data_ptr(), stream),
-                        "iris_mix_frame_active")
+            for buf, act, n in zip(aug.bufs, aug.acts, n_out):
+                self._frame_active(buf, int(n), act, stream)
+
+    def _aug_adopt(self, aug: _VoiceAug, n_out: np.ndarray) -> None:
         self._v_T = n_out
         self.voices = [b[:self.n_bins * int(n) * self.chan2].view(self.n_bins, int(n), self.chan2)
-                       for b, n in zip(st["bufs"], n_out)]
-        dd = getattr(self, "_dd", None)
-        if dd is not None:
-            dd["voice_arrays"]["T"].copy_(torch.from_numpy(n_out.astype(np.int32)))
-        st["rates"] = rates.copy()
-        return st["rates"]
+                       for b, n in zip(aug.bufs, n_out)]
 
     def enable_speed(self, lo: float = 0.9, hi: float = 1.1) -> None:
         raise NotImplementedError("DeviceMixer.enable_speed: a spectrum corpus cannot be resampled in time (speed perturbation "
@@ -468,66 +553,35 @@ class WaveMixer(DeviceMixer):
     for the sources' STFTs on every frame whose window crosses no crop / pad / tiling boundary
     (`iris_mix_waves`, include/iris_frontend.h; oracle: `mix_waves_apply`)."""
 
+    _no_device = "WaveMixer needs a ROCm device (no CPU fallback)"
+    _rank, _rank_error = 2, 'each waveform must be [chan, samples]'
+    _takes_tensors = True
+    _in_samples = True
+    _shape_errors = ("sources must be [chan, samples] with equal chan",
+                     "voices / noises must have the backgrounds' channel count")
+
     def __init__(self, backgrounds: Sequence, voices: Sequence, labels, noises: Optional[Sequence] = None,
                  n_frame: int = 300, n_fft: int = 1024, hop: int = 256, max_voices: int = 10, max_noises: int = 10,
                  n_classes: int = 3, device=None, min_ratio: float = 2 / 3, min_noise_ratio: float = 1 / 2,
                  snr: float = -20, seed=None):
-        labels = np.asarray(labels, np.float32)
-        assert len(backgrounds[0].shape if isinstance(backgrounds[0], torch.Tensor) else np.asarray(backgrounds[0]).shape) == 2, 'each waveform must be [chan, samples]'
-        assert len(voices) == len(labels)
-        assert labels.ndim == 2 and labels.shape[1] == n_classes, \
-            'labels must be in the form of [n_samples, n_classes]'
-        if device is None:
-            if not torch.cuda.is_available():
-                raise RuntimeError("WaveMixer needs a ROCm device (no CPU fallback)")
-            device = torch.device("cuda", torch.cuda.current_device())
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("WaveMixer needs a ROCm device (no CPU fallback)")
-        N.lib()
-        self.n_frame, self.max_voices, self.max_noises, self.n_classes = n_frame, max_voices, max_noises, n_classes
         self.n_fft, self.hop = n_fft, hop
-        self.min_ratio, self.min_noise_ratio, self.snr = min_ratio, min_noise_ratio, snr
-        self.rng = np.random.default_rng(seed)
+        super().__init__(backgrounds, voices, labels, noises, n_frame=n_frame, max_voices=max_voices, max_noises=max_noises,
+                         n_classes=n_classes, device=device, min_ratio=min_ratio, min_noise_ratio=min_noise_ratio, snr=snr,
+                         seed=seed)
 
-        def upload(items):
-            # (a float32 tensor - e.g. a waveform `sj_train.waves_from_specs` left on the device - is taken as it is)
-            out = [x.detach().to(self.device, torch.float32).contiguous() if isinstance(x, torch.Tensor)
-                   else torch.as_tensor(np.ascontiguousarray(np.asarray(x, np.float32))).to(self.device) for x in items]
-            for t in out:
-                if t.dim() != 2 or t.shape[0] != out[0].shape[0] or t.shape[1] < 1:
-                    raise ValueError("sources must be [chan, samples] with equal chan")
-            return out
+    def _source_ok(self, t: torch.Tensor, ref: torch.Tensor) -> bool:
+        """The shape rule: `t` is [chan, samples >= 1] with the channel count of `ref`."""
+        return t.dim() == 2 and t.shape[0] == ref.shape[0] and t.shape[1] >= 1
 
-        self.backgrounds, self.voices = upload(backgrounds), upload(voices)
-        self.noises = upload(noises) if noises is not None else None
-        self.channels = int(self.backgrounds[0].shape[0])
-        for group in (self.voices, self.noises or []):
-            for t in group:
-                if t.shape[0] != self.channels:
-                    raise ValueError("voices / noises must have the backgrounds' channel count")
-        self.label_vecs = torch.from_numpy(labels).to(self.device)
-        frames = lambda t: 1 + int(t.shape[1]) // hop  # noqa: E731
-        self.voice_active = []
-        with torch.cuda.device(self.device):
-            stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            for v in self.voices:
-                act = torch.empty(frames(v), device=self.device, dtype=torch.float32)
-                N.check(N.lib().iris_mix_wave_frame_active(v.data_ptr(), self.channels, int(v.shape[1]), n_fft, hop,
-                                                           act.data_ptr(), stream), "iris_mix_wave_frame_active")
-                self.voice_active.append(act)
-        ptrs = lambda ts: np.array([t.data_ptr() for t in ts], np.uint64)  # noqa: E731
-        lens = lambda ts: np.array([int(t.shape[1]) for t in ts], np.int64)  # noqa: E731
-        self._bg_ptr, self._bg_L = ptrs(self.backgrounds), lens(self.backgrounds)
-        self._v_ptr, self._v_L = ptrs(self.voices), lens(self.voices)
-        self._v_act = ptrs(self.voice_active)
-        self._n_ptr = ptrs(self.noises) if self.noises is not None else None
-        self._n_L = lens(self.noises) if self.noises is not None else None
-        self._bg_T, self._v_T = 1 + self._bg_L // hop, 1 + self._v_L // hop
-        self._n_T = 1 + self._n_L // hop if self.noises is not None else None
-        self._b = _Stream(len(self.backgrounds), self.rng)
-        self._v = _Stream(len(self.voices), self.rng)
-        self._n = _Stream(len(self.noises), self.rng) if self.noises is not None else None
+    def _set_dims(self, ref: torch.Tensor) -> None:
+        self.channels = int(ref.shape[0])
+
+    def _frames(self, n):
+        return 1 + n // self.hop
+
+    def _frame_active(self, src: torch.Tensor, n: int, act: torch.Tensor, stream) -> None:
+        N.check(N.lib().iris_mix_wave_frame_active(src.data_ptr(), self.channels, n, self.n_fft, self.hop, act.data_ptr(), stream),
+                "iris_mix_wave_frame_active")
 
     def enable_stretch(self, lo: float = 0.8, hi: float = 1.2) -> None:
         raise NotImplementedError("WaveMixer.enable_stretch: a waveform corpus has no spectra to stretch (the phase vocoder "
@@ -543,32 +597,7 @@ class WaveMixer(DeviceMixer):
         captured `mix` replayed after a `respeed` reads the new contents through unchanged addresses.  Until the first
         `respeed` the copies hold the voices at rate 1 (bit-identical).  Backgrounds and noises are not perturbed: they carry
         no labels.  No accuracy claim is made for the augmentation."""
-        check_speed_range(lo, hi)
-        if getattr(self, "_sp", None) is not None:
-            raise RuntimeError("enable_speed was already called on this mixer")
-        from . import frontend as _fe
-        orig, orig_L = list(self.voices), self._v_L.copy()
-        cap = np.array([_fe.speed_len(int(n), lo) for n in orig_L], np.int64)
-        if cap.max() > 2 ** 31 - 1:
-            raise ValueError(f"enable_speed: a voice at rate {lo} would have {cap.max()} samples (> 2^31 - 1)")
-        bufs = [torch.zeros(self.channels * int(c), device=self.device, dtype=torch.float32) for c in cap]
-        acts = [torch.zeros(1 + int(c) // self.hop, device=self.device, dtype=torch.float32) for c in cap]
-        table = np.zeros(len(orig), _fe.SPEED_SRC)
-        table["src"], table["dst"] = [t.data_ptr() for t in orig], [b.data_ptr() for b in bufs]
-        table["len_in"] = orig_L
-        act_ptr = np.array([a.data_ptr() for a in acts], np.uint64)
-        self._sp = {"lo": float(lo), "hi": float(hi), "orig": orig, "orig_L": orig_L, "cap": cap, "bufs": bufs, "acts": acts,
-                    "table": table, "rates": None,
-                    "table_dev": torch.empty(max(table.nbytes, 1), dtype=torch.uint8, device=self.device),
-                    "act_ptr_dev": torch.from_numpy(act_ptr.astype(np.int64)).to(self.device)}
-        self.voice_active = acts
-        self._v_ptr = np.array([b.data_ptr() for b in bufs], np.uint64)
-        self._v_act = act_ptr
-        dd = getattr(self, "_dd", None)
-        if dd is not None:
-            dd["voice_arrays"]["src"].copy_(torch.from_numpy(self._v_ptr.astype(np.int64)))
-            dd["voice_arrays"]["act"].copy_(torch.from_numpy(self._v_act.astype(np.int64)))
-        self.respeed(np.ones(len(orig)))
+        _enable_voice_aug(self, "speed", lo, hi)
 
     def respeed(self, rates=None) -> np.ndarray:
         """Resample every ORIGINAL voice anew into its buffer: rate_i ~ U[lo, hi) from the mixer's own NumPy generator (or the
@@ -578,61 +607,35 @@ class WaveMixer(DeviceMixer):
         and their frame counts to 1 + L' // hop, on the host (`_v_L`, `_v_T`, `voices`) and in place in the device corpus of
         `enable_device_draw`.  Call it outside any graph capture.  Backgrounds and noises are not perturbed.  Returns the rates
         used."""
-        sp = getattr(self, "_sp", None)
-        if sp is None:
-            raise RuntimeError("respeed needs enable_speed() first")
-        from . import frontend as _fe
-        n_voice = len(sp["orig"])
-        if rates is None:
-            rates = stretch_rates(self.rng, n_voice, sp["lo"], sp["hi"])
-        rates = np.asarray(rates, np.float64).reshape(-1)
-        if rates.shape[0] != n_voice:
-            raise ValueError(f"respeed: {rates.shape[0]} rates for {n_voice} voices")
-        n_out = np.array([_fe.speed_len(int(n), r) for n, r in zip(sp["orig_L"], rates)], np.int64)
-        if np.any(n_out > sp["cap"]):
-            i = int(np.argmax(n_out > sp["cap"]))
-            raise ValueError(f"respeed: voice {i} at rate {rates[i]} needs {n_out[i]} samples but its buffer holds "
-                             f"{sp['cap'][i]} (rates below lo = {sp['lo']} do not fit)")
-        table = sp["table"]
-        table["len_out"], table["rate"] = n_out, rates
-        table_dev = _fe.speed_perturb_launch(table, self.channels, int(sp["cap"].max()), self.device, sp["table_dev"])
+        return _reaugment(self, "speed", rates)
+
+    _aug_record = (_fe.SPEED_SRC, "len_in", "len_out")
+    _aug_unit = "samples"
+
+    def _aug_sizes(self, cap: np.ndarray, lo: float):
+        if cap.max() > 2 ** 31 - 1:
+            raise ValueError(f"enable_speed: a voice at rate {lo} would have {cap.max()} samples (> 2^31 - 1)")
+        return cap * self.channels, 1 + cap // self.hop
+
+    def _aug_launch(self, aug: _VoiceAug, n_out: np.ndarray) -> None:
+        max_len = int(aug.cap.max())
+        table_dev = _fe.speed_perturb_launch(aug.table, self.channels, max_len, self.device, aug.table_dev)
         with torch.cuda.device(self.device):
-            rc = N.lib().iris_mix_wave_frame_active_batch(table_dev.data_ptr(), n_voice, self.channels, self.n_fft, self.hop,
-                                                          sp["act_ptr_dev"].data_ptr(), 1 + int(sp["cap"].max()) // self.hop,
+            rc = N.lib().iris_mix_wave_frame_active_batch(table_dev.data_ptr(), len(aug.orig), self.channels, self.n_fft, self.hop,
+                                                          aug.act_ptr_dev.data_ptr(), 1 + max_len // self.hop,
                                                           C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
         N.check(rc, "iris_mix_wave_frame_active_batch")
+
+    def _aug_adopt(self, aug: _VoiceAug, n_out: np.ndarray) -> None:
         self._v_L, self._v_T = n_out, 1 + n_out // self.hop
-        self.voices = [b[:self.channels * int(n)].view(self.channels, int(n)) for b, n in zip(sp["bufs"], n_out)]
-        dd = getattr(self, "_dd", None)
-        if dd is not None:
-            dd["voice_arrays"]["T"].copy_(torch.from_numpy(self._v_T.astype(np.int32)))
-            dd["voice_arrays"]["len"].copy_(torch.from_numpy(n_out.astype(np.int32)))
-        sp["rates"] = rates.copy()
-        return sp["rates"]
+        self.voices = [b[:self.channels * int(n)].view(self.channels, int(n)) for b, n in zip(aug.bufs, n_out)]
 
     def mix(self, batch: int, draws=None):
         """One batch of (waveforms [B, C, (n_frame - 1) * hop], labels [B, max_voices, n_frame, n_classes])."""
-        dev = self.device
-        on_device = draws is None and getattr(self, "_dd", None) is not None
-        if on_device:
-            table_d, first_d, n_srcs = self._draw_on_device(batch)
-        else:
-            draws = self.draw_arrays(batch) if draws is None else draws
-            batch = len(draws)
-            table, first = self.table(draws)
-            n_srcs = int(table.shape[0])
-            table_d = torch.from_numpy(table.view(np.uint8).reshape(-1)).to(dev, non_blocking=True)
-            first_d = torch.from_numpy(first).to(dev, non_blocking=True)
-        wav = torch.empty((batch, self.channels, (self.n_frame - 1) * self.hop), device=dev, dtype=torch.float32)
-        label = torch.empty((batch, self.max_voices, self.n_frame, self.n_classes), device=dev, dtype=torch.float32)
-        ws_floats = int(N.lib().iris_mix_workspace(n_srcs, self.n_frame))
-        ws = torch.empty(max(ws_floats, 1), device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev):
-            rc = N.lib().iris_mix_waves(table_d.data_ptr(), n_srcs, first_d.data_ptr(), self.label_vecs.data_ptr(),
-                                        wav.data_ptr(), label.data_ptr(), batch, self.channels, self.hop, self.n_frame,
-                                        self.max_voices, self.n_classes, ws.data_ptr(), ws_floats,
-                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        N.check(rc, "iris_mix_waves")
-        for t in ((ws,) if on_device else (table_d, first_d, ws)):
-            t.record_stream(torch.cuda.current_stream(dev))
+        table_d, first_d, n_srcs, batch, keep = self._batch_table(batch, draws)
+        wav = torch.empty((batch, self.channels, (self.n_frame - 1) * self.hop), device=self.device, dtype=torch.float32)
+        label = torch.empty((batch, self.max_voices, self.n_frame, self.n_classes), device=self.device, dtype=torch.float32)
+        self._launch_mix("iris_mix_waves", n_srcs, keep, lambda ws, ws_floats, stream: N.lib().iris_mix_waves(
+            table_d.data_ptr(), n_srcs, first_d.data_ptr(), self.label_vecs.data_ptr(), wav.data_ptr(), label.data_ptr(), batch,
+            self.channels, self.hop, self.n_frame, self.max_voices, self.n_classes, ws, ws_floats, stream))
         return wav, label

@@ -240,6 +240,31 @@ def make_dataset(config, training=True, n_classes=3, sources=None):
     return _label_tail(pipeline, config)
 
 
+def _draw_bands(band_draw, training, rng, filter_bins, b, n_frame, n_bins):
+    """(t_bands, f_bands) of one batch for the mel kernel: SpecAugment (`augment`, data_utils.py:58-61: 6 time masks, 1
+    frequency mask per sample) on training sets and the `stft_filter` band (data_utils.py:126-136: bins 1..k).  A device-side
+    `band_draw` includes the filter band itself; without one the bands come from `rng` on the host."""
+    if band_draw is not None:
+        return band_draw(b, n_frame, n_bins)
+    tb, fb = _du.augment_draw_batch(b, n_frame, n_bins, rng) if training else (None, None)
+    if filter_bins:
+        flt = np.tile(np.array([[[1, filter_bins]]], np.int32), (b, 1, 1))
+        fb = flt if fb is None else np.concatenate([fb, flt], axis=1)
+    return tb, fb
+
+
+def _every_epoch(fn, steps_per_epoch):
+    """A function to call before every batch: it calls `fn` before every `steps_per_epoch`-th batch after the first."""
+    n_batches = 0
+
+    def tick():
+        nonlocal n_batches
+        if n_batches and n_batches % max(int(steps_per_epoch), 1) == 0:
+            fn()
+        n_batches += 1
+    return tick
+
+
 def make_device_dataset(config, training=True, n_classes=3, sources=None, device=None, seed=None, device_draw=False):
     """MI355X-native `make_dataset`: same stages, same outputs (sj_train.py:74-130), but a whole
     batch at a time on the device.  The corpora stay resident in HBM; `DeviceMixer` synthesises the
@@ -283,22 +308,11 @@ def make_device_dataset(config, training=True, n_classes=3, sources=None, device
         chan_map = random_merge_aug(config.n_chan)
 
     def gen():
-        n_batches = 0
+        reaugment = _every_epoch(mixer.restretch, config.steps_per_epoch) if stretch else (lambda: None)
         while True:
-            if stretch:
-                if n_batches and n_batches % max(int(config.steps_per_epoch), 1) == 0:
-                    mixer.restretch()
-                n_batches += 1
+            reaugment()
             x, y = to_frame_labels(*mixer.mix(config.batch_size))
-            b = int(x.shape[0])
-            tb = fb = None
-            if band_draw is not None:
-                tb, fb = band_draw(b, config.n_frame, mixer.n_bins)  # filter band included
-            elif training:  # `augment` (data_utils.py:58-61): 6 time masks, 1 frequency mask per sample
-                tb, fb = _du.augment_draw_batch(b, config.n_frame, mixer.n_bins, rng)
-            if filter_bins and band_draw is None:  # stft_filter (data_utils.py:126-136): bins 1..k
-                flt = np.tile(np.array([[[1, filter_bins]]], np.int32), (b, 1, 1))
-                fb = flt if fb is None else np.concatenate([fb, flt], axis=1)
+            tb, fb = _draw_bands(band_draw, training, rng, filter_bins, int(x.shape[0]), config.n_frame, mixer.n_bins)
             if chan_map is not None:
                 x, y = chan_map(x, y)
             yield to_mel(x, y, t_bands=tb, f_bands=fb)
@@ -433,25 +447,14 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
         mixer.respeed()
 
     def gen():
-        n_batches = 0
+        reaugment = _every_epoch(mixer.respeed, config.steps_per_epoch) if speed else (lambda: None)
         while True:
-            if speed:
-                if n_batches and n_batches % max(int(config.steps_per_epoch), 1) == 0:
-                    mixer.respeed()
-                n_batches += 1
+            reaugment()
             wav, y = mixer.mix(config.batch_size)
             _, y = to_frame_labels(None, y)
             if config.n_chan == 1 and wav.shape[1] == 2:
                 wav = wav[:, :1] + wav[:, 1:]            # true down-mix (NOT the reference's broadcast mono_chan: see docstring)
-            b = int(wav.shape[0])
-            tb = fb = None
-            if band_draw is not None:
-                tb, fb = band_draw(b, config.n_frame, plan.n_bins)
-            elif training:
-                tb, fb = _du.augment_draw_batch(b, config.n_frame, plan.n_bins, rng)
-            if filter_bins and band_draw is None:
-                flt = np.tile(np.array([[[1, filter_bins]]], np.int32), (b, 1, 1))
-                fb = flt if fb is None else np.concatenate([fb, flt], axis=1)
+            tb, fb = _draw_bands(band_draw, training, rng, filter_bins, int(wav.shape[0]), config.n_frame, plan.n_bins)
             if do_pcen:   # the raw mel out of the fused kernel, then PCEN in place
                 mel = plan.wav_to_logmel(wav.contiguous(), t_bands=tb, f_bands=fb, minmax=False, log=False)
                 yield _fe.pcen(mel, out=mel), y

@@ -30,7 +30,7 @@ def make_mixer(n_voice):
 def launch_bytes(mixer, rates):
     """Bytes one k_speed_perturb launch over the corpus reads (every source once) and writes (every output once)."""
     row = mixer.channels * 4
-    l_in = mixer._sp["orig_L"]
+    l_in = mixer._aug.orig_n
     n_out = np.ceil(l_in / rates).astype(np.int64)
     return int(row * l_in.sum()), int(row * n_out.sum())
 
@@ -91,7 +91,7 @@ def wall(n_voice, reps):
     import torch
     mixer = make_mixer(n_voice)
     rng = np.random.default_rng(RATE_SEED)
-    originals = mixer._sp["orig"]
+    originals = mixer._aug.orig
 
     def torch_loop(rates):
         return [torch_speed(v, float(r)) for v, r in zip(originals, rates)]

@@ -312,20 +312,20 @@ def test_speed_run_name_in_make_wave_dataset(dev):
     sources = S.synthetic_wave_sources(2, 3, n_bg=3, n_voice=7, n_noise=4, seed=3)
     L0 = np.array([v.shape[1] for v in sources[1]])
     ds = S.make_wave_dataset(S.ARGS().get(args + ['--name', 'run_speed']), training=True, sources=sources, device=dev, seed=4)
-    first = ds.mixer._sp["rates"].copy()
+    first = ds.mixer._aug.rates.copy()
     assert not np.array_equal(ds.mixer._v_L, L0) and np.array_equal(ds.mixer._v_L, np.ceil(L0 / first).astype(np.int64))
     it = iter(ds)
     for _ in range(5):   # steps_per_epoch = 2 and a prefetch two batches deep: by the fifth batch a second respeed has run
         bx, by = next(it)
         assert bx.shape == (6, 40, 64, 2) and by.shape == (6, 2, 3)
         assert torch.isfinite(bx).all() and float(by.min()) >= 0 and float(by.max()) <= 1
-    assert not np.array_equal(ds.mixer._sp["rates"], first)
+    assert not np.array_equal(ds.mixer._aug.rates, first)
     assert np.all(ds.mixer._v_L >= np.ceil(L0 / 1.1)) and np.all(ds.mixer._v_L <= np.ceil(L0 / 0.9))
     # validation sets are never perturbed; without the token the mixer has no speed state
     val = S.make_wave_dataset(S.ARGS().get(args + ['--name', 'run_speed']), training=False, sources=sources, device=dev, seed=4)
-    assert getattr(val.mixer, "_sp", None) is None and np.array_equal(val.mixer._v_L, L0)
+    assert val.mixer._aug is None and np.array_equal(val.mixer._v_L, L0)
     plain = S.make_wave_dataset(S.ARGS().get(args + ['--name', 'run']), training=True, sources=sources, device=dev, seed=4)
-    assert getattr(plain.mixer, "_sp", None) is None and np.array_equal(plain.mixer._v_L, L0)
+    assert plain.mixer._aug is None and np.array_equal(plain.mixer._v_L, L0)
     bx, by = next(iter(plain))
     assert bx.shape == (6, 40, 64, 2) and torch.isfinite(bx).all()
 

@@ -253,7 +253,7 @@ def test_stretch_run_name_in_make_device_dataset(dev):
     backgrounds, voices, labels, noises = sources
     T0 = np.array([v.shape[1] for v in voices])
     ds = S.make_device_dataset(S.ARGS().get(args + ['--name', 'run_stretch']), training=True, sources=sources, device=dev, seed=4)
-    assert ds.mixer._st is not None and not np.array_equal(ds.mixer._v_T, T0)
+    assert ds.mixer._aug is not None and not np.array_equal(ds.mixer._v_T, T0)
     it = iter(ds)
     for _ in range(3):   # steps_per_epoch = 2: the third batch comes after a second restretch
         bx, by = next(it)
@@ -262,11 +262,11 @@ def test_stretch_run_name_in_make_device_dataset(dev):
     assert np.all(ds.mixer._v_T >= np.ceil(T0 / 1.2)) and np.all(ds.mixer._v_T <= np.ceil(T0 / 0.8))
     # validation sets are never stretched
     val = S.make_device_dataset(S.ARGS().get(args + ['--name', 'run_stretch']), training=False, sources=sources, device=dev, seed=4)
-    assert getattr(val.mixer, "_st", None) is None and np.array_equal(val.mixer._v_T, T0)
+    assert val.mixer._aug is None and np.array_equal(val.mixer._v_T, T0)
     # without the token: the first batch of the code path as it was (a mixer built here, the same seeds, the same stages)
     cfg = S.ARGS().get(args + ['--name', 'run'])
     plain = S.make_device_dataset(cfg, training=True, sources=sources, device=dev, seed=4)
-    assert getattr(plain.mixer, "_st", None) is None
+    assert plain.mixer._aug is None
     bx, by = next(iter(plain))
     mixer = DeviceMixer(backgrounds, voices, np.eye(3, dtype=np.float32)[np.asarray(labels)], noises, n_frame=64, max_voices=4,
                         max_noises=3, n_classes=3, device=dev, snr=cfg.snr, min_ratio=1, seed=4)
