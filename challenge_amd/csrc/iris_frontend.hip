@@ -25,8 +25,9 @@
 //   host_wino.h        the host side of both: the device packers' entry points and one launch path over the two kernel families
 //   k_conv_wino_wrw.h  the same layers' weight gradient as Winograd F(2x2, 3x3) on the fp32 matrix cores (training)
 //   k_metrics.h      the training metrics er_score / cos_sim / F1 counts of a batch in one launch
+//   decode_core.h    the event decoder's arithmetic (overlap-add average, smoothing, dilation, run boundaries), written once
 //   k_detect.h       window predictions of many files -> smoothed, thresholded event lists (two launches)
-//   k_tune.h         the same decoder at every point of a settings grid, scored against ground truth: event and match counts
+//   k_tune.h         the same decoder (decode_core.h) at every point of a settings grid, scored against ground truth: event and match counts
 //                    per (grid point, file, class) in two launches
 //   k_pcen.h         per-channel energy normalisation: a chunked scan of the IIR smoother along time, then the compression
 //                    (host scalars, or per-band parameters from a device array: the trainable layer's forward)
@@ -60,6 +61,7 @@
 #include "k_resample.h"
 #include "k_agc_adam.h"
 #include "k_metrics.h"
+#include "decode_core.h"
 #include "k_detect.h"
 #include "k_tune.h"
 #include "k_pcen.h"

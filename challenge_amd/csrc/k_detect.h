@@ -1,18 +1,12 @@
 // k_detect.h -- window predictions of F files -> event lists (metrics.py:56-81 + :111-137) in two launches, no host sync.
-// Part of the single translation unit iris_frontend.hip.
+// Part of the single translation unit iris_frontend.hip (after decode_core.h).
 #pragma once
 // ---------------------------------------------------------------------------
-// The arithmetic (include/iris_frontend.h, iris_decode_events; challenge_amd/detect.py restates it on the CPU bit for bit).
-// For file f, class k, frame t < T_f:
-//   1. p[t] = (fp32 sum, from 0, over the windows w with w*hop <= t < w*hop + n_frame in ascending w of
-//      preds[win_off[f] + w, (t - w*hop) / up, k]) / (float)count                      overlap-add average
-//   2. a[t] = (fp32 sum, from 0, of p[u] for u in [t - al, t + ar] ∩ [0, T_f) ascending) / (float)n       AveragePooling1D 'same'
-//   3. d[t] = some u in [t - ml, t + mr] ∩ [0, T_f) has a[u] >= thr, and none of them is NaN     MaxPooling1D 'same', >= thr
-//   4. events = the maximal runs of d as (first, last) frames                          get_start_end_frame
-// ('same' pads: al = (avg - 1) / 2, ar = avg - 1 - al; the same for the max pool.)
-//
+// The arithmetic is decode_core.h's steps 1-4, called and not restated: dec_overlap_avg (1), dec_smooth with dec_is_on /
+// dec_is_nan (2), dec_dilate (3), dec_run_starts / dec_run_ends (4), pads from dec_pad.  Here is how one setting's work is laid
+// out over two launches, and the checks of the arguments that k_tune.h's entry point shares (dec_check_files).
 // Launch 1 (k_decode_bits): one workgroup per tile of kDecTile frames of one file, every class in turn.  The tile's p (with a
-// halo of 64 MW + al / ar frames) goes to LDS; a is computed per frame from LDS and turned by __ballot into two bit words per
+// halo of 64 MW + avg.l / avg.r frames) goes to LDS; a is computed per frame from LDS and turned by __ballot into two bit words per
 // 64 frames (a >= thr, a is NaN) over the tile plus MW words each side; d of a frame is "any on-bit and no NaN-bit in the
 // window", a masked OR over <= 2 MW + 1 words.  d goes out as bit words, file by file, class by class.
 // Launch 2 (k_decode_runs): one wave per (file, class) walks its bit words 64 at a time: run starts / ends are word
@@ -30,35 +24,6 @@ constexpr int kDecMaxMW = 2;
 constexpr int kDecMaxWords = kDecTile / 64 + 2 * kDecMaxMW;
 constexpr int kDecMaxP = kDecTile + 128 * kDecMaxMW + (kDecMaxAvg - 1);
 
-__device__ __forceinline__ int dec_words(int t) { return (t + 63) >> 6; }
-__device__ __forceinline__ int dec_pairs(int t) { return (t + 1) / 2 + 1; }   // event capacity of one (file, class)
-
-// any bit of w[] in [lo, hi] (lo <= hi, indices into the word array)
-__device__ __forceinline__ bool dec_any(const uint64_t* w, int lo, int hi) {
-    const int ja = lo >> 6, jb = hi >> 6;
-    uint64_t acc = 0ull;
-    for (int j = ja; j <= jb; ++j) {
-        uint64_t x = w[j];
-        if (j == ja) x &= ~0ull << (lo & 63);
-        if (j == jb) x &= ~0ull >> (63 - (hi & 63));
-        acc |= x;
-    }
-    return acc != 0ull;
-}
-
-__device__ __forceinline__ int dec_wave_sum(int v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ int dec_wave_incl_scan(int v, int lane) {
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(v, o, 64);
-        if (lane >= o) v += y;
-    }
-    return v;
-}
-
 struct DecLds {
     float p[kDecMaxP];
     uint64_t on[kDecMaxWords];
@@ -70,8 +35,8 @@ struct DecLds {
 
 __global__ __launch_bounds__(kDecThreads) void k_decode_bits(const float* __restrict__ preds, const int* __restrict__ win_off,
                                                              const int* __restrict__ frame_len, int F, int n_frame, int hop,
-                                                             int n_out, int up, int K, int al, int ar, int ml, int mr, int mw,
-                                                             float thr, uint64_t* __restrict__ bits) {
+                                                             int n_out, int up, int K, DecPad avg, DecPad mx, int mw, float thr,
+                                                             uint64_t* __restrict__ bits) {
     __shared__ DecLds L;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, nwv = kDecThreads / 64;
     const int bid = blockIdx.x;
@@ -108,24 +73,15 @@ __global__ __launch_bounds__(kDecThreads) void k_decode_bits(const float* __rest
     const int t0 = L.tile * kDecTile;
     const int w0 = win_off[f], W = win_off[f + 1] - w0;
     const int bbase = t0 - 64 * mw;        // frame of bit 0 of on / nan
-    const int pbase = bbase - al;          // frame of p[0]
-    const int np = kDecTile + 128 * mw + al + ar;
+    const int pbase = bbase - avg.l;       // frame of p[0]
+    const int np = kDecTile + 128 * mw + avg.l + avg.r;
     const int nwb = kDecTile / 64 + 2 * mw;
     uint64_t* out = bits + L.wbase;
     for (int k = 0; k < K; ++k) {
         // 1. overlap-add average over the tile and its halo
         for (int i = tid; i < np; i += kDecThreads) {
             const int v = pbase + i;
-            float p = 0.f;
-            if (v >= 0 && v < T) {
-                const int w_hi = min(v / hop, W - 1);
-                const int w_lo = v >= n_frame ? (v - n_frame) / hop + 1 : 0;
-                float s = 0.f;
-                for (int w = w_lo; w <= w_hi; ++w)
-                    s += preds[((size_t)(w0 + w) * n_out + (v - w * hop) / up) * K + k];
-                p = s / (float)(w_hi - w_lo + 1);
-            }
-            L.p[i] = p;
+            L.p[i] = v >= 0 && v < T ? dec_overlap_avg(preds, w0, W, n_frame, hop, n_out, up, K, v, k) : 0.f;
         }
         __syncthreads();
         // 2. average smoothing -> bit words (a >= thr, a NaN); frames outside [0, T) are neither
@@ -133,12 +89,9 @@ __global__ __launch_bounds__(kDecThreads) void k_decode_bits(const float* __rest
             const int u = bbase + 64 * j + lane;
             bool on = false, isn = false;
             if (u >= 0 && u < T) {
-                const int lo = max(u - al, 0), hi = min(u + ar, T - 1);
-                float s = 0.f;
-                for (int v = lo; v <= hi; ++v) s += L.p[v - pbase];
-                const float a = s / (float)(hi - lo + 1);
-                on = a >= thr;
-                isn = a != a;
+                const float a = dec_smooth(L.p, -pbase, u, avg, T);
+                on = dec_is_on(a, thr);
+                isn = dec_is_nan(a);
             }
             const uint64_t b_on = __ballot(on), b_nan = __ballot(isn);
             if (lane == 0) {
@@ -150,12 +103,8 @@ __global__ __launch_bounds__(kDecThreads) void k_decode_bits(const float* __rest
         // 3. max smoothing + threshold as a bit dilation; frames >= T stay 0 (launch 2 relies on it)
         for (int jj = wv; jj < kDecTile / 64; jj += nwv) {
             const int t = t0 + 64 * jj + lane;
-            bool d = false;
-            if (t < T) {
-                const int lo = 64 * mw + 64 * jj + lane - ml, hi = 64 * mw + 64 * jj + lane + mr;
-                d = dec_any(L.on, lo, hi) && !dec_any(L.nan, lo, hi);
-            }
-            const uint64_t b = __ballot(d);
+            const int i = 64 * mw + 64 * jj + lane;   // the frame's bit in on / nan
+            const uint64_t b = __ballot(t < T && dec_dilate(L.on, L.nan, i - mx.l, i + mx.r));
             const int word = (t0 >> 6) + jj;
             if (lane == 0 && word < nw) out[(size_t)k * nw + word] = b;
         }
@@ -187,8 +136,7 @@ __global__ __launch_bounds__(256) void k_decode_runs(const int* __restrict__ fra
         const uint64_t cur = j < nw ? w[j] : 0ull;
         const uint64_t prev = (j > 0 && j - 1 < nw) ? w[j - 1] : 0ull;
         const uint64_t next = j + 1 < nw ? w[j + 1] : 0ull;
-        uint64_t s = cur & ~((cur << 1) | (prev >> 63));
-        uint64_t en = cur & ~((cur >> 1) | (next << 63));
+        uint64_t s = dec_run_starts(cur, prev >> 63), en = dec_run_ends(cur, next);
         const int cs = __popcll(s), ce = __popcll(en);
         const int is = dec_wave_incl_scan(cs, lane), ie = dec_wave_incl_scan(ce, lane);
         int xs = base_s + is - cs, xe = base_e + ie - ce;
@@ -206,6 +154,32 @@ __global__ __launch_bounds__(256) void k_decode_runs(const int* __restrict__ fra
     if (lane == 0) n_ev[q] = base_s;
 }
 
+// What both decoder entry points (`who`: the name, for the message) ask of the window geometry and of the per-file tables,
+// on the host copies; the totals are what the two need to size their launches and bound their indices.
+struct DecTotals { long long tiles, words, pairs, frames, t_max; };   // sums over the files, and the longest file's frames
+static int dec_check_files(const char* who, const int* win_off_host, const int* frame_len_host, int n_files, int n_frame,
+                           int overlap_hop, int n_out, DecTotals* tot) {
+    if (overlap_hop > n_frame)
+        return fail(IRIS_E_INVALID, "%s: overlap_hop %d > n_frame %d leaves frames no window covers", who, overlap_hop, n_frame);
+    if (n_frame % n_out != 0)
+        return fail(IRIS_E_INVALID, "%s: n_frame %d is not a multiple of the model's %d output frames", who, n_frame, n_out);
+    if (win_off_host[0] < 0) return fail(IRIS_E_INVALID, "%s: win_off[0] = %d < 0", who, win_off_host[0]);
+    *tot = DecTotals{};
+    for (int f = 0; f < n_files; ++f) {
+        const long long tl = frame_len_host[f], nwin = (long long)win_off_host[f + 1] - win_off_host[f];
+        if (tl < 0 || nwin < 0) return fail(IRIS_E_INVALID, "%s: file %d: frame_len %lld, windows %lld", who, f, tl, nwin);
+        if (tl > 0 && (nwin < 1 || tl > (nwin - 1) * overlap_hop + n_frame))
+            return fail(IRIS_E_INVALID, "%s: file %d: frame_len %lld > (%lld - 1) * %d + %d: frames no window covers", who, f, tl,
+                        nwin, overlap_hop, n_frame);
+        tot->tiles += (tl + kDecTile - 1) / kDecTile;
+        tot->words += dec_words(tl);
+        tot->pairs += dec_pairs(tl);
+        tot->frames += tl;
+        tot->t_max = std::max(tot->t_max, tl);
+    }
+    return IRIS_OK;
+}
+
 extern "C" int iris_decode_events(const float* preds, const int* win_off, const int* frame_len, const int* win_off_host,
                                   const int* frame_len_host, int n_files, int n_frame, int overlap_hop, int n_out, int n_classes,
                                   int avg_pool, int max_pool, float threshold, unsigned long long* bits, int* ev, int* n_ev,
@@ -215,38 +189,21 @@ extern "C" int iris_decode_events(const float* preds, const int* win_off, const 
     if (n_files < 1 || n_frame < 1 || overlap_hop < 1 || n_out < 1 || n_classes < 1 || avg_pool < 1 || max_pool < 1)
         return fail(IRIS_E_INVALID, "iris_decode_events: files %d, n_frame %d, overlap_hop %d, n_out %d, K %d, pools %d / %d",
                     n_files, n_frame, overlap_hop, n_out, n_classes, avg_pool, max_pool);
-    if (overlap_hop > n_frame)
-        return fail(IRIS_E_INVALID, "iris_decode_events: overlap_hop %d > n_frame %d leaves frames no window covers", overlap_hop,
-                    n_frame);
-    if (n_frame % n_out != 0)
-        return fail(IRIS_E_INVALID, "iris_decode_events: n_frame %d is not a multiple of the model's %d output frames", n_frame,
-                    n_out);
     if (n_classes > kDecMaxK || avg_pool > kDecMaxAvg || max_pool > kDecMaxMax)
         return fail(IRIS_E_UNSUPPORTED, "iris_decode_events: K %d (<= %d), avg_pool %d (<= %d), max_pool %d (<= %d)", n_classes,
                     kDecMaxK, avg_pool, kDecMaxAvg, max_pool, kDecMaxMax);
-    if (win_off_host[0] < 0) return fail(IRIS_E_INVALID, "iris_decode_events: win_off[0] = %d < 0", win_off_host[0]);
-    long long tiles = 0, words = 0, pairs = 0;
-    for (int f = 0; f < n_files; ++f) {
-        const long long tl = frame_len_host[f], nwin = (long long)win_off_host[f + 1] - win_off_host[f];
-        if (tl < 0 || nwin < 0)
-            return fail(IRIS_E_INVALID, "iris_decode_events: file %d: frame_len %lld, windows %lld", f, tl, nwin);
-        if (tl > 0 && (nwin < 1 || tl > (nwin - 1) * overlap_hop + n_frame))
-            return fail(IRIS_E_INVALID, "iris_decode_events: file %d: frame_len %lld > (%lld - 1) * %d + %d: frames no window covers",
-                        f, tl, nwin, overlap_hop, n_frame);
-        tiles += (tl + kDecTile - 1) / kDecTile;
-        words += (tl + 63) / 64;
-        pairs += (tl + 1) / 2 + 1;
-    }
-    if (tiles > INT_MAX || words * n_classes > INT_MAX || 2 * pairs * n_classes > INT_MAX)
-        return fail(IRIS_E_UNSUPPORTED, "iris_decode_events: %lld frames in one call is too many", words * 64);
-    const int al = (avg_pool - 1) / 2, ar = avg_pool - 1 - al;
-    const int ml = (max_pool - 1) / 2, mr = max_pool - 1 - ml;
-    const int mw = (std::max(ml, mr) + 63) / 64;
+    DecTotals tot;
+    const int rc = dec_check_files("iris_decode_events", win_off_host, frame_len_host, n_files, n_frame, overlap_hop, n_out, &tot);
+    if (rc != IRIS_OK) return rc;
+    if (tot.tiles > INT_MAX || tot.words * n_classes > INT_MAX || 2 * tot.pairs * n_classes > INT_MAX)
+        return fail(IRIS_E_UNSUPPORTED, "iris_decode_events: %lld frames in one call is too many", tot.words * 64);
+    const DecPad avg = dec_pad(avg_pool), mx = dec_pad(max_pool);
+    const int mw = (std::max(mx.l, mx.r) + 63) / 64;
     hipStream_t s = (hipStream_t)stream;
-    if (tiles > 0) {
-        k_decode_bits<<<(unsigned)tiles, kDecThreads, 0, s>>>(preds, win_off, frame_len, n_files, n_frame, overlap_hop, n_out,
-                                                              n_frame / n_out, n_classes, al, ar, ml, mr, mw, threshold,
-                                                              reinterpret_cast<uint64_t*>(bits));
+    if (tot.tiles > 0) {
+        k_decode_bits<<<(unsigned)tot.tiles, kDecThreads, 0, s>>>(preds, win_off, frame_len, n_files, n_frame, overlap_hop, n_out,
+                                                                  n_frame / n_out, n_classes, avg, mx, mw, threshold,
+                                                                  reinterpret_cast<uint64_t*>(bits));
         HIP_TRY(hipGetLastError());
     }
     const int q = n_files * n_classes;

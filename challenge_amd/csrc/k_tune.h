@@ -1,11 +1,12 @@
 // k_tune.h -- the event decoder of k_detect.h at every point of a settings grid, scored against ground truth: per (grid point,
 // file, class) the number of predicted events and the number get_er's greedy rule matches.  Two launches, no host sync.
-// Part of the single translation unit iris_frontend.hip (after k_detect.h, whose helpers it uses).
+// Part of the single translation unit iris_frontend.hip (after decode_core.h, and k_detect.h for its limits and dec_check_files).
 #pragma once
 // ---------------------------------------------------------------------------
 // What it computes (include/iris_frontend.h, iris_decode_sweep; challenge_amd/detect.py sweep_decoder restates it on the CPU).
-// For grid point g = (thr, avg_pool, max_pool), file f, class k: the events of iris_decode_events with that setting (steps 1-4 of
-// k_detect.h: the same fp32 sums in the same order, the same >= and NaN rules); each event (s, e) becomes the second
+// For grid point g = (thr, avg_pool, max_pool), file f, class k: the events of iris_decode_events with that setting, by the
+// functions k_detect.h calls - decode_core.h's dec_overlap_avg (step 1), dec_smooth with dec_is_on / dec_is_nan (2), dec_dilate
+// (3), dec_run_starts / dec_run_ends (4), pads from dec_pad; each event (s, e) becomes the second
 // (int)((((double)(s + e)) / 2) * metric_hop / sample_rate) (metrics.output_to_metric, left to right in fp64); n_pred counts them
 // and matched is metrics.get_er's greedy rule on the (file, class) group of ground-truth rows (start_s, end_s), which the caller
 // keeps sorted by start: each row in turn takes the first prediction not yet taken, in time order, whose second lies in
@@ -22,9 +23,9 @@
 // Launch 2 (k_tune_sweep): one workgroup per (file, class, distinct avg_pool).  Phase A: each frame's a[t] (step 2, from the
 // workspace p) is formed once and compared with every distinct threshold of that avg_pool: one __ballot per threshold gives the
 // "a >= thr" bit words in LDS, one more the NaN words; a itself is never stored.  Phase B: the waves share out the grid points of
-// the avg_pool; per point a wave forms d (step 3) 64 frames at a time as in k_detect.h (masked ORs over the bit words), and walks
-// the run starts and ends of d with wave-uniform control flow: each closed run is one prediction.  Plain stores, integer counts,
-// no atomics: bitwise reproducible.
+// the avg_pool; per point a wave forms d (step 3) 64 frames at a time (file-absolute bits, the window clipped to the file) and
+// walks the run starts and ends of d with wave-uniform control flow: each closed run is one prediction.  Plain stores, integer
+// counts, no atomics: bitwise reproducible.
 // The grid must arrive sorted: equal avg_pool adjacent, and inside one avg_pool equal thresholds adjacent; the groups are found
 // again on the device from the arrays themselves (one wave, ballots over the boundaries).
 // ---------------------------------------------------------------------------
@@ -46,19 +47,6 @@ __device__ __forceinline__ int tune_frames_before(const int* __restrict__ frame_
     return dec_wave_sum(s);
 }
 
-// any bit of w[] (nw words, bit i = frame i) in frames [lo, hi], 0 <= lo <= hi < 64 nw
-__device__ __forceinline__ bool tune_any(const uint64_t* w, int lo, int hi) {
-    const int ja = lo >> 6, jb = hi >> 6;
-    uint64_t acc = 0ull;
-    for (int j = ja; j <= jb; ++j) {
-        uint64_t x = w[j];
-        if (j == ja) x &= ~0ull << (lo & 63);
-        if (j == jb) x &= ~0ull >> (63 - (hi & 63));
-        acc |= x;
-    }
-    return acc != 0ull;
-}
-
 __global__ __launch_bounds__(kTunePThreads) void k_tune_p(const float* __restrict__ preds, const int* __restrict__ win_off,
                                                           const int* __restrict__ frame_len, int n_frame, int hop, int n_out,
                                                           int up, int K, float* __restrict__ p_ws) {
@@ -75,11 +63,7 @@ __global__ __launch_bounds__(kTunePThreads) void k_tune_p(const float* __restric
     const int n = min(kTunePTile, T - t0) * K;
     for (int i = threadIdx.x; i < n; i += kTunePThreads) {
         const int v = t0 + i / K, k = i % K;   // k fastest: the reads of preds coalesce
-        const int w_hi = min(v / hop, W - 1);
-        const int w_lo = v >= n_frame ? (v - n_frame) / hop + 1 : 0;
-        float s = 0.f;
-        for (int w = w_lo; w <= w_hi; ++w) s += preds[((size_t)(w0 + w) * n_out + (v - w * hop) / up) * K + k];
-        out[(size_t)k * T + v] = s / (float)(w_hi - w_lo + 1);
+        out[(size_t)k * T + v] = dec_overlap_avg(preds, w0, W, n_frame, hop, n_out, up, K, v, k);
     }
 }
 
@@ -138,23 +122,17 @@ __global__ __launch_bounds__(kTuneThreads) void k_tune_sweep(const float* __rest
     const int T = frame_len[f], nw = dec_words(T);
     // (the entry point has checked these on the host copies; a grid that differs from them must not run off the LDS arrays)
     if (g0 < 0 || n_thr > kTuneMaxThr || (n_thr + 1) * nw > kTuneMaxWords) return;
-    const int a_pool = g_avg[g0], al = (a_pool - 1) / 2, ar = a_pool - 1 - al;
+    const DecPad avg = dec_pad(g_avg[g0]);
     const float* p = p_ws + (size_t)L.base * K + (size_t)k * T;
     // ---- phase A: a[t] once per frame -> the NaN words and one set of >= words per threshold
     for (int j = wv; j < nw; j += kTuneWaves) {
         const int u = 64 * j + lane;
-        float a = 0.f;
         const bool in = u < T;
-        if (in) {
-            const int lo = max(u - al, 0), hi = min(u + ar, T - 1);
-            float s = 0.f;
-            for (int v = lo; v <= hi; ++v) s += p[v];
-            a = s / (float)(hi - lo + 1);
-        }
-        const uint64_t b_nan = __ballot(in && a != a);
+        const float a = in ? dec_smooth(p, 0, u, avg, T) : 0.f;
+        const uint64_t b_nan = __ballot(in && dec_is_nan(a));
         if (lane == 0) L.words[j] = b_nan;
         for (int h = 0; h < n_thr; ++h) {
-            const uint64_t b = __ballot(in && a >= L.thr[h]);
+            const uint64_t b = __ballot(in && dec_is_on(a, L.thr[h]));
             if (lane == 0) L.words[(size_t)(1 + h) * nw + j] = b;
         }
     }
@@ -168,7 +146,7 @@ __global__ __launch_bounds__(kTuneThreads) void k_tune_sweep(const float* __rest
     }
     for (int it = wv; it < g1 - g0; it += kTuneWaves) {
         const int g = g0 + it;
-        const int m_pool = g_max[g], ml = (m_pool - 1) / 2, mr = m_pool - 1 - ml;
+        const DecPad mx = dec_pad(g_max[g]);
         const uint64_t* w_on = L.words + (size_t)(1 + L.item_h[it]) * nw;
         const uint64_t* w_nan = L.words;
         bool taken = false;
@@ -179,16 +157,10 @@ __global__ __launch_bounds__(kTuneThreads) void k_tune_sweep(const float* __rest
             uint64_t nxt = 0ull;
             if (j < nw) {
                 const int t = 64 * j + lane;
-                bool d = false;
-                if (t < T) {
-                    const int lo = max(t - ml, 0), hi = min(t + mr, T - 1);
-                    d = tune_any(w_on, lo, hi) && !tune_any(w_nan, lo, hi);
-                }
-                nxt = __ballot(d);
+                nxt = __ballot(t < T && dec_dilate(w_on, w_nan, max(t - mx.l, 0), min(t + mx.r, T - 1)));
             }
             if (j > 0) {
-                uint64_t st = cur & ~((cur << 1) | prev_top);
-                uint64_t en = cur & ~((cur >> 1) | (nxt << 63));
+                uint64_t st = dec_run_starts(cur, prev_top), en = dec_run_ends(cur, nxt);
                 const int t_base = 64 * (j - 1);
                 for (;;) {   // starts and ends alternate in frame order (wave-uniform)
                     if (s_open < 0) {
@@ -232,25 +204,12 @@ extern "C" int iris_decode_sweep(const float* preds, const int* win_off, const i
         sample_rate < 1)
         return fail(IRIS_E_INVALID, "iris_decode_sweep: files %d, n_frame %d, overlap_hop %d, n_out %d, K %d, grid %d, hop %d, sr %d",
                     n_files, n_frame, overlap_hop, n_out, n_classes, n_grid, metric_hop, sample_rate);
-    if (overlap_hop > n_frame)
-        return fail(IRIS_E_INVALID, "iris_decode_sweep: overlap_hop %d > n_frame %d leaves frames no window covers", overlap_hop,
-                    n_frame);
-    if (n_frame % n_out != 0)
-        return fail(IRIS_E_INVALID, "iris_decode_sweep: n_frame %d is not a multiple of the model's %d output frames", n_frame,
-                    n_out);
     if (n_classes > kDecMaxK) return fail(IRIS_E_UNSUPPORTED, "iris_decode_sweep: K %d (<= %d)", n_classes, kDecMaxK);
     if (n_grid > kTuneMaxG) return fail(IRIS_E_UNSUPPORTED, "iris_decode_sweep: %d grid points (<= %d)", n_grid, kTuneMaxG);
-    if (win_off_host[0] < 0) return fail(IRIS_E_INVALID, "iris_decode_sweep: win_off[0] = %d < 0", win_off_host[0]);
-    long long frames = 0, t_max = 0;
-    for (int f = 0; f < n_files; ++f) {
-        const long long tl = frame_len_host[f], nwin = (long long)win_off_host[f + 1] - win_off_host[f];
-        if (tl < 0 || nwin < 0) return fail(IRIS_E_INVALID, "iris_decode_sweep: file %d: frame_len %lld, windows %lld", f, tl, nwin);
-        if (tl > 0 && (nwin < 1 || tl > (nwin - 1) * overlap_hop + n_frame))
-            return fail(IRIS_E_INVALID, "iris_decode_sweep: file %d: frame_len %lld > (%lld - 1) * %d + %d: frames no window covers",
-                        f, tl, nwin, overlap_hop, n_frame);
-        frames += tl;
-        t_max = std::max(t_max, tl);
-    }
+    DecTotals tot;
+    const int rc = dec_check_files("iris_decode_sweep", win_off_host, frame_len_host, n_files, n_frame, overlap_hop, n_out, &tot);
+    if (rc != IRIS_OK) return rc;
+    const long long frames = tot.frames, t_max = tot.t_max;   // frames of all files, and of the longest
     if (n_files > kTuneMaxFiles)
         return fail(IRIS_E_UNSUPPORTED, "iris_decode_sweep: %d files in one call (<= %d)", n_files, kTuneMaxFiles);
     if (frames * n_classes > INT_MAX)
@@ -260,7 +219,7 @@ extern "C" int iris_decode_sweep(const float* preds, const int* win_off, const i
         return fail(IRIS_E_UNSUPPORTED, "iris_decode_sweep: %d grid points x %d files x %d classes is too many counts (<= %d)",
                     n_grid, n_files, n_classes, INT_MAX);
     // ---- the grid: ranges, and the sort order launch 2 relies on (each avg_pool one run, each threshold one run inside it)
-    const int nw_max = (int)((t_max + 63) / 64);
+    const int nw_max = (int)dec_words(t_max);
     int n_avg = 0;
     bool seen_avg[kDecMaxAvg + 1] = {};
     for (int g = 0, g0 = 0; g < n_grid; ++g) {

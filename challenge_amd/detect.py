@@ -13,7 +13,7 @@ The front end is metrics.evaluate's (data_utils.load_wav, inference.features_for
 recording).  The windows of all files of a group are cut with inference.frame, stacked and run through `model.predict` in
 batches that cross file boundaries; `decode_events` then turns every window prediction of the group into events in one
 call: on GPU tensors the iris_decode_events launches (csrc/k_detect.h) and one copy back, on CPU tensors the restatement
-below, which follows the kernel's arithmetic bit for bit:
+below, which follows the kernels' arithmetic (csrc/decode_core.h, shared with the sweep) bit for bit:
   1. p[t]: overlap-add average - fp32 sum from 0 over the covering windows in ascending order, / (float) count
   2. a[t]: AveragePooling1D(31, 1, 'same') - fp32 sum of the in-range p in frame order, / (float) frames in range
   3. d[t]: MaxPooling1D(124, 1, 'same') then >= 0.5, as "some a[u] >= 0.5 in the window and no NaN a[u]"

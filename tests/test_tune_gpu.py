@@ -51,6 +51,43 @@ def test_sweep_counts_equal_decode_events_counts():
         assert n_pred[g].tolist() == [[len(c) for c in f] for f in ev]
 
 
+EDGE_LENS = [1, 63, 64, 65, 511, 512, 513, 575, 577, 1025, 0]      # around a 64-frame word, a 512-frame tile, two tiles
+EDGE_GRID = [(0.5, 1, 1), (0.5, 2, 2), (0.5, 126, 255), (0.5, 127, 256), (0.5, 31, 124)]   # pads 0/0, 0/1, and both caps
+EDGE_NAN = [(6, 0, 7, 0), (8, 0, 9, 2), (9, 1, 4, 1)]             # (file, window, model output, class) set to NaN
+
+
+def edge_case(hop):
+    """The files of EDGE_LENS in one batch, noisy runs with a few NaN away from the file ends, and random ground truth."""
+    rng = np.random.default_rng(4100 + hop)
+    preds, win_off = run_preds(rng, EDGE_LENS, 512, hop, 16, noise=0.3)
+    for f, w, j, c in EDGE_NAN:
+        assert w < win_off[f + 1] - win_off[f]
+        preds[win_off[f] + w, j, c] = np.nan
+    return torch.from_numpy(preds), win_off, random_gt(rng, EDGE_LENS)
+
+
+@pytest.mark.parametrize("hop", [512, 128])
+def test_events_and_sweep_at_word_tile_and_cap_edges(hop):
+    """One decoder arithmetic under both index conventions (tile-local bits with halo words in detection, file-absolute clipped
+    frames in the sweep): pool windows across a word edge, across a tile edge and into the widest halo (the caps 127 / 256)
+    give on the device exactly the CPU restatement's events, and the sweep counts exactly those events."""
+    from test_detect_gpu import _same
+    preds, win_off, gt = edge_case(hop)
+    p = preds.to(_dev())
+    a_nan = [torch.isnan(DT._avg_pool_host(DT._overlap_add_host(preds, int(win_off[f]), int(win_off[f + 1] - win_off[f]), t, 512,
+                                                                hop), 127)) for f, t in enumerate(EDGE_LENS) if t > 0]
+    assert any(0 < int(x.sum()) < x.numel() for x in a_nan)                   # a NaN inside some pool windows, not all
+    want_n, want_matched, _ = DT.sweep_decoder(preds, win_off, EDGE_LENS, gt, EDGE_GRID, 512, hop)
+    n_pred, matched, _ = DT.sweep_decoder(p, win_off, EDGE_LENS, gt, EDGE_GRID, 512, hop)
+    for g, (thr, avg, mx) in enumerate(EDGE_GRID):
+        want = DT.decode_events(preds, win_off, EDGE_LENS, 512, hop, avg, mx, thr)
+        counts = [[len(c) for c in f] for f in want]
+        assert sum(map(sum, counts)) > 0, (thr, avg, mx)
+        _same(DT.decode_events(p, win_off, EDGE_LENS, 512, hop, avg, mx, thr), want)
+        assert n_pred[g].tolist() == counts == want_n[g].tolist(), (thr, avg, mx)
+    assert np.array_equal(matched, want_matched) and want_matched.sum() > 0
+
+
 def _launch_setup(seed, n_files=12, grid=None):
     dev = _dev()
     rng = np.random.default_rng(seed)
