@@ -36,6 +36,8 @@
 //                    chunked scan modulo 2 pi
 //   k_speed.h        speed perturbation: a batched band-limited resampler over a ragged set of waveforms, each at its own
 //                    real-valued rate, and the frame activity of the results, one launch each
+//   k_fir.h          reverberation: a batched direct-form FIR over a ragged set of waveforms, each channel with its own taps,
+//                    one launch
 //   host_plan.h      mel matrix, constant tables, plan create / destroy
 //   host_ops.h       the operators' C-ABI entry points
 #include "common.h"
@@ -68,3 +70,4 @@
 #include "k_pcen_grad.h"
 #include "k_vocoder.h"
 #include "k_speed.h"
+#include "k_fir.h"

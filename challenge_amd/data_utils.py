@@ -149,6 +149,14 @@ def wants_speed(name: str) -> bool:
     return 'speed' in name
 
 
+def wants_reverb(name: str) -> bool:
+    """Whether a run name asks for reverberation of the voice corpus: the token 'reverb' in it (the same idiom).  Honoured by
+    `sj_train.make_wave_dataset(training=True)` alone (`WaveMixer.enable_reverb` / `rereverb`); `make_dataset` and
+    `make_device_dataset` refuse it, and a name that also holds 'speed' is refused (a mixer holds one voice augmentation).
+    It does not interact with `feature_compression`."""
+    return 'reverb' in name
+
+
 def augment(specs: torch.Tensor, labels, time_axis: int = -2, freq_axis: int = -3):
     """6 time masks (< 24 frames) then 1 frequency mask (< 16 linear bins) on the complex
     spectrogram (data_utils.py:58-61)."""

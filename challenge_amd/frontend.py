@@ -1117,6 +1117,65 @@ def speed_perturb_batch(waves, rates):
     return results
 
 
+# mirrors iris_fir_src (include/iris_frontend.h)
+FIR_SRC = np.dtype([("src", "<u8"), ("dst", "<u8"), ("taps", "<u8"), ("len", "<i4"), ("n_taps", "<i4")])
+assert FIR_SRC.itemsize == 32
+FIR_MAX_TAPS = 4096   # the longest impulse response `fir_batch` and the mixers take (a quarter of a second at 16 kHz)
+
+
+def fir_launch(table: np.ndarray, channels: int, max_len: int, max_taps: int, device: torch.device,
+               table_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Upload a FIR_SRC table (into `table_dev`, a long-lived uint8 device buffer, when given) and run iris_fir_batch over it
+    on the current stream: one launch.  Returns the device table (tied to the stream when it was allocated here)."""
+    return _launch_records(table, device, table_dev, "iris_fir_batch", lambda ptr, n, stream: N.lib().iris_fir_batch(
+        ptr, n, int(channels), int(max_len), int(max_taps), stream))
+
+
+def fir_batch(waves, taps):
+    """Convolve a ragged batch of waveforms with their own impulse responses in ONE launch (iris_fir_batch): waves is a list of
+    [C, L_i] float32 tensors on one ROCm device (equal C), taps as many [C, K_i] float32 tensors on it, 1 <= K_i <= 4096.
+    Returns a list of new [C, L_i] tensors, y[c, m] = sum_k taps[c, k] x[c, m - k]: the causal convolution cut at the input
+    length (the direct sound at tap 0, the ringing past the end dropped), |out - fp64| <= (K_i + 2) u sum_k |taps| |x|; taps
+    [[1.0]] copy their source.  A mismatch, an empty tap vector, K_i > 4096 or a CPU tensor is a ValueError: there is no CPU
+    fallback."""
+    waves, taps = list(waves), list(taps)
+    if len(waves) != len(taps):
+        raise ValueError(f"fir_batch: {len(waves)} waveforms but {len(taps)} tap arrays")
+    if not waves:
+        return []
+    for name, group in (("waves", waves), ("taps", taps)):
+        for i, t in enumerate(group):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2):
+                what = f"{tuple(t.shape)} {t.dtype} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+                raise ValueError(f"fir_batch: {name}[{i}] must be a 2-D float32 tensor on a ROCm device (there is no CPU "
+                                 f"fallback), got {what}")
+    dev, chan = waves[0].device, int(waves[0].shape[0])
+    table = np.zeros(len(waves), FIR_SRC)
+    results, keep = [], []
+    for i, (w, h) in enumerate(zip(waves, taps)):
+        if int(w.shape[0]) != chan or w.device != dev or int(w.shape[1]) < 1 or chan < 1:
+            raise ValueError(f"fir_batch: waves[{i}] has shape {tuple(w.shape)} on {w.device}; expected [{chan} >= 1, L >= 1] "
+                             f"on {dev}")
+        if int(h.shape[0]) != chan or h.device != dev:
+            raise ValueError(f"fir_batch: taps[{i}] has shape {tuple(h.shape)} on {h.device} for a waveform of {chan} "
+                             f"channel(s) on {dev}: one row of taps per channel")
+        if int(h.shape[1]) < 1:
+            raise ValueError(f"fir_batch: taps[{i}] is empty (an impulse response has at least its direct tap)")
+        if int(h.shape[1]) > FIR_MAX_TAPS:
+            raise ValueError(f"fir_batch: taps[{i}] has {int(h.shape[1])} taps per channel (> {FIR_MAX_TAPS})")
+        if int(w.shape[1]) > 2 ** 31 - 1:
+            raise ValueError(f"fir_batch: waves[{i}] has {int(w.shape[1])} samples (> 2^31 - 1)")
+        w, h = w.contiguous(), h.contiguous()
+        o = torch.empty_like(w)
+        table[i] = (w.data_ptr(), o.data_ptr(), h.data_ptr(), int(w.shape[1]), int(h.shape[1]))
+        results.append(o)
+        keep += [w, h]
+    fir_launch(table, chan, int(table["len"].max()), int(table["n_taps"].max()), dev)
+    for t in keep:   # (a contiguous copy made above must outlive the kernel)
+        t.record_stream(torch.cuda.current_stream(dev))
+    return results
+
+
 # mirrors iris_istft_src (include/iris_frontend.h)
 ISTFT_SRC = np.dtype([("src", "<u8"), ("dst", "<u8"), ("n_frames", "<i4"), ("len_out", "<i4")])
 assert ISTFT_SRC.itemsize == 24

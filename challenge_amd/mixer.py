@@ -23,6 +23,7 @@ import torch
 from . import _native as N
 from . import frontend as _fe
 from . import pipeline as _pl
+from . import transforms as _tr
 
 # mirrors iris_mix_src (include/iris_frontend.h)
 MIX_SRC = np.dtype([("src", "<u8"), ("active", "<u8"), ("T", "<i4"), ("pad", "<i4"), ("off", "<i4"),
@@ -131,7 +132,7 @@ def _reaugment(mixer, word: str, rates) -> np.ndarray:
     """`restretch` / `respeed`: draw the rates (unless given), check that every result fits its buffer, run the class's launch
     and activity pass, then move the voices' lengths on the host and in the device corpus of `enable_device_draw`."""
     aug = mixer._aug if isinstance(mixer, DeviceMixer) else None   # (called unbound on something that is no mixer: not enabled)
-    if aug is None:
+    if not isinstance(aug, _VoiceAug):   # (nothing enabled, or the slot holds `enable_reverb`'s state)
         raise RuntimeError(f"re{word} needs enable_{word}() first")
     n_voice = len(aug.orig)
     if rates is None:
@@ -153,6 +154,27 @@ def _reaugment(mixer, word: str, rates) -> np.ndarray:
             mixer._dd["voice_arrays"]["len"].copy_(torch.from_numpy(mixer._v_L.astype(np.int32)))
     aug.rates = rates.copy()
     return aug.rates
+
+
+@dataclass
+class _ReverbAug:
+    """The voice corpus under `WaveMixer.enable_reverb` (it takes the mixer's one `_aug` slot): the originals, their
+    never-moving reverberated copies, the resident tap buffers and the launch table."""
+    rt60: Tuple[float, float]
+    drr: Tuple[float, float]
+    orig: list                      # the voices as given (device tensors [C, L_i])
+    bufs: list                      # one [C, L_i] buffer per voice: what the mixer reads
+    taps: list                      # one [C, FIR_MAX_TAPS] tap buffer per voice (the first C * K_i floats hold [C, K_i])
+    table: np.ndarray               # FIR_SRC records, src / dst / taps / len filled once
+    table_dev: torch.Tensor         # long-lived device copy of `table`
+    rirs: Optional[list] = None     # the impulse responses of the latest `rereverb`
+
+
+def _check_reverb_range(rt60_lo: float, rt60_hi: float, drr_lo: float, drr_hi: float) -> None:
+    vals = [float(v) for v in (rt60_lo, rt60_hi, drr_lo, drr_hi)]
+    if not (all(np.isfinite(v) for v in vals) and 0 <= vals[0] <= vals[1] and vals[2] <= vals[3]):
+        raise ValueError(f"reverb ranges must satisfy 0 <= rt60_lo <= rt60_hi and drr_lo <= drr_hi (finite), got rt60 "
+                         f"[{vals[0]}, {vals[1]}), drr [{vals[2]}, {vals[3]})")
 
 
 class BatchDraw:
@@ -247,7 +269,7 @@ class DeviceMixer:
         self.min_ratio, self.min_noise_ratio, self.snr = min_ratio, min_noise_ratio, snr
         self.rng = np.random.default_rng(seed)
         self._dd = None    # the device-side corpus and draw state of `enable_device_draw`
-        self._aug = None   # the `_VoiceAug` of `enable_stretch` / `enable_speed`
+        self._aug = None   # the `_VoiceAug` of `enable_stretch` / `enable_speed`, or the `_ReverbAug` of `enable_reverb`
 
         def upload(items):
             # (a float32 tensor - e.g. a waveform `sj_train.waves_from_specs` left on the device - is taken as it is)
@@ -486,6 +508,10 @@ class DeviceMixer:
         raise NotImplementedError("DeviceMixer.enable_speed: a spectrum corpus cannot be resampled in time (speed perturbation "
                                   "works on waveforms: use WaveMixer; this corpus has enable_stretch)")
 
+    def enable_reverb(self, rt60_lo: float = 0.1, rt60_hi: float = 0.4, drr_lo: float = -3.0, drr_hi: float = 12.0) -> None:
+        raise NotImplementedError("DeviceMixer.enable_reverb: a spectrum corpus has no waveform to convolve (reverberation "
+                                  "works on waveforms: use WaveMixer; this corpus has enable_stretch)")
+
     def _draw_on_device(self, batch: int):
         """(table_d [batch * stride, 48 B], first_d [batch + 1], n_srcs) written by iris_mix_draw on the current stream."""
         dd, dev = self._dd, self.device
@@ -629,6 +655,68 @@ class WaveMixer(DeviceMixer):
     def _aug_adopt(self, aug: _VoiceAug, n_out: np.ndarray) -> None:
         self._v_L, self._v_T = n_out, 1 + n_out // self.hop
         self.voices = [b[:self.channels * int(n)].view(self.channels, int(n)) for b, n in zip(aug.bufs, n_out)]
+
+    # -- reverberation of the voice corpus ------------------------------------------------
+    def enable_reverb(self, rt60_lo: float = 0.1, rt60_hi: float = 0.4, drr_lo: float = -3.0, drr_hi: float = 12.0) -> None:
+        """Keep a reverberated copy of every voice beside the original and mix from the copies: `rereverb()` then convolves the
+        whole voice corpus with fresh synthetic room impulse responses (`transforms.synth_rir`: rt60 ~ U[rt60_lo, rt60_hi)
+        seconds, direct-to-reverberant ratio ~ U[drr_lo, drr_hi) dB per voice) in one launch (`iris_fir_batch`; Ko et al. 2017,
+        Kaldi's reverberate_data_dir).  One [C, L_i] buffer and one [C, 4096] tap buffer per voice are allocated here and never
+        move: the pointer tables (and the device-side corpus of `enable_device_draw`, in either call order) are switched to
+        them once, so a captured `mix` replayed after a `rereverb` reads the new contents through unchanged addresses.  Until
+        the first `rereverb` the copies hold the voices under the identity response (bit-identical).
+        The labels follow the DRY voice: the convolution is cut at the voice's length, so lengths and frame counts do not
+        move, and the frame-activity vectors stay the ones computed from the originals at construction - an exactly silent
+        gap inside a voice stays labelled silent although the tail now rings into it.  Backgrounds and noises are not
+        reverberated: they carry no labels.  A mixer holds one voice augmentation: this after `enable_speed` (or the other way
+        round) raises; combining the two is out of scope.  No accuracy claim is made for the augmentation."""
+        _check_reverb_range(rt60_lo, rt60_hi, drr_lo, drr_hi)
+        if self._aug is not None:
+            raise RuntimeError("enable_reverb was already called on this mixer" if isinstance(self._aug, _ReverbAug) else
+                               "enable_speed was already called on this mixer (a mixer holds one voice augmentation)")
+        dev, orig = self.device, list(self.voices)
+        bufs = [torch.zeros_like(v) for v in orig]
+        taps = [torch.zeros((self.channels, _fe.FIR_MAX_TAPS), device=dev, dtype=torch.float32) for _ in orig]
+        table = np.zeros(len(orig), _fe.FIR_SRC)
+        table["src"], table["dst"] = [v.data_ptr() for v in orig], [b.data_ptr() for b in bufs]
+        table["taps"], table["len"] = [t.data_ptr() for t in taps], self._v_L
+        self._aug = _ReverbAug((float(rt60_lo), float(rt60_hi)), (float(drr_lo), float(drr_hi)), orig, bufs, taps, table,
+                               torch.empty(max(table.nbytes, 1), dtype=torch.uint8, device=dev))
+        self.voices = bufs
+        self._v_ptr = np.array([b.data_ptr() for b in bufs], np.uint64)
+        if self._dd is not None:
+            self._dd["voice_arrays"]["src"].copy_(torch.from_numpy(self._v_ptr.astype(np.int64)))
+        self.rereverb([np.ones((self.channels, 1), np.float32)] * len(orig))
+
+    def rereverb(self, rirs=None) -> list:
+        """Reverberate every ORIGINAL voice anew into its buffer: per voice rt60 ~ U[rt60_lo, rt60_hi) and drr_db ~
+        U[drr_lo, drr_hi) from the mixer's own NumPy generator and a `transforms.synth_rir` of them (or the given `rirs`, one
+        [C, K_i <= 4096] array per voice), uploaded into the resident tap buffers, then ONE `iris_fir_batch` launch over the
+        whole voice corpus.  Lengths, frame counts and the frame-activity vectors (the labels) do not change: see
+        `enable_reverb`.  Call it outside any graph capture.  Backgrounds and noises are not reverberated.  Returns the list
+        of impulse responses used."""
+        aug = self._aug
+        if not isinstance(aug, _ReverbAug):
+            raise RuntimeError("rereverb needs enable_reverb() first")
+        n_voice, chan = len(aug.orig), self.channels
+        if rirs is None:
+            rirs = []
+            for _ in range(n_voice):
+                rt60, drr_db = self.rng.uniform(*aug.rt60), self.rng.uniform(*aug.drr)
+                rirs.append(_tr.synth_rir(self.rng, chan, rt60, drr_db, max_taps=_fe.FIR_MAX_TAPS))
+        rirs = [np.ascontiguousarray(np.asarray(h, np.float32)) for h in rirs]
+        if len(rirs) != n_voice:
+            raise ValueError(f"rereverb: {len(rirs)} impulse responses for {n_voice} voices")
+        for i, h in enumerate(rirs):
+            if h.ndim != 2 or h.shape[0] != chan or not 1 <= h.shape[1] <= _fe.FIR_MAX_TAPS:
+                raise ValueError(f"rereverb: rirs[{i}] has shape {h.shape}; expected [{chan}, 1 <= K <= {_fe.FIR_MAX_TAPS}]")
+        for h, buf in zip(rirs, aug.taps):
+            buf.view(-1)[:h.size].copy_(torch.from_numpy(h.reshape(-1)), non_blocking=True)
+        aug.table["n_taps"] = [h.shape[1] for h in rirs]
+        if n_voice:
+            _fe.fir_launch(aug.table, chan, int(self._v_L.max()), int(aug.table["n_taps"].max()), self.device, aug.table_dev)
+        aug.rirs = rirs
+        return rirs
 
     def mix(self, batch: int, draws=None):
         """One batch of (waveforms [B, C, (n_frame - 1) * hop], labels [B, max_voices, n_frame, n_classes])."""

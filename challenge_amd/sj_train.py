@@ -215,6 +215,9 @@ def make_dataset(config, training=True, n_classes=3, sources=None):
     if _du.wants_speed(config.name):
         raise ValueError(f"run name {config.name!r} asks for 'speed': speed perturbation runs on the resident waveform corpus "
                          "(make_wave_dataset); the per-sample host pipeline does not resample")
+    if _du.wants_reverb(config.name):
+        raise ValueError(f"run name {config.name!r} asks for 'reverb': reverberation runs on the resident waveform corpus "
+                         "(make_wave_dataset); the per-sample host pipeline does not convolve")
     backgrounds, voices, labels, noises = _load_sources(config, training, n_classes, sources)
 
     pipeline = make_pipeline(backgrounds, voices, labels, noises, n_frame=config.n_frame,
@@ -281,6 +284,9 @@ def make_device_dataset(config, training=True, n_classes=3, sources=None, device
     from .mixer import DeviceMixer
     if _du.wants_speed(config.name):
         raise ValueError(f"run name {config.name!r} asks for 'speed': a spectrum corpus cannot be resampled in time "
+                         "(use make_wave_dataset; this path has 'stretch')")
+    if _du.wants_reverb(config.name):
+        raise ValueError(f"run name {config.name!r} asks for 'reverb': a spectrum corpus has no waveform to convolve "
                          "(use make_wave_dataset; this path has 'stretch')")
     backgrounds, voices, labels, noises = _load_sources(config, training, n_classes, sources)
     if config.model_type == 'se' and config.v == 9:
@@ -408,6 +414,10 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
     A 'speed' token in config.name (training sets only): the voice corpus is speed-perturbed by rates ~ U[0.9, 1.1) at
     creation and again every config.steps_per_epoch batches (`WaveMixer.enable_speed` / `respeed`: one `iris_speed_perturb`
     and one `iris_mix_wave_frame_active_batch` launch over the corpus); a name without the token takes no new code path.
+    A 'reverb' token (training sets only): the voice corpus is convolved with fresh synthetic room impulse responses (rt60 ~
+    U[0.1, 0.4) s, direct-to-reverberant ratio ~ U[-3, 12) dB) at creation and again every config.steps_per_epoch batches
+    (`WaveMixer.enable_reverb` / `rereverb`: one `iris_fir_batch` launch over the corpus; the labels follow the dry voice); a
+    name without the token takes no new code path.  'speed' and 'reverb' together are refused: they cannot be combined yet.
     spec_sources: the same tuple as SPECTRA ([F, T_i, 2C], integer labels), e.g. the pickled corpora - converted once here by
     `waves_from_specs` at this n_fft / hop and used as `sources` (giving both is a ValueError)."""
     from .mixer import WaveMixer
@@ -417,6 +427,9 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
     if _du.wants_stretch(config.name):
         raise ValueError(f"run name {config.name!r} asks for 'stretch': a waveform corpus has no spectra to stretch "
                          "(use make_device_dataset)")
+    if _du.wants_speed(config.name) and _du.wants_reverb(config.name):
+        raise ValueError(f"run name {config.name!r} asks for both 'speed' and 'reverb': the two cannot be combined yet (a "
+                         "mixer holds one voice augmentation), name one")
     if spec_sources is not None:
         sources = waves_from_specs(spec_sources, n_fft, hop, device)
     if sources is None:
@@ -445,9 +458,15 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
     if speed:   # the voice corpus is perturbed anew now and once per epoch (the validation set never is)
         mixer.enable_speed()
         mixer.respeed()
+    reverb = training and _du.wants_reverb(config.name)
+    if reverb:   # likewise: fresh room impulse responses now and once per epoch
+        mixer.enable_reverb()
+        mixer.rereverb()
 
     def gen():
         reaugment = _every_epoch(mixer.respeed, config.steps_per_epoch) if speed else (lambda: None)
+        if reverb:
+            reaugment = _every_epoch(mixer.rereverb, config.steps_per_epoch)
         while True:
             reaugment()
             wav, y = mixer.mix(config.batch_size)
@@ -471,7 +490,7 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
     if config.loss.upper() in ('MSE', 'MAE'):
         pipeline = pipeline.map(multiply_label(config.mse_multiplier))
     dataset = pipeline.prefetch(AUTOTUNE)
-    dataset.mixer = mixer   # (for inspection: the resident corpus, its draws and - 'speed' runs - the current voice lengths)
+    dataset.mixer = mixer   # (for inspection: the resident corpus, its draws and - 'speed' / 'reverb' runs - the current voices)
     return dataset
 
 

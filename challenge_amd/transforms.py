@@ -261,3 +261,52 @@ def speed_perturb(wav: torch.Tensor, rate: float = 1.0) -> torch.Tensor:
     if isinstance(wav, torch.Tensor) and wav.dim() == 1:
         return _fe.speed_perturb_batch([wav.unsqueeze(0)], [rate])[0][0]
     return _fe.speed_perturb_batch([wav], [rate])[0]
+
+
+def reverb(wav: torch.Tensor, rir) -> torch.Tensor:
+    """Reverberation of one [chan, samples] (or [samples]) float32 waveform on a ROCm device as ONE HIP launch
+    (`frontend.fir_batch`, iris_fir_batch): every channel convolved with its row of the room impulse response `rir`
+    [chan, taps <= 4096] (a tensor on the same device, or an array such as `synth_rir` returns), causal and cut at the input
+    length - the direct sound at tap 0, the ringing past the end dropped.  Returns a new tensor of the input's shape.  CPU
+    waveforms raise: there is no CPU fallback."""
+    if not (isinstance(wav, torch.Tensor) and wav.is_cuda):
+        raise ValueError("reverb: the waveform must be a float32 tensor on a ROCm device (there is no CPU fallback)")
+    if not isinstance(rir, torch.Tensor):
+        rir = torch.as_tensor(np.ascontiguousarray(np.asarray(rir, np.float32))).to(wav.device)
+    if wav.dim() == 1:
+        return _fe.fir_batch([wav.unsqueeze(0)], [rir.reshape(1, -1)])[0][0]
+    return _fe.fir_batch([wav], [rir])[0]
+
+
+def synth_rir(rng: np.random.Generator, channels: int, rt60: float, drr_db: float = 0.0, sample_rate: int = 16000,
+              floor_db: float = -40.0, max_taps: int = 4096) -> np.ndarray:
+    """A synthetic room impulse response [channels, K] float32, built on the host in float64: the exponentially decaying
+    Gaussian-noise model.  K = min(max_taps, max(1, ceil(rt60 * sample_rate * (-floor_db) / 60))) - the decay followed down to
+    `floor_db`; h[c, 0] = 1 (the direct sound) and h[c, k] = g_c n[c, k] 10^(-3 k / (rt60 sample_rate)) for k >= 1 (60 dB of
+    decay per `rt60` seconds) with n ~ N(0, 1) drawn from `rng` independently per channel, g_c such that the tail's energy is
+    10^(-drr_db / 10) times the direct tap's (`drr_db`: the direct-to-reverberant ratio); each channel is finally scaled to
+    unit L2 norm, so a white input keeps its power.  rt60 <= 0 is the identity [[1.0]] * channels."""
+    channels, max_taps = int(channels), int(max_taps)
+    rt60, drr_db, sample_rate, floor_db = float(rt60), float(drr_db), float(sample_rate), float(floor_db)
+    if channels < 1 or max_taps < 1:
+        raise ValueError(f"synth_rir: channels = {channels} and max_taps = {max_taps} must be positive")
+    if not (np.isfinite(rt60) and np.isfinite(drr_db)):
+        raise ValueError(f"synth_rir: rt60 = {rt60} and drr_db = {drr_db} must be finite")
+    if not (np.isfinite(sample_rate) and sample_rate > 0):
+        raise ValueError(f"synth_rir: sample_rate = {sample_rate} must be positive and finite")
+    if not (np.isfinite(floor_db) and floor_db < 0):
+        raise ValueError(f"synth_rir: floor_db = {floor_db} must be negative and finite (how far down the decay is followed)")
+    if rt60 <= 0:
+        return np.ones((channels, 1), np.float32)
+    n_taps = min(max_taps, max(1, int(np.ceil(rt60 * sample_rate * (-floor_db) / 60.0))))
+    h = np.zeros((channels, n_taps), np.float64)
+    h[:, 0] = 1.0
+    if n_taps > 1:
+        k = np.arange(1, n_taps, dtype=np.float64)
+        tail = rng.standard_normal((channels, n_taps - 1)) * np.power(10.0, -3.0 * k / (rt60 * sample_rate))[None, :]
+        energy = np.sum(tail * tail, axis=1, keepdims=True)
+        if np.any(energy <= 0):
+            raise ValueError("synth_rir: the drawn tail has no energy")
+        h[:, 1:] = tail * np.sqrt(np.power(10.0, -drr_db / 10.0) / energy)
+    h /= np.sqrt(np.sum(h * h, axis=1, keepdims=True))
+    return h.astype(np.float32)

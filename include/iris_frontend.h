@@ -838,6 +838,34 @@ int iris_mix_wave_frame_active_batch(const void* table_dev, int n_src, int chann
                                      const void* active_ptrs_dev, int max_frames, void* stream);
 
 /*
+ * Reverberation of waveforms (Ko et al., ICASSP 2017; Kaldi's reverberate_data_dir): a RAGGED BATCH of waveforms, each channel
+ * convolved with its own impulse response, in one launch - a direct-form FIR in fp32.
+ * Per record: src DEVICE [channels, len] fp32, taps DEVICE [channels, n_taps] fp32, dst DEVICE [channels, len] (contiguous;
+ * floats beyond channels * len are not written):
+ *     y[c, m] = sum_{k = 0}^{n_taps - 1} taps[c, k] * x[c, m - k]      for 0 <= m < len,     x[c, i] = 0 for i < 0
+ * - the causal convolution, cut at the input length: the direct sound sits at tap 0 and whatever rings past the end of the
+ * input is dropped (Kaldi's default), so the length of a waveform, its frame count and its labels do not change.
+ * Each output is one fp32 FMA chain in ascending k: against the float64 evaluation |y - ref| <= (n_taps + 2) u S[c, m],
+ * u = 2^-24, S[c, m] = sum_k |taps[c, k]| |x[c, m - k]| (the forward bound of an fp32 inner product of n_taps terms).  An
+ * output sample whose whole support is zero input is exactly 0.  taps = [1] copies the source bit for bit.  A record with a
+ * NULL pointer, len <= 0, n_taps <= 0, len > max_len or n_taps > max_taps is skipped (nothing written): the table lives on the
+ * device and cannot be checked here without a synchronisation.  dst must not overlap src or taps.
+ *   max_len   the largest len of the table (it sizes the grid: tiles of max_len x channels x n_src)
+ *   max_taps  the largest n_taps of the table
+ * Checked before any HIP call (IRIS_E_INVALID): n_src < 0, channels <= 0, NULL table with n_src > 0, max_len <= 0,
+ * max_taps <= 0; IRIS_E_UNSUPPORTED: n_src > 65535, channels > 65535.  n_src == 0 returns 0 and launches nothing.
+ * One launch on `stream`; no workspace, no atomics, no synchronisation: capturable, bitwise reproducible, and a record's
+ * result does not depend on the records around it.  Runs on the current HIP device.
+ */
+typedef struct {
+    const float* src;    /* DEVICE [channels, len] */
+    float*       dst;    /* DEVICE [channels, len]; must not overlap src */
+    const float* taps;   /* DEVICE [channels, n_taps] */
+    int32_t      len, n_taps;
+} iris_fir_src;
+int iris_fir_batch(const void* table_dev, int n_src, int channels, int max_len, int max_taps, void* stream);
+
+/*
  * Inverse STFT of a RAGGED BATCH of complex spectrograms in the reference layout, in one launch: the inverse of iris_stft /
  * load_wav's Spectrogram(n_fft, power = None), i.e. torch.istft(n_fft, hop, window = periodic Hann, center = True, onesided,
  * normalized = False, length = len_out).  n_fft, hop, the channel count C and the constants come from the plan.

@@ -1,0 +1,124 @@
+"""Host tests of the reverberation augmentation: the synthetic room impulse responses of `transforms.synth_rir`, the 'reverb'
+run-name token and its refusals, the float64 yardstick of tests/reverb_ref.py, and the argument checks that
+`iris_fir_batch` makes before any HIP call.  None of them needs a GPU."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+
+from reverb_ref import fir_ref, rule_ratio
+
+
+def _tail_to_direct(h):
+    h = h.astype(np.float64)
+    return np.sum(h[:, 1:] ** 2, axis=1) / h[:, 0] ** 2
+
+
+def test_synth_rir_tap_count_norm_and_energy_ratio():
+    from challenge_amd.transforms import synth_rir
+    for rt60, want in ((0.01, 107), (0.1, 1067), (0.3, 3200), (0.4, 4096), (2.0, 4096)):
+        assert want == min(4096, max(1, math.ceil(rt60 * 16000 * 40 / 60)))
+        for drr_db in (-3.0, 0.0, 12.0):
+            h = synth_rir(np.random.default_rng(3), 2, rt60, drr_db)
+            assert h.shape == (2, want) and h.dtype == np.float32 and np.isfinite(h).all()
+            assert np.allclose(np.sum(h.astype(np.float64) ** 2, axis=1), 1.0, rtol=0, atol=1e-6)
+            assert np.allclose(_tail_to_direct(h), 10.0 ** (-drr_db / 10), rtol=1e-6, atol=0)
+            assert np.all(h[:, 0] > 0) and not np.array_equal(h[0], h[1])       # the channels differ
+    # the other arguments of the formula: sample rate, floor, cap
+    assert synth_rir(np.random.default_rng(0), 1, 0.1, sample_rate=8000).shape == (1, 534)
+    assert synth_rir(np.random.default_rng(0), 1, 0.1, floor_db=-60.0).shape == (1, 1600)
+    assert synth_rir(np.random.default_rng(0), 3, 0.3, max_taps=100).shape == (3, 100)
+    assert np.array_equal(synth_rir(np.random.default_rng(0), 2, 1e-9), np.ones((2, 1), np.float32))   # K = 1: the direct tap
+    # the envelope: 60 dB of decay per rt60 seconds (the median |n| of a Gaussian is 0.6745)
+    h = synth_rir(np.random.default_rng(5), 1, 0.2, 0.0)[0].astype(np.float64)
+    early, late = np.median(np.abs(h[1:201])), np.median(np.abs(h[1601:1801]))
+    assert abs(20 * np.log10(late / early) - (-60 * 1600 / 3200)) < 1.5
+
+
+def test_synth_rir_identity_reproducibility_and_refusals():
+    from challenge_amd.transforms import synth_rir
+    for rt60 in (0.0, -1.0):
+        h = synth_rir(np.random.default_rng(0), 3, rt60)
+        assert h.dtype == np.float32 and np.array_equal(h, np.ones((3, 1), np.float32))
+    a, b = synth_rir(np.random.default_rng(7), 2, 0.25, 4.0), synth_rir(np.random.default_rng(7), 2, 0.25, 4.0)
+    assert np.array_equal(a, b) and not np.array_equal(a, synth_rir(np.random.default_rng(8), 2, 0.25, 4.0))
+    rng = np.random.default_rng(0)
+    for kw in (dict(rt60=float("nan")), dict(rt60=float("inf")), dict(rt60=0.2, drr_db=float("nan")),
+               dict(rt60=0.2, drr_db=float("inf")), dict(rt60=0.2, sample_rate=0), dict(rt60=0.2, sample_rate=-16000),
+               dict(rt60=0.2, sample_rate=float("nan")), dict(rt60=0.2, floor_db=0.0), dict(rt60=0.2, floor_db=40.0),
+               dict(rt60=0.2, floor_db=float("nan")), dict(rt60=0.2, max_taps=0), dict(rt60=0.2, max_taps=-4)):
+        with pytest.raises(ValueError):
+            synth_rir(rng, 2, **kw)
+    for channels in (0, -1):
+        with pytest.raises(ValueError):
+            synth_rir(rng, channels, 0.2)
+
+
+def test_fir_ref_agrees_with_the_explicit_loop():
+    rng = np.random.default_rng(1)
+    x, h = rng.standard_normal((2, 7)).astype(np.float32), rng.standard_normal((2, 3)).astype(np.float32)
+    y, s = fir_ref(x, h)
+    want = np.array([[sum(float(h[c, k]) * float(x[c, m - k]) for k in range(3) if m - k >= 0) for m in range(7)] for c in range(2)])
+    want_s = np.array([[sum(abs(float(h[c, k]) * float(x[c, m - k])) for k in range(3) if m - k >= 0) for m in range(7)] for c in range(2)])
+    assert y.shape == s.shape == (2, 7) and y.dtype == np.float64
+    assert np.allclose(y, want, rtol=0, atol=1e-15) and np.allclose(s, want_s, rtol=0, atol=1e-15)
+    assert rule_ratio(want.astype(np.float32), y, s, 3) <= 1.0          # rounding the exact result once is within the rule
+    assert rule_ratio((want + 1e-4).astype(np.float32), y, s, 3) > 1.0  # ... and an error of 1e-4 is not
+    z = np.zeros((2, 7), np.float32)
+    assert rule_ratio(z, *fir_ref(z, h), 3) == 0.0 and rule_ratio(z + 1e-30, *fir_ref(z, h), 3) == np.inf
+
+
+def test_wants_reverb_and_the_refusals():
+    from challenge_amd import data_utils as D
+    from challenge_amd import sj_train as S
+    assert D.wants_reverb("run_reverb") and D.wants_reverb("reverb") and D.wants_reverb("pcen_reverb_filter")
+    assert not D.wants_reverb("") and not D.wants_reverb("run_filter") and not D.wants_reverb("run_speed")
+    for name, want in (("", "minmax_log"), ("nominmax", "log"), ("pcen", "pcen"), ("pcen_learn", "pcen_learn")):
+        assert D.feature_compression(name) == want == D.feature_compression(name + "_reverb")
+    cfg = S.ARGS().get(['--name', 'run_reverb', '--n_frame', '64', '--batch_size', '2'])
+    with pytest.raises(ValueError, match="make_wave_dataset"):
+        S.make_dataset(cfg, training=True, sources=S.synthetic_sources(2, 3, freq=33, n_bg=2, n_voice=3, n_noise=2))
+    with pytest.raises(ValueError, match="make_wave_dataset"):
+        S.make_device_dataset(cfg, training=True, sources=S.synthetic_sources(2, 3, freq=33, n_bg=2, n_voice=3, n_noise=2))
+    both = S.ARGS().get(['--name', 'run_speed_reverb', '--n_frame', '64', '--batch_size', '2'])
+    for training in (True, False):
+        with pytest.raises(ValueError, match="cannot be combined"):
+            S.make_wave_dataset(both, training=training, sources=S.synthetic_wave_sources(2, 3, n_bg=2, n_voice=3, n_noise=2))
+
+
+def test_mixer_checks_need_no_device():
+    from challenge_amd.mixer import DeviceMixer, WaveMixer
+    with pytest.raises(NotImplementedError, match="spectrum"):
+        DeviceMixer.enable_reverb(object())
+    for ranges in ((-0.1, 0.4, -3.0, 12.0), (0.5, 0.4, -3.0, 12.0), (0.1, 0.4, 13.0, 12.0), (float("nan"), 0.4, -3.0, 12.0),
+                   (0.1, float("inf"), -3.0, 12.0), (0.1, 0.4, float("nan"), 12.0)):
+        with pytest.raises(ValueError):
+            WaveMixer.enable_reverb(object(), *ranges)
+    with pytest.raises(RuntimeError, match="enable_reverb"):
+        WaveMixer.rereverb(type("NoMixer", (), {"_aug": None})())
+
+
+def test_argument_validation_without_gpu():
+    from challenge_amd import _native as N
+    from challenge_amd import frontend as FE
+    assert FE.FIR_SRC.itemsize == 32 and FE.FIR_SRC.names == ("src", "dst", "taps", "len", "n_taps") and FE.FIR_MAX_TAPS == 4096
+    lib = N.lib()
+    p8 = C.c_void_p(8)
+    INVALID, UNSUPPORTED = -1, -2
+
+    def refused(rc, code):
+        assert rc == code, rc
+        assert lib.iris_last_error().startswith(b"iris_fir_batch:"), lib.iris_last_error()
+
+    refused(lib.iris_fir_batch(None, 1, 2, 100, 16, None), INVALID)        # NULL table with n_src > 0
+    refused(lib.iris_fir_batch(p8, -1, 2, 100, 16, None), INVALID)         # n_src < 0
+    refused(lib.iris_fir_batch(p8, 1, 0, 100, 16, None), INVALID)          # channels
+    refused(lib.iris_fir_batch(p8, 1, -2, 100, 16, None), INVALID)
+    refused(lib.iris_fir_batch(p8, 1, 2, 0, 16, None), INVALID)            # max_len
+    refused(lib.iris_fir_batch(p8, 1, 2, -5, 16, None), INVALID)
+    refused(lib.iris_fir_batch(p8, 1, 2, 100, 0, None), INVALID)           # max_taps
+    refused(lib.iris_fir_batch(p8, 1, 2, 100, -1, None), INVALID)
+    refused(lib.iris_fir_batch(p8, 65536, 2, 100, 16, None), UNSUPPORTED)  # more records than the grid holds
+    assert lib.iris_fir_batch(None, 0, 2, 100, 16, None) == 0              # no records: nothing to do, no launch
+    assert lib.iris_fir_batch(p8, 0, 2, 0, 0, None) == 0
