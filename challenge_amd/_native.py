@@ -65,6 +65,8 @@ SIGNATURES = {
     "iris_speed_perturb": (_i, [_vp, _i, _i, _i, _vp]),
     "iris_mix_wave_frame_active_batch": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "iris_fir_batch": (_i, [_vp, _i, _i, _i, _i, _vp]),
+    "iris_fir_batch_pitch": (_i, [_vp, _i, _i, _i, _i, _i, _vp]),
+    "iris_ism_rir": (_i, [_vp, _vp, _i, _i, _i, C.c_double, _i, _vp]),
     "iris_istft_len": (C.c_longlong, [C.c_longlong, _i]),
     "iris_istft": (_i, [_vp, _vp, _i, _i, _vp]),
     "iris_wav_to_logmel": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp]),

@@ -700,3 +700,57 @@ extern "C" int iris_timing_samples(iris_plan* p, int kernel, float* out_ms, int 
     *n_samples = used;
     return IRIS_OK;
 }
+
+// ---------------------------------------------------------------------------
+// shoebox room simulation (k_ism.h): the checks read the HOST copy of the table, the kernel its device copy
+// ---------------------------------------------------------------------------
+static int ism_check_record(const iris_ism_src& r, int i, int channels, int max_taps, double fs) {
+    if (!r.dst) return fail(IRIS_E_INVALID, "iris_ism_rir: record %d: dst is NULL", i);
+    if (r.n_taps < 1 || r.n_taps > kIsmMaxTaps)
+        return fail(IRIS_E_INVALID, "iris_ism_rir: record %d: n_taps = %d is outside 1 .. %d", i, r.n_taps, kIsmMaxTaps);
+    if (max_taps < r.n_taps) return fail(IRIS_E_INVALID, "iris_ism_rir: record %d: max_taps = %d < n_taps = %d", i, max_taps, r.n_taps);
+    for (int a = 0; a < 3; ++a) {
+        if (!(std::isfinite(r.room[a]) && r.room[a] > 0))
+            return fail(IRIS_E_INVALID, "iris_ism_rir: record %d: room[%d] = %g must be positive and finite", i, a, r.room[a]);
+        if (!(r.src[a] >= 0 && r.src[a] <= r.room[a]))
+            return fail(IRIS_E_INVALID, "iris_ism_rir: record %d: src[%d] = %g is outside the room [0, %g]", i, a, r.src[a], r.room[a]);
+        for (int c = 0; c < channels; ++c)
+            if (!(r.mic[c][a] >= 0 && r.mic[c][a] <= r.room[a]))
+                return fail(IRIS_E_INVALID, "iris_ism_rir: record %d: mic[%d][%d] = %g is outside the room [0, %g]", i, c, a,
+                            r.mic[c][a], r.room[a]);
+    }
+    if (!(r.beta >= 0 && r.beta < 1)) return fail(IRIS_E_INVALID, "iris_ism_rir: record %d: beta = %g is outside [0, 1)", i, r.beta);
+    const IsmGeom g = ism_geometry(r, channels, fs);
+    if (!(g.d_min > 0)) return fail(IRIS_E_INVALID, "iris_ism_rir: record %d: the source sits on its nearest microphone", i);
+    if (!(g.images <= 2147483647.0))
+        return fail(IRIS_E_INVALID, "iris_ism_rir: record %d: a lattice of %.0f images (> 2^31 - 1)", i, g.images);
+    return IRIS_OK;
+}
+
+static int ism_check(const iris_ism_src* table_host, const void* table_dev, int n_src, int channels, int max_taps, double fs) {
+    if (n_src < 0) return fail(IRIS_E_INVALID, "iris_ism_rir: n_src = %d is negative", n_src);
+    if (channels <= 0) return fail(IRIS_E_INVALID, "iris_ism_rir: channels = %d must be positive", channels);
+    if (channels > IRIS_ISM_MAX_CHAN)
+        return fail(IRIS_E_UNSUPPORTED, "iris_ism_rir: channels = %d > %d microphones per record", channels, IRIS_ISM_MAX_CHAN);
+    if (n_src == 0) return IRIS_OK;
+    if (!table_host || !table_dev) return fail(IRIS_E_INVALID, "iris_ism_rir: table is NULL");
+    if (max_taps < 1 || max_taps > kIsmMaxTaps)
+        return fail(IRIS_E_INVALID, "iris_ism_rir: max_taps = %d is outside 1 .. %d", max_taps, kIsmMaxTaps);
+    if (!(std::isfinite(fs) && fs > 0)) return fail(IRIS_E_INVALID, "iris_ism_rir: sample_rate = %g must be positive and finite", fs);
+    if (n_src > 65535) return fail(IRIS_E_UNSUPPORTED, "iris_ism_rir: n_src = %d > 65535", n_src);
+    for (int i = 0; i < n_src; ++i) {
+        const int rc = ism_check_record(table_host[i], i, channels, max_taps, fs);
+        if (rc) return rc;
+    }
+    return IRIS_OK;
+}
+
+extern "C" int iris_ism_rir(const iris_ism_src* table_host, const void* table_dev, int n_src, int channels, int max_taps,
+                            double sample_rate, int normalize, void* stream) {
+    const int rc = ism_check(table_host, table_dev, n_src, channels, max_taps, sample_rate);
+    if (rc || n_src == 0) return rc;
+    k_ism_rir<<<(unsigned)n_src, kIsmThreads, 0, (hipStream_t)stream>>>(static_cast<const iris_ism_src*>(table_dev), channels,
+                                                                        max_taps, sample_rate, normalize);
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}

@@ -38,6 +38,8 @@
 //                    real-valued rate, and the frame activity of the results, one launch each
 //   k_fir.h          reverberation: a batched direct-form FIR over a ragged set of waveforms, each channel with its own taps,
 //                    one launch
+//   k_ism.h          shoebox room simulation: image-source room impulse responses of a ragged set of voices, fixed-point LDS
+//                    accumulators, one launch (its entry point and checks: host_ops.h)
 //   host_plan.h      mel matrix, constant tables, plan create / destroy
 //   host_ops.h       the operators' C-ABI entry points
 #include "common.h"
@@ -49,6 +51,7 @@
 #include "k_magmel.h"
 #include "k_elementwise.h"
 #include "host_plan.h"
+#include "k_ism.h"
 #include "host_ops.h"
 #include "k_mix.h"
 #include "k_draw.h"

@@ -2,7 +2,7 @@
 // ragged set of waveforms, each channel with its own taps, in one launch.  Part of the single translation unit
 // iris_frontend.hip.
 //
-// Per record: x [C, L], h [C, K], output y [C, L] (the causal convolution cut at the input length: the direct sound sits at
+// Per record: x [C, L], h [C, K] (rows K floats apart, or `tap_pitch` apart: what k_ism_rir writes), output y [C, L] (the causal convolution cut at the input length: the direct sound sits at
 // tap 0 and what rings past the end of the voice is dropped, so lengths and frame counts do not move):
 //     y[c, m] = sum_{k = 0}^{K - 1} h[c, k] * x[c, m - k],      x[c, i] = 0 for i < 0
 //   blockIdx.z = record, blockIdx.y = channel, blockIdx.x = a tile of kFirTile consecutive output samples.  The 256-thread
@@ -64,7 +64,9 @@ __device__ __forceinline__ void fir_step(float (&acc)[4], const float4& h, const
     if (n > 3) fir_tap<3>(acc, h.w, a, b);
 }
 
-__global__ __launch_bounds__(kFirThreads) void k_fir_batch(const iris_fir_src* __restrict__ table, int max_len, int max_taps) {
+// tap_pitch: floats between the rows of a record's taps (0: the rows are dense, n_taps apart)
+__global__ __launch_bounds__(kFirThreads) void k_fir_batch(const iris_fir_src* __restrict__ table, int max_len, int max_taps,
+                                                           int tap_pitch) {
     __shared__ __attribute__((aligned(16))) float xs[kFirChunk + kFirTile];   // xs[i] = x[m0 - k0 - kFirChunk + i]
     __shared__ __attribute__((aligned(16))) float hs[kFirChunk];              // hs[i] = h[k0 + i]
     const iris_fir_src d = table[blockIdx.z];
@@ -76,7 +78,7 @@ __global__ __launch_bounds__(kFirThreads) void k_fir_batch(const iris_fir_src* _
     const int tile4 = (tile + 3) & ~3;
     const int k_end = (int)min((long long)K, m0 + tile);             // taps k >= m0 + tile meet x = 0 only
     const float* __restrict__ x = d.src + (size_t)blockIdx.y * L;
-    const float* __restrict__ h = d.taps + (size_t)blockIdx.y * K;
+    const float* __restrict__ h = d.taps + (size_t)blockIdx.y * (tap_pitch ? tap_pitch : K);
     float* __restrict__ y = d.dst + (size_t)blockIdx.y * L;
     const bool x16 = (reinterpret_cast<uintptr_t>(x) & 15) == 0, h16 = (reinterpret_cast<uintptr_t>(h) & 15) == 0;
     const bool y16 = (reinterpret_cast<uintptr_t>(y) & 15) == 0;
@@ -146,18 +148,30 @@ __global__ __launch_bounds__(kFirThreads) void k_fir_batch(const iris_fir_src* _
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-extern "C" int iris_fir_batch(const void* table_dev, int n_src, int channels, int max_len, int max_taps, void* stream) {
+static int fir_batch_launch(const void* table_dev, int n_src, int channels, int max_len, int max_taps, int tap_pitch, void* stream) {
     if (n_src < 0) return fail(IRIS_E_INVALID, "iris_fir_batch: n_src = %d is negative", n_src);
     if (channels <= 0) return fail(IRIS_E_INVALID, "iris_fir_batch: channels = %d must be positive", channels);
+    if (tap_pitch < 0) return fail(IRIS_E_INVALID, "iris_fir_batch: tap_pitch = %d is negative", tap_pitch);
     if (n_src == 0) return IRIS_OK;
     if (!table_dev) return fail(IRIS_E_INVALID, "iris_fir_batch: table is NULL");
     if (max_len <= 0) return fail(IRIS_E_INVALID, "iris_fir_batch: max_len = %d must be positive", max_len);
     if (max_taps <= 0) return fail(IRIS_E_INVALID, "iris_fir_batch: max_taps = %d must be positive", max_taps);
+    if (tap_pitch && tap_pitch < max_taps)
+        return fail(IRIS_E_INVALID, "iris_fir_batch: tap_pitch = %d is below max_taps = %d", tap_pitch, max_taps);
     if (n_src > 65535) return fail(IRIS_E_UNSUPPORTED, "iris_fir_batch: n_src = %d > 65535", n_src);
     if (channels > 65535) return fail(IRIS_E_UNSUPPORTED, "iris_fir_batch: channels = %d > 65535", channels);
     const unsigned tiles = (unsigned)(((long long)max_len + kFirTile - 1) / kFirTile);
     k_fir_batch<<<dim3(tiles, (unsigned)channels, (unsigned)n_src), kFirThreads, 0, (hipStream_t)stream>>>(
-        static_cast<const iris_fir_src*>(table_dev), max_len, max_taps);
+        static_cast<const iris_fir_src*>(table_dev), max_len, max_taps, tap_pitch);
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
+}
+
+extern "C" int iris_fir_batch(const void* table_dev, int n_src, int channels, int max_len, int max_taps, void* stream) {
+    return fir_batch_launch(table_dev, n_src, channels, max_len, max_taps, 0, stream);
+}
+
+extern "C" int iris_fir_batch_pitch(const void* table_dev, int n_src, int channels, int max_len, int max_taps, int tap_pitch,
+                                    void* stream) {
+    return fir_batch_launch(table_dev, n_src, channels, max_len, max_taps, tap_pitch, stream);
 }

@@ -157,6 +157,20 @@ def wants_reverb(name: str) -> bool:
     return 'reverb' in name
 
 
+def wants_shoebox(name: str) -> bool:
+    """Whether a run name asks for the shoebox room model of the reverberation: the token 'shoebox' in it (the same idiom).
+    It selects the model of a 'reverb' run (`WaveMixer.enable_reverb(model="shoebox")`: image-source responses that both
+    channels share, instead of independent noise per channel); `check_shoebox` refuses it without 'reverb'."""
+    return 'shoebox' in name
+
+
+def check_shoebox(name: str) -> None:
+    """'shoebox' without 'reverb' in a run name is a ValueError: the token only selects the room model of that augmentation."""
+    if wants_shoebox(name) and not wants_reverb(name):
+        raise ValueError(f"run name {name!r} asks for 'shoebox' without 'reverb': the token selects the room model of the "
+                         "reverberation augmentation, name both")
+
+
 def augment(specs: torch.Tensor, labels, time_axis: int = -2, freq_axis: int = -3):
     """6 time masks (< 24 frames) then 1 frequency mask (< 16 linear bins) on the complex
     spectrogram (data_utils.py:58-61)."""

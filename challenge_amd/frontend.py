@@ -1176,8 +1176,123 @@ def fir_batch(waves, taps):
     return results
 
 
+def fir_pitch_launch(table: np.ndarray, channels: int, max_len: int, max_taps: int, tap_pitch: int, device: torch.device,
+                     table_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`fir_launch` with the rows of every record's taps `tap_pitch` floats apart (iris_fir_batch_pitch): the layout
+    `shoebox_rir_launch` writes.  One launch."""
+    return _launch_records(table, device, table_dev, "iris_fir_batch_pitch", lambda ptr, n, stream: N.lib().iris_fir_batch_pitch(
+        ptr, n, int(channels), int(max_len), int(max_taps), int(tap_pitch), stream))
+
+
+# mirrors iris_ism_src (include/iris_frontend.h)
+ISM_MAX_CHAN = 8      # microphones per record (IRIS_ISM_MAX_CHAN)
+ISM_SRC = np.dtype([("dst", "<u8"), ("room", "<f8", (3,)), ("src", "<f8", (3,)), ("beta", "<f8"), ("n_taps", "<i4"),
+                    ("reserved", "<i4"), ("mic", "<f8", (ISM_MAX_CHAN, 3))])
+assert ISM_SRC.itemsize == 72 + 24 * ISM_MAX_CHAN
+ISM_HALF_WIDTH = 16   # W: half width of the fractional-delay filter; the nearest microphone's direct sound peaks at tap W
+ISM_SOUND = 343.0     # speed of sound, m / s
+
+
+def shoebox_rir_launch(table: np.ndarray, chan: int, max_taps: int, device: torch.device,
+                       table_dev: Optional[torch.Tensor] = None, sample_rate: float = 16000.0, normalize: bool = True) -> torch.Tensor:
+    """Upload an ISM_SRC table (into `table_dev`, a long-lived uint8 device buffer, when given) and run iris_ism_rir over it on
+    the current stream: one launch.  The C entry point checks the host copy of the records before it launches (a ValueError
+    names the record).  Returns the device table (tied to the stream when it was allocated here)."""
+    table = np.ascontiguousarray(table)
+    return _launch_records(table, device, table_dev, "iris_ism_rir", lambda ptr, n, stream: N.lib().iris_ism_rir(
+        table.ctypes.data, ptr, n, int(chan), int(max_taps), float(sample_rate), int(bool(normalize)), stream))
+
+
+def shoebox_records(rooms, sources, mics, betas, n_taps, max_taps: int = FIR_MAX_TAPS, sample_rate: float = 16000.0) -> np.ndarray:
+    """The ISM_SRC table (dst left 0) of rooms [n, 3], sources [n, 3], mics [n, C, 3], betas [n], n_taps [n], after the checks
+    iris_ism_rir makes in C, here as ValueErrors: shapes, 1 <= C <= 8, n_taps in 1 .. min(max_taps, 4096), positive finite room
+    sizes, the source and every microphone inside the room, the source off its nearest microphone, beta in [0, 1), a lattice of
+    at most 2^31 - 1 images."""
+    rooms, sources = np.asarray(rooms, np.float64), np.asarray(sources, np.float64)
+    mics, betas, n_taps = np.asarray(mics, np.float64), np.asarray(betas, np.float64).reshape(-1), np.asarray(n_taps).reshape(-1)
+    n = rooms.shape[0] if rooms.ndim == 2 else -1
+    if rooms.shape != (n, 3) or sources.shape != (n, 3) or mics.ndim != 3 or mics.shape[0] != n or mics.shape[2] != 3 \
+            or betas.shape != (n,) or n_taps.shape != (n,):
+        raise ValueError(f"shoebox_rir_batch: expected rooms [n, 3], sources [n, 3], mics [n, C, 3], betas [n], n_taps [n]; got "
+                         f"{rooms.shape}, {sources.shape}, {mics.shape}, {betas.shape}, {n_taps.shape}")
+    chan = int(mics.shape[1])
+    if not 1 <= chan <= ISM_MAX_CHAN:
+        raise ValueError(f"shoebox_rir_batch: {chan} microphones per voice; 1 .. {ISM_MAX_CHAN} are supported")
+    if not 1 <= int(max_taps) <= FIR_MAX_TAPS:
+        raise ValueError(f"shoebox_rir_batch: max_taps = {max_taps} is outside 1 .. {FIR_MAX_TAPS}")
+    if not (np.isfinite(sample_rate) and sample_rate > 0):
+        raise ValueError(f"shoebox_rir_batch: sample_rate = {sample_rate} must be positive and finite")
+    if n and not np.all(n_taps == np.floor(n_taps)):
+        raise ValueError("shoebox_rir_batch: n_taps must be whole numbers")
+    for i in range(n):
+        k = int(n_taps[i])
+        if not 1 <= k <= int(max_taps):
+            raise ValueError(f"shoebox_rir_batch: n_taps[{i}] = {k} is outside 1 .. {int(max_taps)}")
+        if not (np.all(np.isfinite(rooms[i])) and np.all(rooms[i] > 0)):
+            raise ValueError(f"shoebox_rir_batch: rooms[{i}] = {rooms[i]} must be positive and finite")
+        if not np.all((sources[i] >= 0) & (sources[i] <= rooms[i])):
+            raise ValueError(f"shoebox_rir_batch: sources[{i}] = {sources[i]} is outside the room {rooms[i]}")
+        if not np.all((mics[i] >= 0) & (mics[i] <= rooms[i][None, :])):
+            raise ValueError(f"shoebox_rir_batch: a microphone of mics[{i}] is outside the room {rooms[i]}")
+        if not 0 <= betas[i] < 1:
+            raise ValueError(f"shoebox_rir_batch: betas[{i}] = {betas[i]} is outside [0, 1)")
+        d_min = float(np.sqrt(np.sum((mics[i] - sources[i][None, :]) ** 2, axis=1)).min())
+        if not d_min > 0:
+            raise ValueError(f"shoebox_rir_batch: sources[{i}] sits on its nearest microphone")
+        reach = ISM_SOUND * (d_min * sample_rate / ISM_SOUND + k) / sample_rate
+        images = 8.0 * np.prod(2.0 * (np.floor(reach / (2.0 * rooms[i])) + 1.0) + 1.0)
+        if not images <= 2 ** 31 - 1:
+            raise ValueError(f"shoebox_rir_batch: voice {i} has a lattice of {images:.0f} images (> 2^31 - 1)")
+    table = np.zeros(n, ISM_SRC)
+    table["room"], table["src"], table["beta"], table["n_taps"] = rooms, sources, betas, n_taps.astype(np.int32)
+    table["mic"][:, :chan, :] = mics
+    return table
+
+
+def shoebox_rir_batch(rooms, sources, mics, betas, n_taps, normalize: bool = True, out=None, sample_rate: float = 16000.0,
+                      device=None):
+    """Shoebox room impulse responses of a ragged batch of voices in ONE launch (iris_ism_rir; Allen & Berkley 1979): rooms
+    [n, 3] m, sources [n, 3], mics [n, C <= 8, 3], betas [n] in [0, 1) and n_taps [n] in 1 .. 4096 are arrays.  Returns a list of
+    [C, K_i] float32 device tensors (views of one new buffer with rows max K_i apart), or views out[i][:, :K_i] of the given
+    contiguous float32 [C, max_taps <= 4096] device buffers, whose floats beyond K_i are left alone.  The nearest microphone's
+    direct sound is a unit tap at k = 16 and the delay between the channels is kept; normalize: every channel of a voice
+    times the same 1 / sqrt(mean_c sum_k h^2).  |h - fp64| <= 3.6 u A_k + n_k 2^-33 (include/iris_frontend.h), bitwise
+    reproducible.  device: where to compute when `out` is not given (default cuda:0).  CPU `out` tensors raise: there is no
+    CPU fallback."""
+    n_taps = np.asarray(n_taps).reshape(-1)
+    if out is not None:
+        out = list(out)
+        if len(out) != n_taps.shape[0]:
+            raise ValueError(f"shoebox_rir_batch: {n_taps.shape[0]} voices but {len(out)} output buffers")
+        chan = int(np.asarray(mics).shape[1]) if np.asarray(mics).ndim == 3 else -1
+        for i, buf in enumerate(out):
+            if not (isinstance(buf, torch.Tensor) and buf.is_cuda and buf.dtype == torch.float32 and buf.is_contiguous()
+                    and buf.dim() == 2 and int(buf.shape[0]) == chan and buf.shape == out[0].shape and buf.device == out[0].device):
+                raise ValueError(f"shoebox_rir_batch: out[{i}] must be a contiguous float32 [{chan}, max_taps] tensor on one ROCm "
+                                 f"device (there is no CPU fallback)")
+        max_taps = int(out[0].shape[1]) if out else FIR_MAX_TAPS
+        dev = out[0].device if out else None
+    else:
+        max_taps = int(n_taps.max()) if n_taps.size else 1
+        dev = torch.device("cuda", 0) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError("shoebox_rir_batch: the device must be a ROCm device (there is no CPU fallback)")
+    table = shoebox_records(rooms, sources, mics, betas, n_taps, max_taps, sample_rate)
+    if not len(table):
+        return []
+    chan = int(np.asarray(mics).shape[1])
+    if out is None:
+        whole = torch.zeros((len(table), chan, max_taps), dtype=torch.float32, device=dev)
+        out = list(whole.unbind(0))
+    table["dst"] = [b.data_ptr() for b in out]
+    shoebox_rir_launch(table, chan, max_taps, dev, None, sample_rate, normalize)
+    for b in out:
+        b.record_stream(torch.cuda.current_stream(dev))
+    return [b[:, :int(k)] for b, k in zip(out, table["n_taps"])]
+
+
 # mirrors iris_istft_src (include/iris_frontend.h)
-ISTFT_SRC = np.dtype([("src", "<u8"), ("dst", "<u8"), ("n_frames", "<i4"), ("len_out", "<i4")])
+ISTFT_SRC =np.dtype([("src", "<u8"), ("dst", "<u8"), ("n_frames", "<i4"), ("len_out", "<i4")])
 assert ISTFT_SRC.itemsize == 24
 
 

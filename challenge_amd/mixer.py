@@ -168,6 +168,10 @@ class _ReverbAug:
     table: np.ndarray               # FIR_SRC records, src / dst / taps / len filled once
     table_dev: torch.Tensor         # long-lived device copy of `table`
     rirs: Optional[list] = None     # the impulse responses of the latest `rereverb`
+    model: str = "noise"            # "noise" (`transforms.synth_rir`) or "shoebox" (`iris_ism_rir`)
+    geometry: Optional[list] = None            # shoebox: the `transforms.draw_shoebox` dicts (+ rt60) of the latest draw
+    ism_table: Optional[np.ndarray] = None     # shoebox: ISM_SRC records, dst (the tap buffers) filled once
+    ism_table_dev: Optional[torch.Tensor] = None   # shoebox: long-lived device copy of `ism_table`
 
 
 def _check_reverb_range(rt60_lo: float, rt60_hi: float, drr_lo: float, drr_hi: float) -> None:
@@ -657,7 +661,8 @@ class WaveMixer(DeviceMixer):
         self.voices = [b[:self.channels * int(n)].view(self.channels, int(n)) for b, n in zip(aug.bufs, n_out)]
 
     # -- reverberation of the voice corpus ------------------------------------------------
-    def enable_reverb(self, rt60_lo: float = 0.1, rt60_hi: float = 0.4, drr_lo: float = -3.0, drr_hi: float = 12.0) -> None:
+    def enable_reverb(self, rt60_lo: float = 0.1, rt60_hi: float = 0.4, drr_lo: float = -3.0, drr_hi: float = 12.0,
+                      model: str = "noise") -> None:
         """Keep a reverberated copy of every voice beside the original and mix from the copies: `rereverb()` then convolves the
         whole voice corpus with fresh synthetic room impulse responses (`transforms.synth_rir`: rt60 ~ U[rt60_lo, rt60_hi)
         seconds, direct-to-reverberant ratio ~ U[drr_lo, drr_hi) dB per voice) in one launch (`iris_fir_batch`; Ko et al. 2017,
@@ -669,8 +674,16 @@ class WaveMixer(DeviceMixer):
         move, and the frame-activity vectors stay the ones computed from the originals at construction - an exactly silent
         gap inside a voice stays labelled silent although the tail now rings into it.  Backgrounds and noises are not
         reverberated: they carry no labels.  A mixer holds one voice augmentation: this after `enable_speed` (or the other way
-        round) raises; combining the two is out of scope.  No accuracy claim is made for the augmentation."""
+        round) raises; combining the two is out of scope.  No accuracy claim is made for the augmentation.
+        model = "shoebox": `rereverb()` draws one random shoebox room per voice (`transforms.draw_shoebox`, rt60 ~ U[rt60_lo,
+        rt60_hi)) and computes its image-source response for all channels on the device (`iris_ism_rir`, straight into the
+        resident tap buffers): both channels hear the same room, so the inter-channel delay and level of a voice are those of
+        its geometry, where the "noise" model draws unrelated responses per channel.  The `drr_*` bounds are unused in this
+        model: the direct-to-reverberant ratio follows from the geometry.  The direct sound of the nearest microphone sits at
+        tap 16 (1 ms, far below one hop), so the dry labels stay valid.  At most 8 channels."""
         _check_reverb_range(rt60_lo, rt60_hi, drr_lo, drr_hi)
+        if model not in ("noise", "shoebox"):
+            raise ValueError(f"enable_reverb: model = {model!r}; 'noise' (synth_rir) or 'shoebox' (image-source rooms)")
         if self._aug is not None:
             raise RuntimeError("enable_reverb was already called on this mixer" if isinstance(self._aug, _ReverbAug) else
                                "enable_speed was already called on this mixer (a mixer holds one voice augmentation)")
@@ -681,7 +694,14 @@ class WaveMixer(DeviceMixer):
         table["src"], table["dst"] = [v.data_ptr() for v in orig], [b.data_ptr() for b in bufs]
         table["taps"], table["len"] = [t.data_ptr() for t in taps], self._v_L
         self._aug = _ReverbAug((float(rt60_lo), float(rt60_hi)), (float(drr_lo), float(drr_hi)), orig, bufs, taps, table,
-                               torch.empty(max(table.nbytes, 1), dtype=torch.uint8, device=dev))
+                               torch.empty(max(table.nbytes, 1), dtype=torch.uint8, device=dev), model=model)
+        if model == "shoebox":
+            if self.channels > _fe.ISM_MAX_CHAN:
+                self._aug = None
+                raise ValueError(f"enable_reverb: the shoebox model takes at most {_fe.ISM_MAX_CHAN} channels, not {self.channels}")
+            self._aug.ism_table = np.zeros(len(orig), _fe.ISM_SRC)
+            self._aug.ism_table["dst"] = [t.data_ptr() for t in taps]
+            self._aug.ism_table_dev = torch.empty(max(self._aug.ism_table.nbytes, 1), dtype=torch.uint8, device=dev)
         self.voices = bufs
         self._v_ptr = np.array([b.data_ptr() for b in bufs], np.uint64)
         if self._dd is not None:
@@ -694,11 +714,33 @@ class WaveMixer(DeviceMixer):
         [C, K_i <= 4096] array per voice), uploaded into the resident tap buffers, then ONE `iris_fir_batch` launch over the
         whole voice corpus.  Lengths, frame counts and the frame-activity vectors (the labels) do not change: see
         `enable_reverb`.  Call it outside any graph capture.  Backgrounds and noises are not reverberated.  Returns the list
-        of impulse responses used."""
+        of impulse responses used.
+        Shoebox model with rirs = None: rt60 ~ U[rt60_lo, rt60_hi) and a `transforms.draw_shoebox` per voice from the mixer's
+        generator (kept in `_aug.geometry`), then ONE `iris_ism_rir` launch into the resident tap buffers (rows 4096 apart) and
+        ONE `iris_fir_batch_pitch` launch: two launches, no tap upload.  Returns the list of [C, K_i] device views of the tap
+        buffers.  Given `rirs` work as in the noise model."""
         aug = self._aug
         if not isinstance(aug, _ReverbAug):
             raise RuntimeError("rereverb needs enable_reverb() first")
         n_voice, chan = len(aug.orig), self.channels
+        if rirs is None and aug.model == "shoebox":
+            geometry = []
+            for _ in range(n_voice):
+                rt60 = self.rng.uniform(*aug.rt60)
+                geometry.append(dict(_tr.draw_shoebox(self.rng, chan, rt60, max_taps=_fe.FIR_MAX_TAPS), rt60=rt60))
+            if n_voice:
+                rec = _fe.shoebox_records([g["room"] for g in geometry], [g["source"] for g in geometry],
+                                          [g["mics"] for g in geometry], [g["beta"] for g in geometry],
+                                          [g["n_taps"] for g in geometry], _fe.FIR_MAX_TAPS)
+                for f in ("room", "src", "beta", "n_taps", "mic"):
+                    aug.ism_table[f] = rec[f]
+                _fe.shoebox_rir_launch(aug.ism_table, chan, _fe.FIR_MAX_TAPS, self.device, aug.ism_table_dev)
+                aug.table["n_taps"] = aug.ism_table["n_taps"]
+                _fe.fir_pitch_launch(aug.table, chan, int(self._v_L.max()), int(aug.table["n_taps"].max()), _fe.FIR_MAX_TAPS,
+                                     self.device, aug.table_dev)
+            aug.geometry = geometry
+            aug.rirs = [t[:, :int(k)] for t, k in zip(aug.taps, aug.ism_table["n_taps"])]
+            return aug.rirs
         if rirs is None:
             rirs = []
             for _ in range(n_voice):

@@ -215,6 +215,7 @@ def make_dataset(config, training=True, n_classes=3, sources=None):
     if _du.wants_speed(config.name):
         raise ValueError(f"run name {config.name!r} asks for 'speed': speed perturbation runs on the resident waveform corpus "
                          "(make_wave_dataset); the per-sample host pipeline does not resample")
+    _du.check_shoebox(config.name)
     if _du.wants_reverb(config.name):
         raise ValueError(f"run name {config.name!r} asks for 'reverb': reverberation runs on the resident waveform corpus "
                          "(make_wave_dataset); the per-sample host pipeline does not convolve")
@@ -285,6 +286,7 @@ def make_device_dataset(config, training=True, n_classes=3, sources=None, device
     if _du.wants_speed(config.name):
         raise ValueError(f"run name {config.name!r} asks for 'speed': a spectrum corpus cannot be resampled in time "
                          "(use make_wave_dataset; this path has 'stretch')")
+    _du.check_shoebox(config.name)
     if _du.wants_reverb(config.name):
         raise ValueError(f"run name {config.name!r} asks for 'reverb': a spectrum corpus has no waveform to convolve "
                          "(use make_wave_dataset; this path has 'stretch')")
@@ -418,6 +420,9 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
     U[0.1, 0.4) s, direct-to-reverberant ratio ~ U[-3, 12) dB) at creation and again every config.steps_per_epoch batches
     (`WaveMixer.enable_reverb` / `rereverb`: one `iris_fir_batch` launch over the corpus; the labels follow the dry voice); a
     name without the token takes no new code path.  'speed' and 'reverb' together are refused: they cannot be combined yet.
+    A 'shoebox' token beside 'reverb': the responses are image-source simulations of random shoebox rooms that both channels
+    share (`enable_reverb(model="shoebox")`: one `iris_ism_rir` and one `iris_fir_batch_pitch` launch per epoch, no tap
+    upload), so the inter-channel delay and level of a voice are those of one room; 'shoebox' without 'reverb' is a ValueError.
     spec_sources: the same tuple as SPECTRA ([F, T_i, 2C], integer labels), e.g. the pickled corpora - converted once here by
     `waves_from_specs` at this n_fft / hop and used as `sources` (giving both is a ValueError)."""
     from .mixer import WaveMixer
@@ -427,6 +432,7 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
     if _du.wants_stretch(config.name):
         raise ValueError(f"run name {config.name!r} asks for 'stretch': a waveform corpus has no spectra to stretch "
                          "(use make_device_dataset)")
+    _du.check_shoebox(config.name)
     if _du.wants_speed(config.name) and _du.wants_reverb(config.name):
         raise ValueError(f"run name {config.name!r} asks for both 'speed' and 'reverb': the two cannot be combined yet (a "
                          "mixer holds one voice augmentation), name one")
@@ -460,7 +466,10 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
         mixer.respeed()
     reverb = training and _du.wants_reverb(config.name)
     if reverb:   # likewise: fresh room impulse responses now and once per epoch
-        mixer.enable_reverb()
+        if _du.wants_shoebox(config.name):   # image-source responses of one random room per voice, shared by the channels
+            mixer.enable_reverb(model="shoebox")
+        else:
+            mixer.enable_reverb()
         mixer.rereverb()
 
     def gen():

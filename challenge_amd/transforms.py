@@ -310,3 +310,75 @@ def synth_rir(rng: np.random.Generator, channels: int, rt60: float, drr_db: floa
         h[:, 1:] = tail * np.sqrt(np.power(10.0, -drr_db / 10.0) / energy)
     h /= np.sqrt(np.sum(h * h, axis=1, keepdims=True))
     return h.astype(np.float32)
+
+
+def shoebox_beta(room, rt60: float) -> float:
+    """The wall reflection coefficient (one for the six walls) of a shoebox `room` (L_x, L_y, L_z in metres) whose reverberation
+    time is `rt60` seconds, by Eyring's formula: beta = exp(-12 ln(10) V / (c S rt60)) with V the volume, S the surface and
+    c = 343 m/s (rt60 = 24 ln(10) V / (-c S ln(beta^2))).  rt60 <= 0 gives 0: the anechoic response."""
+    room, rt60 = np.asarray(room, np.float64).reshape(-1), float(rt60)
+    if room.shape != (3,) or not (np.all(np.isfinite(room)) and np.all(room > 0)):
+        raise ValueError(f"shoebox_beta: room = {room} must be three positive finite sizes")
+    if not np.isfinite(rt60):
+        raise ValueError(f"shoebox_beta: rt60 = {rt60} must be finite")
+    if rt60 <= 0:
+        return 0.0
+    volume = float(np.prod(room))
+    surface = 2.0 * float(room[0] * room[1] + room[1] * room[2] + room[0] * room[2])
+    return float(np.exp(-12.0 * np.log(10.0) * volume / (_fe.ISM_SOUND * surface * rt60)))
+
+
+def shoebox_taps(rt60: float, sample_rate: int = 16000, floor_db: float = -40.0, max_taps: int = 4096) -> int:
+    """Taps of a shoebox response that follows the decay down to `floor_db`: `synth_rir`'s rule
+    min(max_taps, max(1, ceil(rt60 sample_rate (-floor_db) / 60))) plus the 2 W = 32 taps of the fractional-delay filter (the
+    direct sound sits at tap W, not 0), capped at `max_taps`."""
+    rt60, sample_rate, floor_db, max_taps = float(rt60), float(sample_rate), float(floor_db), int(max_taps)
+    if not np.isfinite(rt60) or max_taps < 1:
+        raise ValueError(f"shoebox_taps: rt60 = {rt60} must be finite and max_taps = {max_taps} positive")
+    if not (np.isfinite(sample_rate) and sample_rate > 0):
+        raise ValueError(f"shoebox_taps: sample_rate = {sample_rate} must be positive and finite")
+    if not (np.isfinite(floor_db) and floor_db < 0):
+        raise ValueError(f"shoebox_taps: floor_db = {floor_db} must be negative and finite")
+    decay = min(max_taps, max(1, int(np.ceil(max(rt60, 0.0) * sample_rate * (-floor_db) / 60.0))))
+    return min(max_taps, decay + 2 * _fe.ISM_HALF_WIDTH)
+
+
+def draw_shoebox(rng: np.random.Generator, channels: int, rt60: float, mic_spacing: float = 0.1, margin: float = 0.5,
+                 sample_rate: int = 16000, max_taps: int = 4096, tries: int = 100) -> dict:
+    """One random shoebox geometry on the host: a dict of room [3], source [3], mics [channels, 3] (float64, metres), beta
+    (`shoebox_beta(room, rt60)`) and n_taps (`shoebox_taps(rt60)`).  The room is U[3, 8) x U[3, 8) x U[2.5, 4) m; the array
+    centre is uniform in the room at least `margin` from every wall, the microphones sit on a line along x, `mic_spacing`
+    apart, centred there; the source is uniform at least `margin` from every wall and at least `margin` from the array centre,
+    redrawn until that holds (`tries` times at most, then a ValueError).  These ranges are defaults of the augmentation - a
+    living-room-sized box and a small array - not measurements of any corpus."""
+    channels, rt60, mic_spacing, margin = int(channels), float(rt60), float(mic_spacing), float(margin)
+    if not 1 <= channels <= _fe.ISM_MAX_CHAN:
+        raise ValueError(f"draw_shoebox: channels = {channels}; 1 .. {_fe.ISM_MAX_CHAN} microphones are supported")
+    if not (np.isfinite(rt60) and np.isfinite(mic_spacing) and np.isfinite(margin) and mic_spacing >= 0 and margin > 0):
+        raise ValueError(f"draw_shoebox: rt60 = {rt60}, mic_spacing = {mic_spacing} >= 0 and margin = {margin} > 0 must be finite")
+    half = 0.5 * mic_spacing * (channels - 1)
+    if 2.0 * margin >= 2.5 or 2.0 * (margin + half) >= 3.0:
+        raise ValueError(f"draw_shoebox: margin = {margin} and an array {2 * half} m long do not fit the smallest room (3 x 3 x 2.5 m)")
+    room = np.array([rng.uniform(3.0, 8.0), rng.uniform(3.0, 8.0), rng.uniform(2.5, 4.0)])
+    lo = np.array([margin + half, margin, margin])
+    centre = lo + rng.uniform(0.0, 1.0, 3) * (room - 2.0 * lo)
+    mics = np.repeat(centre[None, :], channels, axis=0)
+    mics[:, 0] += mic_spacing * (np.arange(channels) - 0.5 * (channels - 1))
+    for _ in range(int(tries)):
+        source = margin + rng.uniform(0.0, 1.0, 3) * (room - 2.0 * margin)
+        if np.sqrt(np.sum((source - centre) ** 2)) >= margin:
+            return {"room": room, "source": source, "mics": mics, "beta": shoebox_beta(room, rt60),
+                    "n_taps": shoebox_taps(rt60, sample_rate, max_taps=max_taps)}
+    raise ValueError(f"draw_shoebox: no source at least {margin} m from the array in {tries} tries")
+
+
+def shoebox_rir(room, source, mics, rt60: float, device, n_taps=None, normalize: bool = True, sample_rate: int = 16000) -> torch.Tensor:
+    """One shoebox room impulse response [chan, K] float32 on a ROCm `device` as ONE HIP launch (`frontend.shoebox_rir_batch`,
+    iris_ism_rir): the image-source method for the room (L_x, L_y, L_z), the `source` and the microphones `mics` [chan, 3], the
+    wall reflection coefficient from `rt60` by Eyring's formula (`shoebox_beta`), K = `n_taps` or `shoebox_taps(rt60)`.  The
+    nearest microphone's direct sound is a unit tap (before `normalize`) at k = 16.  There is no CPU fallback."""
+    k = shoebox_taps(rt60, sample_rate) if n_taps is None else int(n_taps)
+    mics = np.asarray(mics, np.float64)
+    mics = mics.reshape(1, 3) if mics.ndim == 1 else mics
+    return _fe.shoebox_rir_batch([room], [source], [mics], [shoebox_beta(room, rt60)], [k], normalize=normalize,
+                                 sample_rate=sample_rate, device=device)[0]

@@ -864,6 +864,54 @@ typedef struct {
     int32_t      len, n_taps;
 } iris_fir_src;
 int iris_fir_batch(const void* table_dev, int n_src, int channels, int max_len, int max_taps, void* stream);
+/* The same with the rows of a record's taps `tap_pitch` floats apart (taps DEVICE [channels, tap_pitch], the first n_taps of
+ * each row read): the layout iris_ism_rir writes.  tap_pitch == 0 is iris_fir_batch (rows n_taps apart); 0 < tap_pitch <
+ * max_taps is IRIS_E_INVALID.  The results are those of iris_fir_batch on the same numbers, bit for bit. */
+int iris_fir_batch_pitch(const void* table_dev, int n_src, int channels, int max_len, int max_taps, int tap_pitch, void* stream);
+
+/*
+ * Shoebox room simulation (Allen & Berkley, JASA 1979: the image-source method, as pyroomacoustics and gpuRIR compute it): the
+ * room impulse responses of a RAGGED BATCH of voices, each with its own room, source, microphones, wall reflection coefficient
+ * and tap count, in one launch.  All microphones of a record sit in the same room with the same source, so every reflection
+ * reaches them with its own delay and gain: the inter-channel time and level differences are those of the geometry.
+ * Per record, with c = 343 m/s, fs = sample_rate, W = 16 and L = room: images n in [-N_a, N_a]^3, p in {0, 1}^3 at
+ *     x_a = (1 - 2 p_a) src_a + 2 n_a L_a,      e = sum_a (|n_a - p_a| + |n_a|) reflections,
+ * d = |x - mic[ch]|, tau = d fs / c samples; tau_min = the smallest DIRECT (n = 0, p = 0) delay over the channels of the record
+ * and d_min its distance; t = tau - tau_min + W and
+ *     h[ch][k] = sum_images beta^e (d_min / d) w(k - t)   for 0 <= k < n_taps,
+ *     w(x)     = sinc(x) 0.5 (1 + cos(pi x / W)) for |x| < W, else 0;  sinc(x) = sin(pi x) / (pi x), sinc(0) = 1
+ * - the nearest microphone's direct sound is a unit tap at k = W (1 ms at 16 kHz) and the delay between the channels is kept.
+ * N_a = floor(D / (2 L_a)) + 1 with D = c (tau_min + n_taps) / fs: no image beyond can reach a tap below n_taps, and images
+ * with t - W >= n_taps - 1 are skipped, so within its n_taps taps the response is the complete image sum, not an
+ * order-truncated one.  normalize != 0: every channel of a record is multiplied by the SAME g = 1 / sqrt(mean_ch sum_k h^2)
+ * (white input keeps its mean power, the level difference between the channels is untouched; an all-zero response, such as
+ * n_taps <= W with integer delays, is left as it is).
+ *   dst  DEVICE [channels, max_taps] fp32: row ch receives h[ch][0 .. n_taps); the floats beyond n_taps of a row are not written
+ * Positions, d, tau, t, floor(t) and the fraction are formed in double, the window, the sinc and the products in fp32; each
+ * contribution is rounded to a multiple of 2^-32 and accumulated as a 64-bit integer, so the result does not depend on the
+ * order of the additions: bitwise reproducible run to run.  Against the float64 evaluation
+ *     |h - ref| <= 3.6 u A_k + n_k 2^-33,    u = 2^-24, A_k = sum |beta^e d_min / d| and n_k = the number of images whose
+ * window covers tap k (with normalize, (3.6 u A_k + n_k 2^-33 + 4 u |ref_k|) g against ref g).
+ * Checked on the host before any HIP call, on `table_host` (IRIS_E_INVALID, the record named in iris_last_error): n_src < 0,
+ * channels <= 0, NULL tables with n_src > 0, max_taps outside 1 .. 4096, a sample_rate that is not positive and finite; per
+ * record a NULL dst, n_taps outside 1 .. 4096, max_taps < n_taps, non-finite or non-positive room sizes, a source or a
+ * microphone outside [0, L_a] (NaN included), a source on the nearest microphone (d_min = 0), beta outside [0, 1), a lattice of
+ * more than 2^31 - 1 images.  IRIS_E_UNSUPPORTED: channels > IRIS_ISM_MAX_CHAN, n_src > 65535.  n_src == 0 launches nothing.
+ *   table_host  HOST copy of the records (what the checks read);  table_dev  the same bytes on the DEVICE (what the kernel reads)
+ * One launch on `stream`; no workspace, no synchronisation: capturable, and a record's result does not depend on the records
+ * around it.  Runs on the current HIP device.
+ */
+#define IRIS_ISM_MAX_CHAN 8
+typedef struct {
+    float*  dst;                         /* DEVICE [channels, max_taps] */
+    double  room[3];                     /* L_x, L_y, L_z in metres */
+    double  src[3];                      /* the source */
+    double  beta;                        /* wall reflection coefficient, the same for the six walls, in [0, 1) */
+    int32_t n_taps, reserved;
+    double  mic[IRIS_ISM_MAX_CHAN][3];   /* the first `channels` rows are read */
+} iris_ism_src;
+int iris_ism_rir(const iris_ism_src* table_host, const void* table_dev, int n_src, int channels, int max_taps,
+                 double sample_rate, int normalize, void* stream);
 
 /*
  * Inverse STFT of a RAGGED BATCH of complex spectrograms in the reference layout, in one launch: the inverse of iris_stft /
