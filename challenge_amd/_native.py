@@ -18,6 +18,7 @@ IRIS_MEL_F32, IRIS_MEL_F16_MFMA = 0, 1
 IRIS_EPILOGUE_FUSED, IRIS_EPILOGUE_TWO_KERNELS, IRIS_EPILOGUE_IN_PLACE = 0, 1, 2
 IRIS_WINO_POOL, IRIS_WINO_OUT_NHWC, IRIS_WINO_IN_NHWC, IRIS_WINO_RELU = 1, 2, 4, 8
 IRIS_E_EPILOGUE_TIMEOUT = -5
+IRIS_FILTER_STEP, IRIS_FILTER_LINEAR = 0, 1
 
 # every symbol include/iris_frontend.h declares, with (restype, argtypes)
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
@@ -70,6 +71,9 @@ SIGNATURES = {
     "iris_istft_len": (C.c_longlong, [C.c_longlong, _i]),
     "iris_istft": (_i, [_vp, _vp, _i, _i, _vp]),
     "iris_wav_to_logmel": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
+    "iris_wav_to_logmel_gain": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    "iris_magmel_gain": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    "iris_filter_draw": (_i, [_i, _i, _i, _i, _i, _i, _f, _f, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "iris_mask_apply": (_i, [_vp, _sz, _sz, _sz, _i, _vp, _i, _sz, _vp]),
     "iris_agc_clip": (_i, [_vp, _sz, _f, _f, _f, _vp]),
     "iris_mix_frame_active": (_i, [_vp, _i, _i, _i, _vp, _vp]),

@@ -109,13 +109,16 @@ extern "C" int iris_magphase_to_complex(const float* in, float* out, size_t n_ou
     return IRIS_OK;
 }
 
-extern "C" int iris_magmel(iris_plan* p, const float* spec, float* mel, int batch, int n_frames, int is_magphase,
-                           const int32_t* t_bands, int n_tb, const int32_t* f_bands, int n_fb, void* stream) {
-    if (!p || !spec || !mel) return fail(IRIS_E_INVALID, "iris_magmel: NULL argument");
-    if (batch <= 0 || n_frames <= 0) return fail(IRIS_E_INVALID, "iris_magmel: batch=%d n_frames=%d", batch, n_frames);
-    if (batch > 65535) return fail(IRIS_E_UNSUPPORTED, "iris_magmel: batch %d > 65535", batch);
+// iris_magmel and its FilterAugment sibling iris_magmel_gain (`gain`: the sibling's kernels, which multiply the finished mel
+// values by mel_gain[b, m]); every check happens before the first HIP call
+static int magmel_impl(iris_plan* p, const float* spec, float* mel, int batch, int n_frames, int is_magphase, const int32_t* t_bands,
+                       int n_tb, const int32_t* f_bands, int n_fb, const float* mel_gain, bool gain, void* stream, const char* who) {
+    if (!p || !spec || !mel) return fail(IRIS_E_INVALID, "%s: NULL argument", who);
+    if (batch <= 0 || n_frames <= 0) return fail(IRIS_E_INVALID, "%s: batch=%d n_frames=%d", who, batch, n_frames);
+    if (gain && !mel_gain) return fail(IRIS_E_INVALID, "%s: mel_gain is NULL", who);
+    if (batch > 65535) return fail(IRIS_E_UNSUPPORTED, "%s: batch %d > 65535", who, batch);
     int rc;
-    if ((rc = check_bands(t_bands, n_tb, "iris_magmel")) || (rc = check_bands(f_bands, n_fb, "iris_magmel"))) return rc;
+    if ((rc = check_bands(t_bands, n_tb, who)) || (rc = check_bands(f_bands, n_fb, who))) return rc;
     DeviceGuard guard(p->device);
     MagmelArgs a;
     a.spec = spec;
@@ -156,14 +159,33 @@ extern "C" int iris_magmel(iris_plan* p, const float* spec, float* mel, int batc
         // split the bins over 8 waves when the grid alone cannot fill the chip
         const int threads = (size_t)grid.x * grid.y * 4 < (size_t)p->num_cu * 8 ? 512 : 256;
         const size_t lds = (size_t)p->n_mel * 64 * p->channels * sizeof(float);
-        if (p->channels == 1) k_magmel_tri<1><<<grid, threads, lds, (hipStream_t)stream>>>(t);
-        else k_magmel_tri<2><<<grid, threads, lds, (hipStream_t)stream>>>(t);
+        if (gain) {
+            const MagmelTriGainArgs g = {t, mel_gain};
+            if (p->channels == 1) k_magmel_tri_gain<1><<<grid, threads, lds, (hipStream_t)stream>>>(g);
+            else k_magmel_tri_gain<2><<<grid, threads, lds, (hipStream_t)stream>>>(g);
+        } else {
+            if (p->channels == 1) k_magmel_tri<1><<<grid, threads, lds, (hipStream_t)stream>>>(t);
+            else k_magmel_tri<2><<<grid, threads, lds, (hipStream_t)stream>>>(t);
+        }
     } else {
         const int tc = n_frames * p->channels;
-        k_magmel<<<dim3((tc + 63) / 64, batch), 256, 0, (hipStream_t)stream>>>(a);
+        if (gain) k_magmel_gain<<<dim3((tc + 63) / 64, batch), 256, 0, (hipStream_t)stream>>>(MagmelGainArgs{a, mel_gain});
+        else k_magmel<<<dim3((tc + 63) / 64, batch), 256, 0, (hipStream_t)stream>>>(a);
     }
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
+}
+
+extern "C" int iris_magmel(iris_plan* p, const float* spec, float* mel, int batch, int n_frames, int is_magphase,
+                           const int32_t* t_bands, int n_tb, const int32_t* f_bands, int n_fb, void* stream) {
+    return magmel_impl(p, spec, mel, batch, n_frames, is_magphase, t_bands, n_tb, f_bands, n_fb, nullptr, false, stream, "iris_magmel");
+}
+
+extern "C" int iris_magmel_gain(iris_plan* p, const float* spec, float* mel, int batch, int n_frames, int is_magphase,
+                                const int32_t* t_bands, int n_tb, const int32_t* f_bands, int n_fb, const float* mel_gain,
+                                void* stream) {
+    return magmel_impl(p, spec, mel, batch, n_frames, is_magphase, t_bands, n_tb, f_bands, n_fb, mel_gain, true, stream,
+                       "iris_magmel_gain");
 }
 
 extern "C" size_t iris_minmax_log_workspace(int n_rows, size_t row_len) {
@@ -255,14 +277,15 @@ static hipError_t launch_timed(std::vector<hipEvent_t>& ev, int& used, const voi
     return rc;
 }
 
-extern "C" int iris_wav_to_logmel(iris_plan* p, const float* wav, float* out, int batch, int len, int flags,
-                                  const int32_t* t_bands, int n_tb, const int32_t* f_bands, int n_fb,
-                                  void* stream) {
-    int rc = check_wav_args(p, wav, out, batch, len, "iris_wav_to_logmel");
+// iris_wav_to_logmel and its FilterAugment sibling iris_wav_to_logmel_gain (`gain`: the sibling's kernels - the same forms,
+// geometry and epilogues, the mel values multiplied by mel_gain[b, m] before min / max and log)
+static int wav_to_logmel_impl(iris_plan* p, const float* wav, float* out, int batch, int len, int flags, const int32_t* t_bands,
+                              int n_tb, const int32_t* f_bands, int n_fb, const float* mel_gain, bool gain, void* stream,
+                              const char* who) {
+    if (gain && !mel_gain) return fail(IRIS_E_INVALID, "%s: mel_gain is NULL", who);
+    int rc = check_wav_args(p, wav, out, batch, len, who);
     if (rc) return rc;
-    if ((rc = check_bands(t_bands, n_tb, "iris_wav_to_logmel")) ||
-        (rc = check_bands(f_bands, n_fb, "iris_wav_to_logmel")))
-        return rc;
+    if ((rc = check_bands(t_bands, n_tb, who)) || (rc = check_bands(f_bands, n_fb, who))) return rc;
     if (take_status(p))  // raised by an earlier launch (host-visible word: no synchronisation here)
         return fail(IRIS_E_EPILOGUE_TIMEOUT,
                     "iris_wav_to_logmel: an earlier fused-epilogue launch of this plan gave up waiting for its clip's other "
@@ -292,6 +315,7 @@ extern "C" int iris_wav_to_logmel(iris_plan* p, const float* wav, float* out, in
     a.dbg = p->d_dbg;
     const bool bands = (n_tb > 0) || (n_fb > 0);
     const bool mfma = p->mel_precision == 1 && !bands;  // calls with bands always take the fp32 kernel
+    const bool wclass = bands || gain;  // what decides a variant's wave count and LDS (fused_waves): bands or gains
     const int streams = mfma ? 1 : plan_streams(p);
     // min-max / log inside the kernel (one launch) unless: nothing to apply, the MFMA variant, two frame streams
     // (diag), the plan says two kernels, the stream is being captured (the epoch is a host counter: it would be
@@ -300,6 +324,7 @@ extern "C" int iris_wav_to_logmel(iris_plan* p, const float* wav, float* out, in
     // asks for it, IRIS_EPILOGUE_IN_PLACE: an A/B form - see below)
     int fuse = ((do_minmax || do_log) && !mfma && streams == 1 && p->epilogue != IRIS_EPILOGUE_TWO_KERNELS)
                    ? (p->epilogue == IRIS_EPILOGUE_IN_PLACE ? 2 : 1) : 0;
+    if (gain && fuse == 2) fuse = 0;  // the in-place form has no FilterAugment sibling (host_plan.h: fused_pick)
     if (fuse) {
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) fuse = 0;
@@ -311,14 +336,14 @@ extern "C" int iris_wav_to_logmel(iris_plan* p, const float* wav, float* out, in
     a.tile_ks = p->d_tile_ks;
     a.kb = p->mfma_kb;
     if (mfma) {
-        kernel = mfma_kernel(p->log2n);
+        kernel = mfma_kernel(p->log2n, gain);
         fused_geometry(p, batch, a.T, 1, &a.chunk_frames, &a.chunks_per_clip);
         lds = mfma_lds_bytes(p);
         grid = std::min(batch * a.chunks_per_clip, p->num_cu);
     } else {
         if (fuse) {
-            kernel = fused_kernel(p->log2n, p->mel_mode, p->need_hi != 0, bands, streams, fuse);
-            rc = fused_config(p, kernel, batch, a.T, streams, bands, fuse, &a.chunk_frames, &a.chunks_per_clip, &grid, &lds);
+            kernel = fused_kernel(p->log2n, p->mel_mode, p->need_hi != 0, bands, streams, fuse, gain);
+            rc = fused_config(p, kernel, batch, a.T, streams, wclass, fuse, &a.chunk_frames, &a.chunks_per_clip, &grid, &lds);
             // no fused epilogue when the LDS tile does not fit, or when a clip has more chunks than the grid has workgroups (a
             // workgroup would then wait for a chunk it has yet to process itself): the two-kernel form.  (Round 5 measured the
             // in-place form as the fallback for tiles beyond the LDS: same bytes through the same fabric as the second kernel,
@@ -327,8 +352,8 @@ extern "C" int iris_wav_to_logmel(iris_plan* p, const float* wav, float* out, in
             else if (rc) return rc;
         }
         if (!fuse) {
-            kernel = fused_kernel(p->log2n, p->mel_mode, p->need_hi != 0, bands, streams, 0);
-            if ((rc = fused_config(p, kernel, batch, a.T, streams, bands, 0, &a.chunk_frames, &a.chunks_per_clip, &grid, &lds)))
+            kernel = fused_kernel(p->log2n, p->mel_mode, p->need_hi != 0, bands, streams, 0, gain);
+            if ((rc = fused_config(p, kernel, batch, a.T, streams, wclass, 0, &a.chunk_frames, &a.chunks_per_clip, &grid, &lds)))
                 return rc;
         }
     }
@@ -344,14 +369,14 @@ extern "C" int iris_wav_to_logmel(iris_plan* p, const float* wav, float* out, in
         if (++p->epoch == 0) p->epoch = 1;
         a.epoch = p->epoch;
         a.pitch = fuse == 1 ? fused_tile_pitch(p, a.chunk_frames) : 0;
-        a.tile_off = (int)fused_tile_off(fused_lds_bytes(p, streams, bands, a.chunk_frames, fuse));
+        a.tile_off = (int)fused_tile_off(fused_lds_bytes(p, streams, wclass, a.chunk_frames, fuse));
     }
     if ((size_t)p->n_mel * a.T * p->channels * 4 > 0xffffffffull || (size_t)a.T * p->channels * 4 >= (1u << 24))
-        return fail(IRIS_E_UNSUPPORTED, "iris_wav_to_logmel: clip too long (%d frames x %d channels)", a.T, p->channels);
+        return fail(IRIS_E_UNSUPPORTED, "%s: clip too long (%d frames x %d channels)", who, a.T, p->channels);
     a.n_chunks = batch * a.chunks_per_clip;
     a.chunk_base = a.T / a.chunks_per_clip;
     a.chunk_rem = a.T % a.chunks_per_clip;
-    const int waves = mfma ? kMfmaWaves : fused_waves(p->log2n, streams, bands, p->need_hi != 0, fuse, p->mel_mode);
+    const int waves = mfma ? kMfmaWaves : fused_waves(p->log2n, streams, wclass, p->need_hi != 0, fuse, p->mel_mode);
     const int parts_per_chunk = waves;
     const size_t n_partial = 2 * (size_t)a.n_chunks * parts_per_chunk;
     a.partial = p->d_ws;
@@ -362,11 +387,11 @@ extern "C" int iris_wav_to_logmel(iris_plan* p, const float* wav, float* out, in
         a.n_sq = (int)((row + kChunk - 1) / kChunk);
         float* sq = p->d_ws + n_partial;
         if (n_partial + (size_t)batch * a.n_sq > p->ws_floats)
-            return fail(IRIS_E_CAPACITY, "iris_wav_to_logmel: workspace too small");
+            return fail(IRIS_E_CAPACITY, "%s: workspace too small", who);
         k_sumsq_partial<<<dim3(a.n_sq, batch), 256, 0, s>>>(wav, sq, row, a.n_sq);
         a.sumsq = sq;
     }
-    if (n_partial > p->ws_floats) return fail(IRIS_E_CAPACITY, "iris_wav_to_logmel: workspace too small");
+    if (n_partial > p->ws_floats) return fail(IRIS_E_CAPACITY, "%s: workspace too small", who);
 
     // bench hook (iris_timing_enable): every n-th call carries event pairs around both kernels; the first
     // kTimingSkip calls after enabling are never sampled (first dispatch on an idle GPU, clock ramp)
@@ -374,10 +399,14 @@ extern "C" int iris_wav_to_logmel(iris_plan* p, const float* wav, float* out, in
                        p->ev_used < kMaxTimedLaunches;
     p->launch_no++;
     hipError_t e;
+    FusedGainArgs gargs = {a, mel_gain};  // (a sibling's kernel takes this block; `kernel` is then never called as a fused_kernel_t)
     if (timed) {
         FusedArgs args = a;
-        void* kargs[] = {&args};
+        void* kargs[] = {gain ? (void*)&gargs : (void*)&args};
         e = launch_timed(p->ev, p->ev_used, (const void*)kernel, dim3(grid), dim3(64 * waves), kargs, lds, s);
+    } else if (gain) {
+        void* kargs[] = {&gargs};
+        e = hipLaunchKernel((const void*)kernel, dim3(grid), dim3(64 * waves), kargs, lds, s);
     } else {
         kernel<<<grid, 64 * waves, lds, s>>>(a);
         e = hipGetLastError();
@@ -400,6 +429,19 @@ extern "C" int iris_wav_to_logmel(iris_plan* p, const float* wav, float* out, in
         HIP_TRY(e);
     }
     return IRIS_OK;
+}
+
+extern "C" int iris_wav_to_logmel(iris_plan* p, const float* wav, float* out, int batch, int len, int flags,
+                                  const int32_t* t_bands, int n_tb, const int32_t* f_bands, int n_fb,
+                                  void* stream) {
+    return wav_to_logmel_impl(p, wav, out, batch, len, flags, t_bands, n_tb, f_bands, n_fb, nullptr, false, stream, "iris_wav_to_logmel");
+}
+
+extern "C" int iris_wav_to_logmel_gain(iris_plan* p, const float* wav, float* out, int batch, int len, int flags,
+                                       const int32_t* t_bands, int n_tb, const int32_t* f_bands, int n_fb,
+                                       const float* mel_gain, void* stream) {
+    return wav_to_logmel_impl(p, wav, out, batch, len, flags, t_bands, n_tb, f_bands, n_fb, mel_gain, true, stream,
+                              "iris_wav_to_logmel_gain");
 }
 
 extern "C" int iris_mask_apply(void* x, size_t n_outer, size_t axis_len, size_t n_inner, int elem_size,

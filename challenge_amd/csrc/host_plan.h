@@ -178,49 +178,59 @@ static size_t fused_tile_bytes(const iris_plan* p, int streams, bool bands, int 
 
 typedef void (*fused_kernel_t)(const FusedArgs);
 
+// the kernel as it always was, or its FilterAugment sibling (mel values times the per-sample band gains)
+template <int LOG2N, int MELMODE, bool HI, bool BANDS, int S, int FUSE>
+static fused_kernel_t fused_pick(bool gain) {
+    // (the in-place epilogue, an A/B form that is never the default, has no sibling: a gained call of such a plan takes two kernels)
+    // (a sibling takes FusedGainArgs: its pointer is only ever handed to hipLaunchKernel / the runtime's attribute calls)
+    if constexpr (FUSE == 2) return k_wav_to_mel<LOG2N, MELMODE, HI, BANDS, S, FUSE>;
+    else return gain ? reinterpret_cast<fused_kernel_t>(k_wav_to_mel_gain<LOG2N, MELMODE, HI, BANDS, S, FUSE>)
+                     : k_wav_to_mel<LOG2N, MELMODE, HI, BANDS, S, FUSE>;
+}
 template <int LOG2N, int MELMODE, int S, int FUSE>
-static fused_kernel_t fused_kernel_hb(bool hi, bool bands) {
+static fused_kernel_t fused_kernel_hb(bool hi, bool bands, bool gain) {
     if (hi)
-        return bands ? k_wav_to_mel<LOG2N, MELMODE, true, true, S, FUSE> : k_wav_to_mel<LOG2N, MELMODE, true, false, S, FUSE>;
-    return bands ? k_wav_to_mel<LOG2N, MELMODE, false, true, S, FUSE> : k_wav_to_mel<LOG2N, MELMODE, false, false, S, FUSE>;
+        return bands ? fused_pick<LOG2N, MELMODE, true, true, S, FUSE>(gain) : fused_pick<LOG2N, MELMODE, true, false, S, FUSE>(gain);
+    return bands ? fused_pick<LOG2N, MELMODE, false, true, S, FUSE>(gain) : fused_pick<LOG2N, MELMODE, false, false, S, FUSE>(gain);
 }
 template <int LOG2N, int S, int FUSE>
-static fused_kernel_t fused_kernel_mm(int mel_mode, bool hi, bool bands) {
+static fused_kernel_t fused_kernel_mm(int mel_mode, bool hi, bool bands, bool gain) {
     if constexpr (LOG2N <= 10) {
         if (mel_mode == 0)  // register weights exist only for the half-spectrum variant up to n_fft 1024
-            return bands ? k_wav_to_mel<LOG2N, 0, false, true, S, FUSE> : k_wav_to_mel<LOG2N, 0, false, false, S, FUSE>;
+            return bands ? fused_pick<LOG2N, 0, false, true, S, FUSE>(gain) : fused_pick<LOG2N, 0, false, false, S, FUSE>(gain);
         if (mel_mode == 3)
-            return bands ? k_wav_to_mel<LOG2N, 3, false, true, S, FUSE> : k_wav_to_mel<LOG2N, 3, false, false, S, FUSE>;
+            return bands ? fused_pick<LOG2N, 3, false, true, S, FUSE>(gain) : fused_pick<LOG2N, 3, false, false, S, FUSE>(gain);
     }
-    if (mel_mode == 1) return fused_kernel_hb<LOG2N, 1, S, FUSE>(hi, bands);
-    return fused_kernel_hb<LOG2N, 2, S, FUSE>(hi, bands);
+    if (mel_mode == 1) return fused_kernel_hb<LOG2N, 1, S, FUSE>(hi, bands, gain);
+    return fused_kernel_hb<LOG2N, 2, S, FUSE>(hi, bands, gain);
 }
 // two frame streams per wave exist for n_fft 512 / 1024, in diagnostic builds only
 template <int LOG2N>
-static fused_kernel_t fused_kernel_m(int mel_mode, bool hi, bool bands, int streams, int fuse) {
+static fused_kernel_t fused_kernel_m(int mel_mode, bool hi, bool bands, int streams, int fuse, bool gain) {
 #if IRIS_DIAG
     if constexpr (LOG2N == 9 || LOG2N == 10) {
-        if (streams == 2) return fused_kernel_mm<LOG2N, 2, 0>(mel_mode, hi, bands);
+        if (streams == 2) return fused_kernel_mm<LOG2N, 2, 0>(mel_mode, hi, bands, gain);
     }
 #endif
     (void)streams;
-    if (fuse == 2) return fused_kernel_mm<LOG2N, 1, 2>(mel_mode, hi, bands);
-    return fuse ? fused_kernel_mm<LOG2N, 1, 1>(mel_mode, hi, bands) : fused_kernel_mm<LOG2N, 1, 0>(mel_mode, hi, bands);
+    if (fuse == 2) return fused_kernel_mm<LOG2N, 1, 2>(mel_mode, hi, bands, gain);
+    return fuse ? fused_kernel_mm<LOG2N, 1, 1>(mel_mode, hi, bands, gain) : fused_kernel_mm<LOG2N, 1, 0>(mel_mode, hi, bands, gain);
 }
 // fuse: 0 = raw mel + per-wave partials (two-kernel form), 1 = epilogue from an LDS tile, 2 = epilogue in place through `out`
-static fused_kernel_t fused_kernel(int log2n, int mel_mode, bool hi, bool bands, int streams, int fuse = 0) {
+// gain: the FilterAugment sibling (k_wav_to_mel_gain / k_wav_to_mel_mfma_gain)
+static fused_kernel_t fused_kernel(int log2n, int mel_mode, bool hi, bool bands, int streams, int fuse = 0, bool gain = false) {
     switch (log2n) {
-        case 11: return fused_kernel_m<11>(mel_mode, hi, bands, streams, fuse);
-        case 10: return fused_kernel_m<10>(mel_mode, hi, bands, streams, fuse);
-        case 9: return fused_kernel_m<9>(mel_mode, hi, bands, streams, fuse);
-        default: return fused_kernel_m<8>(mel_mode, hi, bands, streams, fuse);
+        case 11: return fused_kernel_m<11>(mel_mode, hi, bands, streams, fuse, gain);
+        case 10: return fused_kernel_m<10>(mel_mode, hi, bands, streams, fuse, gain);
+        case 9: return fused_kernel_m<9>(mel_mode, hi, bands, streams, fuse, gain);
+        default: return fused_kernel_m<8>(mel_mode, hi, bands, streams, fuse, gain);
     }
 }
-static fused_kernel_t mfma_kernel(int log2n) {
+static fused_kernel_t mfma_kernel(int log2n, bool gain = false) {
     switch (log2n) {
-        case 11: return k_wav_to_mel_mfma<11>;
-        case 10: return k_wav_to_mel_mfma<10>;
-        default: return k_wav_to_mel_mfma<9>;
+        case 11: return gain ? reinterpret_cast<fused_kernel_t>(k_wav_to_mel_mfma_gain<11>) : k_wav_to_mel_mfma<11>;
+        case 10: return gain ? reinterpret_cast<fused_kernel_t>(k_wav_to_mel_mfma_gain<10>) : k_wav_to_mel_mfma<10>;
+        default: return gain ? reinterpret_cast<fused_kernel_t>(k_wav_to_mel_mfma_gain<9>) : k_wav_to_mel_mfma<9>;
     }
 }
 // LDS of the MFMA variant: landing + exchange buffers of its 8 waves, two fp16 magnitude tiles
@@ -246,15 +256,18 @@ static hipError_t allow_big_lds(const iris_plan* p) {
     for (int v = 0; v < (IRIS_DIAG ? 4 : 2); ++v) {
         const int streams = (v & 2) ? 2 : 1;
         if (streams == 2 && p->log2n != 9 && p->log2n != 10) continue;
-        for (int fuse = 0; fuse < (streams == 1 ? 3 : 1); ++fuse) {
-            e = hipFuncSetAttribute((const void*)fused_kernel(p->log2n, p->mel_mode, p->need_hi != 0, (v & 1) != 0, streams, fuse),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
-            if (e != hipSuccess) return e;
-        }
+        for (int fuse = 0; fuse < (streams == 1 ? 3 : 1); ++fuse)
+            for (int gain = 0; gain < (fuse == 2 ? 1 : 2); ++gain) {
+                e = hipFuncSetAttribute((const void*)fused_kernel(p->log2n, p->mel_mode, p->need_hi != 0, (v & 1) != 0, streams, fuse, gain != 0),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
+                if (e != hipSuccess) return e;
+            }
     }
     if (p->mfma_ok) {
-        e = hipFuncSetAttribute((const void*)mfma_kernel(p->log2n), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
-        if (e != hipSuccess) return e;
+        for (int gain = 0; gain < 2; ++gain) {
+            e = hipFuncSetAttribute((const void*)mfma_kernel(p->log2n, gain != 0), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
+            if (e != hipSuccess) return e;
+        }
     }
     e = hipFuncSetAttribute(istft_kernel(p->log2n), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
     if (e != hipSuccess) return e;

@@ -37,7 +37,7 @@ __host__ __device__ inline Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint3
 }
 
 // purposes (counter word 3)
-enum { kDrawSample = 1, kDrawVoice = 2, kDrawNoise = 3, kDrawPerm = 4, kDrawBandT = 5, kDrawBandF = 6 };
+enum { kDrawSample = 1, kDrawVoice = 2, kDrawNoise = 3, kDrawPerm = 4, kDrawBandT = 5, kDrawBandF = 6, kDrawFilter = 7 };
 
 __host__ __device__ inline uint32_t draw_below(uint32_t word, uint32_t range) {  // uniform on [0, range), range >= 1
     return (uint32_t)(((uint64_t)word * range) >> 32);
@@ -262,6 +262,101 @@ extern "C" int iris_augment_draw(int batch, int n_time, int n_time_masks, int ma
     k_augment_draw<<<1, 256, 0, (hipStream_t)stream>>>(batch, n_time, n_time_masks, max_time_mask, n_freq, n_freq_masks,
                                                        max_freq_mask, (uint32_t)seed, (uint32_t)(seed >> 32),
                                                        reinterpret_cast<unsigned long long*>(state_dev), t_bands_out, f_bands_out);
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+
+// ---------------------------------------------------------------------------
+// FilterAugment (Nam, Kim, Park, ICASSP 2022): a random piecewise gain curve over the mel bands for every sample of a batch.
+// The recipe, identical here, in transforms.filter_augment_draw (host, NumPy Generator) and in tests/filtaug_ref.py (the
+// NumPy restatement of this generator).  Per sample b, words from philox(call counter lo, hi, b * 64 + column, kDrawFilter):
+//   1. band count   n = n_band_lo + draw_below(column 0 word x, n_band_hi - n_band_lo + 1)
+//   2. boundaries   uniform over every placement 0 = b_0 < ... < b_n = n_mel with b_{j+1} - b_j >= min_bw:
+//                   slots = n_mel - n * min_bw + (n - 1) free slots; cut i (i = 0 .. n - 2) takes word i % 4 of column
+//                   1 + i / 4, r = draw_below(word, slots - i), then walks the cuts chosen so far in ascending order and
+//                   steps over each one it reaches (r >= s_k: ++r) - a uniform draw among the slots still free - and is
+//                   inserted in order; with the sorted cuts s_0 < ... < s_{n-2}:  b_j = j * min_bw + s_{j-1} - (j - 1)
+//                   (the minimum widths re-inserted), b_n = n_mel; the unused tail of bounds_out is n_mel
+//   3. decibels     value i (step kind: i < n, one per band; linear kind: i <= n, one per boundary) takes word i % 4 of column
+//                   16 + i / 4:  dB = fmaf(db_hi - db_lo, draw_unit(word), db_lo), fp32; the unused tail of db_out is 0
+//   4. gain[b, m]   row m of band j (b_j <= m < b_{j+1}), in double from the stored fp32 dB values, rounded to fp32 once:
+//                   step: 10^(dB_j / 20);  linear: 10^((dB_j + (dB_{j+1} - dB_j) (m - b_j) / (b_{j+1} - b_j)) / 20)
+//                   (the features are mel MAGNITUDES, hence / 20)
+// n_band_hi <= 32 keeps every column below 64, i.e. inside the sample's own counter range.  state[0] = call counter
+// (advanced here); one launch, one workgroup, no atomics: capturable.
+// ---------------------------------------------------------------------------
+constexpr int kFilterMaxBands = 32;
+
+__global__ __launch_bounds__(256) void k_filter_draw(int batch, int n_mel, int linear, int n_lo, int n_hi, int min_bw, float db_lo,
+                                                     float db_hi, uint32_t k0, uint32_t k1, unsigned long long* state, int32_t* bounds,
+                                                     float* db, float* gain) {
+    const unsigned long long ctr = state[0];
+    const uint32_t c0 = (uint32_t)ctr, c1 = (uint32_t)(ctr >> 32);
+    const int pitch = n_hi + 1;
+    auto word = [](const Philox4& r, int i) { return (i & 3) == 0 ? r.x : ((i & 3) == 1 ? r.y : ((i & 3) == 2 ? r.z : r.w)); };
+    __syncthreads();  // every thread has read the state before thread 0 advances it
+    for (int b = threadIdx.x; b < batch; b += blockDim.x) {
+        int32_t* bo = bounds + (size_t)b * pitch;
+        float* dbo = db + (size_t)b * pitch;
+        const Philox4 rc = philox4x32_10(c0, c1, (uint32_t)b * 64u, kDrawFilter, k0, k1);
+        const int n = n_lo + (int)draw_below(rc.x, (uint32_t)(n_hi - n_lo + 1));
+        const int slots = n_mel - n * min_bw + (n - 1);
+        int cuts[kFilterMaxBands];  // ascending
+        Philox4 r = rc;
+        for (int i = 0; i < n - 1; ++i) {
+            if ((i & 3) == 0) r = philox4x32_10(c0, c1, (uint32_t)b * 64u + 1u + (uint32_t)(i >> 2), kDrawFilter, k0, k1);
+            int v = (int)draw_below(word(r, i), (uint32_t)(slots - i));
+            int at = 0;
+            while (at < i && v >= cuts[at]) {
+                ++v;
+                ++at;
+            }
+            for (int k = i; k > at; --k) cuts[k] = cuts[k - 1];
+            cuts[at] = v;
+        }
+        bo[0] = 0;
+        for (int j = 1; j < n; ++j) bo[j] = j * min_bw + cuts[j - 1] - (j - 1);
+        for (int j = n; j <= n_hi; ++j) bo[j] = n_mel;
+        const int n_db = linear ? n + 1 : n;
+        const float span = db_hi - db_lo;
+        for (int i = 0; i <= n_hi; ++i) {
+            if ((i & 3) == 0) r = philox4x32_10(c0, c1, (uint32_t)b * 64u + 16u + (uint32_t)(i >> 2), kDrawFilter, k0, k1);
+            dbo[i] = i < n_db ? fmaf(span, draw_unit(word(r, i)), db_lo) : 0.f;
+        }
+    }
+    __syncthreads();  // the block's own bounds / dB rows are visible to all of its threads
+    for (int i = threadIdx.x; i < batch * n_mel; i += blockDim.x) {
+        const int b = i / n_mel, m = i - b * n_mel;
+        const int32_t* bo = bounds + (size_t)b * pitch;
+        const float* dbo = db + (size_t)b * pitch;
+        int j = 0;
+        while (j < n_hi - 1 && bo[j + 1] <= m) ++j;
+        double d = (double)dbo[j];
+        if (linear) d += ((double)dbo[j + 1] - (double)dbo[j]) * (double)(m - bo[j]) / (double)(bo[j + 1] - bo[j]);
+        gain[i] = (float)exp10(d / 20.0);
+    }
+    if (threadIdx.x == 0) state[0] = ctr + 1;
+}
+
+extern "C" int iris_filter_draw(int batch, int n_mel, int kind, int n_band_lo, int n_band_hi, int min_bw, float db_lo, float db_hi,
+                                uint64_t seed, uint64_t* state_dev, int32_t* bounds_out, float* db_out, float* gain_out,
+                                void* stream) {
+    if (batch < 0) return fail(IRIS_E_INVALID, "iris_filter_draw: batch = %d is negative", batch);
+    if (n_mel <= 0 || min_bw <= 0) return fail(IRIS_E_INVALID, "iris_filter_draw: n_mel = %d, min_bw = %d must be positive", n_mel, min_bw);
+    if (kind != IRIS_FILTER_STEP && kind != IRIS_FILTER_LINEAR) return fail(IRIS_E_INVALID, "iris_filter_draw: unknown kind %d", kind);
+    if (n_band_lo < 1 || n_band_lo > n_band_hi)
+        return fail(IRIS_E_INVALID, "iris_filter_draw: band counts must satisfy 1 <= n_band_lo = %d <= n_band_hi = %d", n_band_lo, n_band_hi);
+    if (n_band_hi > kFilterMaxBands) return fail(IRIS_E_INVALID, "iris_filter_draw: n_band_hi = %d > %d", n_band_hi, kFilterMaxBands);
+    if ((long long)n_mel < (long long)n_band_hi * min_bw)
+        return fail(IRIS_E_INVALID, "iris_filter_draw: n_mel = %d < n_band_hi * min_bw = %d * %d", n_mel, n_band_hi, min_bw);
+    if (!(db_lo <= db_hi) || !std::isfinite(db_lo) || !std::isfinite(db_hi))
+        return fail(IRIS_E_INVALID, "iris_filter_draw: decibel range [%g, %g) is empty or not finite", (double)db_lo, (double)db_hi);
+    if (batch > 0 && (!state_dev || !bounds_out || !db_out || !gain_out)) return fail(IRIS_E_INVALID, "iris_filter_draw: NULL argument");
+    if ((long long)batch * n_mel > 2147483647ll) return fail(IRIS_E_UNSUPPORTED, "iris_filter_draw: batch * n_mel exceeds 2^31 - 1");
+    if (batch == 0) return IRIS_OK;
+    k_filter_draw<<<1, 256, 0, (hipStream_t)stream>>>(batch, n_mel, kind == IRIS_FILTER_LINEAR, n_band_lo, n_band_hi, min_bw, db_lo, db_hi,
+                                                      (uint32_t)seed, (uint32_t)(seed >> 32),
+                                                      reinterpret_cast<unsigned long long*>(state_dev), bounds_out, db_out, gain_out);
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
 }

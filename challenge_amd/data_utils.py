@@ -171,6 +171,42 @@ def check_shoebox(name: str) -> None:
                          "reverberation augmentation, name both")
 
 
+def wants_filtaug(name: str) -> bool:
+    """Whether a run name asks for FilterAugment (a random piecewise gain curve over the mel bands of every training sample,
+    applied inside the mel kernels): the token 'filtaug' in it (the same idiom; 'filtaug' does not contain the reference's
+    'filter' token, nor 'filter' it).  `filtaug_kind` tells the curve's kind.  Honoured by `sj_train.make_device_dataset` and
+    `make_wave_dataset` on training sets; `make_dataset` refuses it.  It touches neither the mixers nor the corpus, so it
+    goes with every other token ('pcen', 'pcen_learn', 'nominmax', 'stretch', 'speed', 'reverb', 'shoebox', 'filter')."""
+    return 'filtaug' in name
+
+
+def filtaug_kind(name: str) -> str:
+    """The kind of a FilterAugment run's gain curve: 'linear' for the token 'filtaug_linear', else 'step'."""
+    return 'linear' if 'filtaug_linear' in name else 'step'
+
+
+class FilterAugmentDraw:
+    """The FilterAugment gains of a batch, float32 [B, n_mel] on `device` (the paper's defaults: transforms.FILTAUG_*).
+    device_draw=True: one `iris_filter_draw` launch (Philox keyed by `seed`, call counter in device memory: no host draw, no
+    upload, replayable from a hipGraph) into a long-lived tensor that the next draw of the same shape overwrites; otherwise
+    `transforms.filter_augment_draw` on the host from `rng`, evaluated by `filter_augment_gains` and uploaded."""
+
+    def __init__(self, device, kind: str = "step", seed: int = 0, device_draw: bool = False,
+                 rng: Optional[np.random.Generator] = None):
+        if kind not in _tr.FILTAUG_KINDS:
+            raise ValueError(f"FilterAugmentDraw: kind must be one of {_tr.FILTAUG_KINDS}, got {kind!r}")
+        self.device, self.kind, self.device_draw = torch.device(device), kind, bool(device_draw)
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.rng = np.random.default_rng(seed) if rng is None else rng
+        self.state = torch.zeros(1, dtype=torch.int64, device=self.device) if device_draw else None
+
+    def __call__(self, batch: int, n_mel: int) -> torch.Tensor:
+        if self.device_draw:
+            return _fe.filter_draw(batch, n_mel, self.kind, seed=self.seed, state=self.state)[2]
+        bounds, db, n_band = _tr.filter_augment_draw(self.rng, batch, n_mel, self.kind)
+        return torch.from_numpy(_tr.filter_augment_gain_batch(bounds, db, n_band, n_mel, self.kind)).to(self.device)
+
+
 def augment(specs: torch.Tensor, labels, time_axis: int = -2, freq_axis: int = -3):
     """6 time masks (< 24 frames) then 1 frequency mask (< 16 linear bins) on the complex
     spectrogram (data_utils.py:58-61)."""

@@ -49,6 +49,16 @@ def _bands_arg(bands, batch: int, device: torch.device, name: str):
     return t, C.c_void_p(t.data_ptr()), int(t.shape[1])
 
 
+def _gain_arg(mel_gain, batch: int, n_mel: int, device: torch.device):
+    """mel_gain: None or float32 [B, n_mel] (FilterAugment: one gain per sample and mel band, shared by the channels)."""
+    if mel_gain is None:
+        return None
+    g = torch.as_tensor(mel_gain)
+    if tuple(g.shape) != (batch, n_mel):
+        raise ValueError(f"mel_gain must have shape [batch={batch}, n_mel={n_mel}], got {tuple(g.shape)}")
+    return g.to(device=device, dtype=torch.float32).contiguous()
+
+
 def mel_weight_matrix(num_mel_bins: int = 20, num_spectrogram_bins: int = 129,
                       sample_rate: float = 8000, lower_edge_hertz: float = 125.0,
                       upper_edge_hertz: float = 3800.0) -> np.ndarray:
@@ -261,8 +271,9 @@ class FrontendPlan:
         spec.record_stream(torch.cuda.current_stream(self.device))
         return wav
 
-    def magmel(self, spec: torch.Tensor, is_magphase: bool = False, t_bands=None, f_bands=None) -> torch.Tensor:
-        """spec [B,F,T,2C] -> mel [B,M,T,C] (complex_to_magphase + magphase_to_mel)."""
+    def magmel(self, spec: torch.Tensor, is_magphase: bool = False, t_bands=None, f_bands=None, mel_gain=None) -> torch.Tensor:
+        """spec [B,F,T,2C] -> mel [B,M,T,C] (complex_to_magphase + magphase_to_mel).  mel_gain ([B, M] float32, optional:
+        FilterAugment): every mel value times its sample's band gain inside the kernel (`iris_magmel_gain`)."""
         spec = _require_device_f32(spec, "spec")
         if spec.dim() != 4 or spec.shape[1] != self.n_bins or spec.shape[3] != 2 * self.channels:
             raise ValueError(f"spec must be [B, {self.n_bins}, T, {2 * self.channels}], got {tuple(spec.shape)}")
@@ -270,18 +281,26 @@ class FrontendPlan:
         mel = torch.empty((b, self.n_mel, t, self.channels), dtype=torch.float32, device=spec.device)
         tb, tbp, ntb = _bands_arg(t_bands, b, spec.device, "t_bands")
         fb, fbp, nfb = _bands_arg(f_bands, b, spec.device, "f_bands")
+        gain = _gain_arg(mel_gain, b, self.n_mel, spec.device)
         if b == 0 or t == 0:
             return mel
         with self._lock, torch.cuda.device(self.device):
-            rc = N.lib().iris_magmel(self._handle, spec.data_ptr(), mel.data_ptr(), b, t,
-                                     1 if is_magphase else 0, tbp, ntb, fbp, nfb, _stream_ptr(self.device))
-        N.check(rc, "iris_magmel")
+            if gain is None:
+                rc = N.lib().iris_magmel(self._handle, spec.data_ptr(), mel.data_ptr(), b, t,
+                                         1 if is_magphase else 0, tbp, ntb, fbp, nfb, _stream_ptr(self.device))
+            else:
+                rc = N.lib().iris_magmel_gain(self._handle, spec.data_ptr(), mel.data_ptr(), b, t, 1 if is_magphase else 0,
+                                              tbp, ntb, fbp, nfb, gain.data_ptr(), _stream_ptr(self.device))
+                gain.record_stream(torch.cuda.current_stream(self.device))
+        N.check(rc, "iris_magmel" if gain is None else "iris_magmel_gain")
         return mel
 
     def wav_to_logmel(self, wav: torch.Tensor, minmax: bool = True, log: bool = True,
                       normalize: bool = False, t_bands=None, f_bands=None,
-                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """The fused hot path: wav [B,C,L] -> log-mel [B,M,T,C]."""
+                      out: Optional[torch.Tensor] = None, mel_gain=None) -> torch.Tensor:
+        """The fused hot path: wav [B,C,L] -> log-mel [B,M,T,C].  mel_gain ([B, M] float32, optional: FilterAugment): every
+        mel magnitude times its sample's band gain inside the kernel, before min-max / log (`iris_wav_to_logmel_gain`);
+        None takes the ungained entry, untouched."""
         wav, b, length = self._check_wav(wav)
         t = self.num_frames(length)
         if out is None:
@@ -294,9 +313,15 @@ class FrontendPlan:
         fb, fbp, nfb = _bands_arg(f_bands, b, self.device, "f_bands")
         flags = (N.IRIS_F_MINMAX if minmax else 0) | (N.IRIS_F_LOG if log else 0) | \
             (N.IRIS_F_NORMALIZE if normalize else 0)
+        gain = _gain_arg(mel_gain, b, self.n_mel, self.device)
         with self._lock, torch.cuda.device(self.device):
-            rc = N.lib().iris_wav_to_logmel(self._handle, wav.data_ptr(), out.data_ptr(), b, length, flags,
-                                            tbp, ntb, fbp, nfb, _stream_ptr(self.device))
+            if gain is None:
+                rc = N.lib().iris_wav_to_logmel(self._handle, wav.data_ptr(), out.data_ptr(), b, length, flags,
+                                                tbp, ntb, fbp, nfb, _stream_ptr(self.device))
+            else:
+                rc = N.lib().iris_wav_to_logmel_gain(self._handle, wav.data_ptr(), out.data_ptr(), b, length, flags,
+                                                     tbp, ntb, fbp, nfb, gain.data_ptr(), _stream_ptr(self.device))
+                gain.record_stream(torch.cuda.current_stream(self.device))
         if rc == N.IRIS_E_EPILOGUE_TIMEOUT:
             self.epilogue = "two_kernels"  # the library has switched the plan for good
         N.check(rc, "iris_wav_to_logmel")
@@ -304,12 +329,13 @@ class FrontendPlan:
 
     # ---- prepared launches ------------------------------------------------------
     def prepare(self, wav: torch.Tensor, out: Optional[torch.Tensor] = None, minmax: bool = True, log: bool = True,
-                normalize: bool = False, t_bands=None, f_bands=None) -> "PreparedCall":
+                normalize: bool = False, t_bands=None, f_bands=None, mel_gain=None) -> "PreparedCall":
         """Validate once, launch many times: returns an object whose `.launch()` is nothing but the C-ABI call of
         `wav_to_logmel(wav, out=out, ...)` with pre-converted arguments (about 3 us of host time instead of ~12 us for the
         checked path) - for steady-state loops over long-lived buffers (serving, benchmarks).  Tensors are bound BY
-        ADDRESS (refill them in place); launches go to the stream that is current NOW; not thread-safe."""
-        return PreparedCall(self, wav, out, minmax, log, normalize, t_bands, f_bands)
+        ADDRESS (refill them in place); launches go to the stream that is current NOW; not thread-safe.  mel_gain: a float32
+        [B, M] DEVICE tensor bound by address like the others (FilterAugment: refill it, e.g. by `filter_draw(out=...)`)."""
+        return PreparedCall(self, wav, out, minmax, log, normalize, t_bands, f_bands, mel_gain)
 
     # ---- hipGraph ------------------------------------------------------------
     def capture(self, wav: torch.Tensor, out: Optional[torch.Tensor] = None, **kwargs) -> "CapturedStep":
@@ -348,7 +374,7 @@ class PreparedCall:
     """One fused frontend call with its arguments converted once (see FrontendPlan.prepare)."""
     __slots__ = ("out", "_fn", "_args", "_keep")
 
-    def __init__(self, plan: FrontendPlan, wav, out, minmax, log, normalize, t_bands, f_bands):
+    def __init__(self, plan: FrontendPlan, wav, out, minmax, log, normalize, t_bands, f_bands, mel_gain=None):
         wav, b, length = plan._check_wav(wav)
         t = plan.num_frames(length)
         if out is None:
@@ -360,10 +386,18 @@ class PreparedCall:
         tb, tbp, ntb = _bands_arg(t_bands, b, plan.device, "t_bands")
         fb, fbp, nfb = _bands_arg(f_bands, b, plan.device, "f_bands")
         flags = (N.IRIS_F_MINMAX if minmax else 0) | (N.IRIS_F_LOG if log else 0) | (N.IRIS_F_NORMALIZE if normalize else 0)
-        self.out, self._keep = out, (plan, wav, tb, fb)     # keep everything the raw pointers refer to alive
-        self._fn = N.lib().iris_wav_to_logmel
-        self._args = (plan._handle, C.c_void_p(wav.data_ptr()), C.c_void_p(out.data_ptr()), b, length, flags, tbp, ntb, fbp, nfb,
-                      _stream_ptr(plan.device))
+        if mel_gain is not None:
+            if not (isinstance(mel_gain, torch.Tensor) and mel_gain.is_cuda and mel_gain.dtype == torch.float32 and
+                    mel_gain.is_contiguous() and tuple(mel_gain.shape) == (b, plan.n_mel)):
+                raise ValueError(f"mel_gain must be a contiguous float32 device tensor [batch={b}, n_mel={plan.n_mel}] (bound by address)")
+        self.out, self._keep = out, (plan, wav, tb, fb, mel_gain)     # keep everything the raw pointers refer to alive
+        self._args = (plan._handle, C.c_void_p(wav.data_ptr()), C.c_void_p(out.data_ptr()), b, length, flags, tbp, ntb, fbp, nfb)
+        if mel_gain is None:
+            self._fn = N.lib().iris_wav_to_logmel
+        else:
+            self._fn = N.lib().iris_wav_to_logmel_gain
+            self._args += (C.c_void_p(mel_gain.data_ptr()),)
+        self._args += (_stream_ptr(plan.device),)
 
     def launch(self) -> torch.Tensor:
         rc = self._fn(*self._args)
@@ -382,6 +416,8 @@ class CapturedStep:
         for k in ("t_bands", "f_bands"):
             if kwargs.get(k) is not None:
                 kwargs[k] = torch.as_tensor(kwargs[k]).to(device=dev, dtype=torch.int32).contiguous()
+        if kwargs.get("mel_gain") is not None:   # likewise read at replay time (FilterAugment: refill it in place)
+            kwargs["mel_gain"] = torch.as_tensor(kwargs["mel_gain"]).to(device=dev, dtype=torch.float32).contiguous()
         self.kwargs = kwargs
         side = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -400,6 +436,51 @@ class CapturedStep:
 # ---------------------------------------------------------------------------
 # plan-free ops (run on the tensor's device / current stream)
 # ---------------------------------------------------------------------------
+def filter_draw(batch: int, n_mel: int, kind: str = "step", n_band=(3, 6), min_bw: int = 6, db=(-6.0, 6.0), seed: int = 0,
+                state: Optional[torch.Tensor] = None, device=None, out=None):
+    """The FilterAugment draws of a batch ON THE DEVICE, one `iris_filter_draw` launch: (bounds int32 [B, n_band_hi + 1],
+    db float32 [B, n_band_hi + 1], gain float32 [B, n_mel]); `gain` is the `mel_gain` of `FrontendPlan.wav_to_logmel` /
+    `.magmel`.  Per sample a band count ~ U{n_band[0] .. n_band[1]}, boundaries uniform over every placement with bands of at
+    least `min_bw` mel rows, dB ~ U[db[0], db[1]) per band ('step') or per boundary ('linear': interpolated across the band),
+    gain = 10^(dB / 20) (`transforms.filter_augment_gains` is the definition).  Philox keyed by `seed`; `state`: an int64 [1]
+    device tensor of this draw's own, zero-initialised once, advanced by every call on the device (None: a fresh zero state,
+    i.e. the first draw of `seed`).  `out`: the (bounds, db, gain) tensors of an earlier call, overwritten in place (for
+    prepared / captured calls that bound `gain` by address).  Capturable."""
+    if kind not in ("step", "linear"):
+        raise ValueError(f"filter_draw: kind must be 'step' or 'linear', got {kind!r}")
+    if state is not None:
+        device = state.device
+    elif device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("filter_draw draws on a ROCm device (transforms.filter_augment_draw is the host draw)")
+    batch, n_mel, hi = int(batch), int(n_mel), int(n_band[1])
+    if state is None:
+        state = torch.zeros(1, dtype=torch.int64, device=device)
+    elif state.dtype != torch.int64 or state.numel() != 1 or not state.is_cuda:
+        raise ValueError("filter_draw: state must be an int64 device tensor of one element")
+    if batch < 0 or n_mel <= 0 or hi < 1:
+        raise ValueError(f"filter_draw: bad sizes (batch {batch}, n_mel {n_mel}, n_band {tuple(n_band)})")
+    if out is None:
+        bounds = torch.empty((batch, hi + 1), dtype=torch.int32, device=device)
+        dbs = torch.empty((batch, hi + 1), dtype=torch.float32, device=device)
+        gain = torch.empty((batch, n_mel), dtype=torch.float32, device=device)
+    else:
+        bounds, dbs, gain = out
+        if (tuple(bounds.shape), tuple(dbs.shape), tuple(gain.shape)) != ((batch, hi + 1), (batch, hi + 1), (batch, n_mel)) or \
+                bounds.dtype != torch.int32 or dbs.dtype != torch.float32 or gain.dtype != torch.float32 or \
+                not (bounds.is_contiguous() and dbs.is_contiguous() and gain.is_contiguous()) or gain.device != device:
+            raise ValueError("filter_draw: out must be the (bounds, db, gain) of a call with the same batch, n_mel and n_band")
+    with torch.cuda.device(device):
+        rc = N.lib().iris_filter_draw(batch, n_mel, N.IRIS_FILTER_LINEAR if kind == "linear" else N.IRIS_FILTER_STEP,
+                                      int(n_band[0]), hi, int(min_bw), float(db[0]), float(db[1]),
+                                      int(seed) & 0xFFFFFFFFFFFFFFFF, state.data_ptr(), bounds.data_ptr(), dbs.data_ptr(),
+                                      gain.data_ptr(), _stream_ptr(device))
+    N.check(rc, "iris_filter_draw")
+    return bounds, dbs, gain
+
+
 def bias_relu_(x: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
     """In place max(x + bias[c], 0) on a channels-last activation: x is [B, C, H, W] with channels_last strides (or any
     dense tensor whose innermost axis is the channel axis).  One HIP launch (iris_bias_relu)."""

@@ -120,10 +120,13 @@ def complex_to_mel(n_mels: int, num_spectrogram_bins: int = 257, sample_rate: fl
     n_fft = 2 * (num_spectrogram_bins - 1)
     plans = {}
 
-    def _complex_to_mel(x, y=None, t_bands=None, f_bands=None):
+    def _complex_to_mel(x, y=None, t_bands=None, f_bands=None, mel_gain=None):
         """t_bands / f_bands ([B, n, 2] (offset, size), optional): SpecAugment / stft_filter bands
-        zeroed in the complex spectrum first (== `augment` / `stft_filter` mapped before this stage)."""
+        zeroed in the complex spectrum first (== `augment` / `stft_filter` mapped before this stage).
+        mel_gain ([B, n_mels], optional): FilterAugment gains, multiplied into the mel values by the kernel."""
         if not x.is_cuda or n_fft not in (256, 512, 1024, 2048):
+            if mel_gain is not None:
+                raise ValueError("complex_to_mel: mel_gain (FilterAugment) needs a ROCm tensor and n_fft 256 / 512 / 1024 / 2048")
             if t_bands is not None:
                 x = _tr.mask_apply(x, -2, t_bands)
             if f_bands is not None:
@@ -137,7 +140,7 @@ def complex_to_mel(n_mels: int, num_spectrogram_bins: int = 257, sample_rate: fl
                 plan = _fe.FrontendPlan(n_fft, None, n_mels, sample_rate, chan, max(int(x.shape[0]), 1), n_fft,
                                         x.device, mel_matrix=to_mel.mel_matrix)
                 plans[key] = plan
-            out = plan.magmel(x.float(), is_magphase=False, t_bands=t_bands, f_bands=f_bands)
+            out = plan.magmel(x.float(), is_magphase=False, t_bands=t_bands, f_bands=f_bands, mel_gain=mel_gain)
         return out if y is None else (out, y)
     return _complex_to_mel
 
@@ -219,6 +222,9 @@ def make_dataset(config, training=True, n_classes=3, sources=None):
     if _du.wants_reverb(config.name):
         raise ValueError(f"run name {config.name!r} asks for 'reverb': reverberation runs on the resident waveform corpus "
                          "(make_wave_dataset); the per-sample host pipeline does not convolve")
+    if _du.wants_filtaug(config.name):
+        raise ValueError(f"run name {config.name!r} asks for 'filtaug': FilterAugment runs inside the batched mel kernels "
+                         "(make_device_dataset, make_wave_dataset); the per-sample host pipeline has no gain stage")
     backgrounds, voices, labels, noises = _load_sources(config, training, n_classes, sources)
 
     pipeline = make_pipeline(backgrounds, voices, labels, noises, n_frame=config.n_frame,
@@ -281,7 +287,11 @@ def make_device_dataset(config, training=True, n_classes=3, sources=None, device
     host only enqueues launches.
     A 'stretch' token in config.name (training sets only): the voice corpus is time-stretched by rates ~ U[0.8, 1.2) at
     creation and again every config.steps_per_epoch batches (`DeviceMixer.enable_stretch` / `restretch`, one
-    `iris_phase_vocoder` launch over the corpus); a name without the token takes no new code path."""
+    `iris_phase_vocoder` launch over the corpus); a name without the token takes no new code path.
+    A 'filtaug' token (training sets only; 'filtaug_linear': the linear kind): FilterAugment - every sample's mel values are
+    multiplied by a fresh random piecewise gain curve over the mel bands inside the mel kernel (`iris_magmel_gain`; the draw
+    is `iris_filter_draw` under device_draw, else `transforms.filter_augment_draw` on the host); a name without the token
+    takes no new code path."""
     from .mixer import DeviceMixer
     if _du.wants_speed(config.name):
         raise ValueError(f"run name {config.name!r} asks for 'speed': a spectrum corpus cannot be resampled in time "
@@ -302,6 +312,10 @@ def make_device_dataset(config, training=True, n_classes=3, sources=None, device
     if device_draw:
         mixer.enable_device_draw(0 if seed is None else seed)
         band_draw = _du.DeviceAugmentDraw(mixer.device, (0 if seed is None else seed) + 1, filter_bins) if training else None
+    gain_draw = None
+    if training and _du.wants_filtaug(config.name):   # (the validation set never is)
+        gain_draw = _du.FilterAugmentDraw(mixer.device, _du.filtaug_kind(config.name), (0 if seed is None else seed) + 2, device_draw,
+                                          None if seed is not None else np.random.default_rng())
     stretch = training and _du.wants_stretch(config.name)
     if stretch:   # the voice corpus is re-stretched now and once per epoch (the validation set never is)
         mixer.enable_stretch()
@@ -323,7 +337,10 @@ def make_device_dataset(config, training=True, n_classes=3, sources=None, device
             tb, fb = _draw_bands(band_draw, training, rng, filter_bins, int(x.shape[0]), config.n_frame, mixer.n_bins)
             if chan_map is not None:
                 x, y = chan_map(x, y)
-            yield to_mel(x, y, t_bands=tb, f_bands=fb)
+            if gain_draw is None:
+                yield to_mel(x, y, t_bands=tb, f_bands=fb)
+            else:
+                yield to_mel(x, y, t_bands=tb, f_bands=fb, mel_gain=gain_draw(int(x.shape[0]), config.n_mels))
 
     dataset = _label_tail(Dataset.from_generator(gen), config)
     dataset.mixer = mixer   # (for inspection: the resident corpus, its draws and - 'stretch' runs - the current voice lengths)
@@ -423,6 +440,10 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
     A 'shoebox' token beside 'reverb': the responses are image-source simulations of random shoebox rooms that both channels
     share (`enable_reverb(model="shoebox")`: one `iris_ism_rir` and one `iris_fir_batch_pitch` launch per epoch, no tap
     upload), so the inter-channel delay and level of a voice are those of one room; 'shoebox' without 'reverb' is a ValueError.
+    A 'filtaug' token (training sets only; 'filtaug_linear': the linear kind): FilterAugment - every sample's mel magnitudes
+    are multiplied by a fresh random piecewise gain curve over the mel bands inside the fused kernel, before min-max / log
+    or PCEN (`iris_wav_to_logmel_gain`: no extra launch, no extra pass; the draw is `iris_filter_draw` under device_draw,
+    else `transforms.filter_augment_draw` on the host).  It goes with every token above; a name without it takes no new code path.
     spec_sources: the same tuple as SPECTRA ([F, T_i, 2C], integer labels), e.g. the pickled corpora - converted once here by
     `waves_from_specs` at this n_fft / hop and used as `sources` (giving both is a ValueError)."""
     from .mixer import WaveMixer
@@ -460,6 +481,10 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
     if device_draw:
         mixer.enable_device_draw(0 if seed is None else seed)
         band_draw = _du.DeviceAugmentDraw(mixer.device, (0 if seed is None else seed) + 1, filter_bins) if training else None
+    gain_draw = None
+    if training and _du.wants_filtaug(config.name):   # (the validation set never is)
+        gain_draw = _du.FilterAugmentDraw(mixer.device, _du.filtaug_kind(config.name), (0 if seed is None else seed) + 2, device_draw,
+                                          None if seed is not None else np.random.default_rng())
     speed = training and _du.wants_speed(config.name)
     if speed:   # the voice corpus is perturbed anew now and once per epoch (the validation set never is)
         mixer.enable_speed()
@@ -483,13 +508,14 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
             if config.n_chan == 1 and wav.shape[1] == 2:
                 wav = wav[:, :1] + wav[:, 1:]            # true down-mix (NOT the reference's broadcast mono_chan: see docstring)
             tb, fb = _draw_bands(band_draw, training, rng, filter_bins, int(wav.shape[0]), config.n_frame, plan.n_bins)
+            kw = {} if gain_draw is None else {"mel_gain": gain_draw(int(wav.shape[0]), config.n_mels)}   # FilterAugment
             if do_pcen:   # the raw mel out of the fused kernel, then PCEN in place
-                mel = plan.wav_to_logmel(wav.contiguous(), t_bands=tb, f_bands=fb, minmax=False, log=False)
+                mel = plan.wav_to_logmel(wav.contiguous(), t_bands=tb, f_bands=fb, minmax=False, log=False, **kw)
                 yield _fe.pcen(mel, out=mel), y
             elif raw_mel:
-                yield plan.wav_to_logmel(wav.contiguous(), t_bands=tb, f_bands=fb, minmax=False, log=False), y
+                yield plan.wav_to_logmel(wav.contiguous(), t_bands=tb, f_bands=fb, minmax=False, log=False, **kw), y
             else:
-                yield plan.wav_to_logmel(wav.contiguous(), t_bands=tb, f_bands=fb, minmax=do_minmax, log=True), y
+                yield plan.wav_to_logmel(wav.contiguous(), t_bands=tb, f_bands=fb, minmax=do_minmax, log=True, **kw), y
 
     pipeline = Dataset.from_generator(gen)
     if config.v in label_downsample_model:

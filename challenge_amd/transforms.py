@@ -103,6 +103,86 @@ def random_shift(specs: torch.Tensor, axis: int = 0, width: int = 16) -> torch.T
 
 
 # ---------------------------------------------------------------------------
+# FilterAugment (Nam, Kim, Park, ICASSP 2022): a random piecewise gain curve over the mel bands of every sample
+# ---------------------------------------------------------------------------
+FILTAUG_N_BAND = (3, 6)    # band count ~ U{3 .. 6}
+FILTAUG_MIN_BW = 6         # mel rows per band, at least
+FILTAUG_DB = (-6.0, 6.0)   # dB ~ U[-6, 6)
+FILTAUG_KINDS = ("step", "linear")
+
+
+def filter_augment_gains(bounds, db, n_mel: int, kind: str = "step") -> np.ndarray:
+    """The gain curve of one sample, float32 [n_mel], evaluated in float64 - THE definition that the device draw
+    (`iris_filter_draw`) and the kernels' `mel_gain` are held to.  `bounds`: n_band + 1 mel-row boundaries 0 = b_0 < b_1 < ...
+    < b_n = n_mel.  kind 'step': band j (rows b_j .. b_{j+1} - 1) gets db[j] (n_band values); 'linear': db holds n_band + 1
+    values at the boundaries and row m of band j gets db[j] + (db[j+1] - db[j]) (m - b_j) / (b_{j+1} - b_j).  The gain is
+    10^(dB / 20): the features are mel MAGNITUDES, not powers."""
+    if kind not in FILTAUG_KINDS:
+        raise ValueError(f"filter_augment_gains: kind must be one of {FILTAUG_KINDS}, got {kind!r}")
+    bounds = np.asarray(bounds, np.int64).reshape(-1)
+    db = np.asarray(db, np.float64).reshape(-1)
+    n_band = bounds.size - 1
+    if n_band < 1 or bounds[0] != 0 or bounds[-1] != int(n_mel) or np.any(np.diff(bounds) <= 0):
+        raise ValueError(f"filter_augment_gains: bounds must rise strictly from 0 to n_mel = {n_mel}, got {bounds.tolist()}")
+    want = n_band if kind == "step" else n_band + 1
+    if db.size != want:
+        raise ValueError(f"filter_augment_gains: kind {kind!r} with {n_band} bands takes {want} dB values, got {db.size}")
+    m = np.arange(int(n_mel))
+    j = np.searchsorted(bounds, m, side="right") - 1          # the band of row m
+    if kind == "step":
+        curve = db[j]
+    else:
+        curve = db[j] + (db[j + 1] - db[j]) * (m - bounds[j]) / (bounds[j + 1] - bounds[j])
+    return np.power(10.0, curve / 20.0).astype(np.float32)
+
+
+def filter_augment_bounds(cuts, n_band: int, n_mel: int, min_bw: int = FILTAUG_MIN_BW) -> np.ndarray:
+    """Sorted distinct cut points among the n_mel - n_band min_bw + (n_band - 1) free slots -> the n_band + 1 boundaries:
+    b_j = j min_bw + cuts[j - 1] - (j - 1) (the minimum widths re-inserted), b_0 = 0, b_n = n_mel."""
+    cuts = np.asarray(cuts, np.int64).reshape(-1)
+    j = np.arange(1, n_band)
+    return np.concatenate([[0], j * min_bw + cuts - (j - 1), [n_mel]]).astype(np.int32)
+
+
+def filter_augment_draw(rng: Optional[np.random.Generator], batch: int, n_mel: int, kind: str = "step",
+                        n_band=FILTAUG_N_BAND, min_bw: int = FILTAUG_MIN_BW, db=FILTAUG_DB):
+    """The random half of FilterAugment for a batch, on the host (the counterpart of `mask_draw_batch`; `iris_filter_draw`
+    makes the same draws on the device from its own generator): returns (bounds int32 [B, n_band_hi + 1], db float32
+    [B, n_band_hi + 1], n_band int32 [B]).  Per sample: n_band ~ U{n_band[0] .. n_band[1]}; the boundaries uniform over every
+    placement whose bands are at least `min_bw` rows wide (n_band - 1 distinct cut points among the n_mel - n_band min_bw +
+    (n_band - 1) free slots, sorted, minimum widths re-inserted); dB ~ U[db[0], db[1]), n_band values ('step') or n_band + 1
+    ('linear').  Unused tail entries: bounds = n_mel, db = 0.  `filter_augment_gains(bounds[b, :n + 1], db[b, :n (+ 1)], ...)`
+    is sample b's curve; `filter_augment_gain_batch` evaluates them all."""
+    rng = _rng if rng is None else rng
+    if kind not in FILTAUG_KINDS:
+        raise ValueError(f"filter_augment_draw: kind must be one of {FILTAUG_KINDS}, got {kind!r}")
+    lo, hi = int(n_band[0]), int(n_band[1])
+    if batch < 0 or lo < 1 or lo > hi or min_bw <= 0 or not db[0] <= db[1]:
+        raise ValueError(f"filter_augment_draw: bad arguments (batch {batch}, bands {lo}..{hi}, min_bw {min_bw}, dB {db})")
+    if n_mel < hi * min_bw:
+        raise ValueError(f"filter_augment_draw: n_mel = {n_mel} < n_band_hi * min_bw = {hi} * {min_bw}")
+    bounds = np.full((batch, hi + 1), n_mel, np.int32)
+    dbs = np.zeros((batch, hi + 1), np.float32)
+    counts = rng.integers(lo, hi + 1, size=batch).astype(np.int32)
+    for b in range(batch):
+        n = int(counts[b])
+        slots = n_mel - n * min_bw + (n - 1)
+        cuts = np.sort(rng.choice(slots, size=n - 1, replace=False))
+        bounds[b, :n + 1] = filter_augment_bounds(cuts, n, n_mel, min_bw)
+        n_db = n if kind == "step" else n + 1
+        dbs[b, :n_db] = (db[0] + (db[1] - db[0]) * rng.random(n_db)).astype(np.float32)
+    return bounds, dbs, counts
+
+
+def filter_augment_gain_batch(bounds, db, n_band, n_mel: int, kind: str = "step") -> np.ndarray:
+    """`filter_augment_gains` for every sample of a `filter_augment_draw`: float32 [B, n_mel]."""
+    out = np.empty((len(n_band), int(n_mel)), np.float32)
+    for b, n in enumerate(np.asarray(n_band).tolist()):
+        out[b] = filter_augment_gains(bounds[b, :n + 1], db[b, :n if kind == "step" else n + 1], n_mel, kind)
+    return out
+
+
+# ---------------------------------------------------------------------------
 # MAGNITUDE-PHASE SPECTROGRAM
 # ---------------------------------------------------------------------------
 def magphase_to_mel(num_mel_bins: int = 80, num_spectrogram_bins: int = 257, sample_rate: float = 16000,

@@ -293,6 +293,23 @@ int iris_wav_to_logmel(iris_plan* plan, const float* wav, float* out, int batch,
                        const int32_t* f_bands, int n_f_bands, void* stream);
 
 /*
+ * FilterAugment (Nam, Kim, Park, ICASSP 2022) inside the hot path: iris_wav_to_logmel / iris_magmel with every finished mel
+ * value multiplied by a per-sample, per-band gain, mel'[b, m, t, c] = fl(mel_gain[b, m] * mel[b, m, t, c]) - ONE separately
+ * rounded fp32 multiply, applied BEFORE the min / max reduction and the log (with IRIS_F_MINMAX and IRIS_F_LOG off the result
+ * is bitwise mel_gain * the ungained result).  mel_gain: DEVICE fp32 [batch, n_mel], read at launch time (a captured call
+ * re-reads it at every replay); all channels of a sample share its row.  Everything else - arguments, forms, epilogues,
+ * capture - is as for the ungained entry, which these siblings leave untouched: the gain is a compile-time variant of the
+ * kernels, not a branch in them.  (A plan set to IRIS_EPILOGUE_IN_PLACE runs a gained call on two kernels.)
+ * IRIS_E_INVALID before any HIP call for a NULL mel_gain.
+ */
+int iris_wav_to_logmel_gain(iris_plan* plan, const float* wav, float* out, int batch, int len,
+                            int flags, const int32_t* t_bands, int n_t_bands,
+                            const int32_t* f_bands, int n_f_bands, const float* mel_gain, void* stream);
+int iris_magmel_gain(iris_plan* plan, const float* spec, float* mel, int batch, int n_frames,
+                     int is_magphase, const int32_t* t_bands, int n_t_bands,
+                     const int32_t* f_bands, int n_f_bands, const float* mel_gain, void* stream);
+
+/*
  * mask apply (transforms.py:12-40, deterministic part): x viewed as
  * [n_outer, axis_len, n_inner]; elements whose axis index falls in any band
  * [offset_i, offset_i + size_i) are set to zero (= multiply by the product of
@@ -766,6 +783,28 @@ int iris_mix_draw(const iris_mix_corpus* backgrounds, const iris_mix_corpus* voi
 int iris_augment_draw(int batch, int n_time, int n_time_masks, int max_time_mask, int n_freq, int n_freq_masks,
                       int max_freq_mask, uint64_t seed, uint64_t* state_dev, int32_t* t_bands_out, int32_t* f_bands_out,
                       void* stream);
+
+/*
+ * The draws of FilterAugment for a batch, on the device, in one launch: per sample a band count n ~ U{n_band_lo .. n_band_hi},
+ * n + 1 band boundaries over the mel rows (uniform over every placement whose bands are at least min_bw rows wide), decibel
+ * values ~ U[db_lo, db_hi) and the resulting gain row for iris_wav_to_logmel_gain / iris_magmel_gain.
+ *   kind IRIS_FILTER_STEP:   band j (rows b_j .. b_{j+1} - 1) gets dB_j (n values)
+ *   kind IRIS_FILTER_LINEAR: n + 1 values at the boundaries, row m of band j gets
+ *                            dB_j + (dB_{j+1} - dB_j) (m - b_j) / (b_{j+1} - b_j)
+ *   gain = 10^(dB / 20) (the features are mel magnitudes), evaluated in double from the stored fp32 dB values.
+ * Generator: Philox4x32-10 keyed by `seed`, counter (call counter, sample * 64 + column, purpose 7) - the exact recipe is the
+ * header comment of csrc/k_draw.h, restated in NumPy by tests/filtaug_ref.py.  state_dev: DEVICE uint64[1] of this
+ * function's own, zero-initialised once by the caller, advanced by every call on the device.  Outputs (DEVICE):
+ * bounds_out int32 [batch, n_band_hi + 1] (unused tail = n_mel), db_out fp32 [batch, n_band_hi + 1] (unused tail = 0),
+ * gain_out fp32 [batch, n_mel].  No atomics, no allocation, no synchronisation: capturable.
+ * Checked before any HIP call (IRIS_E_INVALID): batch < 0, n_mel or min_bw <= 0, unknown kind, n_band_lo < 1 or > n_band_hi,
+ * n_band_hi > 32, n_mel < n_band_hi * min_bw, db_lo > db_hi or not finite, a NULL pointer with batch > 0.  batch == 0 launches
+ * nothing.
+ */
+#define IRIS_FILTER_STEP 0
+#define IRIS_FILTER_LINEAR 1
+int iris_filter_draw(int batch, int n_mel, int kind, int n_band_lo, int n_band_hi, int min_bw, float db_lo, float db_hi,
+                     uint64_t seed, uint64_t* state_dev, int32_t* bounds_out, float* db_out, float* gain_out, void* stream);
 
 /*
  * Time stretching of complex spectrograms: the reference's phase_vocoder (transforms.py:137-195) for a RAGGED BATCH of
