@@ -73,6 +73,7 @@ SIGNATURES = {
     "iris_wav_to_logmel": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     "iris_wav_to_logmel_gain": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
     "iris_magmel_gain": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    "iris_spec_ipd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     "iris_filter_draw": (_i, [_i, _i, _i, _i, _i, _i, _f, _f, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "iris_mask_apply": (_i, [_vp, _sz, _sz, _sz, _i, _vp, _i, _sz, _vp]),
     "iris_agc_clip": (_i, [_vp, _sz, _f, _f, _f, _vp]),

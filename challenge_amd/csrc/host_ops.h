@@ -188,6 +188,43 @@ extern "C" int iris_magmel_gain(iris_plan* p, const float* spec, float* mel, int
                        "iris_magmel_gain");
 }
 
+// iris_spec_ipd: the mel-band inter-channel phase difference of a stereo complex spectrum (k_ipd.h); every check happens
+// before the first HIP call
+extern "C" int iris_spec_ipd(iris_plan* p, const float* spec, float* out, int batch, int n_frames, int is_magphase,
+                             const int32_t* t_bands, int n_tb, const int32_t* f_bands, int n_fb, void* stream) {
+    const char* who = "iris_spec_ipd";
+    if (!p || !spec || !out) return fail(IRIS_E_INVALID, "%s: NULL argument", who);
+    if (batch <= 0 || n_frames <= 0) return fail(IRIS_E_INVALID, "%s: batch=%d n_frames=%d", who, batch, n_frames);
+    if (p->channels != 2) return fail(IRIS_E_UNSUPPORTED, "%s: the plan has %d channel(s); the phase difference is that of a stereo pair", who, p->channels);
+    if (is_magphase) return fail(IRIS_E_UNSUPPORTED, "%s: magnitude / phase input; a complex spectrum (re0, re1, im0, im1) is expected", who);
+    if (batch > 65535) return fail(IRIS_E_UNSUPPORTED, "%s: batch %d > 65535", who, batch);
+    if ((reinterpret_cast<uintptr_t>(spec) & 15) || (reinterpret_cast<uintptr_t>(out) & 7))
+        return fail(IRIS_E_INVALID, "%s: spec must be 16-byte and out 8-byte aligned", who);
+    int rc;
+    if ((rc = check_bands(t_bands, n_tb, who)) || (rc = check_bands(f_bands, n_fb, who))) return rc;
+    DeviceGuard guard(p->device);
+    IpdArgs a;
+    a.spec = spec;
+    a.out = out;
+    a.w = p->d_mel;
+    a.band_lo = p->d_band_lo;
+    a.band_len = p->d_band_len;
+    a.t_bands = n_tb ? t_bands : nullptr;
+    a.n_tb = n_tb;
+    a.f_bands = n_fb ? f_bands : nullptr;
+    a.n_fb = n_fb;
+    a.B = batch;
+    a.F = p->n_bins;
+    a.T = n_frames;
+    a.M = p->n_mel;
+    const dim3 grid((n_frames + 63) / 64, batch);
+    // the bands go over 8 waves when the grid alone cannot fill the chip (as iris_magmel's streaming kernel does)
+    const int threads = (size_t)grid.x * grid.y * 4 < (size_t)p->num_cu * 8 ? 512 : 256;
+    k_spec_ipd<<<grid, threads, 0, (hipStream_t)stream>>>(a);
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+
 extern "C" size_t iris_minmax_log_workspace(int n_rows, size_t row_len) {
     return n_rows > 0 ? 2 * (size_t)n_rows * n_chunks_of(row_len) : 0;
 }

@@ -12,6 +12,7 @@
 //   k_stft.h         STFT in the reference layout
 //   k_istft.h        inverse STFT of a ragged set of spectrograms in that layout (pickled spectrum corpora -> waveforms), one launch
 //   k_magmel.h       spectrum -> mel
+//   k_ipd.h         stereo spectrum -> mel-band inter-channel phase difference (cos, sin), its own streaming kernel (opt-in)
 //   k_elementwise.h  min-max / log, normalize, magnitude-phase, mask, adaptive gradient clipping
 //   k_mix.h          batched sample synthesis (merge_complex_specs)
 //   k_draw.h         the random half of a batch drawn on the device (source table, SpecAugment bands)
@@ -49,6 +50,7 @@
 #include "k_stft.h"
 #include "k_istft.h"
 #include "k_magmel.h"
+#include "k_ipd.h"
 #include "k_elementwise.h"
 #include "host_plan.h"
 #include "k_ism.h"

@@ -185,6 +185,36 @@ def filtaug_kind(name: str) -> str:
     return 'linear' if 'filtaug_linear' in name else 'step'
 
 
+def wants_ipd(name: str) -> bool:
+    """Whether a run name asks for the inter-channel phase features: the token 'ipd' in it (the same idiom).  A FEATURE, not an
+    augmentation: `sj_train.make_device_dataset` and `make_wave_dataset` then yield [B, M, T, 4] on training and validation
+    sets alike - channels 0-1 what they always were, channels 2-3 the (cos, sin) of the phase difference per mel band
+    (`transforms.mel_ipd`, `FrontendPlan.ipd`) of the same mixed spectrum under the same SpecAugment / 'filter' bands, never
+    min-maxed, logged, PCEN'd or gained (the definition is invariant to a band gain) - and `inference.features_for_eval`
+    appends the same two channels; the model's first layer takes `model_in_channels(config)`.  Stereo only (`check_ipd`);
+    `make_dataset` refuses it.  It goes with every other token except 'pcen_learn'."""
+    return 'ipd' in name
+
+
+def check_ipd(config) -> None:
+    """The refusals of an 'ipd' run name: n_chan must be 2 (the feature is the phase difference of a stereo pair), and the
+    trainable PCEN layer of 'pcen_learn' would have to skip the two phase channels, which it does not do yet."""
+    name = getattr(config, 'name', '') or ''
+    if not wants_ipd(name):
+        return
+    if config.n_chan != 2:
+        raise ValueError(f"run name {name!r} asks for 'ipd' at n_chan = {config.n_chan}: the inter-channel phase difference is "
+                         "that of a stereo pair, n_chan must be 2")
+    if feature_compression(name) == 'pcen_learn':
+        raise ValueError(f"run name {name!r} asks for both 'ipd' and 'pcen_learn': the trainable PCEN layer would have to skip "
+                         "the two phase channels, which is not supported yet; name one (the fixed 'pcen' goes with 'ipd')")
+
+
+def model_in_channels(config) -> int:
+    """Channels of the model's input: n_chan, plus the two (cos, sin) phase channels of an 'ipd' run name."""
+    return config.n_chan + 2 if wants_ipd(getattr(config, 'name', '') or '') else config.n_chan
+
+
 class FilterAugmentDraw:
     """The FilterAugment gains of a batch, float32 [B, n_mel] on `device` (the paper's defaults: transforms.FILTAUG_*).
     device_draw=True: one `iris_filter_draw` launch (Philox keyed by `seed`, call counter in device memory: no host draw, no

@@ -608,7 +608,7 @@ def _groups(model, wavs_or_paths: Sequence, config, overlap_hop: int, sample_rat
         del spec
         t_len = int(feats.shape[-2])
         windows = frame(feats, config.n_frame, overlap_hop, pad_end=True, axis=-2)   # [M, W, n_frame, C']
-        windows = windows.permute(1, 0, 2, 3)[..., :config.n_chan].contiguous()
+        windows = windows.permute(1, 0, 2, 3)[..., :D.model_in_channels(config)].contiguous()
         if group and n_group + windows.shape[0] > max_windows:
             yield group
             group, n_group = [], 0

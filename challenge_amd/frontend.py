@@ -295,6 +295,35 @@ class FrontendPlan:
         N.check(rc, "iris_magmel" if gain is None else "iris_magmel_gain")
         return mel
 
+    def ipd(self, spec: torch.Tensor, t_bands=None, f_bands=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Stereo complex spec [B,F,T,4] = (re0, re1, im0, im1) -> [B,M,T,2] = (cos, sin) of the inter-channel phase difference
+        per mel band: the magnitude-weighted band average of X0 conj(X1) over |X0||X1| (`iris_spec_ipd`, its own kernel;
+        `transforms.mel_ipd` states the definition).  t_bands / f_bands as for `magmel`.  `out`: a contiguous float32
+        [B,M,T,2] device tensor to write into (8-byte aligned)."""
+        spec = _require_device_f32(spec, "spec")
+        if self.channels != 2:
+            raise ValueError(f"ipd: the plan has {self.channels} channel(s); the phase difference is that of a stereo pair")
+        if spec.dim() != 4 or spec.shape[1] != self.n_bins or spec.shape[3] != 4:
+            raise ValueError(f"spec must be [B, {self.n_bins}, T, 4], got {tuple(spec.shape)}")
+        if spec.data_ptr() % 16:
+            spec = spec.clone()   # (a view at an odd offset: the kernel loads 16 bytes per bin)
+        b, t = int(spec.shape[0]), int(spec.shape[2])
+        if out is None:
+            out = torch.empty((b, self.n_mel, t, 2), dtype=torch.float32, device=spec.device)
+        else:
+            if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+                    and tuple(out.shape) == (b, self.n_mel, t, 2) and out.device == spec.device and out.data_ptr() % 8 == 0):
+                raise ValueError(f"out must be a contiguous, 8-byte aligned float32 tensor {(b, self.n_mel, t, 2)} on {spec.device}")
+        tb, tbp, ntb = _bands_arg(t_bands, b, spec.device, "t_bands")
+        fb, fbp, nfb = _bands_arg(f_bands, b, spec.device, "f_bands")
+        if b == 0 or t == 0:
+            return out
+        with self._lock, torch.cuda.device(self.device):
+            rc = N.lib().iris_spec_ipd(self._handle, spec.data_ptr(), out.data_ptr(), b, t, 0, tbp, ntb, fbp, nfb,
+                                       _stream_ptr(self.device))
+        N.check(rc, "iris_spec_ipd")
+        return out
+
     def wav_to_logmel(self, wav: torch.Tensor, minmax: bool = True, log: bool = True,
                       normalize: bool = False, t_bands=None, f_bands=None,
                       out: Optional[torch.Tensor] = None, mel_gain=None) -> torch.Tensor:

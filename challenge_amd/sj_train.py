@@ -133,15 +133,27 @@ def complex_to_mel(n_mels: int, num_spectrogram_bins: int = 257, sample_rate: fl
                 x = _tr.mask_apply(x, -3, f_bands)
             out = to_mel(complex_to_magphase(x))
         else:
-            chan = x.shape[-1] // 2
-            key = (x.device.index, chan)
-            plan = plans.get(key)
-            if plan is None or plan.max_batch < x.shape[0]:
-                plan = _fe.FrontendPlan(n_fft, None, n_mels, sample_rate, chan, max(int(x.shape[0]), 1), n_fft,
-                                        x.device, mel_matrix=to_mel.mel_matrix)
-                plans[key] = plan
-            out = plan.magmel(x.float(), is_magphase=False, t_bands=t_bands, f_bands=f_bands, mel_gain=mel_gain)
+            out = _plan(x).magmel(x.float(), is_magphase=False, t_bands=t_bands, f_bands=f_bands, mel_gain=mel_gain)
         return out if y is None else (out, y)
+
+    def _plan(x):
+        chan = x.shape[-1] // 2
+        key = (x.device.index, chan)
+        plan = plans.get(key)
+        if plan is None or plan.max_batch < x.shape[0]:
+            plan = _fe.FrontendPlan(n_fft, None, n_mels, sample_rate, chan, max(int(x.shape[0]), 1), n_fft,
+                                    x.device, mel_matrix=to_mel.mel_matrix)
+            plans[key] = plan
+        return plan
+
+    def _ipd(x, t_bands=None, f_bands=None):
+        """The inter-channel phase channels [B, n_mels, T, 2] of the same stereo spectrum under the same bands and mel
+        matrix (`transforms.mel_ipd`; on a ROCm tensor `FrontendPlan.ipd` of this closure's plan)."""
+        if not x.is_cuda or n_fft not in (256, 512, 1024, 2048):
+            return _tr.mel_ipd(x, to_mel.mel_matrix, t_bands, f_bands)
+        return _plan(x).ipd(x.float(), t_bands=t_bands, f_bands=f_bands)
+
+    _complex_to_mel.ipd = _ipd
     return _complex_to_mel
 
 
@@ -188,11 +200,18 @@ def _load_sources(config, training, n_classes, sources):
     return backgrounds, voices, labels, noises
 
 
-def _label_tail(pipeline, config):
-    """The stages after the mel features (sj_train.py:121-129); a 'pcen' run name maps PCEN instead of min-max + log, a
-    'pcen_learn' one maps no compression at all (the raw mel magnitudes go to the model's trainable PCEN layer)."""
+def _compression_map(config):
+    """The compression stage a run name selects, as a `(mel, labels=None)` map (None: 'pcen_learn', no stage)."""
     compression = _du.feature_compression(config.name)
-    if compression == 'pcen_learn':
+    return {'pcen_learn': None, 'pcen': _du.pcen_on_mel, 'minmax_log': _du.minmax_log_on_mel}.get(compression, log_on_mel)
+
+
+def _label_tail(pipeline, config, compressed=False):
+    """The stages after the mel features (sj_train.py:121-129); a 'pcen' run name maps PCEN instead of min-max + log, a
+    'pcen_learn' one maps no compression at all (the raw mel magnitudes go to the model's trainable PCEN layer).
+    `compressed`: the generator has applied the compression itself (an 'ipd' run: only the mel channels go through it)."""
+    compression = _du.feature_compression(config.name)
+    if compression == 'pcen_learn' or compressed:
         pass
     elif compression == 'pcen':
         pipeline = pipeline.map(_du.pcen_on_mel)
@@ -225,6 +244,9 @@ def make_dataset(config, training=True, n_classes=3, sources=None):
     if _du.wants_filtaug(config.name):
         raise ValueError(f"run name {config.name!r} asks for 'filtaug': FilterAugment runs inside the batched mel kernels "
                          "(make_device_dataset, make_wave_dataset); the per-sample host pipeline has no gain stage")
+    if _du.wants_ipd(config.name):
+        raise ValueError(f"run name {config.name!r} asks for 'ipd': the inter-channel phase features are computed on whole batches "
+                         "(make_device_dataset, make_wave_dataset); the per-sample host pipeline has no such stage")
     backgrounds, voices, labels, noises = _load_sources(config, training, n_classes, sources)
 
     pipeline = make_pipeline(backgrounds, voices, labels, noises, n_frame=config.n_frame,
@@ -291,8 +313,14 @@ def make_device_dataset(config, training=True, n_classes=3, sources=None, device
     A 'filtaug' token (training sets only; 'filtaug_linear': the linear kind): FilterAugment - every sample's mel values are
     multiplied by a fresh random piecewise gain curve over the mel bands inside the mel kernel (`iris_magmel_gain`; the draw
     is `iris_filter_draw` under device_draw, else `transforms.filter_augment_draw` on the host); a name without the token
-    takes no new code path."""
+    takes no new code path.
+    An 'ipd' token (training AND validation sets: a feature, not an augmentation): x is [B, n_mels, n_frame, 4] - channels 0-1
+    exactly what is yielded without the token, channels 2-3 the (cos, sin) of the inter-channel phase difference per mel band
+    (`FrontendPlan.ipd`, one more launch) of the same mixed spectrum under the same bands, not compressed and not gained.
+    n_chan must be 2 and the corpora stereo; 'ipd' with 'pcen_learn' is refused (`data_utils.check_ipd`).  It goes with every
+    other token; a name without it takes no new code path."""
     from .mixer import DeviceMixer
+    _du.check_ipd(config)
     if _du.wants_speed(config.name):
         raise ValueError(f"run name {config.name!r} asks for 'speed': a spectrum corpus cannot be resampled in time "
                          "(use make_wave_dataset; this path has 'stretch')")
@@ -321,6 +349,11 @@ def make_device_dataset(config, training=True, n_classes=3, sources=None, device
         mixer.enable_stretch()
         mixer.restretch()
     to_mel = complex_to_mel(config.n_mels, mixer.n_bins)
+    ipd = _du.wants_ipd(config.name)
+    if ipd and mixer.chan2 != 4:
+        raise ValueError(f"run name {config.name!r} asks for 'ipd' but the corpus has {mixer.chan2 // 2} channel(s): the inter-channel "
+                         "phase difference needs stereo corpora")
+    compress = _compression_map(config) if ipd else None
     chan_map = None
     if config.n_chan == 1:
         chan_map = mono_chan
@@ -337,12 +370,19 @@ def make_device_dataset(config, training=True, n_classes=3, sources=None, device
             tb, fb = _draw_bands(band_draw, training, rng, filter_bins, int(x.shape[0]), config.n_frame, mixer.n_bins)
             if chan_map is not None:
                 x, y = chan_map(x, y)
-            if gain_draw is None:
+            if ipd:
+                tb, fb = (None if v is None else torch.as_tensor(v).to(x.device, torch.int32) for v in (tb, fb))  # one upload for both kernels
+                kw = {} if gain_draw is None else {"mel_gain": gain_draw(int(x.shape[0]), config.n_mels)}
+                mel = to_mel(x, None, t_bands=tb, f_bands=fb, **kw)
+                if compress is not None:
+                    mel = compress(mel)
+                yield torch.cat([mel, to_mel.ipd(x, tb, fb)], dim=-1), y   # the phase channels: neither compressed nor gained
+            elif gain_draw is None:
                 yield to_mel(x, y, t_bands=tb, f_bands=fb)
             else:
                 yield to_mel(x, y, t_bands=tb, f_bands=fb, mel_gain=gain_draw(int(x.shape[0]), config.n_mels))
 
-    dataset = _label_tail(Dataset.from_generator(gen), config)
+    dataset = _label_tail(Dataset.from_generator(gen), config, compressed=ipd)
     dataset.mixer = mixer   # (for inspection: the resident corpus, its draws and - 'stretch' runs - the current voice lengths)
     return dataset
 
@@ -444,6 +484,11 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
     are multiplied by a fresh random piecewise gain curve over the mel bands inside the fused kernel, before min-max / log
     or PCEN (`iris_wav_to_logmel_gain`: no extra launch, no extra pass; the draw is `iris_filter_draw` under device_draw,
     else `transforms.filter_augment_draw` on the host).  It goes with every token above; a name without it takes no new code path.
+    An 'ipd' token (training AND validation sets: a feature, not an augmentation): x is [B, n_mels, n_frame, 4] - channels 0-1
+    exactly what the fused kernel yields without the token, channels 2-3 the (cos, sin) of the inter-channel phase difference
+    per mel band under the same bands, not compressed and not gained.  Deliberately NOT fused into the hot kernel: the batch's
+    spectrum is materialised by `iris_stft` and read by `FrontendPlan.ipd` (two more launches).  n_chan must be 2 and the
+    corpora stereo; 'ipd' with 'pcen_learn' is refused (`data_utils.check_ipd`).  A name without the token takes no new code path.
     spec_sources: the same tuple as SPECTRA ([F, T_i, 2C], integer labels), e.g. the pickled corpora - converted once here by
     `waves_from_specs` at this n_fft / hop and used as `sources` (giving both is a ValueError)."""
     from .mixer import WaveMixer
@@ -454,6 +499,7 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
         raise ValueError(f"run name {config.name!r} asks for 'stretch': a waveform corpus has no spectra to stretch "
                          "(use make_device_dataset)")
     _du.check_shoebox(config.name)
+    _du.check_ipd(config)
     if _du.wants_speed(config.name) and _du.wants_reverb(config.name):
         raise ValueError(f"run name {config.name!r} asks for both 'speed' and 'reverb': the two cannot be combined yet (a "
                          "mixer holds one voice augmentation), name one")
@@ -477,6 +523,10 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
     compression = _du.feature_compression(config.name)
     do_pcen, raw_mel = compression == 'pcen', compression == 'pcen_learn'   # raw_mel: the model's PCEN layer takes the magnitudes
     do_minmax = 'nominmax' not in config.name
+    ipd = _du.wants_ipd(config.name)
+    if ipd and mixer.channels != 2:
+        raise ValueError(f"run name {config.name!r} asks for 'ipd' but the corpus has {mixer.channels} channel(s): the inter-channel "
+                         "phase difference needs stereo corpora")
     band_draw = None
     if device_draw:
         mixer.enable_device_draw(0 if seed is None else seed)
@@ -509,7 +559,16 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
                 wav = wav[:, :1] + wav[:, 1:]            # true down-mix (NOT the reference's broadcast mono_chan: see docstring)
             tb, fb = _draw_bands(band_draw, training, rng, filter_bins, int(wav.shape[0]), config.n_frame, plan.n_bins)
             kw = {} if gain_draw is None else {"mel_gain": gain_draw(int(wav.shape[0]), config.n_mels)}   # FilterAugment
-            if do_pcen:   # the raw mel out of the fused kernel, then PCEN in place
+            if ipd:   # channels 0-1 as below; the batch's spectrum is materialised for the phase channels (never compressed or gained)
+                wav = wav.contiguous()
+                tb, fb = (None if v is None else torch.as_tensor(v).to(wav.device, torch.int32) for v in (tb, fb))  # one upload for both kernels
+                if do_pcen:
+                    mel = plan.wav_to_logmel(wav, t_bands=tb, f_bands=fb, minmax=False, log=False, **kw)
+                    mel = _fe.pcen(mel, out=mel)
+                else:
+                    mel = plan.wav_to_logmel(wav, t_bands=tb, f_bands=fb, minmax=do_minmax, log=True, **kw)
+                yield torch.cat([mel, plan.ipd(plan.stft(wav), t_bands=tb, f_bands=fb)], dim=-1), y
+            elif do_pcen:   # the raw mel out of the fused kernel, then PCEN in place
                 mel = plan.wav_to_logmel(wav.contiguous(), t_bands=tb, f_bands=fb, minmax=False, log=False, **kw)
                 yield _fe.pcen(mel, out=mel), y
             elif raw_mel:

@@ -241,6 +241,62 @@ def magphase_to_mel(num_mel_bins: int = 80, num_spectrogram_bins: int = 257, sam
     return _magphase_to_mel
 
 
+IPD_EPS = 1e-20
+
+
+def mel_ipd(spec: torch.Tensor, mel_matrix, t_bands=None, f_bands=None) -> torch.Tensor:
+    """Inter-channel phase difference per mel band.  spec: a STEREO complex spectrum [B, F, T, 4] (or [F, T, 4]) with last
+    axis (re0, re1, im0, im1); mel_matrix W [F, M]; t_bands / f_bands ([B, n, 2] (offset, size), optional): zeroed in the
+    complex spectrum first, as `complex_to_mel` applies them.  Returns [B, M, T, 2] = (cos, sin):
+        re_k = re0 re1 + im0 im1,  im_k = im0 re1 - re0 im1          (X0 conj X1: phase = phi0 - phi1)
+        a_k  = sqrt((re0^2 + im0^2)(re1^2 + im1^2))                   (= |X0| |X1|)
+        cos_m = sum_k W[k,m] re_k / (sum_k W[k,m] a_k + 1e-20), sin_m likewise with im_k
+    a magnitude-weighted band average, so cos^2 + sin^2 <= 1 (the band's coherence), identical channels give (1, 0), swapping
+    the channels flips sin, silence gives exactly (0, 0) and a common positive scale cancels.  On a ROCm tensor this is one
+    HIP launch (`FrontendPlan.ipd`); on a CPU tensor the torch restatement below, in spec's dtype."""
+    w = np.ascontiguousarray(mel_matrix, np.float32)
+    x = spec if spec.dim() == 4 else spec.unsqueeze(0)
+    if x.dim() != 4 or x.shape[-1] != 4 or w.ndim != 2 or x.shape[1] != w.shape[0]:
+        raise ValueError(f"mel_ipd: spec must be [B, F, T, 4] (a stereo complex spectrum) and mel_matrix [F, M]; got "
+                         f"{tuple(spec.shape)} and {w.shape}")
+    b = int(x.shape[0])
+    if x.is_cuda:
+        key = (x.device.index, w.shape, w.tobytes())
+        plan = _IPD_PLANS.get(key)
+        if plan is None or plan.max_batch < b:
+            n_fft = 2 * (w.shape[0] - 1)
+            if n_fft in (256, 512, 1024, 2048):
+                plan = _fe.FrontendPlan(n_fft, None, w.shape[1], 16000, 2, max(b, 1), n_fft, x.device, mel_matrix=w)
+            else:
+                plan = _fe.FrontendPlan.mel_only(w.shape[1], w.shape[0], 2, max(b, 1), x.device, w)
+            _IPD_PLANS[key] = plan
+        out = plan.ipd(x.float(), t_bands=t_bands, f_bands=f_bands)
+    else:
+        if not torch.is_floating_point(x):
+            x = x.float()
+        for bands, n, shape in ((t_bands, x.shape[2], (b, 1, -1, 1)), (f_bands, x.shape[1], (b, -1, 1, 1))):
+            if bands is None:
+                continue
+            bd = torch.as_tensor(bands).to(torch.int64)
+            if bd.dim() != 3 or bd.shape[0] != b or bd.shape[2] != 2:
+                raise ValueError(f"mel_ipd: bands must have shape [batch={b}, n, 2], got {tuple(bd.shape)}")
+            idx = torch.arange(n)[None, None, :]
+            hit = ((idx >= bd[:, :, :1]) & (idx < bd[:, :, :1] + bd[:, :, 1:])).any(dim=1)   # [B, n]
+            x = torch.where(hit.reshape(shape), torch.zeros((), dtype=x.dtype), x)
+        re0, re1, im0, im1 = x.unbind(-1)
+        re = re0 * re1 + im0 * im1
+        im = im0 * re1 - re0 * im1
+        mag = torch.sqrt((re0 * re0 + im0 * im0) * (re1 * re1 + im1 * im1))
+        wt = torch.from_numpy(w).to(x.dtype)
+        s_re, s_im, s_a = (torch.einsum('bft,fm->bmt', v, wt) for v in (re, im, mag))
+        den = s_a + IPD_EPS
+        out = torch.stack((s_re / den, s_im / den), dim=-1)
+    return out if spec.dim() == 4 else out[0]
+
+
+_IPD_PLANS = {}
+
+
 def log_magphase(specs: torch.Tensor, labels=None, n_chan: int = 2):
     """ln(x + EPSILON) on the first n_chan trailing channels, the rest passes through
     (transforms.py:80-86)."""

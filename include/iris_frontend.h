@@ -225,6 +225,25 @@ int iris_magmel(iris_plan* plan, const float* spec, float* mel, int batch, int n
                 const int32_t* f_bands, int n_f_bands, void* stream);
 
 /*
+ * Inter-channel phase difference per mel band (opt-in feature; its own kernel, k_spec_ipd - the mel kernels are untouched).
+ * spec: a STEREO complex spectrum [batch, n_bins, n_frames, 4] with last axis (re0, re1, im0, im1) - what iris_stft and the
+ * mixers write.  out [batch, n_mel, n_frames, 2] = (cos, sin) of the magnitude-weighted band average of X0 conj(X1):
+ *     re_k = re0 re1 + im0 im1,  im_k = im0 re1 - re0 im1,  a_k = sqrt((re0^2 + im0^2)(re1^2 + im1^2))
+ *     den_m = sum_k W[k,m] a_k,  cos_m = sum_k W[k,m] re_k / (den_m + 1e-20),  sin_m = sum_k W[k,m] im_k / (den_m + 1e-20)
+ * with W the plan's mel matrix (any matrix, a user-supplied one included).  cos^2 + sin^2 <= 1 (the length is the band's
+ * coherence); identical channels give (1, 0); swapping the channels flips sin; a silent or fully masked band or frame gives
+ * exactly (0, 0); a common positive scale of the spectrum cancels.  fp32 error against the float64 form from the same fp32
+ * spectrum: at most (2 n_m + 9) 2^-24 on every element, n_m = non-zero weights of band m.
+ * t_bands / f_bands: as for iris_magmel (zeroed in the complex spectrum first).  Arguments as iris_magmel; refused before any
+ * HIP call: NULL pointers, empty shapes (IRIS_E_INVALID), a plan whose channel count is not 2, is_magphase != 0 (complex
+ * spectra only; IRIS_E_UNSUPPORTED), spec not 16-byte or out not 8-byte aligned (IRIS_E_INVALID).  One launch on `stream`,
+ * no workspace, no atomics: bitwise reproducible, capturable.
+ */
+int iris_spec_ipd(iris_plan* plan, const float* spec, float* out, int batch, int n_frames,
+                  int is_magphase, const int32_t* t_bands, int n_t_bands,
+                  const int32_t* f_bands, int n_f_bands, void* stream);
+
+/*
  * minmax + log_on_mel (data_utils.py:37-55; fused twin trainer.py:63-77),
  * in place on x[n_rows, row_len]: per row (x - min) / max(max - min, eps_div)
  * when do_minmax, then ln(x + eps_log) when do_log.  A batched [B,M,T,C] tensor
