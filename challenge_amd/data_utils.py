@@ -5,6 +5,7 @@ kernels (ROCm device tensors, no CPU fallback); the channel / label helpers are 
 device-agnostic torch glue."""
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Optional
 
 import numpy as np
@@ -122,97 +123,124 @@ def pcen_on_mel(mel: torch.Tensor, labels=None, **params):
     return mel
 
 
-def feature_compression(name: str) -> str:
-    """The compression a run name selects, by the tokens in it (the reference's idiom for 'filter' / 'nominmax'):
-    'pcen_learn' (no compression stage: the datasets yield raw mel magnitudes and the model's own trainable `model.PCEN`
-    layer follows), 'pcen' (pcen_on_mel, fixed parameters), 'log' ('nominmax': log_on_mel alone) or 'minmax_log' (the
-    default).  A name holding both 'pcen' and 'nominmax' is refused: PCEN replaces the whole min-max / log stage."""
+@dataclass(frozen=True)
+class RunTokens:
+    """What a run name asks for, by the tokens in it (the reference's idiom for 'filter' / 'nominmax': a substring test, so
+    'pcen' is found inside 'pcen_learn', 'filter' is not found inside 'filtaug', and a name such as 'skipdrop' holds 'ipd').
+    `run_tokens` is the one parse; `check_builder` tells which dataset builder of sj_train honours what.
+
+    compression: the stage behind the mel features - 'minmax_log' (the default), 'log' ('nominmax': log_on_mel alone), 'pcen'
+        (pcen_on_mel, fixed parameters) or 'pcen_learn' (no stage: the datasets yield raw mel magnitudes and the model's own
+        trainable `model.PCEN` layer follows).  'pcen' with 'nominmax' is refused: PCEN replaces the whole min-max / log stage.
+    filter: the reference's `stft_filter` - the bins 1..3 (200 Hz) of every training and validation spectrum are zeroed.
+    stretch, speed, reverb: ONE augmentation of the voice corpus, on training sets, at creation and again every
+        config.steps_per_epoch batches.  stretch: time-stretched by rates ~ U[0.8, 1.2) (`DeviceMixer.enable_stretch` /
+        `restretch`, one `iris_phase_vocoder` launch over the corpus).  speed: speed-perturbed by rates ~ U[0.9, 1.1)
+        (`WaveMixer.enable_speed` / `respeed`: one `iris_speed_perturb` and one `iris_mix_wave_frame_active_batch` launch).
+        reverb: convolved with fresh synthetic room impulse responses, rt60 ~ U[0.1, 0.4) s, direct-to-reverberant ratio ~
+        U[-3, 12) dB (`WaveMixer.enable_reverb` / `rereverb`: one `iris_fir_batch` launch; the labels follow the dry voice).
+    shoebox: the room model of a 'reverb' run - image-source simulations of random shoebox rooms that both channels share
+        (`enable_reverb(model="shoebox")`: one `iris_ism_rir` and one `iris_fir_batch_pitch` launch per epoch, no tap upload),
+        so the inter-channel delay and level of a voice are those of one room, instead of independent noise per channel.
+        Refused without 'reverb': it only selects that augmentation's model.
+    filtaug: FilterAugment, None or the kind of its gain curve ('step'; 'linear' for 'filtaug_linear') - every training
+        sample's mel magnitudes are multiplied by a fresh random piecewise gain curve over the mel bands inside the mel kernels,
+        before any compression (`iris_magmel_gain`, `iris_wav_to_logmel_gain`: no extra launch, no extra pass; the draw is
+        `iris_filter_draw` on the device, else `transforms.filter_augment_draw` on the host).  It touches neither the mixers
+        nor the corpus, so it goes with every other token.
+    ipd: the inter-channel phase features.  A FEATURE, not an augmentation: the batched datasets then yield [B, M, T, 4] on
+        training and validation sets alike - channels 0-1 what they always were, channels 2-3 the (cos, sin) of the phase
+        difference per mel band (`transforms.mel_ipd`, `FrontendPlan.ipd`) of the same mixed spectrum under the same
+        SpecAugment / 'filter' bands, never min-maxed, logged, PCEN'd or gained (the definition is invariant to a band gain) -
+        `inference.features_for_eval` appends the same two channels, and the model's first layer takes
+        `model_in_channels(config)`.  Stereo only: n_chan must be 2 and the corpora stereo.  Refused with 'pcen_learn' (the
+        trainable PCEN layer would have to skip the two phase channels); it goes with every other token.
+    A name without a token takes no code path of that token."""
+    name: str
+    compression: str
+    filter: bool
+    stretch: bool
+    speed: bool
+    reverb: bool
+    shoebox: bool
+    filtaug: Optional[str]
+    ipd: bool
+
+
+def run_tokens(config_or_name) -> RunTokens:
+    """The tokens of a run name, given the name or a config (whose `name` may be missing or None).  Raises the refusals that
+    the name alone decides and, given a config, 'ipd' at n_chan != 2."""
+    config = None if config_or_name is None or isinstance(config_or_name, str) else config_or_name
+    name = (config_or_name if config is None else getattr(config, 'name', '')) or ''
     pcen, nominmax = 'pcen' in name, 'nominmax' in name
     if pcen and nominmax:
         raise ValueError(f"run name {name!r} asks for both 'pcen' and 'nominmax': PCEN replaces min-max + log, name one")
-    if 'pcen_learn' in name:
-        return 'pcen_learn'
-    return 'pcen' if pcen else ('log' if nominmax else 'minmax_log')
-
-
-def wants_stretch(name: str) -> bool:
-    """Whether a run name asks for time-stretch augmentation of the voice corpus: the token 'stretch' in it (the same
-    idiom).  Honoured by `sj_train.make_device_dataset(training=True)` alone (`DeviceMixer.enable_stretch` / `restretch`);
-    `make_dataset` and `make_wave_dataset` refuse it.  It does not interact with `feature_compression`."""
-    return 'stretch' in name
-
-
-def wants_speed(name: str) -> bool:
-    """Whether a run name asks for speed perturbation of the voice corpus: the token 'speed' in it (the same idiom).
-    Honoured by `sj_train.make_wave_dataset(training=True)` alone (`WaveMixer.enable_speed` / `respeed`); `make_dataset` and
-    `make_device_dataset` refuse it.  It does not interact with `feature_compression`."""
-    return 'speed' in name
-
-
-def wants_reverb(name: str) -> bool:
-    """Whether a run name asks for reverberation of the voice corpus: the token 'reverb' in it (the same idiom).  Honoured by
-    `sj_train.make_wave_dataset(training=True)` alone (`WaveMixer.enable_reverb` / `rereverb`); `make_dataset` and
-    `make_device_dataset` refuse it, and a name that also holds 'speed' is refused (a mixer holds one voice augmentation).
-    It does not interact with `feature_compression`."""
-    return 'reverb' in name
-
-
-def wants_shoebox(name: str) -> bool:
-    """Whether a run name asks for the shoebox room model of the reverberation: the token 'shoebox' in it (the same idiom).
-    It selects the model of a 'reverb' run (`WaveMixer.enable_reverb(model="shoebox")`: image-source responses that both
-    channels share, instead of independent noise per channel); `check_shoebox` refuses it without 'reverb'."""
-    return 'shoebox' in name
-
-
-def check_shoebox(name: str) -> None:
-    """'shoebox' without 'reverb' in a run name is a ValueError: the token only selects the room model of that augmentation."""
-    if wants_shoebox(name) and not wants_reverb(name):
+    tokens = RunTokens(
+        name=name,
+        compression='pcen_learn' if 'pcen_learn' in name else 'pcen' if pcen else 'log' if nominmax else 'minmax_log',
+        filter='filter' in name, stretch='stretch' in name, speed='speed' in name, reverb='reverb' in name,
+        shoebox='shoebox' in name,
+        filtaug=('linear' if 'filtaug_linear' in name else 'step') if 'filtaug' in name else None,
+        ipd='ipd' in name)
+    if tokens.shoebox and not tokens.reverb:
         raise ValueError(f"run name {name!r} asks for 'shoebox' without 'reverb': the token selects the room model of the "
                          "reverberation augmentation, name both")
-
-
-def wants_filtaug(name: str) -> bool:
-    """Whether a run name asks for FilterAugment (a random piecewise gain curve over the mel bands of every training sample,
-    applied inside the mel kernels): the token 'filtaug' in it (the same idiom; 'filtaug' does not contain the reference's
-    'filter' token, nor 'filter' it).  `filtaug_kind` tells the curve's kind.  Honoured by `sj_train.make_device_dataset` and
-    `make_wave_dataset` on training sets; `make_dataset` refuses it.  It touches neither the mixers nor the corpus, so it
-    goes with every other token ('pcen', 'pcen_learn', 'nominmax', 'stretch', 'speed', 'reverb', 'shoebox', 'filter')."""
-    return 'filtaug' in name
-
-
-def filtaug_kind(name: str) -> str:
-    """The kind of a FilterAugment run's gain curve: 'linear' for the token 'filtaug_linear', else 'step'."""
-    return 'linear' if 'filtaug_linear' in name else 'step'
-
-
-def wants_ipd(name: str) -> bool:
-    """Whether a run name asks for the inter-channel phase features: the token 'ipd' in it (the same idiom).  A FEATURE, not an
-    augmentation: `sj_train.make_device_dataset` and `make_wave_dataset` then yield [B, M, T, 4] on training and validation
-    sets alike - channels 0-1 what they always were, channels 2-3 the (cos, sin) of the phase difference per mel band
-    (`transforms.mel_ipd`, `FrontendPlan.ipd`) of the same mixed spectrum under the same SpecAugment / 'filter' bands, never
-    min-maxed, logged, PCEN'd or gained (the definition is invariant to a band gain) - and `inference.features_for_eval`
-    appends the same two channels; the model's first layer takes `model_in_channels(config)`.  Stereo only (`check_ipd`);
-    `make_dataset` refuses it.  It goes with every other token except 'pcen_learn'."""
-    return 'ipd' in name
-
-
-def check_ipd(config) -> None:
-    """The refusals of an 'ipd' run name: n_chan must be 2 (the feature is the phase difference of a stereo pair), and the
-    trainable PCEN layer of 'pcen_learn' would have to skip the two phase channels, which it does not do yet."""
-    name = getattr(config, 'name', '') or ''
-    if not wants_ipd(name):
-        return
-    if config.n_chan != 2:
+    if tokens.ipd and config is not None and config.n_chan != 2:
         raise ValueError(f"run name {name!r} asks for 'ipd' at n_chan = {config.n_chan}: the inter-channel phase difference is "
                          "that of a stereo pair, n_chan must be 2")
-    if feature_compression(name) == 'pcen_learn':
+    if tokens.ipd and tokens.compression == 'pcen_learn':
         raise ValueError(f"run name {name!r} asks for both 'ipd' and 'pcen_learn': the trainable PCEN layer would have to skip "
                          "the two phase channels, which is not supported yet; name one (the fixed 'pcen' goes with 'ipd')")
+    return tokens
+
+
+# Which dataset builder of sj_train honours which token (None), and why the others refuse it
+BUILDER_REFUSALS = {
+    'make_dataset': {
+        'stretch': "time stretching runs on the device-resident corpus (make_device_dataset); the per-sample host pipeline "
+                   "does not stretch",
+        'speed': "speed perturbation runs on the resident waveform corpus (make_wave_dataset); the per-sample host pipeline "
+                 "does not resample",
+        'reverb': "reverberation runs on the resident waveform corpus (make_wave_dataset); the per-sample host pipeline does "
+                  "not convolve",
+        'filtaug': "FilterAugment runs inside the batched mel kernels (make_device_dataset, make_wave_dataset); the per-sample "
+                   "host pipeline has no gain stage",
+        'ipd': "the inter-channel phase features are computed on whole batches (make_device_dataset, make_wave_dataset); the "
+               "per-sample host pipeline has no such stage"},
+    'make_device_dataset': {
+        'stretch': None,
+        'speed': "a spectrum corpus cannot be resampled in time (use make_wave_dataset; this path has 'stretch')",
+        'reverb': "a spectrum corpus has no waveform to convolve (use make_wave_dataset; this path has 'stretch')",
+        'filtaug': None,
+        'ipd': None},
+    'make_wave_dataset': {
+        'stretch': "a waveform corpus has no spectra to stretch (use make_device_dataset)",
+        'speed': None,
+        'reverb': None,
+        'filtaug': None,
+        'ipd': None},
+}
+
+
+def check_builder(tokens: RunTokens, builder: str) -> None:
+    """ValueError if `builder` (a key of BUILDER_REFUSALS) does not honour a token of the name, or - a mixer holds one voice
+    augmentation - if the name asks it for both 'speed' and 'reverb'."""
+    for token, reason in BUILDER_REFUSALS[builder].items():
+        if reason is not None and getattr(tokens, token):
+            raise ValueError(f"run name {tokens.name!r} asks for {token!r}: {reason}")
+    if tokens.speed and tokens.reverb:
+        raise ValueError(f"run name {tokens.name!r} asks for both 'speed' and 'reverb': the two cannot be combined yet (a "
+                         "mixer holds one voice augmentation), name one")
+
+
+def feature_compression(name: str) -> str:
+    """`run_tokens(name).compression`."""
+    return run_tokens(name).compression
 
 
 def model_in_channels(config) -> int:
     """Channels of the model's input: n_chan, plus the two (cos, sin) phase channels of an 'ipd' run name."""
-    return config.n_chan + 2 if wants_ipd(getattr(config, 'name', '') or '') else config.n_chan
+    return config.n_chan + 2 if run_tokens(config).ipd else config.n_chan
 
 
 class FilterAugmentDraw:

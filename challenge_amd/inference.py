@@ -69,13 +69,12 @@ def smooth(preds: torch.Tensor, sr: int = 16000, hop: int = 256) -> torch.Tensor
 
 def features_for_eval(spec: torch.Tensor, config) -> torch.Tensor:
     """[F, T, 2C] complex spectrogram -> log-mel [M, T, C'] as metrics.py:42-54 prepares it.  A 'pcen' run name
-    (data_utils.feature_compression) applies PCEN instead of min-max + log, over the whole recording before it is cut
+    (`data_utils.RunTokens`) applies PCEN instead of min-max + log, over the whole recording before it is cut
     into windows (training applies it per clip: see data_utils.pcen_on_mel).  A 'pcen_learn' run name returns the raw mel
     magnitudes: the trainable PCEN layer is inside the model and runs per window, which is what training saw per clip.
-    An 'ipd' run name returns [M, T, 4]: the same two channels, then the (cos, sin) phase channels (`transforms.mel_ipd`)."""
-    compression = D.feature_compression(getattr(config, 'name', ''))
-    pcen = compression == 'pcen'
-    D.check_ipd(config)   # an 'ipd' run name: stereo only, not with 'pcen_learn'
+    An 'ipd' run name returns [M, T, 4]: the same two channels, then the (cos, sin) phase channels (`transforms.mel_ipd`) of
+    the filtered spectrum, uncompressed (per-frame quantities: cutting windows later does not change them)."""
+    tokens = D.run_tokens(config)
     inputs = spec
     if config.n_chan == 1:
         inputs = D.mono_chan(inputs)
@@ -84,24 +83,17 @@ def features_for_eval(spec: torch.Tensor, config) -> torch.Tensor:
     elif config.n_chan > 3:
         inputs = D.random_merge_aug(config.n_chan)(inputs, None)
     inputs = D.stft_filter(int(round(256 * 1000 / 16000)))(inputs)
-    if D.wants_ipd(getattr(config, 'name', '') or ''):
-        # an 'ipd' run name: the (cos, sin) phase channels of the filtered spectrum, over the whole recording (per-frame
-        # quantities: cutting windows later does not change them), appended uncompressed behind the channels computed below
-        if inputs.shape[-1] != 4:
-            raise ValueError(f"run name {config.name!r} asks for 'ipd' but the recording has {inputs.shape[-1] // 2} channel(s)")
-        to_mel = T.magphase_to_mel(config.n_mels, inputs.shape[0])
-        phase = T.mel_ipd(inputs, to_mel.mel_matrix)
-        mel = to_mel(T.complex_to_magphase(inputs))
-        mel = D.pcen_on_mel(mel) if pcen else D.log_on_mel(D.minmax(mel))
-        return torch.cat([mel, phase], dim=-1)
-    inputs = T.complex_to_magphase(inputs)
-    inputs = T.magphase_to_mel(config.n_mels, inputs.shape[0])(inputs)
-    if compression == 'pcen_learn':
-        return inputs
-    if pcen:
-        return D.pcen_on_mel(inputs)
-    inputs = D.minmax(inputs)       # unbatched: per-mel-row min-max (the reference's behaviour)
-    return D.log_on_mel(inputs)
+    if tokens.ipd and inputs.shape[-1] != 4:
+        raise ValueError(f"run name {config.name!r} asks for 'ipd' but the recording has {inputs.shape[-1] // 2} channel(s)")
+    to_mel = T.magphase_to_mel(config.n_mels, inputs.shape[0])
+    mel = to_mel(T.complex_to_magphase(inputs))
+    if tokens.compression == 'pcen':
+        mel = D.pcen_on_mel(mel)
+    elif tokens.compression != 'pcen_learn':
+        mel = D.log_on_mel(D.minmax(mel))   # unbatched: per-mel-row min-max (the reference's behaviour)
+    if tokens.ipd:
+        mel = torch.cat([mel, T.mel_ipd(inputs, to_mel.mel_matrix)], dim=-1)
+    return mel
 
 
 @torch.no_grad()

@@ -227,11 +227,9 @@ class CustomModel(nn.Module):
         self.config_v, self.model_type = config.v, config.model_type
         # a 'pcen_learn' run name: the datasets feed raw mel magnitudes and the trainable PCEN layer is the model's first stage
         # (registered first; models of other names have no such submodule and the state_dict keys they always had)
-        from .data_utils import feature_compression
-        self.pcen = PCEN(config.n_mels) if feature_compression(getattr(config, 'name', '') or '') == 'pcen_learn' else None
-        from .data_utils import check_ipd, model_in_channels   # n_chan, + the two phase channels of an 'ipd' run name
-        check_ipd(config)
-        blocks = [ConvMPBlock(model_in_channels(config), 2, fsize, BN=True)]
+        from .data_utils import model_in_channels, run_tokens   # (the parse refuses 'ipd' at n_chan != 2 or with 'pcen_learn')
+        self.pcen = PCEN(config.n_mels) if run_tokens(config).compression == 'pcen_learn' else None
+        blocks = [ConvMPBlock(model_in_channels(config), 2, fsize, BN=True)]   # n_chan, + the two phase channels of an 'ipd' name
         cin, width = fsize, config.n_frame // 2
         for i in range(1, 5):
             if config.model_type == 'vad' and config.v == 6:

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import argparse
 import csv
+import functools
 import math
 import os
 import time
@@ -200,25 +201,22 @@ def _load_sources(config, training, n_classes, sources):
     return backgrounds, voices, labels, noises
 
 
+_FILTER_BINS = int(round(200 / (16000 / 256)))   # the band of a 'filter' run name: `stft_filter` zeroes the bins 1..3
+
+
 def _compression_map(config):
-    """The compression stage a run name selects, as a `(mel, labels=None)` map (None: 'pcen_learn', no stage)."""
-    compression = _du.feature_compression(config.name)
-    return {'pcen_learn': None, 'pcen': _du.pcen_on_mel, 'minmax_log': _du.minmax_log_on_mel}.get(compression, log_on_mel)
+    """The compression stage a run name selects, as a `(mel, labels=None)` map (None: 'pcen_learn', no stage - the raw mel
+    magnitudes go to the model's trainable PCEN layer)."""
+    return {'pcen_learn': None, 'pcen': _du.pcen_on_mel, 'minmax_log': _du.minmax_log_on_mel,   # (min-max + log: :121-123 fused)
+            'log': log_on_mel}[_du.run_tokens(config).compression]
 
 
 def _label_tail(pipeline, config, compressed=False):
-    """The stages after the mel features (sj_train.py:121-129); a 'pcen' run name maps PCEN instead of min-max + log, a
-    'pcen_learn' one maps no compression at all (the raw mel magnitudes go to the model's trainable PCEN layer).
-    `compressed`: the generator has applied the compression itself (an 'ipd' run: only the mel channels go through it)."""
-    compression = _du.feature_compression(config.name)
-    if compression == 'pcen_learn' or compressed:
-        pass
-    elif compression == 'pcen':
-        pipeline = pipeline.map(_du.pcen_on_mel)
-    elif compression == 'minmax_log':
-        pipeline = pipeline.map(_du.minmax_log_on_mel)  # :121-123 fused
-    else:
-        pipeline = pipeline.map(log_on_mel)
+    """The stages after the mel features (sj_train.py:121-129): the compression of `_compression_map`, then the labels'.
+    `compressed`: a batched builder, whose generator has applied the compression itself."""
+    compress = None if compressed else _compression_map(config)
+    if compress is not None:
+        pipeline = pipeline.map(compress)
     if config.v in label_downsample_model:
         pipeline = pipeline.map(label_downsample(32))
     elif config.v == 5:
@@ -231,22 +229,8 @@ def _label_tail(pipeline, config, compressed=False):
 def make_dataset(config, training=True, n_classes=3, sources=None):
     """Stage order of sj_train.py:74-130.  `sources` = (backgrounds, voices, labels, noises)
     overrides the pickle files (used with --synthetic and by the tests)."""
-    if _du.wants_stretch(config.name):
-        raise ValueError(f"run name {config.name!r} asks for 'stretch': time stretching runs on the device-resident corpus "
-                         "(make_device_dataset); the per-sample host pipeline does not stretch")
-    if _du.wants_speed(config.name):
-        raise ValueError(f"run name {config.name!r} asks for 'speed': speed perturbation runs on the resident waveform corpus "
-                         "(make_wave_dataset); the per-sample host pipeline does not resample")
-    _du.check_shoebox(config.name)
-    if _du.wants_reverb(config.name):
-        raise ValueError(f"run name {config.name!r} asks for 'reverb': reverberation runs on the resident waveform corpus "
-                         "(make_wave_dataset); the per-sample host pipeline does not convolve")
-    if _du.wants_filtaug(config.name):
-        raise ValueError(f"run name {config.name!r} asks for 'filtaug': FilterAugment runs inside the batched mel kernels "
-                         "(make_device_dataset, make_wave_dataset); the per-sample host pipeline has no gain stage")
-    if _du.wants_ipd(config.name):
-        raise ValueError(f"run name {config.name!r} asks for 'ipd': the inter-channel phase features are computed on whole batches "
-                         "(make_device_dataset, make_wave_dataset); the per-sample host pipeline has no such stage")
+    tokens = _du.run_tokens(config)
+    _du.check_builder(tokens, 'make_dataset')
     backgrounds, voices, labels, noises = _load_sources(config, training, n_classes, sources)
 
     pipeline = make_pipeline(backgrounds, voices, labels, noises, n_frame=config.n_frame,
@@ -264,34 +248,59 @@ def make_dataset(config, training=True, n_classes=3, sources=None):
         pipeline = pipeline.map(stereo_mono)
     elif config.n_chan > 3:
         pipeline = pipeline.map(random_merge_aug(config.n_chan))
-    if 'filter' in config.name:
-        pipeline = pipeline.map(stft_filter(int(round(200 / (16000 / 256)))))
+    if tokens.filter:
+        pipeline = pipeline.map(stft_filter(_FILTER_BINS))
     pipeline = pipeline.batch(config.batch_size, drop_remainder=False)
     n_bins = int(np.asarray(backgrounds[0]).shape[0])
     pipeline = pipeline.map(complex_to_mel(config.n_mels, n_bins))  # :119-120 fused
     return _label_tail(pipeline, config)
 
 
-def _draw_bands(band_draw, training, rng, filter_bins, b, n_frame, n_bins):
-    """(t_bands, f_bands) of one batch for the mel kernel: SpecAugment (`augment`, data_utils.py:58-61: 6 time masks, 1
-    frequency mask per sample) on training sets and the `stft_filter` band (data_utils.py:126-136: bins 1..k).  A device-side
-    `band_draw` includes the filter band itself; without one the bands come from `rng` on the host."""
-    if band_draw is not None:
-        return band_draw(b, n_frame, n_bins)
-    tb, fb = _du.augment_draw_batch(b, n_frame, n_bins, rng) if training else (None, None)
-    if filter_bins:
-        flt = np.tile(np.array([[[1, filter_bins]]], np.int32), (b, 1, 1))
-        fb = flt if fb is None else np.concatenate([fb, flt], axis=1)
-    return tb, fb
+class BatchDraws:
+    """The per-batch random draws of a batched dataset, and the one place that says which stream each comes from: the mixer
+    keeps `seed` for the batch itself, the SpecAugment bands take `seed + 1` and the FilterAugment gains `seed + 2` (seed
+    None: unseeded host generators; the device generators, which are keyed by an integer, take 0).  Calling it with a batch
+    size (and the batch's frame and mel counts) gives (t_bands, f_bands, mel_gain) for the mel kernels:
+    - the bands of SpecAugment (`augment`, data_utils.py:58-61: 6 time masks, 1 frequency mask per sample) on training sets,
+      and behind them the `stft_filter` band (data_utils.py:126-136: bins 1..k) of a 'filter' name on every set; None
+      where there is nothing to mask.  device_draw: one `iris_augment_draw` launch into long-lived device tensors (the filter
+      band included), else NumPy on the host - uploaded here, once for both kernels that read them, on an 'ipd' run;
+    - the gains [B, n_mels] of a 'filtaug' name on training sets (`FilterAugmentDraw`), else None.
+    A validation set draws neither SpecAugment bands nor gains."""
+
+    def __init__(self, tokens, training, device, seed, device_draw, n_bins):
+        key = 0 if seed is None else seed
+        self.training, self.device, self.n_bins = training, device, n_bins
+        self.filter_bins = _FILTER_BINS if tokens.filter else 0
+        self.upload = tokens.ipd
+        self.rng = np.random.default_rng(None if seed is None else seed + 1)
+        self.band_draw = _du.DeviceAugmentDraw(device, key + 1, self.filter_bins) if device_draw and training else None
+        self.gain_draw = None
+        if training and tokens.filtaug:
+            self.gain_draw = _du.FilterAugmentDraw(device, tokens.filtaug, key + 2, device_draw,
+                                                   None if seed is not None else np.random.default_rng())
+
+    def __call__(self, b, n_frame, n_mels):
+        if self.band_draw is not None:
+            tb, fb = self.band_draw(b, n_frame, self.n_bins)
+        else:
+            tb, fb = _du.augment_draw_batch(b, n_frame, self.n_bins, self.rng) if self.training else (None, None)
+            if self.filter_bins:
+                flt = np.tile(np.array([[[1, self.filter_bins]]], np.int32), (b, 1, 1))
+                fb = flt if fb is None else np.concatenate([fb, flt], axis=1)
+        if self.upload:
+            tb, fb = (None if v is None else torch.as_tensor(v).to(self.device, torch.int32) for v in (tb, fb))
+        return tb, fb, None if self.gain_draw is None else self.gain_draw(b, n_mels)
 
 
 def _every_epoch(fn, steps_per_epoch):
-    """A function to call before every batch: it calls `fn` before every `steps_per_epoch`-th batch after the first."""
+    """A function to call before every batch: it calls `fn` (None: nothing) before every `steps_per_epoch`-th batch after the
+    first."""
     n_batches = 0
 
     def tick():
         nonlocal n_batches
-        if n_batches and n_batches % max(int(steps_per_epoch), 1) == 0:
+        if fn is not None and n_batches and n_batches % max(int(steps_per_epoch), 1) == 0:
             fn()
         n_batches += 1
     return tick
@@ -307,53 +316,30 @@ def make_device_dataset(config, training=True, n_classes=3, sources=None, device
     device_draw=True: the random half of a batch (sources, offsets, gains, SpecAugment bands) is drawn by two small HIP
     kernels on the device (`iris_mix_draw`, `iris_augment_draw`) instead of NumPy on the host - no table upload, the
     host only enqueues launches.
-    A 'stretch' token in config.name (training sets only): the voice corpus is time-stretched by rates ~ U[0.8, 1.2) at
-    creation and again every config.steps_per_epoch batches (`DeviceMixer.enable_stretch` / `restretch`, one
-    `iris_phase_vocoder` launch over the corpus); a name without the token takes no new code path.
-    A 'filtaug' token (training sets only; 'filtaug_linear': the linear kind): FilterAugment - every sample's mel values are
-    multiplied by a fresh random piecewise gain curve over the mel bands inside the mel kernel (`iris_magmel_gain`; the draw
-    is `iris_filter_draw` under device_draw, else `transforms.filter_augment_draw` on the host); a name without the token
-    takes no new code path.
-    An 'ipd' token (training AND validation sets: a feature, not an augmentation): x is [B, n_mels, n_frame, 4] - channels 0-1
-    exactly what is yielded without the token, channels 2-3 the (cos, sin) of the inter-channel phase difference per mel band
-    (`FrontendPlan.ipd`, one more launch) of the same mixed spectrum under the same bands, not compressed and not gained.
-    n_chan must be 2 and the corpora stereo; 'ipd' with 'pcen_learn' is refused (`data_utils.check_ipd`).  It goes with every
-    other token; a name without it takes no new code path."""
+    Of the run-name tokens (`data_utils.RunTokens`) this builder honours 'stretch', 'filtaug' and 'ipd' and refuses 'speed'
+    and 'reverb' (`data_utils.BUILDER_REFUSALS`).  With 'ipd' x is [B, n_mels, n_frame, 4]: one more launch
+    (`FrontendPlan.ipd`) over the same mixed spectrum; the corpora must be stereo."""
     from .mixer import DeviceMixer
-    _du.check_ipd(config)
-    if _du.wants_speed(config.name):
-        raise ValueError(f"run name {config.name!r} asks for 'speed': a spectrum corpus cannot be resampled in time "
-                         "(use make_wave_dataset; this path has 'stretch')")
-    _du.check_shoebox(config.name)
-    if _du.wants_reverb(config.name):
-        raise ValueError(f"run name {config.name!r} asks for 'reverb': a spectrum corpus has no waveform to convolve "
-                         "(use make_wave_dataset; this path has 'stretch')")
+    tokens = _du.run_tokens(config)
+    _du.check_builder(tokens, 'make_device_dataset')
     backgrounds, voices, labels, noises = _load_sources(config, training, n_classes, sources)
     if config.model_type == 'se' and config.v == 9:
         raise NotImplementedError("model_type 'se' is outside the accelerated path (SURVEY.md section 2)")
     mixer = DeviceMixer(backgrounds, voices, labels, noises, n_frame=config.n_frame, max_voices=config.max_voices,
                         max_noises=config.max_noises, n_classes=n_classes, device=device, snr=config.snr,
                         min_ratio=1, seed=seed)
-    rng = np.random.default_rng(None if seed is None else seed + 1)
-    filter_bins = int(round(200 / (16000 / 256))) if 'filter' in config.name else 0
-    band_draw = None
     if device_draw:
         mixer.enable_device_draw(0 if seed is None else seed)
-        band_draw = _du.DeviceAugmentDraw(mixer.device, (0 if seed is None else seed) + 1, filter_bins) if training else None
-    gain_draw = None
-    if training and _du.wants_filtaug(config.name):   # (the validation set never is)
-        gain_draw = _du.FilterAugmentDraw(mixer.device, _du.filtaug_kind(config.name), (0 if seed is None else seed) + 2, device_draw,
-                                          None if seed is not None else np.random.default_rng())
-    stretch = training and _du.wants_stretch(config.name)
+    draws = BatchDraws(tokens, training, mixer.device, seed, device_draw, mixer.n_bins)
+    stretch = training and tokens.stretch
     if stretch:   # the voice corpus is re-stretched now and once per epoch (the validation set never is)
         mixer.enable_stretch()
         mixer.restretch()
     to_mel = complex_to_mel(config.n_mels, mixer.n_bins)
-    ipd = _du.wants_ipd(config.name)
-    if ipd and mixer.chan2 != 4:
+    if tokens.ipd and mixer.chan2 != 4:
         raise ValueError(f"run name {config.name!r} asks for 'ipd' but the corpus has {mixer.chan2 // 2} channel(s): the inter-channel "
                          "phase difference needs stereo corpora")
-    compress = _compression_map(config) if ipd else None
+    compress = _compression_map(config)
     chan_map = None
     if config.n_chan == 1:
         chan_map = mono_chan
@@ -363,26 +349,21 @@ def make_device_dataset(config, training=True, n_classes=3, sources=None, device
         chan_map = random_merge_aug(config.n_chan)
 
     def gen():
-        reaugment = _every_epoch(mixer.restretch, config.steps_per_epoch) if stretch else (lambda: None)
+        reaugment = _every_epoch(mixer.restretch if stretch else None, config.steps_per_epoch)
         while True:
             reaugment()
             x, y = to_frame_labels(*mixer.mix(config.batch_size))
-            tb, fb = _draw_bands(band_draw, training, rng, filter_bins, int(x.shape[0]), config.n_frame, mixer.n_bins)
+            tb, fb, gain = draws(int(x.shape[0]), config.n_frame, config.n_mels)
             if chan_map is not None:
                 x, y = chan_map(x, y)
-            if ipd:
-                tb, fb = (None if v is None else torch.as_tensor(v).to(x.device, torch.int32) for v in (tb, fb))  # one upload for both kernels
-                kw = {} if gain_draw is None else {"mel_gain": gain_draw(int(x.shape[0]), config.n_mels)}
-                mel = to_mel(x, None, t_bands=tb, f_bands=fb, **kw)
-                if compress is not None:
-                    mel = compress(mel)
-                yield torch.cat([mel, to_mel.ipd(x, tb, fb)], dim=-1), y   # the phase channels: neither compressed nor gained
-            elif gain_draw is None:
-                yield to_mel(x, y, t_bands=tb, f_bands=fb)
-            else:
-                yield to_mel(x, y, t_bands=tb, f_bands=fb, mel_gain=gain_draw(int(x.shape[0]), config.n_mels))
+            mel = to_mel(x, None, t_bands=tb, f_bands=fb, mel_gain=gain)
+            if compress is not None:
+                mel, y = compress(mel, y)   # (called as `Dataset.map` calls a stage)
+            if tokens.ipd:   # the phase channels: neither compressed nor gained
+                mel = torch.cat([mel, to_mel.ipd(x, tb, fb)], dim=-1)
+            yield mel, y
 
-    dataset = _label_tail(Dataset.from_generator(gen), config, compressed=ipd)
+    dataset = _label_tail(Dataset.from_generator(gen), config, compressed=True)
     dataset.mixer = mixer   # (for inspection: the resident corpus, its draws and - 'stretch' runs - the current voice lengths)
     return dataset
 
@@ -455,6 +436,24 @@ def waves_from_specs(sources, n_fft=512, hop=256, device=None):
     return waves
 
 
+def wave_features(plan, compression, do_minmax, wav, t_bands=None, f_bands=None, mel_gain=None, out=None, ipd=False):
+    """The features [B, M, T, C] of the waveforms `wav` [B, C, L] on `plan`, one body for `make_wave_dataset` and
+    `WaveFrontend`: compression 'log' is ONE launch of the fused kernel (STFT, bands, mel, gains, min-max if `do_minmax`,
+    log); 'mel' the same launch stopping at the (gained) mel magnitudes; 'pcen' that, then `frontend.pcen` in place (a
+    second launch).  `out` (optional) receives these channels.  ipd: the batch's spectrum is materialised as well (`iris_stft`)
+    and the two phase channels (`FrontendPlan.ipd`) under the same bands, neither compressed nor gained, are appended - two
+    more launches and a `torch.cat`: deliberately NOT fused into the hot kernel.  Capturable into a hipGraph in every form."""
+    if compression == 'log':
+        mel = plan.wav_to_logmel(wav, minmax=do_minmax, log=True, t_bands=t_bands, f_bands=f_bands, out=out, mel_gain=mel_gain)
+    else:
+        mel = plan.wav_to_logmel(wav, minmax=False, log=False, t_bands=t_bands, f_bands=f_bands, out=out, mel_gain=mel_gain)
+        if compression == 'pcen':
+            mel = _fe.pcen(mel, out=mel)
+    if ipd:
+        return torch.cat([mel, plan.ipd(plan.stft(wav), t_bands=t_bands, f_bands=f_bands)], dim=-1)
+    return mel
+
+
 def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=None, seed=None, n_fft=512, hop=256,
                       sample_rate=16000, device_draw=False, spec_sources=None):
     """`make_device_dataset` from WAVEFORMS (waveform-domain variant): the corpora
@@ -470,39 +469,16 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
     the boundary frames of the waveform-domain mix.  The augmenting maps of n_chan > 2 mix spectra with per-bin
     factors and are not available here.  device_draw=True: sources / offsets / gains / SpecAugment bands are drawn on
     the device (`iris_mix_draw`, `iris_augment_draw`), as in `make_device_dataset`.
-    A 'speed' token in config.name (training sets only): the voice corpus is speed-perturbed by rates ~ U[0.9, 1.1) at
-    creation and again every config.steps_per_epoch batches (`WaveMixer.enable_speed` / `respeed`: one `iris_speed_perturb`
-    and one `iris_mix_wave_frame_active_batch` launch over the corpus); a name without the token takes no new code path.
-    A 'reverb' token (training sets only): the voice corpus is convolved with fresh synthetic room impulse responses (rt60 ~
-    U[0.1, 0.4) s, direct-to-reverberant ratio ~ U[-3, 12) dB) at creation and again every config.steps_per_epoch batches
-    (`WaveMixer.enable_reverb` / `rereverb`: one `iris_fir_batch` launch over the corpus; the labels follow the dry voice); a
-    name without the token takes no new code path.  'speed' and 'reverb' together are refused: they cannot be combined yet.
-    A 'shoebox' token beside 'reverb': the responses are image-source simulations of random shoebox rooms that both channels
-    share (`enable_reverb(model="shoebox")`: one `iris_ism_rir` and one `iris_fir_batch_pitch` launch per epoch, no tap
-    upload), so the inter-channel delay and level of a voice are those of one room; 'shoebox' without 'reverb' is a ValueError.
-    A 'filtaug' token (training sets only; 'filtaug_linear': the linear kind): FilterAugment - every sample's mel magnitudes
-    are multiplied by a fresh random piecewise gain curve over the mel bands inside the fused kernel, before min-max / log
-    or PCEN (`iris_wav_to_logmel_gain`: no extra launch, no extra pass; the draw is `iris_filter_draw` under device_draw,
-    else `transforms.filter_augment_draw` on the host).  It goes with every token above; a name without it takes no new code path.
-    An 'ipd' token (training AND validation sets: a feature, not an augmentation): x is [B, n_mels, n_frame, 4] - channels 0-1
-    exactly what the fused kernel yields without the token, channels 2-3 the (cos, sin) of the inter-channel phase difference
-    per mel band under the same bands, not compressed and not gained.  Deliberately NOT fused into the hot kernel: the batch's
-    spectrum is materialised by `iris_stft` and read by `FrontendPlan.ipd` (two more launches).  n_chan must be 2 and the
-    corpora stereo; 'ipd' with 'pcen_learn' is refused (`data_utils.check_ipd`).  A name without the token takes no new code path.
+    Of the run-name tokens (`data_utils.RunTokens`) this builder honours 'speed', 'reverb' (with 'shoebox'), 'filtaug' and
+    'ipd' and refuses 'stretch', and 'speed' beside 'reverb' (`data_utils.BUILDER_REFUSALS`).  With 'ipd' x is
+    [B, n_mels, n_frame, 4] (`wave_features`); the corpora must be stereo.
     spec_sources: the same tuple as SPECTRA ([F, T_i, 2C], integer labels), e.g. the pickled corpora - converted once here by
     `waves_from_specs` at this n_fft / hop and used as `sources` (giving both is a ValueError)."""
     from .mixer import WaveMixer
-    if spec_sources is not None:
-        if sources is not None:
-            raise ValueError("make_wave_dataset: give `sources` (waveforms) or `spec_sources` (spectra), not both")
-    if _du.wants_stretch(config.name):
-        raise ValueError(f"run name {config.name!r} asks for 'stretch': a waveform corpus has no spectra to stretch "
-                         "(use make_device_dataset)")
-    _du.check_shoebox(config.name)
-    _du.check_ipd(config)
-    if _du.wants_speed(config.name) and _du.wants_reverb(config.name):
-        raise ValueError(f"run name {config.name!r} asks for both 'speed' and 'reverb': the two cannot be combined yet (a "
-                         "mixer holds one voice augmentation), name one")
+    if spec_sources is not None and sources is not None:
+        raise ValueError("make_wave_dataset: give `sources` (waveforms) or `spec_sources` (spectra), not both")
+    tokens = _du.run_tokens(config)
+    _du.check_builder(tokens, 'make_wave_dataset')
     if spec_sources is not None:
         sources = waves_from_specs(spec_sources, n_fft, hop, device)
     if sources is None:
@@ -516,74 +492,40 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
     mixer = WaveMixer(backgrounds, voices, labels, noises, n_frame=config.n_frame, n_fft=n_fft, hop=hop,
                       max_voices=config.max_voices, max_noises=config.max_noises, n_classes=n_classes, device=device,
                       snr=config.snr, min_ratio=1, seed=seed)
-    rng = np.random.default_rng(None if seed is None else seed + 1)
     length = (config.n_frame - 1) * hop
     plan = _fe.FrontendPlan(n_fft, hop, config.n_mels, sample_rate, config.n_chan, config.batch_size, length, mixer.device)
-    filter_bins = int(round(200 / (16000 / 256))) if 'filter' in config.name else 0
-    compression = _du.feature_compression(config.name)
-    do_pcen, raw_mel = compression == 'pcen', compression == 'pcen_learn'   # raw_mel: the model's PCEN layer takes the magnitudes
-    do_minmax = 'nominmax' not in config.name
-    ipd = _du.wants_ipd(config.name)
-    if ipd and mixer.channels != 2:
+    # `wave_features`' words for the compression: the raw mel magnitudes of 'pcen_learn' go to the model's PCEN layer
+    compression = {'pcen': 'pcen', 'pcen_learn': 'mel'}.get(tokens.compression, 'log')
+    do_minmax = tokens.compression == 'minmax_log'
+    if tokens.ipd and mixer.channels != 2:
         raise ValueError(f"run name {config.name!r} asks for 'ipd' but the corpus has {mixer.channels} channel(s): the inter-channel "
                          "phase difference needs stereo corpora")
-    band_draw = None
     if device_draw:
         mixer.enable_device_draw(0 if seed is None else seed)
-        band_draw = _du.DeviceAugmentDraw(mixer.device, (0 if seed is None else seed) + 1, filter_bins) if training else None
-    gain_draw = None
-    if training and _du.wants_filtaug(config.name):   # (the validation set never is)
-        gain_draw = _du.FilterAugmentDraw(mixer.device, _du.filtaug_kind(config.name), (0 if seed is None else seed) + 2, device_draw,
-                                          None if seed is not None else np.random.default_rng())
-    speed = training and _du.wants_speed(config.name)
-    if speed:   # the voice corpus is perturbed anew now and once per epoch (the validation set never is)
+    draws = BatchDraws(tokens, training, mixer.device, seed, device_draw, plan.n_bins)
+    # the voice corpus is augmented anew now and once per epoch (the validation set never is)
+    respeed = rereverb = None
+    if training and tokens.speed:
         mixer.enable_speed()
-        mixer.respeed()
-    reverb = training and _du.wants_reverb(config.name)
-    if reverb:   # likewise: fresh room impulse responses now and once per epoch
-        if _du.wants_shoebox(config.name):   # image-source responses of one random room per voice, shared by the channels
-            mixer.enable_reverb(model="shoebox")
-        else:
-            mixer.enable_reverb()
-        mixer.rereverb()
+        respeed = mixer.respeed
+        respeed()
+    if training and tokens.reverb:
+        mixer.enable_reverb(model="shoebox" if tokens.shoebox else "noise")
+        rereverb = mixer.rereverb
+        rereverb()
 
     def gen():
-        reaugment = _every_epoch(mixer.respeed, config.steps_per_epoch) if speed else (lambda: None)
-        if reverb:
-            reaugment = _every_epoch(mixer.rereverb, config.steps_per_epoch)
+        reaugment = _every_epoch(respeed or rereverb, config.steps_per_epoch)
         while True:
             reaugment()
             wav, y = mixer.mix(config.batch_size)
             _, y = to_frame_labels(None, y)
             if config.n_chan == 1 and wav.shape[1] == 2:
                 wav = wav[:, :1] + wav[:, 1:]            # true down-mix (NOT the reference's broadcast mono_chan: see docstring)
-            tb, fb = _draw_bands(band_draw, training, rng, filter_bins, int(wav.shape[0]), config.n_frame, plan.n_bins)
-            kw = {} if gain_draw is None else {"mel_gain": gain_draw(int(wav.shape[0]), config.n_mels)}   # FilterAugment
-            if ipd:   # channels 0-1 as below; the batch's spectrum is materialised for the phase channels (never compressed or gained)
-                wav = wav.contiguous()
-                tb, fb = (None if v is None else torch.as_tensor(v).to(wav.device, torch.int32) for v in (tb, fb))  # one upload for both kernels
-                if do_pcen:
-                    mel = plan.wav_to_logmel(wav, t_bands=tb, f_bands=fb, minmax=False, log=False, **kw)
-                    mel = _fe.pcen(mel, out=mel)
-                else:
-                    mel = plan.wav_to_logmel(wav, t_bands=tb, f_bands=fb, minmax=do_minmax, log=True, **kw)
-                yield torch.cat([mel, plan.ipd(plan.stft(wav), t_bands=tb, f_bands=fb)], dim=-1), y
-            elif do_pcen:   # the raw mel out of the fused kernel, then PCEN in place
-                mel = plan.wav_to_logmel(wav.contiguous(), t_bands=tb, f_bands=fb, minmax=False, log=False, **kw)
-                yield _fe.pcen(mel, out=mel), y
-            elif raw_mel:
-                yield plan.wav_to_logmel(wav.contiguous(), t_bands=tb, f_bands=fb, minmax=False, log=False, **kw), y
-            else:
-                yield plan.wav_to_logmel(wav.contiguous(), t_bands=tb, f_bands=fb, minmax=do_minmax, log=True, **kw), y
+            tb, fb, gain = draws(int(wav.shape[0]), config.n_frame, config.n_mels)
+            yield wave_features(plan, compression, do_minmax, wav.contiguous(), tb, fb, gain, None, tokens.ipd), y
 
-    pipeline = Dataset.from_generator(gen)
-    if config.v in label_downsample_model:
-        pipeline = pipeline.map(label_downsample(32))
-    elif config.v == 5:
-        pipeline = pipeline.map(label_downsample(config.n_frame // (config.n_frame * 256 // 16000)))
-    if config.loss.upper() in ('MSE', 'MAE'):
-        pipeline = pipeline.map(multiply_label(config.mse_multiplier))
-    dataset = pipeline.prefetch(AUTOTUNE)
+    dataset = _label_tail(Dataset.from_generator(gen), config, compressed=True)
     dataset.mixer = mixer   # (for inspection: the resident corpus, its draws and - 'speed' / 'reverb' runs - the current voices)
     return dataset
 
@@ -595,7 +537,9 @@ class WaveFrontend:
     + magphase_to_mel + minmax + log_on_mel without materialising the spectrum.
     compression='pcen': the fused kernel stops at the mel magnitudes and `frontend.pcen` follows in place (a second
     launch) instead of min-max + log; compression='mel': the mel magnitudes themselves, for a model whose first layer is the
-    trainable `PCEN` (a 'pcen_learn' run name)."""
+    trainable `PCEN` (a 'pcen_learn' run name).
+    `features(wav, t_bands=None, f_bands=None, out=None)`: the features of `wav` with the given bands (no draws) -
+    `wave_features` bound to this plan and compression, with nothing in between."""
 
     def __init__(self, n_fft=1024, hop=256, n_mels=64, sample_rate=16000, n_chan=1, batch=64, length=130816,
                  device=None, training=True, filter_bins: int = 0, do_minmax: bool = True,
@@ -610,6 +554,7 @@ class WaveFrontend:
         self.device_draw = device_draw
         self.rng = np.random.default_rng(seed)
         self._seed, self._ddraw = int(seed), None
+        self.features = functools.partial(wave_features, self.plan, compression, do_minmax)
 
     def draw_bands(self, batch: int, n_time: int):
         """Host draw (NumPy Generator): exact integer distributions of transforms.py:25-26."""
@@ -638,17 +583,6 @@ class WaveFrontend:
                 flt = np.tile(np.array([[[1, self.filter_bins]]], np.int32), (b, 1, 1))
                 fb = flt if fb is None else np.concatenate([fb, flt], axis=1)
         return self.features(wav, tb, fb, out=out)
-
-    def features(self, wav: torch.Tensor, t_bands=None, f_bands=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """The features of `wav` with the given bands (no draws): the fused kernel with min-max + log, or with
-        compression='pcen' the raw mel followed by PCEN in place, with 'mel' the raw mel alone.  Capturable into a hipGraph
-        in every form."""
-        if self.compression == 'mel':
-            return self.plan.wav_to_logmel(wav, minmax=False, log=False, t_bands=t_bands, f_bands=f_bands, out=out)
-        if self.compression == 'pcen':
-            mel = self.plan.wav_to_logmel(wav, minmax=False, log=False, t_bands=t_bands, f_bands=f_bands, out=out)
-            return _fe.pcen(mel, out=mel)
-        return self.plan.wav_to_logmel(wav, minmax=self.do_minmax, log=True, t_bands=t_bands, f_bands=f_bands, out=out)
 
 
 # ---------------------------------------------------------------------------

@@ -92,11 +92,11 @@ def test_host_draw_refuses_too_few_mel_rows():
 
 
 def test_token_parsing():
-    assert DU.wants_filtaug("run_filtaug") is True
-    assert DU.wants_filtaug("run_filter") is False
-    assert DU.wants_filtaug("") is False
-    assert DU.wants_filtaug("run_filtaug_linear_pcen") is True
-    assert DU.filtaug_kind("run_filtaug") == "step" and DU.filtaug_kind("run_filtaug_linear") == "linear"
+    assert DU.run_tokens("run_filtaug").filtaug == "step"
+    assert DU.run_tokens("run_filter").filtaug is None and DU.run_tokens("run_filter").filter is True
+    assert DU.run_tokens("").filtaug is None
+    assert DU.run_tokens("run_filtaug_linear_pcen").filtaug == "linear"
+    assert DU.run_tokens("run_filtaug_linear").filtaug == "linear" and DU.run_tokens("run_filtaug_linear").filter is False
     assert "filter" not in "run_filtaug_linear"      # the reference's stft_filter token is not triggered by it
 
 

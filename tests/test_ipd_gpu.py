@@ -203,8 +203,8 @@ def test_token_in_the_batched_datasets(dev, which, training):
         # band draw is the host draw the datasets make (seed + 1)
         cfg = _args(name)
         mixer = build(plain).mixer
-        filter_bins = int(round(200 / (16000 / 256))) if 'filter' in name else 0
-        tb, fb = S._draw_bands(None, training, np.random.default_rng(seed + 1), filter_bins, 2, 64, 257)
+        from challenge_amd import data_utils as D
+        tb, fb, _ = S.BatchDraws(D.run_tokens(name), training, dev, seed, False, 257)(2, 64, 40)
         plan = FE().FrontendPlan(512, 256, 40, 16000, 2, 2, 63 * 256, dev)
         mixed = mixer.mix(2)[0]
         spec = plan.stft(mixed.contiguous()) if which == "wave" else mixed

@@ -148,11 +148,49 @@ def test_torch_form_within_the_bound(f, m, user):
 # ---------------------------------------------------------------------------
 def test_token_and_input_channels():
     from challenge_amd import data_utils as D
-    assert D.wants_ipd("run_ipd") and D.wants_ipd("ipd_filter_pcen") and not D.wants_ipd("run_filter_pcen_learn") and not D.wants_ipd("")
+    wants = lambda name: D.run_tokens(name).ipd  # noqa: E731
+    assert wants("run_ipd") and wants("ipd_filter_pcen") and not wants("run_filter_pcen_learn") and not wants("")
+    assert wants("skipdrop") and not wants(None) and not D.run_tokens(type("NoName", (), {"n_chan": 2})()).ipd
     assert D.model_in_channels(_cfg("ipd")) == 4 and D.model_in_channels(_cfg("run")) == 2
     assert D.model_in_channels(_cfg("run", "--n_chan", "1")) == 1
-    D.check_ipd(_cfg("ipd_pcen_filter_filtaug_reverb_shoebox"))     # goes with every other token
-    D.check_ipd(_cfg("pcen_learn"))                                  # no token: nothing to refuse
+    assert D.run_tokens(_cfg("ipd_pcen_filter_filtaug_reverb_shoebox")).ipd     # goes with every other token
+    assert not D.run_tokens(_cfg("pcen_learn", "--n_chan", "1")).ipd             # no token: nothing to refuse
+
+
+def test_which_builder_honours_which_token():
+    """Every (builder, single token) pair of the refusal table is accepted or refused as stated here.  The grid was recorded
+    from the three builders while each still held its own chain of refusals, not read off the table."""
+    from challenge_amd import data_utils as D
+    from challenge_amd import sj_train as S
+    tokens = ('stretch', 'speed', 'reverb', 'filtaug', 'ipd')
+    honoured = {'make_dataset':        (False, False, False, False, False),      # noqa: E241
+                'make_device_dataset': (True,  False, False, True,  True),       # noqa: E241
+                'make_wave_dataset':   (False, True,  True,  True,  True)}       # noqa: E241
+    assert set(D.BUILDER_REFUSALS) == set(honoured)
+    for builder, row in D.BUILDER_REFUSALS.items():
+        assert tuple(row) == tokens
+        for token, want in zip(row, honoured[builder]):
+            cfg = _cfg("run_" + token)
+            assert getattr(D.run_tokens(cfg), token)
+            if want:
+                D.check_builder(D.run_tokens(cfg), builder)
+            else:
+                with pytest.raises(ValueError, match=f"asks for '{token}'"):
+                    D.check_builder(D.run_tokens(cfg), builder)
+            # ... and the builder itself: a refusal is that ValueError, raised before any corpus or device is touched; an
+            # honoured token gets past it (to a dataset on a GPU, to the mixer's demand for one without)
+            if builder == 'make_wave_dataset':
+                sources = S.synthetic_wave_sources(2, 3, n_bg=1, n_voice=2, n_noise=1)
+            else:
+                sources = S.synthetic_sources(2, 3, n_bg=1, n_voice=2, n_noise=1)
+            try:
+                getattr(S, builder)(cfg, training=True, sources=sources)
+                refused = False
+            except ValueError as exc:
+                refused = f"asks for '{token}'" in str(exc)
+            except RuntimeError:
+                refused = False
+            assert refused == (not want), (builder, token)
 
 
 def test_refusals():
@@ -254,9 +292,9 @@ def test_run_name_round_trips():
     for name in ("ipd", "run_ipd", "ipd_filter_pcen"):
         cfg = _cfg(name, "--n_mels", "40", "--n_frame", "128")
         full = F.run_name(cfg)[:-len('.h5')]      # (eval is given the name without the checkpoint suffix)
-        assert D.wants_ipd(full)
+        assert D.run_tokens(full).ipd
         back = _cfg(full, "--n_mels", "80", "--n_frame", "512", "--n_chan", "1")
         back = E.parse_name(back)
         assert (back.v, back.n_mels, back.n_chan, back.n_frame) == (9, 40, 2, 128)
         assert D.model_in_channels(back) == 4
-        D.check_ipd(back)
+        assert D.run_tokens(back).ipd

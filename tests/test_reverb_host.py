@@ -72,8 +72,9 @@ def test_fir_ref_agrees_with_the_explicit_loop():
 def test_wants_reverb_and_the_refusals():
     from challenge_amd import data_utils as D
     from challenge_amd import sj_train as S
-    assert D.wants_reverb("run_reverb") and D.wants_reverb("reverb") and D.wants_reverb("pcen_reverb_filter")
-    assert not D.wants_reverb("") and not D.wants_reverb("run_filter") and not D.wants_reverb("run_speed")
+    wants = lambda name: D.run_tokens(name).reverb  # noqa: E731
+    assert wants("run_reverb") and wants("reverb") and wants("pcen_reverb_filter")
+    assert not wants("") and not wants("run_filter") and not wants("run_speed")
     for name, want in (("", "minmax_log"), ("nominmax", "log"), ("pcen", "pcen"), ("pcen_learn", "pcen_learn")):
         assert D.feature_compression(name) == want == D.feature_compression(name + "_reverb")
     cfg = S.ARGS().get(['--name', 'run_reverb', '--n_frame', '64', '--batch_size', '2'])

@@ -127,9 +127,10 @@ def test_draw_shoebox_margins_and_reproducibility():
 def test_wants_shoebox_and_the_refusals():
     from challenge_amd import data_utils as D
     from challenge_amd import sj_train as S
-    assert D.wants_shoebox("run_reverb_shoebox") and D.wants_shoebox("shoebox") and not D.wants_shoebox("run_reverb")
-    assert not D.wants_shoebox("") and D.wants_reverb("run_reverb_shoebox")
-    D.check_shoebox("run_reverb_shoebox"), D.check_shoebox("run_reverb"), D.check_shoebox("run")
+    assert D.run_tokens("run_reverb_shoebox").shoebox and not D.run_tokens("run_reverb").shoebox
+    assert not D.run_tokens("").shoebox and D.run_tokens("run_reverb_shoebox").reverb and not D.run_tokens("run").shoebox
+    with pytest.raises(ValueError, match="without 'reverb'"):      # the bare token is found, and refused by the parse itself
+        D.run_tokens("shoebox")
     alone = S.ARGS().get(['--name', 'run_shoebox', '--n_frame', '64', '--batch_size', '2'])
     for training in (True, False):
         with pytest.raises(ValueError, match="without 'reverb'"):

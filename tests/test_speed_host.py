@@ -111,8 +111,9 @@ def test_sign_convention_rate_above_one_raises_the_pitch():
 def test_wants_speed_and_the_refusals():
     from challenge_amd import data_utils as D
     from challenge_amd import sj_train as S
-    assert D.wants_speed("run_speed") and D.wants_speed("speed") and D.wants_speed("pcen_speed_filter")
-    assert not D.wants_speed("") and not D.wants_speed("run_filter") and not D.wants_speed("run_stretch")
+    wants = lambda name: D.run_tokens(name).speed  # noqa: E731
+    assert wants("run_speed") and wants("speed") and wants("pcen_speed_filter")
+    assert not wants("") and not wants("run_filter") and not wants("run_stretch")
     for name, want in (("", "minmax_log"), ("nominmax", "log"), ("pcen", "pcen"), ("pcen_learn", "pcen_learn")):
         assert D.feature_compression(name) == want == D.feature_compression(name + "_speed") == D.feature_compression("speed_" + name)
     cfg = S.ARGS().get(['--name', 'run_speed', '--n_frame', '64', '--batch_size', '2'])

@@ -144,8 +144,9 @@ def test_shape_law_and_fp64_grid(n_frames):
 def test_wants_stretch_and_the_refusals():
     from challenge_amd import data_utils as D
     from challenge_amd import sj_train as S
-    assert D.wants_stretch("run_stretch") and D.wants_stretch("stretch") and D.wants_stretch("pcen_stretch_filter")
-    assert not D.wants_stretch("") and not D.wants_stretch("run_filter") and not D.wants_stretch("pcen_learn")
+    wants = lambda name: D.run_tokens(name).stretch  # noqa: E731
+    assert wants("run_stretch") and wants("stretch") and wants("pcen_stretch_filter")
+    assert not wants("") and not wants("run_filter") and not wants("pcen_learn")
     for name, want in (("", "minmax_log"), ("nominmax", "log"), ("pcen", "pcen"), ("pcen_learn", "pcen_learn"), ("filter", "minmax_log")):
         assert D.feature_compression(name) == want == D.feature_compression(name + "_stretch") == D.feature_compression("stretch_" + name)
     with pytest.raises(ValueError):
