@@ -248,7 +248,7 @@ __global__ __launch_bounds__(256) void k_conv0_bwd(const float* __restrict__ x, 
                     part[k] += g;
                     part[4 + k] = fmaf(g, (z[k] - mu[k]) * rs[k], part[4 + k]);
                 } else {
-                    const float dz = fmaf(a[k], g, fmaf(bq[k], z[k], dq[k]));
+                    const float dz = inv_m == 1.f ? 0.f : fmaf(a[k], g, fmaf(bq[k], z[k], dq[k]));  // one pixel: dz = 0 (as k_bn_relu_bwd_dx)
                     if constexpr (DZ) dzv[k] = dz;
 #pragma unroll
                     for (int c = 0; c < CIN; ++c)

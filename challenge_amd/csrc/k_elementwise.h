@@ -483,11 +483,13 @@ __global__ __launch_bounds__(256) void k_bn_relu_bwd_dx(const float* z, const fl
     const int C = 4 * C4;
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
         const float sg = (float)bn_sum(sums, C, c), sgx = (float)bn_sum(sums, C, C + c);
-        const float a = gamma[c] * rstd[c], b = -a * rstd[c] * sgx * inv_m;
+        // ONE row (inv_m == 1): the row is its own mean, dz is identically 0.  The general form leaves fma(a, g, -fl(a g)) there,
+        // the rounding residue of a g (2e-5 at rstd = 1 / sqrt(1e-5)): all four coefficients 0 make every dz an exact 0.
+        const float a = inv_m == 1.f ? 0.f : gamma[c] * rstd[c], b = -a * rstd[c] * sgx * inv_m;
         coef[c] = a;
         coef[C + c] = b;
         coef[2 * C + c] = -a * sg * inv_m - b * mean[c];
-        coef[3 * C + c] = beta[c] - mean[c] * a;
+        coef[3 * C + c] = inv_m == 1.f ? 0.f : beta[c] - mean[c] * a;
         if (blockIdx.x == 0) {
             dbeta[c] = sg;
             dgamma[c] = sgx;
@@ -671,11 +673,13 @@ __global__ __launch_bounds__(256) void k_bn_relu_pool_bwd_dx(const float* z, con
     const int C = 4 * C4;
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
         const float sg = (float)bn_sum(sums, C, c), sgx = (float)bn_sum(sums, C, C + c);
-        const float a = gamma[c] * rstd[c], b = -a * rstd[c] * sgx * inv_m;
+        // ONE row (inv_m == 1): the row is its own mean, dz is identically 0.  The general form leaves fma(a, g, -fl(a g)) there,
+        // the rounding residue of a g (2e-5 at rstd = 1 / sqrt(1e-5)): all four coefficients 0 make every dz an exact 0.
+        const float a = inv_m == 1.f ? 0.f : gamma[c] * rstd[c], b = -a * rstd[c] * sgx * inv_m;
         coef[c] = a;
         coef[C + c] = b;
         coef[2 * C + c] = -a * sg * inv_m - b * mean[c];
-        coef[3 * C + c] = beta[c] - mean[c] * a;
+        coef[3 * C + c] = inv_m == 1.f ? 0.f : beta[c] - mean[c] * a;
         if (blockIdx.x == 0) {
             dbeta[c] = sg;
             dgamma[c] = sgx;
