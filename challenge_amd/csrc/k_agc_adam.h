@@ -53,13 +53,15 @@ __global__ __launch_bounds__(256) void k_agc_clip_adam(const iris_agc_adam_row* 
                 }
             }
             const float p_norm = sqrtf(wave_sum(sp)), g_norm = sqrtf(wave_sum(sg));
-            const float max_norm = fmaxf(p_norm, eps_agc) * clip_factor;
-            scale = g_norm < max_norm ? 1.0f : max_norm / fmaxf(g_norm, 1e-6f);
+            // (a NaN norm stays NaN through both floors, as in torch.clamp / tf.maximum: fmaxf would drop it and hand a unit with one
+            // NaN gradient a factor of max_norm / 1e-6 for its other elements)
+            const float max_norm = (p_norm < eps_agc ? eps_agc : p_norm) * clip_factor;
+            scale = g_norm < max_norm ? 1.0f : max_norm / (g_norm < 1e-6f ? 1e-6f : g_norm);
         }
         auto one = [&](float& pp, float& gg, float& mm, float& vv) {
             // (scale == 1 leaves the gradient's bits alone, as k_agc_clip does by skipping the unit)
             float x = scale == 1.0f ? gg : gg * scale;
-            if (clamp) x = fminf(fmaxf(x, -clipvalue), clipvalue);
+            if (clamp) x = clamp_keep_nan(x, clipvalue);
             gg = x;
             mm = mm + (x - mm) * w1;
             vv = beta2 * vv + w2 * x * x;

@@ -152,6 +152,10 @@ __global__ void k_mask_apply(T* x, size_t n_outer, size_t axis_len, size_t n_inn
 // ---------------------------------------------------------------------------
 // adaptive gradient clipping + clipvalue, one wave per output unit (row)
 // ---------------------------------------------------------------------------
+// clamp(x, -c, +c) as torch.clamp / tf.clip_by_value define it: a NaN stays a NaN (fminf(fmaxf(NaN, -c), c) is -c - a diverged
+// gradient would reach the optimiser as -clipvalue in every element)
+__device__ __forceinline__ float clamp_keep_nan(float x, float c) { return x < -c ? -c : (x > c ? c : x); }
+
 __global__ __launch_bounds__(256) void k_agc_clip(const iris_agc_row* rows, size_t n_rows, float clip_factor,
                                                   float eps, float clipvalue) {
     const int lane = threadIdx.x & 63;
@@ -177,8 +181,10 @@ __global__ __launch_bounds__(256) void k_agc_clip(const iris_agc_row* rows, size
             }
         }
         const float p_norm = sqrtf(wave_sum(sp)), g_norm = sqrtf(wave_sum(sg));
-        const float max_norm = fmaxf(p_norm, eps) * clip_factor;
-        const float scale = g_norm < max_norm ? 1.0f : max_norm / fmaxf(g_norm, 1e-6f);
+        // (a NaN norm stays NaN through both floors, as in torch.clamp / tf.maximum: fmaxf would drop it and hand a unit with one
+        // NaN gradient a factor of max_norm / 1e-6 for its other elements)
+        const float max_norm = (p_norm < eps ? eps : p_norm) * clip_factor;
+        const float scale = g_norm < max_norm ? 1.0f : max_norm / (g_norm < 1e-6f ? 1e-6f : g_norm);
         const bool clamp = clipvalue > 0.f;
         if (scale == 1.0f && !clamp) continue;  // wave-uniform
         if (vec) {
@@ -186,17 +192,17 @@ __global__ __launch_bounds__(256) void k_agc_clip(const iris_agc_row* rows, size
                 float4 b = *reinterpret_cast<float4*>(g + i);
                 b.x *= scale; b.y *= scale; b.z *= scale; b.w *= scale;
                 if (clamp) {
-                    b.x = fminf(fmaxf(b.x, -clipvalue), clipvalue);
-                    b.y = fminf(fmaxf(b.y, -clipvalue), clipvalue);
-                    b.z = fminf(fmaxf(b.z, -clipvalue), clipvalue);
-                    b.w = fminf(fmaxf(b.w, -clipvalue), clipvalue);
+                    b.x = clamp_keep_nan(b.x, clipvalue);
+                    b.y = clamp_keep_nan(b.y, clipvalue);
+                    b.z = clamp_keep_nan(b.z, clipvalue);
+                    b.w = clamp_keep_nan(b.w, clipvalue);
                 }
                 *reinterpret_cast<float4*>(g + i) = b;
             }
         } else {
             for (long i = lane; i < len; i += kWave) {
                 float v = g[i] * scale;
-                if (clamp) v = fminf(fmaxf(v, -clipvalue), clipvalue);
+                if (clamp) v = clamp_keep_nan(v, clipvalue);
                 g[i] = v;
             }
         }

@@ -43,6 +43,10 @@ class FusedAGC:
     def __init__(self, params):
         self.params = [p for p in params]
         self._adam = None   # a torch.optim.Adam whose update rides in the same launch (`adam_step`), or None
+        # the attached optimiser's step counters when they are KNOWN to hold one value (`_counters_uniform`): (the tensors, their
+        # autograd versions), or None; `_counters_apart`: the tensors that were found to differ
+        self._counters = None
+        self._counters_apart = None
         self._sig = None
         self._table = None
         self._slow = []
@@ -170,7 +174,8 @@ class FusedAGC:
 
     def attach_adam(self, opt) -> bool:
         """Let `adam_step` run `opt`'s update: creates the optimiser state torch would create at its first step (same keys,
-        dtypes and layouts: state_dict() / load_state_dict() stay interchangeable).  False: not an optimiser this kernel covers."""
+        dtypes and layouts: state_dict() / load_state_dict() stay interchangeable).  False: not an optimiser this kernel covers, or
+        one whose per-parameter step counters differ (`_counters_uniform`)."""
         if not self.adam_fusable(opt) or [id(p) for p in opt.param_groups[0]['params']] != [id(p) for p in self.params]:
             return False
         for p in self.params:
@@ -183,13 +188,49 @@ class FusedAGC:
                     and st['exp_avg'].stride() == p.stride() and st['exp_avg_sq'].stride() == p.stride()
                     and st['exp_avg'].dtype == torch.float32 and st['exp_avg_sq'].dtype == torch.float32):
                 return False
+        # (GraphedTrainStep attaches once before it captures: inside the capture the answer is already known)
+        if not self._counters_uniform([opt.state[p]['step'] for p in self.params]):
+            return False
         if self._adam is not opt:
             self._reset_tables(opt)
         return True
 
+    def _counters_uniform(self, steps) -> bool:
+        """Do the optimiser's per-parameter step counters hold ONE value?  The launch reads one counter for every row, torch's Adam
+        each parameter's own; they come apart when a step went through `optimizer.step()` while a parameter had no gradient, or
+        with a loaded state.  The answer is read from the device once (one host synchronisation) and kept for as long as the
+        counters are the same tensors at the autograd versions this object left them at - every in-place write from outside,
+        torch's own step included, moves a version; a replaced state brings new tensors - so the steady-state step compares a few
+        dozen integers and never waits for the device.  Inside a capture nothing can be read: unknown counts as apart.
+        The two verdicts are kept differently, on purpose.  "Equal" is tied to the versions: believing it wrongly would apply a
+        wrong bias correction.  "Apart" is tied to the tensors alone: torch's own step moves every version, so tying it to them
+        would read the device in every step of a state that stays apart; the price is that counters equalised IN PLACE afterwards
+        (fill_ / copy_ on the same tensors) keep the two-launch path, which is right, only slower, until the state is replaced
+        (load_state_dict brings new tensors) or another optimiser is attached.  Likewise a model that sends a parameter down the
+        torch path every step (`_slow`) lets torch's step move the versions, and each `attach_adam` then re-reads the counters:
+        one host synchronisation per step on a path that already runs four launches instead of one."""
+        known = self._counters
+        if known is not None and len(known[0]) == len(steps) and all(a is b for a, b in zip(known[0], steps)) \
+                and known[1] == [t._version for t in steps]:
+            return True
+        self._counters = None
+        apart = self._counters_apart
+        if apart is not None and len(apart) == len(steps) and all(a is b for a, b in zip(apart, steps)):
+            return False
+        self._counters_apart = None
+        if not steps or torch.cuda.is_current_stream_capturing():
+            return False
+        values = torch.stack([t.detach().reshape(()) for t in steps])
+        if bool((values == values[0]).all()):
+            self._counters = (list(steps), [t._version for t in steps])
+            return True
+        self._counters_apart = list(steps)
+        return False
+
     def adam_step(self, clip_factor=0.01, eps=1e-3, clipvalue=None, use_agc=True) -> bool:
-        """AGC + clipvalue + the attached optimiser's Adam update in ONE launch (iris_agc_clip_adam).  False (nothing done): a
-        parameter without a gradient or with a layout the kernel does not take - the caller then runs the two steps apart."""
+        """AGC + clipvalue + the attached optimiser's Adam update in ONE launch (iris_agc_clip_adam).  False (nothing done, no counter
+        moved): a parameter without a gradient or with a layout the kernel does not take, or step counters that differ between
+        the parameters (`_counters_uniform`) - the caller then runs the two steps apart."""
         import ctypes as C
         if getattr(self, '_frozen', False):
             raise RuntimeError("FusedAGC: this instance belongs to a captured hipGraph (GraphedTrainStep) and cannot be called eagerly")
@@ -211,7 +252,10 @@ class FusedAGC:
             return False
         g = opt.param_groups[0]
         steps = [opt.state[p]['step'] for p in self.params]
+        if not self._counters_uniform(steps):   # the kernel applies ONE bias correction: torch's path, each parameter's own counter
+            return False
         torch._foreach_add_(steps, 1)
+        self._counters = (self._counters[0], [t._version for t in steps])
         lr = g['lr']
         dev = self.params[0].device
         from . import _native as N
@@ -222,6 +266,8 @@ class FusedAGC:
                                             float(g['betas'][0]), float(g['betas'][1]), float(g['eps']), steps[0].data_ptr(),
                                             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
         N.check(rc, "iris_agc_clip_adam")
+        # the weights have moved behind their autograd versions: every Winograd packing of them is stale (harmless in a capture)
+        _PACKS.invalidate()
         return True
 
     def reserve(self) -> None:
@@ -536,8 +582,9 @@ class _PackBook:
     asked for it is packed on the spot, as before, into a buffer this book keeps - and remembered; from the next forward pass on,
     `prepack()` (called by CustomModel.forward in training mode) packs everything remembered in one launch per kind, and `take`
     hands those buffers out.  A packing is used only while the weight's autograd version is the one it was packed at (any in-place
-    update - the optimiser step, load_state_dict, SWA - makes it stale and `take` packs again), so a layer called on its own, two
-    forwards before one backward, or an evaluation in between all stay correct.  Entries are keyed by the weight's storage address,
+    update - torch's optimiser step, load_state_dict, SWA - makes it stale and `take` packs again; the one-launch update of
+    `FusedAGC.adam_step` writes through raw pointers and calls `invalidate` itself, as a graph replay's caller does), so a layer
+    called on its own, two forwards before one backward, or an evaluation in between all stay correct.  Entries are keyed by the weight's storage address,
     shape and strides, not by the tensor object: GraphedTrainStep runs the model on ALIASES of the parameters over the same storage
     (they share the version counter).  The buffers persist, so a captured graph replays the one-launch packing and the
     convolutions on fixed addresses."""

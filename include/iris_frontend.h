@@ -347,6 +347,8 @@ int iris_mask_apply(void* x, size_t n_outer, size_t axis_len, size_t n_inner, in
  *     max_norm = max(||param||, eps) * clip_factor
  *     grad    *= max_norm / max(||grad||, 1e-6)      where ||grad|| >= max_norm
  *     grad     = clamp(grad, -clipvalue, +clipvalue)  when clipvalue > 0
+ * A NaN anywhere in a row's gradient makes that whole row NaN, as torch.clamp / tf.maximum do (neither max nor the clamp drops it);
+ * other rows are untouched by it.
  * Runs on the current HIP device.
  */
 typedef struct {
