@@ -184,7 +184,8 @@ class GraphedTrainStep:
             saved = ([t.detach().clone() for t in tensors], tensors,
                      {id(p): {k: (v.detach().clone() if torch.is_tensor(v) else v) for k, v in opt.state.get(p, {}).items()}
                       for g in opt.param_groups for p in g['params']},
-                     {id(t): t.clone() for t in (self.metrics.state_tensors() if self.metrics is not None else [])})
+                     {id(t): t.clone() for t in (self.metrics.state_tensors() if self.metrics is not None else [])},
+                     [(t, t.detach().clone()) for t in (model._ema.state_tensors() if model._ema is not None else [])])
 
         def restore():
             opt.zero_grad(set_to_none=True)
@@ -202,6 +203,10 @@ class GraphedTrainStep:
                 if self.metrics is not None:   # F1 counts and epoch accumulators: the warm-up steps counted nothing
                     for t in self.metrics.state_tensors():
                         t.copy_(saved[3][id(t)]) if id(t) in saved[3] else t.zero_()
+                for t, old in saved[4]:   # the weight EMA's shadows: the warm-up steps averaged nothing
+                    t.copy_(old)
+                if model._ema is not None:
+                    model._ema.bump_generation()
             model.bump_generation()
             torch.cuda.synchronize(dev)
 
@@ -237,6 +242,8 @@ class GraphedTrainStep:
         self._agc = FusedAGC(list(model.parameters())) if model.use_agc else None
         if self._agc is not None:
             self._agc.attach_adam(opt)   # (before `reserve`: an attached optimiser makes the table five columns wide)
+            if model._ema is not None:   # (and a weight EMA six)
+                model._ema.attach(self._agc)
             self._agc.reserve()
         self._flats, self._buckets = [], []
         if self.world:
@@ -331,10 +338,11 @@ class GraphedTrainStep:
                 raise RuntimeError("GraphedTrainStep: a parameter received no gradient - its bucket was never exchanged")
             for w in works:
                 w.wait()                      # the capture stream joins RCCL's stream again
-        stepped = False
+        stepped, averaged = False, False
         if model.use_agc:
-            if self._agc.attach_adam(opt):   # AGC + clipvalue + Adam in one launch (hip_autograd.FusedAGC.adam_step)
+            if self._agc.attach_adam(opt):   # AGC + clipvalue + Adam (+ the weight EMA) in one launch (hip_autograd.FusedAGC.adam_step)
                 stepped = self._agc.adam_step(0.01, 1e-3, model.clipvalue)
+                averaged = stepped and self._agc.ema_attached
             if not stepped:
                 self._agc(0.01, 1e-3, model.clipvalue)
             self._agc.freeze()
@@ -342,6 +350,8 @@ class GraphedTrainStep:
             torch.nn.utils.clip_grad_value_([p for p in model.parameters() if p.grad is not None], model.clipvalue)
         if not stepped:
             opt.step()
+        if model._ema is not None and not averaged:   # the same definition with torch ops: captured like everything else
+            model._ema.update(opt)
         opt.zero_grad(set_to_none=True)
         self.loss = loss.detach()
         self._pool_marks = _ZERO_POOL.marks(dev) if SW.ZERO_POOL else {}
@@ -354,6 +364,8 @@ class GraphedTrainStep:
         if self._pool_marks:
             _ZERO_POOL.mark_dirty(self._pool_marks)   # the replay has written into the zero pool behind its back
         self.model.bump_generation()  # a replay moves parameters and BatchNorm statistics behind ATen's back
+        if self.model._ema is not None:
+            self.model._ema.bump_generation()   # and the weight EMA's shadows
         if self.metric_out:
             return {'loss': self.loss, **self.metric_out}
         return {'loss': self.loss}
@@ -375,7 +387,8 @@ def graph_step_possible(model: "CustomModel") -> bool:
 
 def fit(model: CustomModel, train_set, epochs, steps_per_epoch, validation_data=None, validation_steps=16,
         scheduler=None, csv_path=None, checkpoint_path=None, patience=None, rank=0, world=1, verbose=True,
-        swa=None, graph: Optional[bool] = None, checkpoint_monitor: Optional[str] = None, callbacks=()):
+        swa=None, graph: Optional[bool] = None, checkpoint_monitor: Optional[str] = None, callbacks=(), ema=None,
+        ema_checkpoint_path=None):
     """Minimal Keras-fit equivalent for this path: per-epoch LR schedule, CSV log,
     best-val-loss checkpoint, early stopping, TerminateOnNaN (sj_train.py:489-519).
     Compiled metrics (`model.compile(metrics=...)`) are accumulated on the device and read once per epoch: rows gain their names
@@ -387,9 +400,18 @@ def fit(model: CustomModel, train_set, epochs, steps_per_epoch, validation_data=
     capturable optimiser (make_optimizer(..., capturable=True)), batches of one shape, under DDP the RCCL backend; a batch of
     another shape (a ragged last one) takes the eager step.  The step then costs what its kernels cost (10 ms per batch of 64)
     however slow the host is at launching ~260 kernels.  A capture that fails is reported ONCE (warnings.warn, every rank) and
-    the run goes on eagerly - on every rank alike, from the state the model had before the attempt."""
+    the run goes on eagerly - on every rank alike, from the state the model had before the attempt.
+    `ema`: the ema.WeightEMA the model was compiled with (`model.compile(..., ema=ema)`; its module compiled by `ema.compile`).
+    After the live model's validation pass a second one runs over the same validation batches (copies: nothing more is drawn from
+    `validation_data`) on the EMA module with the live BatchNorm statistics copied in, all-reduced like the first; the row gains
+    'val_ema_loss' and the 'val_ema_*' metrics.  Everything the
+    live model's row, early stopping and checkpoint depend on is computed as without it.  `ema_checkpoint_path` is written when
+    'val_ema_<the checkpoint's monitor>' improves strictly."""
     best, bad, history = math.inf, 0, []
     best_ckpt = math.inf
+    best_ema = math.inf
+    if ema is not None and model._ema is not ema:
+        raise ValueError("fit: `ema` must be the WeightEMA the model was compiled with (model.compile(..., ema=ema))")
     ms = model._metrics
 
     def metric_sums(phase, dev):
@@ -437,6 +459,8 @@ def fit(model: CustomModel, train_set, epochs, steps_per_epoch, validation_data=
         for _ in range(steps_per_epoch):
             losses.append(one_step(next(it))['loss'].clone() if graph else one_step(next(it))['loss'])
         loss = torch.stack(losses).mean()
+        if ema is not None:
+            ema.bump_generation()   # the shadows moved behind ATen's back all epoch: `predict` on the EMA module rebuilds its engine
         # The one place per epoch where the frontend plans' status words are read for certain (the hot path also reports a
         # failed earlier launch at the plan's next call, without a sync): EpilogueTimeout naming the plan instead of training
         # on NaN features.  Under DDP the failure of ONE rank must not leave the others waiting in the collectives below, so
@@ -476,7 +500,14 @@ def fit(model: CustomModel, train_set, epochs, steps_per_epoch, validation_data=
             break
         if validation_data is not None:
             vit = iter(validation_data)
-            vl = torch.stack([model.test_step(next(vit))['loss'] for _ in range(validation_steps)]).mean()
+            kept = [] if ema is not None else None   # the EMA pass sees the SAME batches: copies, and no further draw from the set
+
+            def vbatch():
+                batch = next(vit)
+                if kept is not None:
+                    kept.append(tuple(t.clone() if torch.is_tensor(t) else t for t in batch) if isinstance(batch, (tuple, list)) else batch)
+                return batch
+            vl = torch.stack([model.test_step(vbatch())['loss'] for _ in range(validation_steps)]).mean()
             if coll:  # every rank validates its own shard: the monitored value is the mean over ranks
                 torch.distributed.all_reduce(vl)
                 vl = vl / world
@@ -486,6 +517,25 @@ def fit(model: CustomModel, train_set, epochs, steps_per_epoch, validation_data=
                 host = torch.cat([vl.double().view(1), metric_sums('val', vl.device)]).tolist()
                 row['val_loss'] = host[0]
                 row.update(ms.epoch_values(host[1:], 'val_'))
+            if ema is not None:   # the second pass: the averaged weights under the live model's BatchNorm statistics
+                ema.copy_buffers(model)
+                ems = ema.module._metrics
+                if ems is not None:
+                    ems.reset()
+                evl = torch.stack([ema.module.test_step(batch)['loss'] for batch in kept]).mean()
+                if coll:
+                    torch.distributed.all_reduce(evl)
+                    evl = evl / world
+                if ems is None:
+                    row['val_ema_loss'] = float(evl)
+                else:
+                    acc = ems.accum(evl.device, 'val')
+                    if coll:
+                        acc = acc.clone()
+                        torch.distributed.all_reduce(acc)
+                    host = torch.cat([evl.double().view(1), acc]).tolist()
+                    row['val_ema_loss'] = host[0]
+                    row.update(ems.epoch_values(host[1:], 'val_ema_'))
         history.append(row)
         if swa is not None:
             swa.on_epoch_end(epoch, model)
@@ -503,6 +553,13 @@ def fit(model: CustomModel, train_set, epochs, steps_per_epoch, validation_data=
             save = cm is not None and cm < best_ckpt
             if save:
                 best_ckpt = cm
+        save_ema = False
+        if ema is not None:   # the EMA's own best-only checkpoint, on the EMA pass's twin of the checkpoint's monitor
+            name = checkpoint_monitor if checkpoint_monitor is not None else 'val_loss'
+            em = row.get('val_ema_' + name[len('val_'):]) if name.startswith('val_') else None
+            save_ema = em is not None and em < best_ema
+            if save_ema:
+                best_ema = em
         if rank == 0:
             if verbose:
                 print(row)
@@ -515,6 +572,8 @@ def fit(model: CustomModel, train_set, epochs, steps_per_epoch, validation_data=
                     w.writerow(row)
             if save and checkpoint_path:
                 torch.save(model.state_dict(), checkpoint_path)
+            if save_ema and ema_checkpoint_path:
+                torch.save(ema.state_dict(), ema_checkpoint_path)
         for cb in callbacks:
             cb.on_epoch_end(epoch, model)
         stop = patience is not None and not improved and bad >= patience  # Keras EarlyStopping: wait >= patience, tested on a non-improving epoch

@@ -43,6 +43,7 @@ class FusedAGC:
     def __init__(self, params):
         self.params = [p for p in params]
         self._adam = None   # a torch.optim.Adam whose update rides in the same launch (`adam_step`), or None
+        self._ema = None    # (shadow parameters, decay): a weight EMA that rides in that launch too (`attach_ema`), or None
         # the attached optimiser's step counters when they are KNOWN to hold one value (`_counters_uniform`): (the tensors, their
         # autograd versions), or None; `_counters_apart`: the tensors that were found to differ
         self._counters = None
@@ -96,10 +97,13 @@ class FusedAGC:
             table[:, 0] = np.array([p.data_ptr() for p in fast], np.int64)[rep] + offs
             table[:, 1] = np.array([p.grad.data_ptr() for p in fast], np.int64)[rep] + offs
             table[:, 2] = length
-            if cols == 5:   # iris_agc_adam_row: the two moments lie in the parameter's own layout
+            if cols >= 5:   # iris_agc_adam_row: the two moments lie in the parameter's own layout
                 st = self._adam.state
                 table[:, 3] = np.array([st[p]['exp_avg'].data_ptr() for p in fast], np.int64)[rep] + offs
                 table[:, 4] = np.array([st[p]['exp_avg_sq'].data_ptr() for p in fast], np.int64)[rep] + offs
+            if cols == 6:   # iris_agc_adam_ema_row: and so does the parameter's shadow
+                shadow = {id(p): e for p, e in zip(self.params, self._ema[0])}
+                table[:, 5] = np.array([shadow[id(p)].data_ptr() for p in fast], np.int64)[rep] + offs
         recs = [table]
         table = np.concatenate(recs) if recs else np.zeros((0, cols), np.int64)
         # pinned staging + asynchronous copy: legal while a hipGraph is being captured (it becomes a copy node of the graph).
@@ -139,14 +143,22 @@ class FusedAGC:
     def _signature(self):
         """(parameter address, gradient address, gradient strides) per parameter: a gradient buffer handed back at the same
         address in another layout must not reuse a table built for the old one (fast / slow classification, row stride).
-        With an optimiser attached: + the address of its first moment (a replaced state means a new table)."""
+        With an optimiser attached: + the address of its first moment (a replaced state means a new table); with a weight EMA
+        attached as well: + the address of the parameter's shadow."""
         adam = self._adam
+        if adam is not None and self._ema is not None:
+            return tuple((p.data_ptr(),) + ((-1, ()) if p.grad is None else (p.grad.data_ptr(), tuple(p.grad.stride())))
+                         + ((adam.state[p]['exp_avg'].data_ptr(),) if 'exp_avg' in adam.state.get(p, {}) else ()) + (e.data_ptr(),)
+                         for p, e in zip(self.params, self._ema[0]))
         return tuple((p.data_ptr(),) + ((-1, ()) if p.grad is None else (p.grad.data_ptr(), tuple(p.grad.stride())))
                      + ((adam.state[p]['exp_avg'].data_ptr(),) if adam is not None and 'exp_avg' in adam.state.get(p, {}) else ())
                      for p in self.params)
 
     def _cols(self) -> int:
-        return 5 if self._adam is not None else 3
+        """3: iris_agc_row; 5: iris_agc_adam_row (an optimiser attached); 6: iris_agc_adam_ema_row (and a weight EMA)."""
+        if self._adam is None:
+            return 3
+        return 6 if self._ema is not None else 5
 
     def _reset_tables(self, adam) -> None:
         """Another table format from here on: forget the cached tables (their arena slots are reused from the first, so nothing
@@ -154,6 +166,37 @@ class FusedAGC:
         if self._cache and self.params and self.params[0].is_cuda:
             torch.cuda.synchronize(self.params[0].device)
         self._adam, self._sig, self._cache = adam, None, {}
+
+    # ---- a weight EMA in the optimiser's launch -------------------------------------------------------------------------------
+    @property
+    def ema_attached(self) -> bool:
+        return self._ema is not None
+
+    def attach_ema(self, shadow_params, decay: float = 0.0) -> bool:
+        """Let `adam_step` keep an exponential moving average of the weights in the same launch (iris_agc_clip_adam_ema):
+        `shadow_params[i]` is the average of `params[i]` - a float32 device tensor of its shape and strides that takes no gradient
+        (`ema.WeightEMA` owns them) - and the table becomes six columns wide.  None detaches: five columns and the old entry point
+        again.  False (and detached): shadows the kernel cannot address row by row as it addresses the parameters."""
+        if shadow_params is None:
+            if self._ema is not None:
+                self._ema = None
+                self._reset_tables(self._adam)
+            return False
+        if not (0.0 <= float(decay) < 1.0):
+            raise ValueError(f"FusedAGC.attach_ema: decay {decay} outside [0, 1)")
+        cur = self._ema
+        if cur is not None and cur[0] is shadow_params:   # (the steady state: the same list every step)
+            self._ema = (shadow_params, float(decay))
+            return True
+        shadow = list(shadow_params)
+        ok = len(shadow) == len(self.params) and all(
+            e.is_cuda and e.device == p.device and e.dtype == torch.float32 and p.dtype == torch.float32 and e.shape == p.shape
+            and e.stride() == p.stride() and not e.requires_grad and e.data_ptr() != p.data_ptr() for p, e in zip(self.params, shadow))
+        if not ok:
+            return self.attach_ema(None)
+        self._ema = (shadow_params if isinstance(shadow_params, list) else shadow, float(decay))
+        self._reset_tables(self._adam)
+        return True
 
     # ---- the optimiser's update in the same launch (round 6) -----------------------------------------------------------------
     @staticmethod
@@ -228,9 +271,10 @@ class FusedAGC:
         return False
 
     def adam_step(self, clip_factor=0.01, eps=1e-3, clipvalue=None, use_agc=True) -> bool:
-        """AGC + clipvalue + the attached optimiser's Adam update in ONE launch (iris_agc_clip_adam).  False (nothing done, no counter
-        moved): a parameter without a gradient or with a layout the kernel does not take, or step counters that differ between
-        the parameters (`_counters_uniform`) - the caller then runs the two steps apart."""
+        """AGC + clipvalue + the attached optimiser's Adam update in ONE launch (iris_agc_clip_adam; with a weight EMA attached,
+        iris_agc_clip_adam_ema, which updates the shadows too).  False (nothing done, no counter moved, no shadow touched): a
+        parameter without a gradient or with a layout the kernel does not take, or step counters that differ between the
+        parameters (`_counters_uniform`) - the caller then runs the steps apart."""
         import ctypes as C
         if getattr(self, '_frozen', False):
             raise RuntimeError("FusedAGC: this instance belongs to a captured hipGraph (GraphedTrainStep) and cannot be called eagerly")
@@ -248,7 +292,7 @@ class FusedAGC:
                     self._cache.clear()
                 self._build()
                 self._cache[self._sig] = (self._table, self._slow, getattr(self, '_host_table', None))
-        if self._slow or self._table.shape[1] != 5:
+        if self._slow or self._table.shape[1] != self._cols():
             return False
         g = opt.param_groups[0]
         steps = [opt.state[p]['step'] for p in self.params]
@@ -259,13 +303,16 @@ class FusedAGC:
         lr = g['lr']
         dev = self.params[0].device
         from . import _native as N
+        head = (self._table.data_ptr(), int(self._table.shape[0]), float(clip_factor), float(eps), float(clipvalue or 0.0), 1 if use_agc else 0,
+                lr.data_ptr() if torch.is_tensor(lr) else None, 0.0 if torch.is_tensor(lr) else float(lr), float(g['betas'][0]),
+                float(g['betas'][1]), float(g['eps']), steps[0].data_ptr())
         with torch.cuda.device(dev):
-            rc = N.lib().iris_agc_clip_adam(self._table.data_ptr(), int(self._table.shape[0]), float(clip_factor), float(eps),
-                                            float(clipvalue or 0.0), 1 if use_agc else 0,
-                                            lr.data_ptr() if torch.is_tensor(lr) else None, 0.0 if torch.is_tensor(lr) else float(lr),
-                                            float(g['betas'][0]), float(g['betas'][1]), float(g['eps']), steps[0].data_ptr(),
-                                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        N.check(rc, "iris_agc_clip_adam")
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            if self._ema is None:
+                name, rc = "iris_agc_clip_adam", N.lib().iris_agc_clip_adam(*head, stream)
+            else:
+                name, rc = "iris_agc_clip_adam_ema", N.lib().iris_agc_clip_adam_ema(*head, self._ema[1], stream)
+        N.check(rc, name)
         # the weights have moved behind their autograd versions: every Winograd packing of them is stale (harmless in a capture)
         _PACKS.invalidate()
         return True

@@ -263,6 +263,7 @@ class CustomModel(nn.Module):
         object.__setattr__(self, '_ddp', None)  # not a submodule: DDP wraps this very module
         object.__setattr__(self, '_fused_agc', None)
         object.__setattr__(self, '_metrics', None)   # compile(metrics=...): a metrics.MetricSet
+        object.__setattr__(self, '_ema', None)       # compile(ema=...): an ema.WeightEMA of this model (not a submodule)
         # bumped by everything that changes parameters or buffers WITHOUT going through ATen's version counters: the raw-
         # pointer BatchNorm / AGC kernels, hipGraph replays (GraphedTrainStep), load_state_dict; `predict` keys its cached
         # InferenceEngine on it
@@ -302,11 +303,14 @@ class CustomModel(nn.Module):
         return self.head(self.fc_post(x))
 
     # ---- Keras-like training surface ------------------------------------
-    def compile(self, optimizer, loss, clipvalue: Optional[float] = None, use_agc: bool = True, ddp=None, metrics=None):
+    def compile(self, optimizer, loss, clipvalue: Optional[float] = None, use_agc: bool = True, ddp=None, metrics=None, ema=None):
         """`metrics`: the reference's list (metrics.py: er_score(...), f1_score(), cos_sim); train_step / test_step then
-        return them beside 'loss', from the same (detached) predictions - one HIP launch per step on a GPU."""
+        return them beside 'loss', from the same (detached) predictions - one HIP launch per step on a GPU.
+        `ema`: an ema.WeightEMA of this model; train_step (and GraphedTrainStep's captured step) update it after every optimiser
+        step - inside the fused AGC + Adam launch where that runs, with torch ops elsewhere."""
         self.optimizer, self.loss_fn, self.clipvalue, self.use_agc = optimizer, loss, clipvalue, use_agc
         object.__setattr__(self, '_ddp', ddp)
+        object.__setattr__(self, '_ema', ema)
         if metrics:
             from .metrics import MetricSet
             metrics = MetricSet(metrics)
@@ -341,12 +345,16 @@ class CustomModel(nn.Module):
         mark('backward')
         fused = self.use_agc and x.is_cuda  # one HIP launch for AGC + clipvalue over the whole model
         stepped = False
+        ema, averaged = self._ema, False
         if fused:
             if self._fused_agc is None:
                 object.__setattr__(self, '_fused_agc', FusedAGC(list(self.parameters())))
+            if ema is not None or self._fused_agc.ema_attached:   # the weight EMA rides in the same launch (six-column table)
+                self._fused_agc.attach_ema(ema.shadow, ema.decay) if ema is not None else self._fused_agc.attach_ema(None)
             # AGC + clipvalue, and - for the plain Adam make_optimizer builds - the optimiser's update in the same launch
             if self._fused_agc.attach_adam(self.optimizer):
                 stepped = self._fused_agc.adam_step(0.01, 1e-3, self.clipvalue)
+                averaged = stepped and self._fused_agc.ema_attached
             if not stepped:
                 self._fused_agc(0.01, 1e-3, self.clipvalue)
         else:
@@ -360,6 +368,10 @@ class CustomModel(nn.Module):
         mark('agc_clip')
         if not stepped:
             self.optimizer.step()
+        if ema is not None and not averaged:   # no fused launch (CPU, sgd / rmsprop, a declined step): the same definition, torch ops
+            ema.update(self.optimizer)
+        if ema is not None:
+            ema.bump_generation()   # (the launch writes the shadows behind their autograd versions, as it writes the weights)
         mark('optimizer')
         if self._metrics is None:
             return {'loss': loss.detach()}
@@ -422,7 +434,7 @@ def fold_batchnorm(model: nn.Module) -> nn.Module:
     fp32 rounding (CPU test: <= 1e-5 on the sigmoid outputs); 18 + 5 normalisation launches fewer per forward of
     the v9 CRNN.  The copy is put in eval mode; training keeps the original (BN needs batch statistics there)."""
     import copy
-    keep = {k: model.__dict__.get(k) for k in ('optimizer', '_ddp', '_fused_agc', '_predict_engine')}  # stays with the original
+    keep = {k: model.__dict__.get(k) for k in ('optimizer', '_ddp', '_fused_agc', '_predict_engine', '_ema')}  # stays with the original
     try:
         for k in keep:
             if k in model.__dict__:

@@ -102,6 +102,13 @@ class ARGS:
         a('--no_clipvalue_after_agc', action='store_true',
           help="skip Adam's element-wise clipvalue (TF < 2.4 behaviour of the custom train_step)")
         a('--validation_steps', type=int, default=16)
+        a('--ema', type=float, default=0.0, metavar='DECAY',
+          help='keep an exponential moving average of the weights, updated every step (inside the fused AGC + Adam launch where that '
+               'runs), validate it beside the live model (val_ema_* columns) and save the best as <name>_EMA.pt; 0 (default): off. '
+               'Not part of the run name')
+        a('--reset_bn', type=int, default=0, metavar='N',
+          help='recompute the BatchNorm running statistics of the averaged models (<name>_SWA.pt, <name>_EMA.pt) from N training '
+               'batches before they are written at the end of the run; 0 (default): off')
         a('--metrics', type=str, default='none', choices=['none', 'reference'],
           help="'reference': compile cos_sim, f1_score() and (v != 5) er_score(smoothing=False) as sj_train.py:454-457 does, "
                "checkpoint on val_er and score the checkpoint every 5 epochs against ./sample_answer.json and ./*.wav "
@@ -670,8 +677,17 @@ def main(argv=None):
         monitor = 'val_er'
         if rank == 0:
             callbacks.append(eval_callback(config, NAME.replace('.h5', '.pt')))
+    ema = None
+    if config.ema:   # after the metrics are known, before DDP wraps the model: a second CustomModel, not a submodule
+        from .ema import WeightEMA
+        ema = WeightEMA(model, config.ema)
+        own = None
+        if metrics is not None:   # fresh metric objects: the F1 counts of the EMA pass must not land in the live model's
+            from .metrics import cos_sim, er_score, f1_score
+            own = [cos_sim, f1_score()] + ([er_score(smoothing=False)] if config.v != 5 else [])
+        ema.compile(loss, metrics=own)
     model.compile(opt, loss, clipvalue=None if config.no_clipvalue_after_agc else config.clipvalue,
-                  ddp=wrap_ddp(model, device, world), metrics=metrics)
+                  ddp=wrap_ddp(model, device, world), metrics=metrics, ema=ema)
     if rank == 0:
         print(NAME, sum(p.numel() for p in model.parameters()), 'parameters')
     if config.pretrain:
@@ -679,10 +695,14 @@ def main(argv=None):
         # reference - its Keras weights as an .npz next to it (scripts/dump_keras_weights.py writes one from the .h5)
         if os.path.exists(NAME.replace('.h5', '.pt')):
             model.load_state_dict(torch.load(NAME.replace('.h5', '.pt'), map_location=device))
+            if ema is not None:
+                ema.load_state_dict(model.state_dict())
             if rank == 0:
                 print('loaded pretrained model', NAME.replace('.h5', '.pt'))
         elif os.path.exists(NAME.replace('.h5', '.npz')):
             load_keras_weights(model, NAME.replace('.h5', '.npz'))
+            if ema is not None:
+                ema.load_state_dict(model.state_dict())
             if rank == 0:
                 print('loaded pretrained Keras weights', NAME.replace('.h5', '.npz'))
     if device.type == 'cuda' and config.online_stft:
@@ -712,9 +732,27 @@ def main(argv=None):
     fit(model, train_set, config.epochs, config.steps_per_epoch, test_set, config.validation_steps,
         scheduler=custom_scheduler(4096, config.epochs / 12, config.lr_div),
         csv_path=NAME.replace('.h5', '.csv'), checkpoint_path=NAME.replace('.h5', '.pt'),
-        patience=config.patience, rank=rank, world=world, swa=swa, checkpoint_monitor=monitor, callbacks=callbacks)
+        patience=config.patience, rank=rank, world=world, swa=swa, checkpoint_monitor=monitor, callbacks=callbacks,
+        **({} if ema is None else {'ema': ema, 'ema_checkpoint_path': NAME.replace('.h5', '_EMA.pt')}))
+
+    def bn_batches():   # --reset_bn N: the next N training batches
+        it = iter(train_set)
+        for _ in range(config.reset_bn):
+            yield next(it)
+    if ema is not None and config.reset_bn > 0:
+        # the best EMA checkpoint of the run (else the EMA as training left it) with statistics of its own instead of the live
+        # model's: every rank recalibrates (the ranks' statistics are averaged), rank 0 writes
+        path = NAME.replace('.h5', '_EMA.pt')
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            torch.distributed.barrier()
+        if os.path.exists(path):
+            ema.load_state_dict(torch.load(path, map_location=device))
+        from .ema import recalibrate_bn
+        recalibrate_bn(ema.module, bn_batches(), world)
+        if rank == 0:
+            torch.save(ema.state_dict(), path)
     try:
-        swa.finalize(model)
+        swa.finalize(model, reset_bn=bn_batches() if config.reset_bn > 0 else None, world=world)
         if rank == 0:
             torch.save(model.state_dict(), NAME.replace('.h5', '_SWA.pt'))
             print('best model:', NAME.replace('.h5', '_SWA.pt'))

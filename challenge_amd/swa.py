@@ -36,8 +36,15 @@ class SWA:
                     self.swa_state[k] = v
         self.n_models += 1
 
-    def finalize(self, model: torch.nn.Module):
+    def finalize(self, model: torch.nn.Module, reset_bn=None, world: int = 1):
+        """`reset_bn`: an iterable of batches.  The averaged state carries BatchNorm running statistics that are themselves
+        averages and belong to no set of weights (the reference prints "Please Reset BN" here); with batches given they are
+        recomputed for the averaged weights (ema.recalibrate_bn) and the returned state holds the new ones."""
         if self.swa_state is None:
             raise NO_SWA_ERROR("training ended before the first SWA epoch")
         model.load_state_dict(copy.deepcopy(self.swa_state))
+        if reset_bn is not None:
+            from .ema import recalibrate_bn
+            recalibrate_bn(model, reset_bn, world)
+            self.swa_state = {k: v.detach().clone() for k, v in model.state_dict().items()}
         return self.swa_state

@@ -378,6 +378,28 @@ int iris_agc_clip_adam(const iris_agc_adam_row* rows_dev, size_t n_rows, float c
                        const float* step_dev, void* stream);
 
 /*
+ * The same launch once more, carrying on into an exponential moving average of the weights (model EMA / mean teacher): after
+ * p' = p - step m' / denom, still in its register,
+ *     d_t = min(decay, (1 + t) / (10 + t))        in double; t = step_dev[0], the counter the bias corrections read
+ *     e'  = e + (p' - e) (float)(1 - d_t)          fp32, written back to `ema`
+ * (TensorFlow's ExponentialMovingAverage(num_updates) warm-up; formed on the device, so a replayed hipGraph sees every step).
+ * decay in [0, 1).  Rows as for iris_agc_clip_adam plus `ema`, a contiguous row in the parameter's own layout; the float4 path
+ * runs where all FIVE pointers are 16-byte aligned and 4 | len, the scalar path elsewhere.  param, grad and both moments come out
+ * bit for bit as from iris_agc_clip_adam.  A NaN in p' goes into e' (the parameter is lost at that point anyway).
+ */
+typedef struct {
+    float* param;
+    float* grad;
+    int64_t len;
+    float* exp_avg;
+    float* exp_avg_sq;
+    float* ema;
+} iris_agc_adam_ema_row;
+int iris_agc_clip_adam_ema(const iris_agc_adam_ema_row* rows_dev, size_t n_rows, float clip_factor, float eps_agc, float clipvalue,
+                           int use_agc, const float* lr_dev, float lr_host, double beta1, double beta2, float eps,
+                           const float* step_dev, double decay, void* stream);
+
+/*
  * The reference's training metrics of one batch (metrics.py:217-299) in ONE launch, capturable:
  *   y_true [B, T, K], y_pred [B, T', K] fp32 contiguous; 1 <= K <= 16, 1 <= T, T' <= 8192, B >= 1.
  *   er_out   [B]  er_score per clip: yt = y_true >= threshold, yp = y_pred >= threshold (after AveragePooling1D(pool,
