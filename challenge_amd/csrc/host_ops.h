@@ -581,7 +581,8 @@ static size_t bn_reduce_lds(int C4) {
     return (size_t)tys * 2 * cols * 4 * sizeof(float);
 }
 
-extern "C" size_t iris_bn_sums_len(int channels) { return channels > 0 ? (size_t)bn_slots(channels) * 2 * channels : 0; }
+// (kBnBins blocks of [slot][2][channels]: the statistics passes use the first, a convolution's epilogue all of them - bn_epilogue.h)
+extern "C" size_t iris_bn_sums_len(int channels) { return channels > 0 ? (size_t)kBnBins * bn_region(channels) : 0; }
 
 extern "C" int iris_bn_stats(const float* z, size_t rows, int channels, double* sums_zeroed, void* stream) {
     int rc = bn_check(z, sums_zeroed, rows, channels, "iris_bn_stats");

@@ -133,7 +133,7 @@ __global__ __launch_bounds__(256) void k_conv0_bn_relu(const float* __restrict__
     float* coef = c0mem;
     float* tile = c0mem + 2 * C;
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        const double m = bn_sum(sums, C, c) * inv_m, var = fmax(bn_sum(sums, C, C + c) * inv_m - m * m, 0.0);
+        const double m = bn_sum(sums, C, c) * inv_m, var = bn_var_floor(bn_sum(sums, C, C + c) * inv_m - m * m);
         const float mu = (float)m, rs = (float)(1.0 / sqrt(var + (double)eps));
         coef[c] = gamma[c] * rs;
         coef[C + c] = beta[c] - mu * (gamma[c] * rs);
@@ -159,10 +159,10 @@ __global__ __launch_bounds__(256) void k_conv0_bn_relu(const float* __restrict__
             float z[4];
             conv0_z<CIN>(t, wreg, z);
             float4 r;
-            r.x = fmaxf(fmaf(z[0], sc.x, sh.x), 0.f);
-            r.y = fmaxf(fmaf(z[1], sc.y, sh.y), 0.f);
-            r.z = fmaxf(fmaf(z[2], sc.z, sh.z), 0.f);
-            r.w = fmaxf(fmaf(z[3], sc.w, sh.w), 0.f);
+            r.x = relu_keep_nan(fmaf(z[0], sc.x, sh.x));
+            r.y = relu_keep_nan(fmaf(z[1], sc.y, sh.y));
+            r.z = relu_keep_nan(fmaf(z[2], sc.z, sh.z));
+            r.w = relu_keep_nan(fmaf(z[3], sc.w, sh.w));
             y4[((size_t)row * W + wq) * C4 + tx] = r;
         }
     }
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(256) void k_conv0_bias_relu(const float* __restrict
             float z[4];
             conv0_z<CIN>(t, wreg, z);
             y4[((size_t)row * W + wq) * C4 + tx] =
-                make_float4(fmaxf(z[0] + bv.x, 0.f), fmaxf(z[1] + bv.y, 0.f), fmaxf(z[2] + bv.z, 0.f), fmaxf(z[3] + bv.w, 0.f));
+                make_float4(relu_keep_nan(z[0] + bv.x), relu_keep_nan(z[1] + bv.y), relu_keep_nan(z[2] + bv.z), relu_keep_nan(z[3] + bv.w));
         }
     }
 }

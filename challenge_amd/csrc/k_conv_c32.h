@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_c32(const float* __restrict_
                     if constexpr (RAW && BN) bn_epilogue_add(bn, acc[r], (orow < H && ocol < W) ? 1.f : 0.f);
                     if (orow < H && ocol < W)
                         y[CHUNKED ? ((((size_t)b * 4 + (i >> 3)) * H + orow) * W + ocol) * 8 + (i & 7)
-                                  : (((size_t)b * H + orow) * W + ocol) * kC32 + i] = RAW ? acc[r] : fmaxf(acc[r] + bj, 0.f);
+                                  : (((size_t)b * H + orow) * W + ocol) * kC32 + i] = RAW ? acc[r] : relu_keep_nan(acc[r] + bj);
                 }
                 if constexpr (RAW && BN) {   // this patch's share, about zero, in fp64
                     const double K = (double)bn.k, n = (double)bn.n, S1 = (double)bn.s1, S2 = (double)bn.s2;
@@ -167,24 +167,24 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_c32(const float* __restrict_
                     const int q = 2 * g + hl;  // pooled column inside the wave's patch
                     const int oc0 = w0 + 16 * wv + 2 * q, or0 = h0 + 2 * t;
                     float m = acc[4 * g];      // (or0, oc0) is inside whenever the pooled pixel exists
-                    if (oc0 + 1 < W) m = fmaxf(m, acc[4 * g + 1]);
+                    if (oc0 + 1 < W) m = max_keep_nan(m, acc[4 * g + 1]);
                     if (or0 + 1 < H) {
-                        m = fmaxf(m, acc[4 * g + 2]);
-                        if (oc0 + 1 < W) m = fmaxf(m, acc[4 * g + 3]);
+                        m = max_keep_nan(m, acc[4 * g + 2]);
+                        if (oc0 + 1 < W) m = max_keep_nan(m, acc[4 * g + 3]);
                     }
                     const int pcol = (w0 >> 1) + 8 * wv + q;
                     if (prow < Ho && pcol < Wo && or0 < H && oc0 < W)
                         y[CHUNKED ? ((((size_t)b * 4 + (i >> 3)) * Ho + prow) * Wo + pcol) * 8 + (i & 7)
-                                  : (((size_t)b * Ho + prow) * Wo + pcol) * kC32 + i] = fmaxf(m + bj, 0.f);
+                                  : (((size_t)b * Ho + prow) * Wo + pcol) * kC32 + i] = relu_keep_nan(m + bj);
                 }
             }
         }
     }
     if constexpr (RAW && BN) {
-        if (bn_t2 > 0.0) {
+        if (!(bn_t2 <= 0.0)) {   // an all-zero share adds nothing; a NaN total is NOT <= 0 and reaches the sums
             const int slot = (int)(blockIdx.x % (unsigned)bn_slots(kC32));
-            atomicAdd(bn_sums + (size_t)slot * 2 * kC32 + i, bn_t1);
-            atomicAdd(bn_sums + (size_t)slot * 2 * kC32 + kC32 + i, bn_t2);
+            bn_binned_add(bn_sums + (size_t)slot * 2 * kC32 + i, bn_region(kC32), bn_t1);
+            bn_binned_add(bn_sums + (size_t)slot * 2 * kC32 + kC32 + i, bn_region(kC32), bn_t2);
         }
     }
 }

@@ -56,10 +56,10 @@ __global__ __launch_bounds__(256) void k_conv3x3_small_bias_relu(const float* __
                     }
                 }
             }
-            acc.x = fmaxf(acc.x, 0.f);
-            acc.y = fmaxf(acc.y, 0.f);
-            acc.z = fmaxf(acc.z, 0.f);
-            acc.w = fmaxf(acc.w, 0.f);
+            acc.x = relu_keep_nan(acc.x);
+            acc.y = relu_keep_nan(acc.y);
+            acc.z = relu_keep_nan(acc.z);
+            acc.w = relu_keep_nan(acc.w);
             *reinterpret_cast<float4*>(yo + (size_t)co * H * W) = acc;
         }
     }

@@ -280,7 +280,7 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float* __restrict
         // ---- output transform, bias, ReLU (, MaxPool) and store: lane = output channel, register r = tile
         const int co = cb * kWinoTN + 32 * wn + li;
         const float bj = bias ? bias[co] : 0.f;
-        const float floor_ = relu ? 0.f : -INFINITY;  // max(v, floor_): ReLU, or nothing
+        const float floor_ = relu ? 0.f : -INFINITY;  // max_keep_nan(v, floor_): ReLU, or v itself (NaN included)
         const int Ho = POOL ? TH : H, Wo = POOL ? TW : W;
         constexpr int kPix = POOL ? 1 : 4;                       // output pixels per tile
         constexpr int kCcStride = 32 * kPix * 8 + 8;             // floats between channel chunks in the staging area (+ 8: banks)
@@ -334,12 +334,12 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float* __restrict
             float pooled = 0.f;
             if constexpr (POOL) {
                 pooled = o[0][0];  // (oh, ow) is inside whenever the tile exists; values outside the image never win
-                if (col1) pooled = fmaxf(pooled, o[0][1]);
+                if (col1) pooled = max_keep_nan(pooled, o[0][1]);
                 if (e_row1[ss]) {
-                    pooled = fmaxf(pooled, o[1][0]);
-                    if (col1) pooled = fmaxf(pooled, o[1][1]);
+                    pooled = max_keep_nan(pooled, o[1][0]);
+                    if (col1) pooled = max_keep_nan(pooled, o[1][1]);
                 }
-                pooled = fmaxf(pooled + bj, floor_);
+                pooled = max_keep_nan(pooled + bj, floor_);
             }
             if constexpr (BN && !POOL) {
                 {   // the statistics of what is stored below: z itself (no bias, no ReLU here)
@@ -358,12 +358,16 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float* __restrict
                         yp[0] = pooled;
                     } else {
                         const unsigned rowp = (unsigned)(Wo * ps);
-                        yp[0] = fmaxf(o[0][0] + bj, floor_);
-                        if (col1) yp[ps] = fmaxf(o[0][1] + bj, floor_);
+                        // (TC == 16 as a select: its instantiations, at the register limit, keep 4-8 bytes less scratch that way and
+                        // 12 more with the max; the others 4-52 bytes less with the max - compiler resource report)
+#define WINO_EPI(v) (TC == 16 ? (relu ? relu_keep_nan((v) + bj) : (v) + bj) : max_keep_nan((v) + bj, floor_))
+                        yp[0] = WINO_EPI(o[0][0]);
+                        if (col1) yp[ps] = WINO_EPI(o[0][1]);
                         if (e_row1[ss]) {
-                            yp[rowp] = fmaxf(o[1][0] + bj, floor_);
-                            if (col1) yp[rowp + ps] = fmaxf(o[1][1] + bj, floor_);
+                            yp[rowp] = WINO_EPI(o[1][0]);
+                            if (col1) yp[rowp + ps] = WINO_EPI(o[1][1]);
                         }
+#undef WINO_EPI
                     }
                 }
             } else {
@@ -374,7 +378,7 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino(const float* __restrict
 #pragma unroll
                     for (int i = 0; i < 2; ++i)
 #pragma unroll
-                        for (int j = 0; j < 2; ++j) sp[((i * 32 + row) * 2 + j) * 8] = fmaxf(o[i][j] + bj, floor_);
+                        for (int j = 0; j < 2; ++j) sp[((i * 32 + row) * 2 + j) * 8] = max_keep_nan(o[i][j] + bj, floor_);
                 }
             }
         }

@@ -529,20 +529,20 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino_b3(const float* __restr
                     float* const yb = y + (size_t)b_ * Ho * Wo * Cout + (out_nhwc ? (size_t)co : ((size_t)(co >> 3) * Ho * Wo) * 8 + (co & 7));
                     if constexpr (POOL) {
                         float pooled = o[0][0];
-                        if (col1) pooled = fmaxf(pooled, o[0][1]);
+                        if (col1) pooled = max_keep_nan(pooled, o[0][1]);
                         if (row1) {
-                            pooled = fmaxf(pooled, o[1][0]);
-                            if (col1) pooled = fmaxf(pooled, o[1][1]);
+                            pooled = max_keep_nan(pooled, o[1][0]);
+                            if (col1) pooled = max_keep_nan(pooled, o[1][1]);
                         }
-                        yb[((size_t)th_ * Wo + tw_) * ps] = fmaxf(pooled + bj, floor_);
+                        yb[((size_t)th_ * Wo + tw_) * ps] = max_keep_nan(pooled + bj, floor_);
                     } else {
                         float* const yp = yb + ((size_t)(2 * th_) * Wo + ow) * ps;
                         const size_t rowp = (size_t)Wo * ps;
-                        yp[0] = fmaxf(o[0][0] + bj, floor_);
-                        if (col1) yp[ps] = fmaxf(o[0][1] + bj, floor_);
+                        yp[0] = max_keep_nan(o[0][0] + bj, floor_);
+                        if (col1) yp[ps] = max_keep_nan(o[0][1] + bj, floor_);
                         if (row1) {
-                            yp[rowp] = fmaxf(o[1][0] + bj, floor_);
-                            if (col1) yp[rowp + ps] = fmaxf(o[1][1] + bj, floor_);
+                            yp[rowp] = max_keep_nan(o[1][0] + bj, floor_);
+                            if (col1) yp[rowp + ps] = max_keep_nan(o[1][1] + bj, floor_);
                         }
                     }
                 }

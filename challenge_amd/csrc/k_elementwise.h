@@ -1,6 +1,7 @@
 // k_elementwise.h -- min-max / log, normalize, magnitude-phase, mask apply, adaptive gradient clipping.
 // Part of the single translation unit iris_frontend.hip.
 #pragma once
+#include "bn_epilogue.h"   // max_keep_nan / relu_keep_nan; kBnSlots, bn_slots(), and the statistics a convolution's epilogue accumulates
 // ---------------------------------------------------------------------------
 // K4/K5: min-max (+ log): partial reduce, then apply
 // ---------------------------------------------------------------------------
@@ -247,10 +248,10 @@ __global__ __launch_bounds__(256) void k_bias_relu(float* x, const float* bias, 
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n_vec4; i += (size_t)gridDim.x * blockDim.x, col.next()) {
         float4 v = x4[i];
         const float4 b = b4[col.c];
-        v.x = fmaxf(v.x + b.x, 0.f);
-        v.y = fmaxf(v.y + b.y, 0.f);
-        v.z = fmaxf(v.z + b.z, 0.f);
-        v.w = fmaxf(v.w + b.w, 0.f);
+        v.x = relu_keep_nan(v.x + b.x);
+        v.y = relu_keep_nan(v.y + b.y);
+        v.z = relu_keep_nan(v.z + b.z);
+        v.w = relu_keep_nan(v.w + b.w);
         x4[i] = v;
     }
 }
@@ -269,19 +270,19 @@ __global__ __launch_bounds__(256) void k_bias_relu_pool(const float* x, const fl
         float4 m = x4[w.base];
         auto take = [&](size_t off) {
             const float4 v = x4[w.base + off];
-            m.x = fmaxf(m.x, v.x);
-            m.y = fmaxf(m.y, v.y);
-            m.z = fmaxf(m.z, v.z);
-            m.w = fmaxf(m.w, v.w);
+            m.x = max_keep_nan(m.x, v.x);
+            m.y = max_keep_nan(m.y, v.y);
+            m.z = max_keep_nan(m.z, v.z);
+            m.w = max_keep_nan(m.w, v.w);
         };
         if (w.w1) take(C4);
         if (w.h1) take(w.down);
         if (w.h1 && w.w1) take(w.down + C4);
         const float4 bb = b4[c];
-        m.x = fmaxf(m.x + bb.x, 0.f);
-        m.y = fmaxf(m.y + bb.y, 0.f);
-        m.z = fmaxf(m.z + bb.z, 0.f);
-        m.w = fmaxf(m.w + bb.w, 0.f);
+        m.x = relu_keep_nan(m.x + bb.x);
+        m.y = relu_keep_nan(m.y + bb.y);
+        m.z = relu_keep_nan(m.z + bb.z);
+        m.w = relu_keep_nan(m.w + bb.w);
         y4[i] = m;
     }
 }
@@ -296,10 +297,10 @@ __global__ __launch_bounds__(256) void k_bias_relu_nchw(float* x, const float* b
         // (32-bit quotients when they fit: a 64-bit division costs more than the rest of the loop body)
         const float b = n_vec4 <= 0xffffffffull ? bias[((unsigned)i / (unsigned)inner4) % (unsigned)C] : bias[(i / inner4) % C];
         float4 v = x4[i];
-        v.x = fmaxf(v.x + b, 0.f);
-        v.y = fmaxf(v.y + b, 0.f);
-        v.z = fmaxf(v.z + b, 0.f);
-        v.w = fmaxf(v.w + b, 0.f);
+        v.x = relu_keep_nan(v.x + b);
+        v.y = relu_keep_nan(v.y + b);
+        v.z = relu_keep_nan(v.z + b);
+        v.w = relu_keep_nan(v.w + b);
         x4[i] = v;
     }
 }
@@ -321,20 +322,20 @@ __global__ __launch_bounds__(256) void k_bias_relu_pool_nchw(const float* x, con
         if (in) {
             if (pairs) {
                 const float2 r0 = *reinterpret_cast<const float2*>(p);
-                m = fmaxf(r0.x, r0.y);
+                m = max_keep_nan(r0.x, r0.y);
                 if (h1) {
                     const float2 r1 = *reinterpret_cast<const float2*>(p + W);
-                    m = fmaxf(m, fmaxf(r1.x, r1.y));
+                    m = max_keep_nan(m, max_keep_nan(r1.x, r1.y));
                 }
             } else {
                 m = p[0];
-                if (w1) m = fmaxf(m, p[1]);
+                if (w1) m = max_keep_nan(m, p[1]);
                 if (h1) {
-                    m = fmaxf(m, p[W]);
-                    if (w1) m = fmaxf(m, p[W + 1]);
+                    m = max_keep_nan(m, p[W]);
+                    if (w1) m = max_keep_nan(m, p[W + 1]);
                 }
             }
-            m = fmaxf(m + bias[c], 0.f);
+            m = relu_keep_nan(m + bias[c]);
         }
         if (lane < tile_w) tile[lane * (C + 1) + c] = m;
     }
@@ -362,12 +363,25 @@ __global__ __launch_bounds__(256) void k_bias_relu_pool_nchw(const float* x, con
 #ifndef IRIS_BN_POOL_ROWS
 #define IRIS_BN_POOL_ROWS 8
 #endif
-#include "bn_epilogue.h"   // kBnSlots, bn_slots(), and the statistics a convolution's epilogue accumulates
 __device__ __forceinline__ double bn_sum(const double* sums, int C, int i) {
     const int n = bn_slots(C);
     double v = 0.0;
     for (int s = 0; s < n; ++s) v += sums[(size_t)s * 2 * C + i];
     return v;
+}
+// the sums a convolution's epilogue left in exponent windows (bn_epilogue.h): windows and slots in a fixed order; each window's
+// fold is exact, the two additions at the end are the only roundings
+__device__ __forceinline__ double bn_sum_binned(const double* sums, int C, int i) {
+    const int n = bn_slots(C);
+    const size_t region = bn_region(C);
+    double hi = 0.0, mid = 0.0, lo = 0.0;
+    for (int s = 0; s < n; ++s) {
+        const double* p = sums + (size_t)s * 2 * C + i;
+        hi += p[0];
+        mid += p[region];
+        lo += p[2 * region];
+    }
+    return hi + (mid + lo);
 }
 constexpr int kBnRows = IRIS_BN_ROWS;           // rows per thread-row pass
 constexpr int kBnPoolRows = IRIS_BN_POOL_ROWS;  // pooled rows (windows of four) per thread-row pass: 4x the blocks of the same tensor
@@ -449,7 +463,9 @@ __global__ __launch_bounds__(256) void k_bn_relu_apply(const float* z, float* y,
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
         // sums are of (z - K), K = z[row 0][c] (k_bn_reduce) - or K = 0 when a convolution's epilogue accumulated them in fp64
         // (bn_epilogue_flush): mean = K + E[z - K], var = E[(z - K)^2] - E[z - K]^2
-        const double ms = bn_sum(sums, C, c) * inv_m, var = fmax(bn_sum(sums, C, C + c) * inv_m - ms * ms, 0.0);
+        const double s1 = sums_about_zero ? bn_sum_binned(sums, C, c) : bn_sum(sums, C, c);
+        const double s2 = sums_about_zero ? bn_sum_binned(sums, C, C + c) : bn_sum(sums, C, C + c);
+        const double ms = s1 * inv_m, var = bn_var_floor(s2 * inv_m - ms * ms);
         const double m = (sums_about_zero ? 0.0 : (double)z[c]) + ms;
         const float mu = (float)m, rs = (float)(1.0 / sqrt(var + (double)eps));
         coef[c] = gamma[c] * rs;
@@ -472,10 +488,10 @@ __global__ __launch_bounds__(256) void k_bn_relu_apply(const float* z, float* y,
         const int c = col.c;
         const float4 v = z4[i], sc = sc4[c], sh = sh4[c];
         float4 r;
-        r.x = fmaxf(fmaf(v.x, sc.x, sh.x), 0.f);
-        r.y = fmaxf(fmaf(v.y, sc.y, sh.y), 0.f);
-        r.z = fmaxf(fmaf(v.z, sc.z, sh.z), 0.f);
-        r.w = fmaxf(fmaf(v.w, sc.w, sh.w), 0.f);
+        r.x = relu_keep_nan(fmaf(v.x, sc.x, sh.x));
+        r.y = relu_keep_nan(fmaf(v.y, sc.y, sh.y));
+        r.z = relu_keep_nan(fmaf(v.z, sc.z, sh.z));
+        r.w = relu_keep_nan(fmaf(v.w, sc.w, sh.w));
         y4[i] = r;
     }
 }
@@ -550,7 +566,9 @@ __global__ __launch_bounds__(256) void k_bn_relu_pool_apply(const float* z, floa
     const int C = 4 * C4;
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
         // sums are of (z - K), K = z[row 0][c] (k_bn_reduce) or 0 (a convolution's epilogue): mean = K + E[z - K], var = E[(z - K)^2] - E[z - K]^2
-        const double ms = bn_sum(sums, C, c) * inv_m, var = fmax(bn_sum(sums, C, C + c) * inv_m - ms * ms, 0.0);
+        const double s1 = sums_about_zero ? bn_sum_binned(sums, C, c) : bn_sum(sums, C, c);
+        const double s2 = sums_about_zero ? bn_sum_binned(sums, C, C + c) : bn_sum(sums, C, C + c);
+        const double ms = s1 * inv_m, var = bn_var_floor(s2 * inv_m - ms * ms);
         const double m = (sums_about_zero ? 0.0 : (double)z[c]) + ms;
         const float mu = (float)m, rs = (float)(1.0 / sqrt(var + (double)eps));
         coef[c] = gamma[c] * rs;
@@ -578,10 +596,10 @@ __global__ __launch_bounds__(256) void k_bn_relu_pool_apply(const float* z, floa
         float4 m = make_float4(0.f, 0.f, 0.f, 0.f);  // y >= 0
         auto take = [&](size_t off) {
             const float4 v = z4[w.base + off];
-            m.x = fmaxf(m.x, fmaf(v.x, sc.x, sh.x));
-            m.y = fmaxf(m.y, fmaf(v.y, sc.y, sh.y));
-            m.z = fmaxf(m.z, fmaf(v.z, sc.z, sh.z));
-            m.w = fmaxf(m.w, fmaf(v.w, sc.w, sh.w));
+            m.x = max_keep_nan(m.x, fmaf(v.x, sc.x, sh.x));
+            m.y = max_keep_nan(m.y, fmaf(v.y, sc.y, sh.y));
+            m.z = max_keep_nan(m.z, fmaf(v.z, sc.z, sh.z));
+            m.w = max_keep_nan(m.w, fmaf(v.w, sc.w, sh.w));
         };
         take(0);
         if (w.w1) take(C4);

@@ -568,7 +568,9 @@ def bias_relu_maxpool(x: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
 def conv3x3_small_bias_relu(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, channels_last: bool = False) -> torch.Tensor:
     """relu(conv2d(x, weight, padding=1) + bias) for a contiguous [B, 1 or 2, H, W] input in ONE pass: the CRNN's first layer,
     which writes 16-32x what it reads.  Output contiguous (iris_conv3x3_small_bias_relu_nchw; W a multiple of 4) or
-    channels_last (iris_conv3x3_small_bias_relu_nhwc; W <= 2048, output channels 4 .. 256 dividing 1024)."""
+    channels_last (iris_conv3x3_small_bias_relu_nhwc; W <= 2048, output channels 4 .. 256 dividing 1024).
+    A NaN in x is a NaN in every output (all channels) whose 3x3 window holds it, as with torch's conv2d + relu - the ReLU does not
+    turn it into 0 - and no other output changes; an infinity leaves those outputs non-finite wherever conv2d + relu does."""
     if (x.dim() != 4 or not x.is_contiguous() or not x.is_cuda or x.dtype != torch.float32 or x.shape[1] not in (1, 2)
             or tuple(weight.shape[1:]) != (x.shape[1], 3, 3) or not weight.is_contiguous()):
         raise ValueError("conv3x3_small_bias_relu: x must be a contiguous float32 device tensor [B, 1|2, H, W], "
@@ -620,7 +622,10 @@ def conv3x3_c32_bias_relu(x: torch.Tensor, weight: torch.Tensor, bias: torch.Ten
 def conv3x3_c32(x: torch.Tensor, weight: torch.Tensor, transposed: bool = False, bn_sums: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The bare conv2d(x, weight, padding=1) of a 32 -> 32 layer on the fp32 matrix cores (iris_conv3x3_c32: the inference
     kernel without bias / ReLU) for a channels_last [B, 32, H, W] input and a [32, 32, 3, 3] weight in any dense layout;
-    `transposed`: the backward-data pass, conv2d(x, weight.flip(2, 3).transpose(0, 1), padding=1) with x = dz."""
+    `transposed`: the backward-data pass, conv2d(x, weight.flip(2, 3).transpose(0, 1), padding=1) with x = dz.
+    A NaN in x (or in a weight) is a NaN in every output that sums it and in no other; with `bn_sums` the sums of a channel whose z
+    holds a NaN are NaN (the BatchNorm behind it then gives NaN over that channel, as torch's does).  conv3x3_c32_bias_relu: its
+    ReLU and its max-pool keep a NaN too (a pooled window with a NaN among its in-image elements is NaN)."""
     if (x.dim() != 4 or x.shape[1] != 32 or not x.is_contiguous(memory_format=torch.channels_last) or not x.is_cuda
             or x.dtype != torch.float32 or tuple(weight.shape) != (32, 32, 3, 3) or weight.dtype != torch.float32):
         raise ValueError("conv3x3_c32: x must be a float32 channels_last device tensor [B, 32, H, W], weight a float32 [32, 32, 3, 3]")
@@ -727,7 +732,12 @@ def conv3x3_wino(x: torch.Tensor, packed: torch.Tensor, bias: Optional[torch.Ten
     (iris_conv3x3_wino).  x: channel-chunked [B, Cin / 8, H, W, 8], or a channels_last [B, Cin, H, W] tensor (read where it
     lies: IRIS_WINO_IN_NHWC); packed: `wino_pack_weights[_device]` with the same `split_bf16`, on x's device (a shorter packing is
     refused; a split-bf16 packing given to the fp32 kernel is long enough and cannot be told apart); returns the chunked
-    [B, cout / 8, Ho, Wo, 8] or, with `out_nhwc`, a channels_last [B, cout, Ho, Wo] tensor."""
+    [B, cout / 8, Ho, Wo, 8] or, with `out_nhwc`, a channels_last [B, cout, Ho, Wo] tensor.
+    NaN: a NaN in x is a NaN in every output, in all channels, whose 3x3 window holds it - through bias + ReLU, through the max-pool (a
+    window with a NaN among its in-image elements is NaN) and in the bare form (relu=False, which hands z on as it is, no -inf in its
+    place) - and, with `bn_sums`, in the channel's sums.  The other outputs of the 2x2 tiles whose 4x4 input patch holds it may be
+    NaN as well (the Winograd transform mixes the patch); every other tile has the bits of the run without it.  An infinity leaves
+    the same places non-finite."""
     if not (x.is_cuda and x.dtype == torch.float32):
         raise ValueError("conv3x3_wino: x must be a float32 device tensor (no CPU fallback)")
     if x.dim() == 5 and x.shape[4] == 8 and x.is_contiguous():

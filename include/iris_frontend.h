@@ -523,7 +523,9 @@ int iris_bias_relu_maxpool(const float* x, const float* bias, float* y, int batc
 /* Round 6: the forward statistics can come out of the CONVOLUTION's epilogue instead (iris_conv3x3_wino_bn, iris_conv3x3_wino_b3_bn,
  * iris_conv3x3_c32_bn: the bare convolution + sum z / sum z^2 per output channel into a zeroed [iris_bn_sums_len] buffer, accumulated
  * from the registers z is stored from) - the iris_bn_stats pass over z disappears; the *_sums0 forms of the apply entry points
- * consume sums taken about zero (iris_bn_stats' are taken about row 0 of z).  Replaces the same layers of sj_train.py:191-201. */
+ * consume sums taken about zero (iris_bn_stats' are taken about row 0 of z).  Replaces the same layers of sj_train.py:191-201.
+ * These sums repeat bit for bit from call to call: the buffer holds three exponent windows of the per-channel copies, inside which
+ * the kernels' fp64 atomics are exact in any order (the statistics passes use the first window only). */
 size_t iris_bn_sums_len(int channels);
 int iris_bn_relu_apply_sums0(const float* z, float* y, size_t rows, int channels, const double* sums, const float* gamma,
                              const float* beta, const float* conv_bias, float eps, float momentum, float* running_mean,

@@ -135,8 +135,8 @@ def test_bn_channel_limit_is_stated(dev):
 
 @pytest.mark.parametrize("pool", [False, True])
 def test_statistics_handed_in_by_the_convolution(dev, pool):
-    """`sums0`: (sum z, sum z^2) in slot 0 of an otherwise zero iris_bn_sums_len(c) buffer, as a convolution's epilogue leaves them
-    (about zero, no shift K).  The same result as the separate statistics pass: within the bounds everywhere, and bit for bit in
+    """`sums0`: (sum z, sum z^2) in slot 0 of the first window of an otherwise zero iris_bn_sums_len(c) buffer - a convolution's epilogue
+    leaves them split over the slots and windows, which the consumer adds up (about zero, no shift K).  The same result as the separate statistics pass: within the bounds everywhere, and bit for bit in
     the channels whose two means agree bit for bit."""
     from challenge_amd import _native as N
     shape = (2, 33, 65, 68)
@@ -144,7 +144,7 @@ def test_statistics_handed_in_by_the_convolution(dev, pool):
     own = _run_bn(dev, case, True, False)
     c = shape[3]
     n = int(N.lib().iris_bn_sums_len(c))
-    assert n == 4 * 2 * c                                          # 68 channels: four copies
+    assert n == 3 * 4 * 2 * c                                      # 68 channels: four copies, in each of the three exponent windows
     rows = case["z"].reshape(-1, c).astype(F64)
     sums = np.zeros(n, F64)
     sums[:c], sums[c:2 * c] = rows.sum(axis=0), np.square(rows).sum(axis=0)
