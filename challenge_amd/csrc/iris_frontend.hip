@@ -67,6 +67,7 @@
 #include "k_conv_wino_wrw.h"
 #include "k_resample.h"
 #include "k_agc_adam.h"
+#include "k_agc_optim.h"
 #include "k_metrics.h"
 #include "decode_core.h"
 #include "k_detect.h"

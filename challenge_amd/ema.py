@@ -4,9 +4,10 @@ teacher), and BatchNorm recalibration for averaged weights.
     d_t = min(decay, (1 + t) / (10 + t))            t = the optimiser's step counter after its increment (TensorFlow's
     e'  = e + (p' - e) (float)(1 - d_t)                 ExponentialMovingAverage(num_updates) warm-up); p' the updated parameter
 
-On a GPU with the Adam `make_optimizer` builds the update rides in the one launch that already does AGC, clipvalue and Adam
-(`FusedAGC.attach_ema`, iris_agc_clip_adam_ema of csrc/k_agc_adam.h: the updated parameter is still in a register, the shadow costs
-8 more bytes of traffic per parameter and no launch); everywhere else - a CPU model, sgd / rmsprop, IRIS_FUSED_ADAM_AGC=0, a step the
+On a GPU with the optimisers `make_optimizer` builds the update rides in the one launch that already does AGC, clipvalue and the
+optimiser's update (`FusedAGC.attach_ema`, iris_agc_clip_adam_ema of csrc/k_agc_adam.h and its sgd / rmsprop siblings of
+csrc/k_agc_optim.h: the updated parameter is still in a register, the shadow costs 8 more bytes of traffic per parameter and no
+launch); everywhere else - a CPU model, IRIS_FUSED_ADAM_AGC=0 / IRIS_FUSED_OPTIM_AGC=0, a step the
 kernel declines - `WeightEMA.update` applies the same definition with torch ops after `optimizer.step()`.  Both are capturable: the
 weight is formed on the device from the counter, so a replayed hipGraph sees every step.  Only parameters are averaged; buffers
 (BatchNorm running statistics) are copied from the live model (`copy_buffers`) or recomputed (`recalibrate_bn`)."""
@@ -79,7 +80,7 @@ class WeightEMA:
     # ---- the update ----------------------------------------------------------------------------------------------------------
     def attach(self, agc) -> bool:
         """Let `agc` (a FusedAGC over the live parameters) carry the update in its launch."""
-        return agc.attach_ema(self.shadow, self.decay)
+        return agc.attach_ema(self.shadow, self.decay, self._t)
 
     def _counter(self, optimizer):
         """The optimiser's step counter where it is a tensor on the parameters' device (after `step()`: already incremented);

@@ -18,13 +18,24 @@ from .model import CustomModel
 
 
 def make_optimizer(config, params, capturable: bool = False):
-    """`capturable`: Adam with its step count and learning rate in device tensors, for `GraphedTrainStep`."""
+    """`capturable`: the optimiser with its learning rate (and, where it keeps one, its step count) in device tensors and a
+    `step()` that is legal inside a hipGraph capture, for `GraphedTrainStep`: Adam and RMSprop with capturable=True; SGD with
+    fused=True - torch.optim.SGD has no `capturable` key, its foreach form reads a tensor rate back to the host
+    (`_foreach_add_(..., alpha=-lr)`), its fused form hands the tensor to the kernel."""
     params = list(params)
     if capturable:
-        if config.optimizer != 'adam' or not (params and params[0].is_cuda):
-            raise ValueError("make_optimizer(capturable=True): Adam on a GPU")
-        return torch.optim.Adam(params, lr=torch.tensor(float(config.lr), device=params[0].device), eps=1e-7, fused=True,
-                                capturable=True)
+        if config.optimizer == 'adabelief':
+            raise ValueError('adabelief is deprecated')
+        if not (params and params[0].is_cuda):
+            raise ValueError("make_optimizer(capturable=True): adam, sgd or rmsprop on a GPU")
+        lr = torch.tensor(float(config.lr), device=params[0].device)
+        if config.optimizer == 'adam':
+            return torch.optim.Adam(params, lr=lr, eps=1e-7, fused=True, capturable=True)
+        if config.optimizer == 'sgd':
+            return torch.optim.SGD(params, lr=lr, momentum=0.9, fused=True)
+        if config.optimizer == 'rmsprop':
+            return torch.optim.RMSprop(params, lr=lr, momentum=0.9, alpha=0.9, eps=1e-7, foreach=True, capturable=True)
+        raise ValueError(f"make_optimizer: unknown optimizer {config.optimizer!r}")
     # foreach=True on a GPU: the update AND zero_grad run as a handful of multi-tensor kernels instead of one per
     # parameter (86 fills of ~3.6 us each per step otherwise)
     fe = bool(params) and params[0].is_cuda
@@ -37,6 +48,20 @@ def make_optimizer(config, params, capturable: bool = False):
     if config.optimizer == 'rmsprop':
         return torch.optim.RMSprop(params, lr=config.lr, momentum=0.9, alpha=0.9, eps=1e-7, foreach=fe)
     raise ValueError('adabelief is deprecated')
+
+
+def optimizer_capturable(opt) -> bool:
+    """Can `opt.step()` run inside a hipGraph capture, and will a replay see a new learning rate?  The rate of every group in a
+    device tensor, and a step that reads nothing back to the host: torch's `capturable=True` (Adam, RMSprop), or - torch.optim.SGD
+    has no such key - its fused form, which takes the rate tensor as a kernel argument."""
+    if opt is None:
+        return False
+    for g in opt.param_groups:
+        if not (torch.is_tensor(g['lr']) and g['lr'].is_cuda):
+            return False
+        if not (g.get('capturable', False) or (type(opt) is torch.optim.SGD and g.get('fused'))):
+            return False
+    return True
 
 
 def run_name(config) -> str:
@@ -154,7 +179,7 @@ class GraphedTrainStep:
     into a flat buffer, pre-divides it by the world size and starts `all_reduce` on it asynchronously (RCCL's stream joins the
     capture as a parallel branch: the collective of one bucket overlaps the backward kernels of the layers below, as under DDP);
     after backward the capture waits for the collectives, the gradients become views of the flat buffers, and AGC, clipvalue and
-    Adam act on the averaged gradients - identically on every rank.  Whether the capture succeeded is agreed on by ALL ranks
+    the optimiser act on the averaged gradients - identically on every rank.  Whether the capture succeeded is agreed on by ALL ranks
     (one MIN all-reduce of a flag) before anyone replays: a rank never replays a graph while another one runs eager DDP."""
 
     def __init__(self, model: "CustomModel", example, warmup: int = 3, preserve_state: bool = False):
@@ -165,7 +190,7 @@ class GraphedTrainStep:
         if not x.is_cuda:
             raise RuntimeError("GraphedTrainStep: a GPU tensor is required (hipGraph capture; no CPU fallback)")
         opt = model.optimizer
-        if not all(g.get('capturable', False) for g in opt.param_groups):
+        if not optimizer_capturable(opt):
             raise ValueError("GraphedTrainStep: the optimiser must be capturable - make_optimizer(config, params, capturable=True)")
         self.world = 0   # > 0: the capture holds the gradient all-reduce of that many ranks
         if model._ddp is not None:
@@ -241,7 +266,7 @@ class GraphedTrainStep:
         # freeing - the buffers the graph replays from.
         self._agc = FusedAGC(list(model.parameters())) if model.use_agc else None
         if self._agc is not None:
-            self._agc.attach_adam(opt)   # (before `reserve`: an attached optimiser makes the table five columns wide)
+            self._agc.attach_optimizer(opt)   # (before `reserve`: an attached optimiser makes the table five columns wide)
             if model._ema is not None:   # (and a weight EMA six)
                 model._ema.attach(self._agc)
             self._agc.reserve()
@@ -340,8 +365,8 @@ class GraphedTrainStep:
                 w.wait()                      # the capture stream joins RCCL's stream again
         stepped, averaged = False, False
         if model.use_agc:
-            if self._agc.attach_adam(opt):   # AGC + clipvalue + Adam (+ the weight EMA) in one launch (hip_autograd.FusedAGC.adam_step)
-                stepped = self._agc.adam_step(0.01, 1e-3, model.clipvalue)
+            if self._agc.attach_optimizer(opt):   # AGC + clipvalue + the optimiser (+ the weight EMA) in one launch (FusedAGC.optimizer_step)
+                stepped = self._agc.optimizer_step(0.01, 1e-3, model.clipvalue)
                 averaged = stepped and self._agc.ema_attached
             if not stepped:
                 self._agc(0.01, 1e-3, model.clipvalue)
@@ -380,7 +405,7 @@ class GraphedTrainStep:
 
 def graph_step_possible(model: "CustomModel") -> bool:
     """Can `fit` try GraphedTrainStep for this compiled model?  A capturable optimiser, and - under DDP - the RCCL backend."""
-    if model.optimizer is None or not all(g.get('capturable', False) for g in model.optimizer.param_groups):
+    if not optimizer_capturable(model.optimizer):
         return False
     return model._ddp is None or torch.distributed.get_backend() == 'nccl'
 

@@ -42,8 +42,12 @@ class FusedAGC:
 
     def __init__(self, params):
         self.params = [p for p in params]
-        self._adam = None   # a torch.optim.Adam whose update rides in the same launch (`adam_step`), or None
-        self._ema = None    # (shadow parameters, decay): a weight EMA that rides in that launch too (`attach_ema`), or None
+        # the optimiser whose update rides in the same launch (`attach_optimizer` / `optimizer_step`), or None, and which one it is:
+        # 'adam', 'sgd' or 'rmsprop'
+        self._adam = None
+        self._kind = None
+        # (shadow parameters, decay, the EMA's own counter): a weight EMA that rides in that launch too (`attach_ema`), or None
+        self._ema = None
         # the attached optimiser's step counters when they are KNOWN to hold one value (`_counters_uniform`): (the tensors, their
         # autograd versions), or None; `_counters_apart`: the tensors that were found to differ
         self._counters = None
@@ -99,8 +103,12 @@ class FusedAGC:
             table[:, 2] = length
             if cols >= 5:   # iris_agc_adam_row: the two moments lie in the parameter's own layout
                 st = self._adam.state
-                table[:, 3] = np.array([st[p]['exp_avg'].data_ptr() for p in fast], np.int64)[rep] + offs
-                table[:, 4] = np.array([st[p]['exp_avg_sq'].data_ptr() for p in fast], np.int64)[rep] + offs
+                first, second = self._STATE_KEYS[self._kind]
+                table[:, 3] = np.array([st[p][first].data_ptr() for p in fast], np.int64)[rep] + offs
+                if second is not None:
+                    table[:, 4] = np.array([st[p][second].data_ptr() for p in fast], np.int64)[rep] + offs
+                else:   # sgd keeps one state row: the launch never reads this slot
+                    table[:, 4] = 0
             if cols == 6:   # iris_agc_adam_ema_row: and so does the parameter's shadow
                 shadow = {id(p): e for p, e in zip(self.params, self._ema[0])}
                 table[:, 5] = np.array([shadow[id(p)].data_ptr() for p in fast], np.int64)[rep] + offs
@@ -146,13 +154,17 @@ class FusedAGC:
         With an optimiser attached: + the address of its first moment (a replaced state means a new table); with a weight EMA
         attached as well: + the address of the parameter's shadow."""
         adam = self._adam
+        key = self._STATE_KEYS[self._kind][0] if adam is not None else None   # (exp_avg, or the momentum buffer of sgd / rmsprop)
         if adam is not None and self._ema is not None:
             return tuple((p.data_ptr(),) + ((-1, ()) if p.grad is None else (p.grad.data_ptr(), tuple(p.grad.stride())))
-                         + ((adam.state[p]['exp_avg'].data_ptr(),) if 'exp_avg' in adam.state.get(p, {}) else ()) + (e.data_ptr(),)
+                         + ((adam.state[p][key].data_ptr(),) if key in adam.state.get(p, {}) else ()) + (e.data_ptr(),)
                          for p, e in zip(self.params, self._ema[0]))
         return tuple((p.data_ptr(),) + ((-1, ()) if p.grad is None else (p.grad.data_ptr(), tuple(p.grad.stride())))
-                     + ((adam.state[p]['exp_avg'].data_ptr(),) if adam is not None and 'exp_avg' in adam.state.get(p, {}) else ())
+                     + ((adam.state[p][key].data_ptr(),) if adam is not None and key in adam.state.get(p, {}) else ())
                      for p in self.params)
+
+    # the state rows of the table's fourth and fifth column, per optimiser
+    _STATE_KEYS = {'adam': ('exp_avg', 'exp_avg_sq'), 'sgd': ('momentum_buffer', None), 'rmsprop': ('momentum_buffer', 'square_avg')}
 
     def _cols(self) -> int:
         """3: iris_agc_row; 5: iris_agc_adam_row (an optimiser attached); 6: iris_agc_adam_ema_row (and a weight EMA)."""
@@ -160,11 +172,15 @@ class FusedAGC:
             return 3
         return 6 if self._ema is not None else 5
 
-    def _reset_tables(self, adam) -> None:
+    def _reset_tables(self, adam, kind=None) -> None:
         """Another table format from here on: forget the cached tables (their arena slots are reused from the first, so nothing
-        in flight may still read them)."""
+        in flight may still read them).  `kind`: which optimiser `adam` is (None: the one attached now)."""
         if self._cache and self.params and self.params[0].is_cuda:
             torch.cuda.synchronize(self.params[0].device)
+        if adam is None:
+            self._kind = None
+        elif kind is not None:
+            self._kind = kind
         self._adam, self._sig, self._cache = adam, None, {}
 
     # ---- a weight EMA in the optimiser's launch -------------------------------------------------------------------------------
@@ -172,11 +188,13 @@ class FusedAGC:
     def ema_attached(self) -> bool:
         return self._ema is not None
 
-    def attach_ema(self, shadow_params, decay: float = 0.0) -> bool:
-        """Let `adam_step` keep an exponential moving average of the weights in the same launch (iris_agc_clip_adam_ema):
-        `shadow_params[i]` is the average of `params[i]` - a float32 device tensor of its shape and strides that takes no gradient
-        (`ema.WeightEMA` owns them) - and the table becomes six columns wide.  None detaches: five columns and the old entry point
-        again.  False (and detached): shadows the kernel cannot address row by row as it addresses the parameters."""
+    def attach_ema(self, shadow_params, decay: float = 0.0, counter=None) -> bool:
+        """Let `optimizer_step` keep an exponential moving average of the weights in the same launch (iris_agc_clip_adam_ema and its
+        sgd / rmsprop siblings): `shadow_params[i]` is the average of `params[i]` - a float32 device tensor of its shape and strides
+        that takes no gradient (`ema.WeightEMA` owns them) - and the table becomes six columns wide.  None detaches: five columns and
+        the old entry point again.  False (and detached): shadows the kernel cannot address row by row as it addresses the parameters.
+        `counter`: the average's own step counter (`WeightEMA._t`, a one-element fp32 device tensor), which the launch increments and
+        reads where the optimiser keeps no counter on the device (sgd); without one such a step is declined."""
         if shadow_params is None:
             if self._ema is not None:
                 self._ema = None
@@ -186,7 +204,7 @@ class FusedAGC:
             raise ValueError(f"FusedAGC.attach_ema: decay {decay} outside [0, 1)")
         cur = self._ema
         if cur is not None and cur[0] is shadow_params:   # (the steady state: the same list every step)
-            self._ema = (shadow_params, float(decay))
+            self._ema = (shadow_params, float(decay), counter)
             return True
         shadow = list(shadow_params)
         ok = len(shadow) == len(self.params) and all(
@@ -194,7 +212,7 @@ class FusedAGC:
             and e.stride() == p.stride() and not e.requires_grad and e.data_ptr() != p.data_ptr() for p, e in zip(self.params, shadow))
         if not ok:
             return self.attach_ema(None)
-        self._ema = (shadow_params if isinstance(shadow_params, list) else shadow, float(decay))
+        self._ema = (shadow_params if isinstance(shadow_params, list) else shadow, float(decay), counter)
         self._reset_tables(self._adam)
         return True
 
@@ -235,7 +253,7 @@ class FusedAGC:
         if not self._counters_uniform([opt.state[p]['step'] for p in self.params]):
             return False
         if self._adam is not opt:
-            self._reset_tables(opt)
+            self._reset_tables(opt, 'adam')
         return True
 
     def _counters_uniform(self, steps) -> bool:
@@ -279,20 +297,7 @@ class FusedAGC:
         if getattr(self, '_frozen', False):
             raise RuntimeError("FusedAGC: this instance belongs to a captured hipGraph (GraphedTrainStep) and cannot be called eagerly")
         opt = self._adam
-        if opt is None or any(p.grad is None for p in self.params):
-            return False
-        sig = self._signature()
-        if sig != self._sig:
-            hit = self._cache.get(sig)
-            if hit is not None:
-                self._sig, self._table, self._slow, self._host_table = sig, hit[0], hit[1], hit[2]
-            else:
-                if len(self._cache) >= 8:   # the arena's slots are reused from the first: nothing in flight may still read them
-                    torch.cuda.synchronize(self.params[0].device)
-                    self._cache.clear()
-                self._build()
-                self._cache[self._sig] = (self._table, self._slow, getattr(self, '_host_table', None))
-        if self._slow or self._table.shape[1] != self._cols():
+        if opt is None or self._kind != 'adam' or not self._table_for_step():
             return False
         g = opt.param_groups[0]
         steps = [opt.state[p]['step'] for p in self.params]
@@ -315,6 +320,130 @@ class FusedAGC:
         N.check(rc, name)
         # the weights have moved behind their autograd versions: every Winograd packing of them is stale (harmless in a capture)
         _PACKS.invalidate()
+        return True
+
+    def _table_for_step(self) -> bool:
+        """The row table of this step's address set, from the cache or built now.  False: a parameter without a gradient or on the
+        torch path (`_slow`), or a table of another width - the caller declines the step."""
+        if any(p.grad is None for p in self.params):
+            return False
+        sig = self._signature()
+        if sig != self._sig:
+            hit = self._cache.get(sig)
+            if hit is not None:
+                self._sig, self._table, self._slow, self._host_table = sig, hit[0], hit[1], hit[2]
+            else:
+                if len(self._cache) >= 8:   # the arena's slots are reused from the first: nothing in flight may still read them
+                    torch.cuda.synchronize(self.params[0].device)
+                    self._cache.clear()
+                self._build()
+                self._cache[self._sig] = (self._table, self._slow, getattr(self, '_host_table', None))
+        return not self._slow and self._table.shape[1] == self._cols()
+
+    # ---- sgd and rmsprop in the same launch, and the one surface over all three ---------------------------------------------------
+    @staticmethod
+    def optimizer_kind(opt):
+        """'adam' (`adam_fusable`), or 'sgd' / 'rmsprop' for a plain torch.optim.SGD / torch.optim.RMSprop as `make_optimizer` builds
+        them: one group, a momentum in (0, 1) (without one torch keeps no buffer), no weight decay / nesterov / dampening / centered
+        / maximize / differentiable, fp32 device parameters, the learning rate a float or a one-element fp32 device tensor.  None:
+        torch's own step."""
+        if type(opt) is torch.optim.Adam:
+            return 'adam' if FusedAGC.adam_fusable(opt) else None
+        kind = {torch.optim.SGD: 'sgd', torch.optim.RMSprop: 'rmsprop'}.get(type(opt))
+        if kind is None or not SW.FUSED_OPTIM or len(opt.param_groups) != 1:
+            return None
+        g = opt.param_groups[0]
+        if any(g.get(k) for k in ('weight_decay', 'nesterov', 'dampening', 'centered', 'maximize', 'differentiable')):
+            return None
+        if not (isinstance(g['momentum'], float) and 0.0 < g['momentum'] < 1.0):
+            return None
+        if kind == 'rmsprop' and not (isinstance(g['alpha'], float) and 0.0 <= g['alpha'] < 1.0 and isinstance(g['eps'], float)
+                                      and g['eps'] >= 0.0):
+            return None
+        lr = g['lr']
+        if torch.is_tensor(lr):
+            if not (lr.is_cuda and lr.dtype == torch.float32 and lr.numel() == 1):
+                return None
+        elif not isinstance(lr, (int, float)):
+            return None
+        return kind if all(p.is_cuda and p.dtype == torch.float32 for p in g['params']) else None
+
+    def attach_optimizer(self, opt) -> bool:
+        """Let `optimizer_step` run `opt`'s update - Adam (`attach_adam`), SGD or RMSprop: creates the optimiser state torch would
+        create at its first step (same keys, dtypes and layouts: state_dict() / load_state_dict() stay interchangeable; a zero
+        momentum buffer gives torch's first step exactly, mu 0 + x = x).  False: not an optimiser these kernels cover."""
+        kind = self.optimizer_kind(opt)
+        if kind == 'adam':
+            return self.attach_adam(opt)
+        if kind is None or [id(p) for p in opt.param_groups[0]['params']] != [id(p) for p in self.params]:
+            return False
+        on_device = bool(opt.param_groups[0].get('capturable'))
+        for p in self.params:
+            st = opt.state[p]
+            if kind == 'rmsprop' and len(st) == 0:   # (RMSprop._init_group)
+                st['step'] = torch.zeros((), dtype=torch.float32, device=p.device if on_device else None)
+                st['square_avg'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            if st.get('momentum_buffer') is None:
+                st['momentum_buffer'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            rows = [st['momentum_buffer']] + ([st.get('square_avg')] if kind == 'rmsprop' else [])
+            # (torch's first sgd step clones the GRADIENT: on a dimension of length 1 its stride may differ from the parameter's,
+            # which places no element differently)
+            where = [s for s, n in zip(p.stride(), p.shape) if n > 1]
+            if not all(torch.is_tensor(t) and t.device == p.device and t.dtype == torch.float32 and t.shape == p.shape
+                       and [s for s, n in zip(t.stride(), t.shape) if n > 1] == where for t in rows):
+                return False
+            if kind == 'rmsprop' and not torch.is_tensor(st.get('step')):
+                return False
+        if self._adam is not opt or self._kind != kind:
+            self._reset_tables(opt, kind)
+        return True
+
+    def optimizer_step(self, clip_factor=0.01, eps=1e-3, clipvalue=None, use_agc=True) -> bool:
+        """AGC + clipvalue + the attached optimiser's update (+ the attached weight EMA) in ONE launch: `adam_step` for Adam,
+        iris_agc_clip_sgd / iris_agc_clip_rmsprop and their _ema siblings otherwise.  False (nothing done, no counter moved, no
+        shadow touched): the caller runs the steps apart.
+        The counter the _ema siblings read is the one `WeightEMA._counter` would hand the torch path - rmsprop's device-side `step`
+        where it has one (capturable), else the average's own, incremented here before the launch - so a step that is declined
+        continues the same sequence through `WeightEMA.update`.  rmsprop's `step` entries are incremented as torch's step
+        increments them, although no arithmetic reads them."""
+        if self._kind == 'adam':
+            return self.adam_step(clip_factor, eps, clipvalue, use_agc)
+        import ctypes as C
+        if getattr(self, '_frozen', False):
+            raise RuntimeError("FusedAGC: this instance belongs to a captured hipGraph (GraphedTrainStep) and cannot be called eagerly")
+        opt, kind = self._adam, self._kind
+        if opt is None or not self._table_for_step():
+            return False
+        g = opt.param_groups[0]
+        dev = self.params[0].device
+        steps = [opt.state[p]['step'] for p in self.params] if kind == 'rmsprop' else []
+        counter, own = None, False
+        if self._ema is not None:
+            if steps and steps[0].device == dev:
+                counter = steps[0]
+            else:
+                counter, own = self._ema[2], True
+                if not (torch.is_tensor(counter) and counter.device == dev and counter.dtype == torch.float32 and counter.numel() == 1):
+                    return False
+        if steps:
+            torch._foreach_add_(steps, 1)
+        if own:
+            counter.add_(1)
+        lr = g['lr']
+        from . import _native as N
+        head = (self._table.data_ptr(), int(self._table.shape[0]), float(clip_factor), float(eps), float(clipvalue or 0.0), 1 if use_agc else 0,
+                lr.data_ptr() if torch.is_tensor(lr) else None, 0.0 if torch.is_tensor(lr) else float(lr), float(g['momentum']))
+        if kind == 'rmsprop':
+            head += (float(g['alpha']), float(g['eps']))
+        name = "iris_agc_clip_" + kind + ("_ema" if self._ema is not None else "")
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            if self._ema is None:
+                rc = getattr(N.lib(), name)(*head, stream)
+            else:
+                rc = getattr(N.lib(), name)(*head, counter.data_ptr(), self._ema[1], stream)
+        N.check(rc, name)
+        _PACKS.invalidate()   # (as after the Adam launch: the weights have moved behind their autograd versions)
         return True
 
     def reserve(self) -> None:

@@ -350,10 +350,10 @@ class CustomModel(nn.Module):
             if self._fused_agc is None:
                 object.__setattr__(self, '_fused_agc', FusedAGC(list(self.parameters())))
             if ema is not None or self._fused_agc.ema_attached:   # the weight EMA rides in the same launch (six-column table)
-                self._fused_agc.attach_ema(ema.shadow, ema.decay) if ema is not None else self._fused_agc.attach_ema(None)
-            # AGC + clipvalue, and - for the plain Adam make_optimizer builds - the optimiser's update in the same launch
-            if self._fused_agc.attach_adam(self.optimizer):
-                stepped = self._fused_agc.adam_step(0.01, 1e-3, self.clipvalue)
+                self._fused_agc.attach_ema(ema.shadow, ema.decay, ema._t) if ema is not None else self._fused_agc.attach_ema(None)
+            # AGC + clipvalue, and - for the plain Adam / SGD / RMSprop make_optimizer builds - the optimiser's update in the same launch
+            if self._fused_agc.attach_optimizer(self.optimizer):
+                stepped = self._fused_agc.optimizer_step(0.01, 1e-3, self.clipvalue)
                 averaged = stepped and self._fused_agc.ema_attached
             if not stepped:
                 self._fused_agc(0.01, 1e-3, self.clipvalue)
@@ -368,7 +368,7 @@ class CustomModel(nn.Module):
         mark('agc_clip')
         if not stepped:
             self.optimizer.step()
-        if ema is not None and not averaged:   # no fused launch (CPU, sgd / rmsprop, a declined step): the same definition, torch ops
+        if ema is not None and not averaged:   # no fused launch (CPU, a switch off, a declined step): the same definition, torch ops
             ema.update(self.optimizer)
         if ema is not None:
             ema.bump_generation()   # (the launch writes the shadows behind their autograd versions, as it writes the weights)

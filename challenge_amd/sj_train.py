@@ -103,7 +103,7 @@ class ARGS:
           help="skip Adam's element-wise clipvalue (TF < 2.4 behaviour of the custom train_step)")
         a('--validation_steps', type=int, default=16)
         a('--ema', type=float, default=0.0, metavar='DECAY',
-          help='keep an exponential moving average of the weights, updated every step (inside the fused AGC + Adam launch where that '
+          help='keep an exponential moving average of the weights, updated every step (inside the fused AGC + optimiser launch where that '
                'runs), validate it beside the live model (val_ema_* columns) and save the best as <name>_EMA.pt; 0 (default): off. '
                'Not part of the run name')
         a('--reset_bn', type=int, default=0, metavar='N',
@@ -623,7 +623,7 @@ from .model import (ConvMPBlock, CustomModel, FullyConnectedLayer, InferenceEngi
 from .distributed import (_gradient_buckets, average_bn_statistics, collectives_on, distributed_env,  # noqa: E402,F401
                           force_process_group, init_distributed, wrap_ddp)
 from .fit import (GraphCaptureError, GraphedTrainStep, configure_miopen, fit, graph_step_possible, make_optimizer,  # noqa: E402,F401
-                  miopen_db_status, run_name)
+                  miopen_db_status, optimizer_capturable, run_name)
 
 
 class _SjTrainModule(type(os)):
@@ -657,10 +657,10 @@ def main(argv=None):
         print(config)
     NAME = run_name(config)
     model = get_model(config).to(device).to(memory_format=torch.channels_last)
-    # a GPU, Adam (and not IRIS_GRAPH_STEP=0): the step as one replayed hipGraph - the optimiser then keeps its rate on the
-    # device; with more than one rank the gradient all-reduce over RCCL is part of the graph (GraphedTrainStep)
+    # a GPU, adam / sgd / rmsprop (and not IRIS_GRAPH_STEP=0): the step as one replayed hipGraph - the optimiser then keeps its rate
+    # on the device; with more than one rank the gradient all-reduce over RCCL is part of the graph (GraphedTrainStep)
     opt = make_optimizer(config, model.parameters(),
-                         capturable=SW.GRAPH_STEP and device.type == 'cuda' and config.optimizer == 'adam')
+                         capturable=SW.GRAPH_STEP and device.type == 'cuda' and config.optimizer in ('adam', 'sgd', 'rmsprop'))
     loss = binary_crossentropy if config.loss == 'BCE' else \
         (lambda yt, yp: sigmoid_focal_crossentropy(yt, yp).mean())
     metrics, callbacks, monitor = None, [], None

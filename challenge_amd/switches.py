@@ -43,6 +43,9 @@ FUSED_PACK = _on("IRIS_FUSED_PACK")
 # round 6: AGC + clipvalue + the Adam update in ONE launch (iris_agc_clip_adam) for the optimiser make_optimizer builds (plain Adam,
 # fused or capturable); 0: iris_agc_clip, then torch's fused Adam (three more launches, 143 us for the CRNN)
 FUSED_ADAM = _on("IRIS_FUSED_ADAM_AGC")
+# the same for the sgd / rmsprop make_optimizer builds (iris_agc_clip_sgd / iris_agc_clip_rmsprop and their _ema siblings);
+# 0: iris_agc_clip, then torch's own launches (and one lerp per parameter with a weight EMA)
+FUSED_OPTIM = _on("IRIS_FUSED_OPTIM_AGC")
 
 # --- the convolutions themselves in the training step -------------------------------------------------------------------------------
 # The bare 3x3 convolutions of blocks 2-5 - forward and backward-data - as Winograd F(2x2, 3x3) on the fp32 matrix cores
@@ -71,7 +74,7 @@ WINO_SPLIT_BF16 = _on("IRIS_WINO_SPLIT_BF16", "0")
 WINO_CONVS = _on("IRIS_WINO")   # blocks 2-5 of the InferenceEngine as Winograd F(2x2, 3x3) on the fp32 MFMA (0: MIOpen + HIP epilogue)
 
 # --- the step as a whole ------------------------------------------------------------------------------------------------------------
-# fit / main run the training step as ONE replayed hipGraph wherever that is possible (a GPU, Adam, batches of one shape; under
+# fit / main run the training step as ONE replayed hipGraph wherever that is possible (a GPU, adam / sgd / rmsprop, batches of one shape; under
 # DistributedDataParallel: over RCCL, the gradient all-reduce inside the graph): the step then costs what its kernels cost however
 # slow the host is at launching ~260 of them - with eight ranks on one host that is the scaling risk, not xGMI.  0: eager.
 GRAPH_STEP = _on("IRIS_GRAPH_STEP")
@@ -84,6 +87,6 @@ DDP_BUCKET_MB = int(os.environ.get("IRIS_DDP_BUCKET_MB", "12"))
 # --- test hook ------------------------------------------------------------------------------------------------------------------------
 _PLAN_CHECK_ON_CPU = False  # tests/test_ddp_gloo.py: consult the frontend plans' status for a CPU-resident loss too
 
-NAMES = ("FUSED_BN_RELU", "FUSED_FC_BN", "FUSED_BN_POOL", "FUSED_BN_STATS", "FUSED_PACK", "FUSED_ADAM", "FUSED_CONV0", "FUSED_LSTM", "ZERO_POOL", "PCEN_LEARN_HIP", "WINO_TRAIN",
+NAMES = ("FUSED_BN_RELU", "FUSED_FC_BN", "FUSED_BN_POOL", "FUSED_BN_STATS", "FUSED_PACK", "FUSED_ADAM", "FUSED_OPTIM", "FUSED_CONV0", "FUSED_LSTM", "ZERO_POOL", "PCEN_LEARN_HIP", "WINO_TRAIN",
          "WINO_TRAIN_MIN_C_FWD", "WINO_TRAIN_MIN_C_BWD", "WINO_TRAIN_WRW", "C32_TRAIN", "WINO_SPLIT_BF16", "WINO_CONVS", "GRAPH_STEP", "DDP_BUCKET_MB",
          "_PLAN_CHECK_ON_CPU")

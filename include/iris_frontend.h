@@ -400,6 +400,31 @@ int iris_agc_clip_adam_ema(const iris_agc_adam_ema_row* rows_dev, size_t n_rows,
                            const float* step_dev, double decay, void* stream);
 
 /*
+ * The siblings of iris_agc_clip_adam for the other two optimisers of sj_train.py:436-439: AGC + clipvalue exactly as above (x, the
+ * clipped gradient, is written back to `grad`), then
+ *     sgd      b' = mu b + x;                                                  p' = p - lr b'
+ *     rmsprop  s' = alpha s + (float)(1 - alpha) x x;  b' = mu b + x / (sqrtf(s') + eps);  p' = p - lr b'
+ * torch.optim.SGD (momentum, no dampening / nesterov / weight decay) and torch.optim.RMSprop (momentum, not centered, no weight
+ * decay) in fp32; a zero momentum buffer gives torch's first step.  The rows are iris_agc_adam_row / iris_agc_adam_ema_row with the
+ * momentum buffer in `exp_avg` and rmsprop's square average in `exp_avg_sq`; the sgd entry points never read the `exp_avg_sq`
+ * slot (it may hold anything).  mu, alpha in [0, 1), eps >= 0; lr_dev: nullable DEVICE float, else lr_host.  Neither update has a
+ * bias correction: only the _ema siblings take a counter - step_dev, a DEVICE float holding t >= 1 of THIS update - for
+ *     e' = e + (p' - e) (float)(1 - min(decay, (1 + t) / (10 + t)))            decay in [0, 1)
+ * The float4 path runs where 4 | len and every pointer the entry point reads is 16-byte aligned.  Arguments are checked before any
+ * HIP call; n_rows == 0 returns IRIS_OK; nothing is allocated or synchronised, the launch goes to `stream`.
+ */
+int iris_agc_clip_sgd(const iris_agc_adam_row* rows_dev, size_t n_rows, float clip_factor, float eps_agc, float clipvalue,
+                      int use_agc, const float* lr_dev, float lr_host, double mu, void* stream);
+int iris_agc_clip_sgd_ema(const iris_agc_adam_ema_row* rows_dev, size_t n_rows, float clip_factor, float eps_agc, float clipvalue,
+                          int use_agc, const float* lr_dev, float lr_host, double mu, const float* step_dev, double decay,
+                          void* stream);
+int iris_agc_clip_rmsprop(const iris_agc_adam_row* rows_dev, size_t n_rows, float clip_factor, float eps_agc, float clipvalue,
+                          int use_agc, const float* lr_dev, float lr_host, double mu, double alpha, float eps, void* stream);
+int iris_agc_clip_rmsprop_ema(const iris_agc_adam_ema_row* rows_dev, size_t n_rows, float clip_factor, float eps_agc, float clipvalue,
+                              int use_agc, const float* lr_dev, float lr_host, double mu, double alpha, float eps,
+                              const float* step_dev, double decay, void* stream);
+
+/*
  * The reference's training metrics of one batch (metrics.py:217-299) in ONE launch, capturable:
  *   y_true [B, T, K], y_pred [B, T', K] fp32 contiguous; 1 <= K <= 16, 1 <= T, T' <= 8192, B >= 1.
  *   er_out   [B]  er_score per clip: yt = y_true >= threshold, yp = y_pred >= threshold (after AveragePooling1D(pool,
