@@ -51,6 +51,7 @@ SIGNATURES = {
     "iris_agc_clip_rmsprop": (_i, [_vp, _sz, _f, _f, _f, _i, _vp, _f, C.c_double, C.c_double, _f, _vp]),
     "iris_agc_clip_rmsprop_ema": (_i, [_vp, _sz, _f, _f, _f, _i, _vp, _f, C.c_double, C.c_double, _f, _vp, C.c_double, _vp]),
     "iris_event_metrics": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "iris_score_hist": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "iris_decode_events": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "iris_decode_sweep": (_i, [_vp] * 5 + [_i] * 5 + [_vp] * 6 + [_i] + [_vp] * 3 + [_i, _i] + [_vp] * 4),
     "iris_resample_len": (C.c_longlong, [C.c_longlong, _i, _i]),

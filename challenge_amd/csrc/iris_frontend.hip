@@ -26,6 +26,7 @@
 //   host_wino.h        the host side of both: the device packers' entry points and one launch path over the two kernel families
 //   k_conv_wino_wrw.h  the same layers' weight gradient as Winograd F(2x2, 3x3) on the fp32 matrix cores (training)
 //   k_metrics.h      the training metrics er_score / cos_sim / F1 counts of a batch in one launch
+//   k_curves.h       the validation score histogram per (class, label): integer counts behind ROC-AUC / average precision / best F1
 //   decode_core.h    the event decoder's arithmetic (overlap-add average, smoothing, dilation, run boundaries), written once
 //   k_detect.h       window predictions of many files -> smoothed, thresholded event lists (two launches)
 //   k_tune.h         the same decoder (decode_core.h) at every point of a settings grid, scored against ground truth: event and match counts
@@ -69,6 +70,7 @@
 #include "k_agc_adam.h"
 #include "k_agc_optim.h"
 #include "k_metrics.h"
+#include "k_curves.h"
 #include "decode_core.h"
 #include "k_detect.h"
 #include "k_tune.h"

@@ -1,12 +1,16 @@
 """Drop-in counterpart of the reference's eval.py: score a trained model against sample_answer.json.
 
-    python -m challenge_amd.eval --name <run name> [--p] [--path DIR] [--verbose True]
+    python -m challenge_amd.eval --name <run name> [--p] [--path DIR] [--verbose True] [--curves OUT.json [--curve_bins 1024]]
 
 loads <path>/<name>.pt (this package's checkpoint) - or, for a model trained with the reference, its Keras weights as
 <path>/<name>.npz (scripts/dump_keras_weights.py) - and runs metrics.evaluate on the *.wav files of the working directory.
+`--curves OUT.json` also writes the threshold-free numbers of the files' frame posteriors against the answer's frame labels
+(metrics.ScoreHistogram.compute: ROC-AUC, average precision, best F1 and its threshold, calibration error per class, with the
+macro values) as JSON.
 `--p` parses model / v / n_mels / n_chan / n_frame out of the run name as eval.py:51-62 does."""
 from __future__ import annotations
 
+import json
 import os
 
 import numpy as np
@@ -68,17 +72,33 @@ def load_model(config, path: str = '', device=None):
     return model
 
 
-def main(argv=None):
+def build_args():
+    """The trainer's flags (the model is described by them) plus this tool's own."""
     from .sj_train import ARGS
-    config = ARGS()
+    config = ARGS(trainer_flags=False)
     config.args.add_argument('--verbose', help='verbose', type=bool, default=True)
     config.args.add_argument('--p', help='parsing name', action='store_true')
     config.args.add_argument('--path', type=str, default='')
-    config = config.get(argv)
+    config.args.add_argument('--curves', type=str, default=None, metavar='OUT.json',
+                             help='also write ROC-AUC / average precision / best F1 per class and their macro values, from the score '
+                                  'histogram of the frame posteriors, to this file')
+    config.args.add_argument('--curve_bins', type=int, default=1024)
+    return config
+
+
+def main(argv=None):
+    config = build_args().get(argv)
     if config.p:
         parse_name(config)
     model = load_model(config, config.path)
-    return evaluate(config, model, verbose=config.verbose)
+    if not config.curves:
+        return evaluate(config, model, verbose=config.verbose)
+    from .metrics import ScoreHistogram
+    hist = ScoreHistogram(3, config.curve_bins)
+    scores = evaluate(config, model, verbose=config.verbose, curves=hist)
+    with open(config.curves, 'w') as f:
+        json.dump(hist.compute(), f, indent=1)
+    return scores
 
 
 if __name__ == "__main__":

@@ -410,6 +410,19 @@ def graph_step_possible(model: "CustomModel") -> bool:
     return model._ddp is None or torch.distributed.get_backend() == 'nccl'
 
 
+def monitor_maximised(name: Optional[str]) -> bool:
+    """Is a row entry better when LARGER?  The threshold-free validation numbers of a compiled score_curves() - 'auc', 'map',
+    'best_f1' behind 'val_' / 'val_ema_' - are; every other name (losses, er, ...) keeps Keras' mode min."""
+    if not name:
+        return False
+    for prefix in ('val_ema_', 'val_'):
+        if name.startswith(prefix):
+            name = name[len(prefix):]
+            break
+    from .metrics import CURVE_NAMES
+    return name in CURVE_NAMES
+
+
 def fit(model: CustomModel, train_set, epochs, steps_per_epoch, validation_data=None, validation_steps=16,
         scheduler=None, csv_path=None, checkpoint_path=None, patience=None, rank=0, world=1, verbose=True,
         swa=None, graph: Optional[bool] = None, checkpoint_monitor: Optional[str] = None, callbacks=(), ema=None,
@@ -431,8 +444,12 @@ def fit(model: CustomModel, train_set, epochs, steps_per_epoch, validation_data=
     `validation_data`) on the EMA module with the live BatchNorm statistics copied in, all-reduced like the first; the row gains
     'val_ema_loss' and the 'val_ema_*' metrics.  Everything the
     live model's row, early stopping and checkpoint depend on is computed as without it.  `ema_checkpoint_path` is written when
-    'val_ema_<the checkpoint's monitor>' improves strictly."""
+    'val_ema_<the checkpoint's monitor>' improves strictly.
+    A compiled metrics.score_curves() adds 'val_auc', 'val_map', 'val_best_f1' (and their 'val_ema_' twins) after the validation
+    pass, from the validation histogram summed over the ranks; a `checkpoint_monitor` with such a name is MAXIMISED (strictly
+    larger saves), and so is the EMA's twin of it."""
     best, bad, history = math.inf, 0, []
+    ckpt_sign = -1.0 if monitor_maximised(checkpoint_monitor) else 1.0   # best_ckpt / best_ema hold sign * value: smaller is better
     best_ckpt = math.inf
     best_ema = math.inf
     if ema is not None and model._ema is not ema:
@@ -542,6 +559,8 @@ def fit(model: CustomModel, train_set, epochs, steps_per_epoch, validation_data=
                 host = torch.cat([vl.double().view(1), metric_sums('val', vl.device)]).tolist()
                 row['val_loss'] = host[0]
                 row.update(ms.epoch_values(host[1:], 'val_'))
+                if ms.curves is not None:
+                    row.update(ms.curve_values('val_', all_reduce=coll))
             if ema is not None:   # the second pass: the averaged weights under the live model's BatchNorm statistics
                 ema.copy_buffers(model)
                 ems = ema.module._metrics
@@ -561,6 +580,8 @@ def fit(model: CustomModel, train_set, epochs, steps_per_epoch, validation_data=
                     host = torch.cat([evl.double().view(1), acc]).tolist()
                     row['val_ema_loss'] = host[0]
                     row.update(ems.epoch_values(host[1:], 'val_ema_'))
+                    if ems.curves is not None:
+                        row.update(ems.curve_values('val_ema_', all_reduce=coll))
         history.append(row)
         if swa is not None:
             swa.on_epoch_end(epoch, model)
@@ -575,16 +596,16 @@ def fit(model: CustomModel, train_set, epochs, steps_per_epoch, validation_data=
         save = improved
         if checkpoint_monitor is not None:   # Keras ModelCheckpoint(save_best_only=True): strictly better, mode min
             cm = row.get(checkpoint_monitor)
-            save = cm is not None and cm < best_ckpt
+            save = cm is not None and ckpt_sign * cm < best_ckpt
             if save:
-                best_ckpt = cm
+                best_ckpt = ckpt_sign * cm
         save_ema = False
         if ema is not None:   # the EMA's own best-only checkpoint, on the EMA pass's twin of the checkpoint's monitor
             name = checkpoint_monitor if checkpoint_monitor is not None else 'val_loss'
             em = row.get('val_ema_' + name[len('val_'):]) if name.startswith('val_') else None
-            save_ema = em is not None and em < best_ema
+            save_ema = em is not None and ckpt_sign * em < best_ema
             if save_ema:
-                best_ema = em
+                best_ema = ckpt_sign * em
         if rank == 0:
             if verbose:
                 print(row)

@@ -212,6 +212,185 @@ def _cos_sim_metric(y_true, y_pred):
 _cos_sim_metric.__name__ = 'cos_sim'
 
 
+# ---------------------------------------------------------------------------
+# threshold-free validation numbers from a score histogram (no counterpart in the reference)
+# ---------------------------------------------------------------------------
+CURVE_MIN_BINS, CURVE_MAX_BINS, CURVE_MAX_CLASSES = 16, 4096, 16
+
+
+def check_curve_bins(bins) -> int:
+    bins = int(bins)
+    if bins < CURVE_MIN_BINS or bins > CURVE_MAX_BINS or bins & (bins - 1):
+        raise ValueError(f"score histogram: bins must be a power of two in [{CURVE_MIN_BINS}, {CURVE_MAX_BINS}], got {bins}")
+    return bins
+
+
+def score_hist_host(y_true: torch.Tensor, y_pred: torch.Tensor, bins: int) -> torch.Tensor:
+    """The counts [K, 2, bins + 1] (int64) of one batch with torch ops, on the tensors' device - the CPU path of
+    `ScoreHistogram.update`, and the rule iris_score_hist restates: label = y_true >= 0.5 (NaN: negative), slot =
+    min(bins - 1, max(0, floor(p * bins))) in fp32 (p * bins is exact: bins is a power of two), slot `bins` for a NaN p."""
+    yt = y_true.detach().to(torch.float32)
+    yp = y_pred.detach().to(torch.float32)
+    k = yp.shape[-1]
+    label = (yt >= 0.5).to(torch.int64)
+    slot = torch.clamp(torch.floor(yp * float(bins)), 0.0, float(bins - 1))
+    slot = torch.where(torch.isnan(yp), torch.full_like(slot, float(bins)), slot).to(torch.int64)
+    cls = torch.arange(k, device=yp.device, dtype=torch.int64).expand_as(slot)
+    idx = (cls * 2 + label) * (bins + 1) + slot
+    return torch.bincount(idx.reshape(-1), minlength=k * 2 * (bins + 1)).view(k, 2, bins + 1)
+
+
+def _nanmean(values) -> float:
+    kept = [v for v in values if v == v]
+    return sum(kept) / len(kept) if kept else float('nan')
+
+
+def curve_metrics(counts) -> dict:
+    """Host arithmetic on a score histogram [K, 2, bins + 1] of integers (NumPy or a tensor; one rank's or the sum over ranks):
+    counts[k, 0] the negative frames, counts[k, 1] the positive ones, slot `bins` the NaN predictions (excluded from every curve).
+    With pos[b], neg[b] the counts of a class, P, N their sums over the real bins, TP_b = sum_{j >= b} pos[j], FP_b likewise:
+      auroc          sum_b pos[b] (2 sum_{j < b} neg[j] + neg[b]) / (2 P N): ties inside a bin count half; NaN if P or N is 0
+      ap             sum_b (pos[b] / P) TP_b / (TP_b + FP_b): sklearn's step-wise average precision on the binned scores; NaN if P = 0
+      best_f1        max_b 2 TP_b / (TP_b + FP_b + P), best_threshold = b / bins for the smallest such b; NaN if P = 0
+      ece            sum_b (n_b / n) |pos[b] / n_b - (b + 0.5) / bins| over the non-empty bins, n_b = pos[b] + neg[b]; NaN if n = 0
+    The sums are formed in Python integers (exact); each quotient is rounded once.  Returns {'per_class': {name: [K values]} with
+    the names above and the integer fields n_pos, n_neg, n_nan; 'auc', 'map', 'best_f1': the means over the classes where the
+    value is defined (NaN if there is none); 'bins'}."""
+    c = np.asarray(counts.detach().cpu() if torch.is_tensor(counts) else counts)
+    if c.ndim != 3 or c.shape[1] != 2 or c.shape[2] < 2 or not np.issubdtype(c.dtype, np.integer):
+        raise ValueError(f"curve_metrics: integer counts [K, 2, bins + 1], got {c.dtype} {tuple(c.shape)}")
+    bins = c.shape[2] - 1
+    nan = float('nan')
+    per = {n: [] for n in ('auroc', 'ap', 'best_f1', 'best_threshold', 'ece', 'n_pos', 'n_neg', 'n_nan')}
+    for k in range(c.shape[0]):
+        neg = [int(v) for v in c[k, 0, :bins]]
+        pos = [int(v) for v in c[k, 1, :bins]]
+        p_all, n_all = sum(pos), sum(neg)
+        per['n_pos'].append(p_all)
+        per['n_neg'].append(n_all)
+        per['n_nan'].append(int(c[k, 0, bins]) + int(c[k, 1, bins]))
+        below, num = 0, 0
+        for b in range(bins):
+            num += pos[b] * (2 * below + neg[b])
+            below += neg[b]
+        per['auroc'].append(num / (2 * p_all * n_all) if p_all and n_all else nan)
+        ap, clean, tp, fp = 0.0, 0, 0, 0
+        best_num, best_den, best_b = -1, 1, 0
+        for b in range(bins - 1, -1, -1):   # thresholds from the top: TP_b, FP_b as running sums
+            tp += pos[b]
+            fp += neg[b]
+            if pos[b] and not fp:
+                clean += pos[b]             # precision exactly 1: summed as integers (perfect separation gives exactly 1.0)
+            elif pos[b]:
+                ap += (pos[b] * tp) / (p_all * (tp + fp))
+            # F1_b = 2 TP_b / (TP_b + FP_b + P), compared exactly by cross-multiplication; `>=` on the way down keeps the smallest b
+            if p_all and 2 * tp * best_den >= best_num * (tp + fp + p_all):
+                best_num, best_den, best_b = 2 * tp, tp + fp + p_all, b
+        per['ap'].append(clean / p_all + ap if p_all else nan)
+        per['best_f1'].append(best_num / best_den if p_all else nan)
+        per['best_threshold'].append(best_b / bins if p_all else nan)
+        n = p_all + n_all
+        ece = 0.0
+        for b in range(bins):
+            nb = pos[b] + neg[b]
+            if nb:
+                ece += (nb / n) * abs(pos[b] / nb - (b + 0.5) / bins)
+        per['ece'].append(ece if n else nan)
+    return {'per_class': per, 'auc': _nanmean(per['auroc']), 'map': _nanmean(per['ap']), 'best_f1': _nanmean(per['best_f1']),
+            'bins': bins}
+
+
+class ScoreHistogram:
+    """The score histogram per (class, label) of everything `update` has seen: int64 [K, 2, bins + 1], one state per device (as
+    `_F1Score` keeps its states).  On GPU tensors an update is ONE iris_score_hist launch on the current stream (integer adds:
+    exact, independent of the order, no host sync); on CPU tensors `score_hist_host`, the same rule with torch ops."""
+
+    def __init__(self, n_classes: int, bins: int = 1024):
+        self.n_classes, self.bins = int(n_classes), check_curve_bins(bins)
+        if not 1 <= self.n_classes <= CURVE_MAX_CLASSES:
+            raise ValueError(f"ScoreHistogram: n_classes in [1, {CURVE_MAX_CLASSES}], got {n_classes}")
+        self.states: Dict[torch.device, torch.Tensor] = {}
+
+    def state(self, device) -> torch.Tensor:
+        device = torch.device(device)
+        if device.type == 'cuda' and device.index is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        if device not in self.states:
+            self.states[device] = torch.zeros(self.n_classes, 2, self.bins + 1, dtype=torch.int64, device=device)
+        return self.states[device]
+
+    @torch.no_grad()
+    def update(self, y_true: torch.Tensor, y_pred: torch.Tensor) -> None:
+        y_true, y_pred = _first(y_true), _first(y_pred)
+        if y_true.dim() != 3 or y_pred.dim() != 3 or y_true.shape != y_pred.shape:
+            raise ValueError(f"ScoreHistogram.update: y_true and y_pred [B, T, K] at the same frame rate, got {tuple(y_true.shape)} "
+                             f"/ {tuple(y_pred.shape)}")
+        if y_pred.shape[2] != self.n_classes:
+            raise ValueError(f"ScoreHistogram.update: {y_pred.shape[2]} classes, made for {self.n_classes}")
+        if not (y_true.is_floating_point() and y_pred.is_floating_point()):
+            raise ValueError(f"ScoreHistogram.update: floating-point tensors, got {y_true.dtype} / {y_pred.dtype}")
+        if y_true.device != y_pred.device:
+            raise ValueError(f"ScoreHistogram.update: y_true on {y_true.device}, y_pred on {y_pred.device}")
+        if y_pred.numel() == 0:
+            return
+        st = self.state(y_pred.device)
+        if not y_pred.is_cuda:
+            st += score_hist_host(y_true, y_pred, self.bins)
+            return
+        yt = y_true.detach().to(torch.float32).contiguous()
+        yp = y_pred.detach().to(torch.float32).contiguous()
+        b, t, k = yp.shape
+        N.check(N.lib().iris_score_hist(yt.data_ptr(), yp.data_ptr(), b, t, k, self.bins, st.data_ptr(),
+                                        torch.cuda.current_stream(yp.device).cuda_stream), "iris_score_hist")
+
+    def reset(self) -> None:
+        for s in self.states.values():
+            s.zero_()
+
+    def counts(self) -> torch.Tensor:
+        """The counts on the host, summed over this object's devices."""
+        out = torch.zeros(self.n_classes, 2, self.bins + 1, dtype=torch.int64)
+        for s in self.states.values():
+            out += s.cpu()
+        return out
+
+    def compute(self) -> dict:
+        return curve_metrics(self.counts())
+
+
+CURVE_NAMES = ('auc', 'map', 'best_f1')   # what `MetricSet.curve_values` adds to a row; `fit` MAXIMISES a monitor with such a name
+
+
+class _ScoreCurves:
+    """score_curves(bins): the compiled metric behind val_auc / val_map / val_best_f1.  A `MetricSet` feeds its histogram in
+    the 'val' phase only and returns no per-step value for it; the histogram is made by the first batch (its class count)."""
+
+    def __init__(self, bins=1024):
+        self.bins = check_curve_bins(bins)
+        self.hist: Optional[ScoreHistogram] = None
+        self.__name__ = 'score_curves'
+
+    def update(self, y_true, y_pred) -> None:
+        y_pred = _first(y_pred)
+        if self.hist is None:
+            self.hist = ScoreHistogram(y_pred.shape[-1], self.bins)
+        self.hist.update(y_true, y_pred)
+
+    def reset(self) -> None:
+        if self.hist is not None:
+            self.hist.reset()
+
+    def __call__(self, y_true, y_pred):
+        raise TypeError("score_curves() has no per-batch value: compile it (model.compile(metrics=[...])) and read "
+                        "MetricSet.curve_values after the validation pass")
+
+
+def score_curves(bins=1024):
+    """A metric for `compile(metrics=[...])`: ROC-AUC, average precision and the best frame F1 of the validation pass, from an
+    on-device score histogram with `bins` bins (`fit` logs val_auc, val_map, val_best_f1)."""
+    return _ScoreCurves(bins)
+
+
 def _is_cos(m):
     return m is cos_sim or m is _cos_sim_metric
 
@@ -224,14 +403,20 @@ class MetricSet:
     """A compiled metric list (`CustomModel.compile(metrics=...)`).  Any of er_score / f1_score / cos_sim are served by ONE
     iris_event_metrics launch per batch on a GPU (at most one of each kind; other callables are called as they are).  Each call
     adds to the epoch accumulator of its phase ('train' / 'val'): fp64 [5] = sum er, sum cos, sum f1, clips, batches - zeroed by
-    `reset`, read once per epoch by `fit` (Keras' means: per-clip metrics weighted by clips, the scalar F1 by batches)."""
+    `reset`, read once per epoch by `fit` (Keras' means: per-clip metrics weighted by clips, the scalar F1 by batches).
+    A score_curves() in the list (at most one) is fed in the 'val' phase only - one more launch, iris_score_hist - and read with
+    `curve_values`; a 'train'-phase call launches nothing for it, so the captured training step is what it is without it."""
 
     def __init__(self, metrics):
         self.metrics = list(metrics)
         self.er = next((m for m in self.metrics if isinstance(m, _ErScore)), None)
         self.f1 = next((m for m in self.metrics if isinstance(m, _F1Score)), None)
         self.cos = any(_is_cos(m) for m in self.metrics)
-        fused = {id(self.er), id(self.f1)}
+        curves = [m for m in self.metrics if isinstance(m, _ScoreCurves)]
+        if len(curves) > 1:
+            raise ValueError("MetricSet: at most one score_curves() in a metric list")
+        self.curves = curves[0] if curves else None   # fed in the 'val' phase only; no per-step value
+        fused = {id(self.er), id(self.f1), id(self.curves)}
         self.others = [m for m in self.metrics if id(m) not in fused and not _is_cos(m)]
         self.names = [metric_name(m) for m in self.metrics]
         dup = sorted({n for n in self.names if self.names.count(n) > 1})
@@ -254,6 +439,8 @@ class MetricSet:
         for (_, ph), a in self.accums.items():
             if phase is None or ph == phase:
                 a.zero_()
+        if self.curves is not None and phase in (None, 'val'):
+            self.curves.reset()
 
     @torch.no_grad()
     def __call__(self, y_true, y_pred, phase: str = 'train') -> Dict[str, torch.Tensor]:
@@ -288,7 +475,27 @@ class MetricSet:
                                 acc.new_tensor(float(b)), acc.new_tensor(1.0)])
         for m in self.others:
             res[metric_name(m)] = m(y_true, y_pred)
+        if self.curves is not None and phase == 'val':   # one iris_score_hist launch on a GPU; the train phase launches nothing
+            self.curves.update(y_true, y_pred)
         return {n: res[n] for n in self.names if n in res}
+
+    def curve_values(self, prefix: str = '', all_reduce: bool = False) -> Dict[str, float]:
+        """Row entries of a compiled score_curves(): {prefix + 'auc', 'map', 'best_f1'} (macro means) from the validation
+        histogram - summed over the ranks first with `all_reduce` (int64 SUM: exact, every rank gets the same values) - in one
+        copy to the host.  Every rank must have seen a validation batch, or none."""
+        if self.curves is None:
+            return {}
+        hist = self.curves.hist
+        if hist is None or not hist.states:
+            return {prefix + n: float('nan') for n in CURVE_NAMES}
+        states = list(hist.states.values())
+        total = states[0].clone() if all_reduce or len(states) > 1 else states[0]
+        for s in states[1:]:
+            total += s.to(total.device)
+        if all_reduce:
+            torch.distributed.all_reduce(total)
+        values = curve_metrics(total.cpu())
+        return {prefix + n: values[n] for n in CURVE_NAMES}
 
     def epoch_values(self, sums: torch.Tensor, prefix: str = '') -> Dict[str, float]:
         """Row entries from an accumulator's (possibly all-reduced) host values."""
@@ -382,9 +589,11 @@ def output_to_metric(hop, sr):
 # challenge score                                              metrics.py:14-87
 # ---------------------------------------------------------------------------
 def evaluate(config, model, overlap_hop=512, verbose: bool = False, *, wav_dir: str = '.',
-             answer_path: str = 'sample_answer.json', device=None):
+             answer_path: str = 'sample_answer.json', device=None, curves: Optional["ScoreHistogram"] = None):
     """Per-file ER of `model` on sorted(glob(wav_dir/*.wav)) against answer_path's 'task2_answer' (metrics.py:31-87): the
-    frame decisions of inference.predict_frames (smoothed, >= 0.5), then get_start_end_frame -> output_to_metric -> get_er."""
+    frame decisions of inference.predict_frames (smoothed, >= 0.5), then get_start_end_frame -> output_to_metric -> get_er.
+    `curves`: a ScoreHistogram that is also fed every file's frame posteriors (the smoothed probabilities, before the 0.5
+    decision) against the `second2frame` labels of the file's answer; the decisions and the scores are what they are without it."""
     from . import data_utils as D
     from .inference import features_for_eval, predict_frames
     with open(answer_path) as f:
@@ -396,10 +605,18 @@ def evaluate(config, model, overlap_hop=512, verbose: bool = False, *, wav_dir: 
     final_score = []
     for path in sorted(glob(os.path.join(wav_dir, '*.wav'))):
         spec = D.load_wav(path, device)
-        preds = predict_frames(model, features_for_eval(spec, config), config, overlap_hop)
+        name = os.path.basename(path)[:-4]
+        if curves is None:
+            preds = predict_frames(model, features_for_eval(spec, config), config, overlap_hop)
+        else:
+            from .eval import second2frame
+            post = predict_frames(model, features_for_eval(spec, config), config, overlap_hop, threshold=False)
+            labels = second2frame(answer_gt[name], post.shape[0], sr / hop).to(post.device)
+            curves.update(labels[None], post.to(torch.float32)[None])
+            preds = (post >= 0.5).to(torch.float32)   # (predict_frames' own decision)
         cls0, cls1, cls2 = metric.get_start_end_frame(preds.cpu().numpy())
         predict = output_to_metric(hop, sr)(cls0, cls1, cls2)
-        final_score.append(get_er(answer_gt[os.path.basename(path)[:-4]], predict))
+        final_score.append(get_er(answer_gt[name], predict))
     if verbose:
         print('FINAL SCORE:', np.mean(final_score))
     return final_score

@@ -36,11 +36,36 @@ from .transforms import complex_to_magphase, magphase_to_mel
 from .utils import label_downsample_model, load_data, sigmoid_focal_crossentropy, unitwise_norm
 
 
+def _curve_bins(text):
+    """--curves: 0 (off) or a bin count the score histogram takes."""
+    from .metrics import check_curve_bins
+    try:
+        bins = int(text)
+        return bins if bins == 0 else check_curve_bins(bins)
+    except ValueError as exc:
+        raise argparse.ArgumentTypeError(str(exc))
+
+
+def row_names(config) -> list:
+    """The entries `main`'s `fit` rows hold besides epoch / lr / time for these flags: what --checkpoint_monitor may name."""
+    names = ['loss']
+    if getattr(config, 'metrics', 'none') == 'reference':
+        names += ['cos_sim', 'f1_score'] + (['er'] if config.v != 5 else [])
+    val = ['val_' + n for n in names]
+    if getattr(config, 'curves', 0):
+        from .metrics import CURVE_NAMES
+        val += ['val_' + n for n in CURVE_NAMES]
+    ema = ['val_ema_' + n[len('val_'):] for n in val] if getattr(config, 'ema', 0) else []
+    return names + val + ema
+
+
 class ARGS:
     """Same flags and defaults as sj_train.py:20-71, plus the knobs the reference has no
     equivalent for (synthetic data, device, distributed launch)."""
 
-    def __init__(self) -> None:
+    def __init__(self, trainer_flags: bool = True) -> None:
+        """trainer_flags=False: without the flags that only `main` here reads (--curves, --checkpoint_monitor), for a tool that
+        extends this parser with flags of its own (`eval`, whose --curves names a file)."""
         self.args = argparse.ArgumentParser()
         a = self.args.add_argument
         a('--name', type=str, default='')
@@ -114,8 +139,22 @@ class ARGS:
                "checkpoint on val_er and score the checkpoint every 5 epochs against ./sample_answer.json and ./*.wav "
                "(metrics.eval_callback; the file must exist); 'none': loss only")
 
+        if not trainer_flags:
+            return
+        a('--curves', type=_curve_bins, default=0, metavar='BINS',
+          help='log the threshold-free validation numbers val_auc (macro ROC-AUC), val_map (macro average precision) and '
+               'val_best_f1 (best frame F1 over thresholds) from an on-device score histogram with BINS bins (a power of two in '
+               '[16, 4096]; metrics.score_curves, one more launch per validation batch); 0 (default): off.  Not part of the run name')
+        a('--checkpoint_monitor', type=str, default=None, metavar='NAME',
+          help="the row entry the checkpoint follows, e.g. val_map (auc / map / best_f1 are maximised, everything else "
+               "minimised); default: val_er with --metrics reference, else val_loss")
+
     def get(self, argv=None):
-        return self.args.parse_args(argv)
+        config = self.args.parse_args(argv)
+        monitor = getattr(config, 'checkpoint_monitor', None)
+        if monitor is not None and monitor not in row_names(config):
+            raise ValueError(f"--checkpoint_monitor {monitor!r}: the rows of this run will hold {row_names(config)}")
+        return config
 
 
 # ---------------------------------------------------------------------------
@@ -677,14 +716,22 @@ def main(argv=None):
         monitor = 'val_er'
         if rank == 0:
             callbacks.append(eval_callback(config, NAME.replace('.h5', '.pt')))
+    if config.curves:   # with --metrics none the only metric
+        from .metrics import score_curves
+        metrics = (metrics or []) + [score_curves(config.curves)]
+    if config.checkpoint_monitor is not None:
+        monitor = config.checkpoint_monitor
     ema = None
     if config.ema:   # after the metrics are known, before DDP wraps the model: a second CustomModel, not a submodule
         from .ema import WeightEMA
         ema = WeightEMA(model, config.ema)
         own = None
-        if metrics is not None:   # fresh metric objects: the F1 counts of the EMA pass must not land in the live model's
+        if config.metrics == 'reference':   # fresh metric objects: the F1 counts of the EMA pass must not land in the live model's
             from .metrics import cos_sim, er_score, f1_score
             own = [cos_sim, f1_score()] + ([er_score(smoothing=False)] if config.v != 5 else [])
+        if config.curves:   # (and a histogram of its own)
+            from .metrics import score_curves
+            own = (own or []) + [score_curves(config.curves)]
         ema.compile(loss, metrics=own)
     model.compile(opt, loss, clipvalue=None if config.no_clipvalue_after_agc else config.clipvalue,
                   ddp=wrap_ddp(model, device, world), metrics=metrics, ema=ema)

@@ -445,6 +445,23 @@ int iris_event_metrics(const float* y_true, const float* y_pred, int batch, int 
                        float* f1_out, double* accum, double* slab, unsigned int* ticket, void* stream);
 
 /*
+ * Score histogram of one batch per (class, label), ONE launch on `stream`, capturable; the primitive behind the threshold-free
+ * validation numbers (ROC-AUC, average precision, best-F1 threshold, calibration error: host arithmetic on the counts).
+ *   y_true, y_pred [B, T, K] fp32 contiguous, at the same frame rate; 1 <= K <= 16, B * T <= 2^31 - 1.
+ *   bins     a power of two in [16, 4096].
+ *   counts   [K][2][bins + 1] int64, DEVICE, CUMULATIVE (the caller zeroes it): counts[k][label][slot] += 1 per frame with
+ *            label = y_true >= 0.5f (a NaN label is negative; labels above 1 are positive) and, for a prediction p,
+ *            slot = min(bins - 1, max(0, (int)floorf(p * bins))) - p <= 0, -0.0, subnormals and -inf: 0; p >= 1 and +inf:
+ *            bins - 1 - or slot = bins for a NaN prediction (kept, never folded into a bin).  p * bins is exact in fp32, so
+ *            "slot >= b" is the predicate p >= b / bins.
+ * Integer adds only: independent of the order, bitwise reproducible, and the counts of several ranks sum exactly.
+ * Refused before any HIP call: NULL pointers, B / T / K < 1 (INVALID); K > 16, bins not a power of two in range,
+ * B * T > 2^31 - 1 (UNSUPPORTED).
+ */
+int iris_score_hist(const float* y_true, const float* y_pred, int batch, int n_time, int n_classes, int bins,
+                    long long* counts, void* stream);
+
+/*
  * Window predictions of F files -> event lists (metrics.py:56-81 from the model's outputs on, then get_start_end_frame,
  * metrics.py:111-137), two launches, capturable:
  *   preds      [W_total, n_out, K] fp32, DEVICE: the model's outputs for every window of every file, file after file
