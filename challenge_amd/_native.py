@@ -81,6 +81,8 @@ SIGNATURES = {
     "iris_magmel_gain": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
     "iris_spec_ipd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     "iris_filter_draw": (_i, [_i, _i, _i, _i, _i, _i, _f, _f, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
+    "iris_crop_windows": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "iris_crop_draw": (_i, [_vp, _i, _i, C.c_uint64, _vp, _vp, _vp]),
     "iris_mask_apply": (_i, [_vp, _sz, _sz, _sz, _i, _vp, _i, _sz, _vp]),
     "iris_agc_clip": (_i, [_vp, _sz, _f, _f, _f, _vp]),
     "iris_mix_frame_active": (_i, [_vp, _i, _i, _i, _vp, _vp]),

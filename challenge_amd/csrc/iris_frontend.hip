@@ -16,6 +16,8 @@
 //   k_elementwise.h  min-max / log, normalize, magnitude-phase, mask, adaptive gradient clipping
 //   k_mix.h          batched sample synthesis (merge_complex_specs)
 //   k_draw.h         the random half of a batch drawn on the device (source table, SpecAugment bands)
+//   k_crop.h         training windows cut from labelled recordings: the draws (recording, first frame) and the gather of the
+//                    windows and their frame labels, one launch each
 //   k_lstm.h         the CRNN's bidirectional LSTM: forward and backward through time, one launch each
 //   k_conv_small.h   the CRNN's first convolution (1-2 input channels) with bias + ReLU, one pass (inference)
 //   k_conv0_bn.h     the same layer in training mode: convolution recomputed inside the BatchNorm + ReLU passes
@@ -58,6 +60,7 @@
 #include "host_ops.h"
 #include "k_mix.h"
 #include "k_draw.h"
+#include "k_crop.h"
 #include "k_lstm.h"
 #include "k_conv_small.h"
 #include "k_conv0_bn.h"

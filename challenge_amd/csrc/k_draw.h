@@ -37,7 +37,7 @@ __host__ __device__ inline Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint3
 }
 
 // purposes (counter word 3)
-enum { kDrawSample = 1, kDrawVoice = 2, kDrawNoise = 3, kDrawPerm = 4, kDrawBandT = 5, kDrawBandF = 6, kDrawFilter = 7 };
+enum { kDrawSample = 1, kDrawVoice = 2, kDrawNoise = 3, kDrawPerm = 4, kDrawBandT = 5, kDrawBandF = 6, kDrawFilter = 7, kDrawCrop = 8 };
 
 __host__ __device__ inline uint32_t draw_below(uint32_t word, uint32_t range) {  // uniform on [0, range), range >= 1
     return (uint32_t)(((uint64_t)word * range) >> 32);

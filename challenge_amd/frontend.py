@@ -510,6 +510,82 @@ def filter_draw(batch: int, n_mel: int, kind: str = "step", n_band=(3, 6), min_b
     return bounds, dbs, gain
 
 
+# mirrors iris_crop_rec (include/iris_frontend.h)
+CROP_REC = np.dtype([("base", "<u8"), ("row_stride", "<i8"), ("len", "<i4"), ("ev_first", "<i4"), ("ev_count", "<i4"),
+                     ("reserved", "<i4")])
+assert CROP_REC.itemsize == 32
+
+
+def _require_device_int(t, dtype, name: str, what: str) -> torch.Tensor:
+    if not (isinstance(t, torch.Tensor) and t.is_cuda):
+        raise RuntimeError(f"{what}: {name} must be a tensor on a ROCm device (no CPU fallback)")
+    if t.dtype != dtype or not t.is_contiguous():
+        raise TypeError(f"{what}: {name} must be a contiguous {dtype} tensor")
+    return t
+
+
+def crop_windows(recs: torch.Tensor, events: torch.Tensor, draws: torch.Tensor, channels: int, hop: int, n_frame: int,
+                 n_classes: int = 3, out=None):
+    """A batch of windows of labelled recordings and their frame labels, ONE `iris_crop_windows` launch:
+    (wav float32 [B, channels, (n_frame - 1) * hop], y float32 [B, n_frame, n_classes]).  recs: the CROP_REC table of the
+    recordings as a uint8 device tensor (device addresses, row strides, lengths, event rows); events: int32 [rows, 3] of
+    (class, start frame, end frame) on the device; draws: int32 [B, 2] of (recording, first frame) on the device
+    (`crop_draw`).  Samples at or beyond a recording's length are exactly 0 and are never read; y counts the events that
+    cover a frame.  `out`: the (wav, y) of an earlier call of the same shape, overwritten in place.  Capturable."""
+    what = "crop_windows"
+    recs = _require_device_int(recs, torch.uint8, "recs", what)
+    events = _require_device_int(events, torch.int32, "events", what)
+    draws = _require_device_int(draws, torch.int32, "draws", what)
+    if recs.numel() == 0 or recs.numel() % CROP_REC.itemsize:
+        raise ValueError(f"{what}: recs must hold a whole, positive number of {CROP_REC.itemsize}-byte records")
+    if draws.dim() != 2 or draws.shape[1] != 2:
+        raise ValueError(f"{what}: draws must be [batch, 2], got {tuple(draws.shape)}")
+    if events.dim() != 2 or events.shape[1] != 3 or events.shape[0] < 1:
+        raise ValueError(f"{what}: events must be [rows >= 1, 3], got {tuple(events.shape)}")
+    device, batch = draws.device, int(draws.shape[0])
+    channels, hop, n_frame, n_classes = int(channels), int(hop), int(n_frame), int(n_classes)
+    shapes = (batch, channels, max(n_frame - 1, 0) * max(hop, 0)), (batch, max(n_frame, 0), max(n_classes, 0))
+    if out is None:
+        wav = torch.empty(shapes[0], dtype=torch.float32, device=device)
+        y = torch.empty(shapes[1], dtype=torch.float32, device=device)
+    else:
+        wav, y = out
+        if (tuple(wav.shape), tuple(y.shape)) != shapes or wav.dtype != torch.float32 or y.dtype != torch.float32 or \
+                not (wav.is_contiguous() and y.is_contiguous()) or wav.device != device or y.device != device:
+            raise ValueError(f"{what}: out must be the (wav, y) of a call with the same batch and sizes")
+    with torch.cuda.device(device):
+        rc = N.lib().iris_crop_windows(recs.data_ptr(), recs.numel() // CROP_REC.itemsize, events.data_ptr(), draws.data_ptr(),
+                                       batch, channels, hop, n_frame, n_classes, wav.data_ptr(), y.data_ptr(), _stream_ptr(device))
+    N.check(rc, "iris_crop_windows")
+    return wav, y
+
+
+def crop_draw(prefix: torch.Tensor, batch: int, seed: int = 0, state: Optional[torch.Tensor] = None, out=None) -> torch.Tensor:
+    """The window draws of a batch ON THE DEVICE, one `iris_crop_draw` launch: int32 [B, 2] of (recording, first frame), every
+    window of the corpus equally likely.  prefix: int64 [n + 1] device tensor, the prefix sums of the recordings' position
+    counts max((len - L) // hop, 0) + 1.  Philox keyed by `seed`; `state`: an int64 [1] device tensor of this draw's own,
+    zero-initialised once, advanced by every call on the device (None: a fresh zero state, i.e. the first draw of `seed`).
+    `out`: the draws of an earlier call of the same batch, overwritten in place.  Capturable."""
+    what = "crop_draw"
+    prefix = _require_device_int(prefix, torch.int64, "prefix", what)
+    if prefix.dim() != 1 or prefix.numel() < 2:
+        raise ValueError(f"{what}: prefix must be [n + 1] with n >= 1, got {tuple(prefix.shape)}")
+    device, batch = prefix.device, int(batch)
+    if state is None:
+        state = torch.zeros(1, dtype=torch.int64, device=device)
+    elif not isinstance(state, torch.Tensor) or state.dtype != torch.int64 or state.numel() != 1 or state.device != device:
+        raise ValueError(f"{what}: state must be an int64 tensor of one element on the device of prefix")
+    if out is None:
+        out = torch.empty((max(batch, 0), 2), dtype=torch.int32, device=device)
+    elif tuple(out.shape) != (batch, 2) or out.dtype != torch.int32 or not out.is_contiguous() or out.device != device:
+        raise ValueError(f"{what}: out must be the int32 [batch, 2] draws of an earlier call")
+    with torch.cuda.device(device):
+        rc = N.lib().iris_crop_draw(prefix.data_ptr(), int(prefix.numel()) - 1, batch, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                    state.data_ptr(), out.data_ptr(), _stream_ptr(device))
+    N.check(rc, "iris_crop_draw")
+    return out
+
+
 def bias_relu_(x: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
     """In place max(x + bias[c], 0) on a channels-last activation: x is [B, C, H, W] with channels_last strides (or any
     dense tensor whose innermost axis is the channel axis).  One HIP launch (iris_bias_relu)."""

@@ -64,8 +64,8 @@ class ARGS:
     equivalent for (synthetic data, device, distributed launch)."""
 
     def __init__(self, trainer_flags: bool = True) -> None:
-        """trainer_flags=False: without the flags that only `main` here reads (--curves, --checkpoint_monitor), for a tool that
-        extends this parser with flags of its own (`eval`, whose --curves names a file)."""
+        """trainer_flags=False: without the flags that only `main` here reads (--curves, --checkpoint_monitor,
+        --recordings*), for a tool that extends this parser with flags of its own (`eval`, whose --curves names a file)."""
         self.args = argparse.ArgumentParser()
         a = self.args.add_argument
         a('--name', type=str, default='')
@@ -148,12 +148,36 @@ class ARGS:
         a('--checkpoint_monitor', type=str, default=None, metavar='NAME',
           help="the row entry the checkpoint follows, e.g. val_map (auc / map / best_f1 are maximised, everything else "
                "minimised); default: val_er with --metrics reference, else val_loss")
+        a('--recordings', type=str, default=None, metavar='DIR',
+          help='--online_stft only.  Cut a share of every training batch from the labelled recordings DIR/*.wav '
+               '(recordings.load_recordings: resampled to 16 kHz, scaled as load_wav scales a file) - random windows, drawn and '
+               'gathered on the device (iris_crop_draw, iris_crop_windows), labelled from --recordings_answer; the rest of the '
+               'batch is synthetic as before.  The validation set is unchanged.  Not part of the run name')
+        a('--recordings_answer', type=str, default=None, metavar='FILE',
+          help="the recordings' events: a JSON in sample_answer.json's schema whose 'task2_answer' has an entry per wav of "
+               "--recordings (default: DIR/answer.json)")
+        a('--recordings_share', type=float, default=0.5, metavar='S',
+          help='the share of a batch cut from --recordings, in (0, 1]: max(1, round(S * batch_size)) windows; 1: no synthetic '
+               'corpus is loaded at all (default 0.5)')
 
     def get(self, argv=None):
         config = self.args.parse_args(argv)
         monitor = getattr(config, 'checkpoint_monitor', None)
         if monitor is not None and monitor not in row_names(config):
             raise ValueError(f"--checkpoint_monitor {monitor!r}: the rows of this run will hold {row_names(config)}")
+        if getattr(config, 'recordings', None) is not None:
+            if not config.online_stft:
+                raise ValueError("--recordings cuts waveform windows and needs the waveform path: add --online_stft")
+            if not 0.0 < config.recordings_share <= 1.0:
+                raise ValueError(f"--recordings_share {config.recordings_share} is outside (0, 1]")
+            if config.metrics == 'reference':
+                from glob import glob
+                scored = {os.path.realpath(p) for p in glob(os.path.join('.', '*.wav'))}
+                both = sorted(p for p in glob(os.path.join(config.recordings, '*.wav')) if os.path.realpath(p) in scored)
+                if both:
+                    raise ValueError(f"--recordings {config.recordings!r} holds {both}, which --metrics reference scores every 5 "
+                                     "epochs (./*.wav against ./sample_answer.json): fine-tuning on the scored files flatters val_er "
+                                     "and test_er; train on other recordings or drop --metrics reference")
         return config
 
 
@@ -501,7 +525,7 @@ def wave_features(plan, compression, do_minmax, wav, t_bands=None, f_bands=None,
 
 
 def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=None, seed=None, n_fft=512, hop=256,
-                      sample_rate=16000, device_draw=False, spec_sources=None):
+                      sample_rate=16000, device_draw=False, spec_sources=None, recordings=None, recordings_share=0.5):
     """`make_device_dataset` from WAVEFORMS (waveform-domain variant): the corpora
     stay resident in HBM as [chan, L_i] waveforms, `WaveMixer` mixes a batch before the STFT (which is linear), and
     the fused kernel takes it from there - STFT, SpecAugment / `stft_filter` bands, mel, min-max, log in one pass;
@@ -519,53 +543,110 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
     'ipd' and refuses 'stretch', and 'speed' beside 'reverb' (`data_utils.BUILDER_REFUSALS`).  With 'ipd' x is
     [B, n_mels, n_frame, 4] (`wave_features`); the corpora must be stereo.
     spec_sources: the same tuple as SPECTRA ([F, T_i, 2C], integer labels), e.g. the pickled corpora - converted once here by
-    `waves_from_specs` at this n_fft / hop and used as `sources` (giving both is a ValueError)."""
+    `waves_from_specs` at this n_fft / hop and used as `sources` (giving both is a ValueError).
+    recordings: a `recordings.RecordingSampler` (built for this n_frame and hop), or a (waves, events) pair - what
+    `recordings.load_recordings` returns - that is wrapped in one here (seeded `seed`, drawing on the device under
+    `device_draw`).  Training sets only (a validation set is what it is without it): with k = max(1, round(recordings_share *
+    batch_size)) every batch holds k windows cut from the recordings, labelled from their events, FIRST, then batch_size - k
+    synthetic samples of the mixer; the concatenated batch takes the one `BatchDraws` / `wave_features` call, so SpecAugment
+    bands, 'filter', 'filtaug', 'pcen', 'pcen_learn', 'ipd' and the n_chan == 1 down-mix apply to all of it, while the
+    voice-corpus augmentations 'speed' / 'reverb' ('shoebox') touch the synthetic part only.  At recordings_share == 1.0 no mixer
+    is built and no synthetic corpus is loaded (`dataset.mixer` is None).  `dataset.recordings` is the sampler (None without).
+    ValueError: a share outside (0, 1], a sampler of another n_frame / hop, recordings whose channel count differs from the
+    synthetic corpus's, 'ipd' with mono recordings - each before the device is touched."""
     from .mixer import WaveMixer
     if spec_sources is not None and sources is not None:
         raise ValueError("make_wave_dataset: give `sources` (waveforms) or `spec_sources` (spectra), not both")
     tokens = _du.run_tokens(config)
     _du.check_builder(tokens, 'make_wave_dataset')
-    if spec_sources is not None:
-        sources = waves_from_specs(spec_sources, n_fft, hop, device)
-    if sources is None:
-        sources = synthetic_wave_sources(2, n_classes, hop, seed=0 if training else 1)
-    backgrounds, voices, labels, noises = sources
-    labels = np.eye(n_classes, dtype='float32')[np.asarray(labels)]
+    sampler, n_rec = None, 0
+    if recordings is not None:
+        from .recordings import RecordingSampler, _channels_of
+        if not 0.0 < float(recordings_share) <= 1.0:
+            raise ValueError(f"make_wave_dataset: recordings_share = {recordings_share} is outside (0, 1]")
+        if isinstance(recordings, RecordingSampler):
+            if (recordings.n_frame, recordings.hop) != (config.n_frame, hop):
+                raise ValueError(f"make_wave_dataset: the RecordingSampler cuts windows of n_frame {recordings.n_frame} at hop "
+                                 f"{recordings.hop}, this dataset is built for n_frame {config.n_frame} at hop {hop}")
+            rec_chan = recordings.channels
+        else:
+            rec_chan = _channels_of(recordings[0])
+        if tokens.ipd and rec_chan != 2:
+            raise ValueError(f"run name {config.name!r} asks for 'ipd' but the recordings have {rec_chan} channel(s): the "
+                             "inter-channel phase difference needs stereo recordings")
+        if float(recordings_share) < 1.0:
+            corpus_chan = 2 if sources is None else int(sources[0][0].shape[0])
+            if spec_sources is not None:
+                corpus_chan = int(spec_sources[0][0].shape[2]) // 2
+            if rec_chan != corpus_chan:
+                raise ValueError(f"make_wave_dataset: the recordings have {rec_chan} channel(s), the synthetic corpus {corpus_chan}: "
+                                 "one batch holds both")
+        if training:
+            n_rec = min(max(1, int(round(float(recordings_share) * config.batch_size))), config.batch_size)
+            sampler = recordings
     if config.model_type == 'se' and config.v == 9:
         raise NotImplementedError("model_type 'se' is outside the accelerated path (SURVEY.md section 2)")
     if config.n_chan not in (1, 2):
         raise NotImplementedError("make_wave_dataset: n_chan 1 (mono sum) or 2; the augmenting channel maps mix spectra")
-    mixer = WaveMixer(backgrounds, voices, labels, noises, n_frame=config.n_frame, n_fft=n_fft, hop=hop,
-                      max_voices=config.max_voices, max_noises=config.max_noises, n_classes=n_classes, device=device,
-                      snr=config.snr, min_ratio=1, seed=seed)
+    mixer = None
+    if sampler is None or float(recordings_share) < 1.0:
+        if spec_sources is not None:
+            sources = waves_from_specs(spec_sources, n_fft, hop, device)
+        if sources is None:
+            sources = synthetic_wave_sources(2, n_classes, hop, seed=0 if training else 1)
+        backgrounds, voices, labels, noises = sources
+        labels = np.eye(n_classes, dtype='float32')[np.asarray(labels)]
+        mixer = WaveMixer(backgrounds, voices, labels, noises, n_frame=config.n_frame, n_fft=n_fft, hop=hop,
+                          max_voices=config.max_voices, max_noises=config.max_noises, n_classes=n_classes, device=device,
+                          snr=config.snr, min_ratio=1, seed=seed)
+    if sampler is not None and not isinstance(sampler, RecordingSampler):
+        sampler = RecordingSampler(sampler[0], sampler[1], config.n_frame, hop, n_classes, device if mixer is None else mixer.device, seed)
+        if device_draw:
+            sampler.enable_device_draw(0 if seed is None else seed)
+    dev = sampler.device if mixer is None else mixer.device
     length = (config.n_frame - 1) * hop
-    plan = _fe.FrontendPlan(n_fft, hop, config.n_mels, sample_rate, config.n_chan, config.batch_size, length, mixer.device)
+    plan = _fe.FrontendPlan(n_fft, hop, config.n_mels, sample_rate, config.n_chan, config.batch_size, length, dev)
     # `wave_features`' words for the compression: the raw mel magnitudes of 'pcen_learn' go to the model's PCEN layer
     compression = {'pcen': 'pcen', 'pcen_learn': 'mel'}.get(tokens.compression, 'log')
     do_minmax = tokens.compression == 'minmax_log'
-    if tokens.ipd and mixer.channels != 2:
+    if tokens.ipd and mixer is not None and mixer.channels != 2:
         raise ValueError(f"run name {config.name!r} asks for 'ipd' but the corpus has {mixer.channels} channel(s): the inter-channel "
                          "phase difference needs stereo corpora")
-    if device_draw:
+    if device_draw and mixer is not None:
         mixer.enable_device_draw(0 if seed is None else seed)
-    draws = BatchDraws(tokens, training, mixer.device, seed, device_draw, plan.n_bins)
+    draws = BatchDraws(tokens, training, dev, seed, device_draw, plan.n_bins)
     # the voice corpus is augmented anew now and once per epoch (the validation set never is)
     respeed = rereverb = None
-    if training and tokens.speed:
+    if training and tokens.speed and mixer is not None:
         mixer.enable_speed()
         respeed = mixer.respeed
         respeed()
-    if training and tokens.reverb:
+    if training and tokens.reverb and mixer is not None:
         mixer.enable_reverb(model="shoebox" if tokens.shoebox else "noise")
         rereverb = mixer.rereverb
         rereverb()
+
+    def synthetic(n):
+        wav, y = mixer.mix(n)
+        _, y = to_frame_labels(None, y)
+        return wav, y
+
+    def mixed(n):
+        """n_rec windows of the recordings, then the mixer's samples.  The sampler's outputs are long-lived buffers that its next
+        call overwrites, and the dataset prefetches: what leaves this function is a copy (`cat`, or `clone` where there is no
+        synthetic part; the waveform alone is consumed by the feature launch before the next draw)."""
+        wav, y = sampler.sample(n_rec)
+        if n == n_rec:
+            return wav, y.clone()
+        syn_wav, syn_y = synthetic(n - n_rec)
+        return torch.cat([wav, syn_wav]), torch.cat([y, syn_y])
+    batch = synthetic if sampler is None else mixed
 
     def gen():
         reaugment = _every_epoch(respeed or rereverb, config.steps_per_epoch)
         while True:
             reaugment()
-            wav, y = mixer.mix(config.batch_size)
-            _, y = to_frame_labels(None, y)
+            wav, y = batch(config.batch_size)
             if config.n_chan == 1 and wav.shape[1] == 2:
                 wav = wav[:, :1] + wav[:, 1:]            # true down-mix (NOT the reference's broadcast mono_chan: see docstring)
             tb, fb, gain = draws(int(wav.shape[0]), config.n_frame, config.n_mels)
@@ -573,6 +654,7 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
 
     dataset = _label_tail(Dataset.from_generator(gen), config, compressed=True)
     dataset.mixer = mixer   # (for inspection: the resident corpus, its draws and - 'speed' / 'reverb' runs - the current voices)
+    dataset.recordings = sampler   # (the RecordingSampler of a training set built with `recordings`, else None)
     return dataset
 
 
@@ -762,8 +844,17 @@ def main(argv=None):
                 return None
             backgrounds, voices, onehot, noises = _load_sources(config, training, 3, None)
             return backgrounds, voices, onehot.argmax(-1), noises
+        recordings = None
+        if config.recordings is not None:   # loaded once per rank; each rank draws its own windows
+            from .recordings import RecordingSampler, load_recordings
+            recordings = RecordingSampler(*load_recordings(config.recordings, config.recordings_answer, device), config.n_frame, 256,
+                                          device=device, seed=3000 + rank)
+            if dd:
+                recordings.enable_device_draw(3000 + rank)
+        synthetic_part = recordings is None or config.recordings_share < 1.0
         train_set = make_wave_dataset(config, training=True, device=device, seed=1000 + rank, device_draw=dd,
-                                      spec_sources=spec_sources(True))
+                                      spec_sources=spec_sources(True) if synthetic_part else None, recordings=recordings,
+                                      recordings_share=config.recordings_share)
         test_set = make_wave_dataset(config, training=False, device=device, seed=2000 + rank, device_draw=dd,
                                      spec_sources=spec_sources(False))
     elif device.type == 'cuda' and not config.per_sample_pipeline:

@@ -894,6 +894,50 @@ int iris_filter_draw(int batch, int n_mel, int kind, int n_band_lo, int n_band_h
                      uint64_t seed, uint64_t* state_dev, int32_t* bounds_out, float* db_out, float* gain_out, void* stream);
 
 /*
+ * Training windows cut from LABELLED RECORDINGS on the device: a ragged set of `n` recordings, each [channels, len_i] fp32
+ * with its events as frame intervals, and per sample of a batch a draw (recording i, first frame q).
+ *
+ * iris_crop_windows gathers the batch in one launch.  recs_dev: DEVICE [n] records - `base` the DEVICE address of the
+ * recording's first channel row, `row_stride` the floats between channel rows (>= len), `len` the samples per channel that
+ * exist, `ev_first` / `ev_count` the recording's rows of the shared event table.  events_dev: DEVICE int32 [rows, 3] of
+ * (class, start frame, end frame); it must be a valid address even when no recording has events.  draws_dev: DEVICE int32
+ * [batch, 2] of (i, q).  With L = (n_frame - 1) * hop:
+ *   wav_out  DEVICE fp32 [batch, channels, L]: sample s of channel c is base[c * row_stride + q * hop + s] where
+ *            q * hop + s < len and exactly 0.0f otherwise - nothing at or beyond index len of a row is ever read, on either
+ *            path, so whatever lies behind a row (another recording, padding, NaN) cannot reach the batch
+ *   y_out    DEVICE fp32 [batch, n_frame, n_classes]: entry (f, k) is the NUMBER of the recording's events with class == k
+ *            and start <= q + f < end (overlapping events add up, as eval.second2frame's labels do)
+ * A draw with i outside [0, n) or q < 0 gives a zero window and zero labels.  The launch is a streaming copy: a (sample,
+ * channel) row whose source address and destination address are both 16-byte aligned (and L % 4 == 0) moves as 16-byte loads
+ * and stores; any other row takes a scalar path with the same result.  Rows that start on 16-byte boundaries with hop % 4 == 0
+ * always take the wide path.  No atomics, no allocation, no synchronisation: capturable, bitwise reproducible.
+ * Checked before any HIP call (IRIS_E_INVALID): batch < 0, n <= 0, hop <= 0, n_frame < 2, n_classes <= 0, channels not 1 or
+ * 2, a NULL pointer with batch > 0; IRIS_E_UNSUPPORTED: a window or label row beyond 2^31 entries, batch * (channels + 1) >
+ * 65535.  batch == 0 launches nothing.
+ *
+ * iris_crop_draw makes the draws in one small launch, every window of the corpus equally likely.  Recording i has
+ * n_pos[i] = max((len_i - L) / hop, 0) + 1 positions (integer division; a recording shorter than a window has the one
+ * position q = 0 and its tail comes out as zeros); prefix_dev: DEVICE int64 [n + 1], their prefix sums (prefix[0] = 0).
+ * Per sample b: the words (x, y) of Philox4x32-10 keyed by `seed` at counter (call counter lo, hi, b * 64, purpose 8) make
+ * the 64-bit word x << 32 | y; u = the high 64 bits of word * prefix[n] (uniform on [0, total), bias < total / 2^64); i is
+ * found by binary search (prefix[i] <= u < prefix[i + 1]) and q = u - prefix[i].  The recipe is restated in the header
+ * comment of csrc/k_crop.h and in NumPy by tests/crop_ref.py.  state_dev: DEVICE uint64[1] of this function's own,
+ * zero-initialised once by the caller, advanced by every call on the device (a captured launch replays with fresh draws).
+ * draws_out: DEVICE int32 [batch, 2].  One workgroup, no atomics: capturable.
+ * Checked before any HIP call (IRIS_E_INVALID): batch < 0, n <= 0, a NULL pointer with batch > 0; IRIS_E_UNSUPPORTED:
+ * batch > 2^25.  batch == 0 launches nothing (and does not advance the counter).
+ */
+typedef struct {
+    const float* base;
+    int64_t row_stride;
+    int32_t len, ev_first, ev_count, reserved;
+} iris_crop_rec;
+int iris_crop_windows(const iris_crop_rec* recs_dev, int n, const int32_t* events_dev, const int32_t* draws_dev, int batch,
+                      int channels, int hop, int n_frame, int n_classes, float* wav_out, float* y_out, void* stream);
+int iris_crop_draw(const int64_t* prefix_dev, int n, int batch, uint64_t seed, uint64_t* state_dev, int32_t* draws_out,
+                   void* stream);
+
+/*
  * Time stretching of complex spectrograms: the reference's phase_vocoder (transforms.py:137-195) for a RAGGED BATCH of
  * sources, each with its own rate, in one launch.  Per record: src DEVICE [n_bins, n_in, chan2] fp32 (re block | im block
  * last), rate > 0, dst DEVICE buffer whose first n_bins * n_out * chan2 floats receive the contiguous [n_bins, n_out, chan2]
