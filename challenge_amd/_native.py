@@ -73,6 +73,8 @@ SIGNATURES = {
     "iris_mix_wave_frame_active_batch": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "iris_fir_batch": (_i, [_vp, _i, _i, _i, _i, _vp]),
     "iris_fir_batch_pitch": (_i, [_vp, _i, _i, _i, _i, _i, _vp]),
+    "iris_fft_fir_workspace": (C.c_longlong, [_i, _i, _i]),
+    "iris_fft_fir_batch": (_i, [_vp, _i, _i, _i, _i, _i, _vp, C.c_longlong, _vp]),
     "iris_ism_rir": (_i, [_vp, _vp, _i, _i, _i, C.c_double, _i, _vp]),
     "iris_istft_len": (C.c_longlong, [C.c_longlong, _i]),
     "iris_istft": (_i, [_vp, _vp, _i, _i, _vp]),

@@ -42,6 +42,8 @@
 //                    real-valued rate, and the frame activity of the results, one launch each
 //   k_fir.h          reverberation: a batched direct-form FIR over a ragged set of waveforms, each channel with its own taps,
 //                    one launch
+//   k_fft_fir.h      the same convolution for long impulse responses (up to 32768 taps): partitioned overlap-save on the FFT
+//                    core, two launches
 //   k_ism.h          shoebox room simulation: image-source room impulse responses of a ragged set of voices, fixed-point LDS
 //                    accumulators, one launch (its entry point and checks: host_ops.h)
 //   host_plan.h      mel matrix, constant tables, plan create / destroy
@@ -82,3 +84,4 @@
 #include "k_vocoder.h"
 #include "k_speed.h"
 #include "k_fir.h"
+#include "k_fft_fir.h"

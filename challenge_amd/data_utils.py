@@ -143,6 +143,10 @@ class RunTokens:
         (`enable_reverb(model="shoebox")`: one `iris_ism_rir` and one `iris_fir_batch_pitch` launch per epoch, no tap upload),
         so the inter-channel delay and level of a voice are those of one room, instead of independent noise per channel.
         Refused without 'reverb': it only selects that augmentation's model.
+    reverb_long: the 'reverb' run with long rooms ('reverb' is then true as well, as 'filtaug_linear' holds 'filtaug'): rt60 ~
+        U[0.2, 1.0) s followed down to -40 dB without truncation - up to 10667 taps in [C, 16384] tap buffers - through the
+        partitioned FFT convolution (`enable_reverb(rt60_lo=0.2, rt60_hi=1.0, max_taps=16384)`: one `iris_fft_fir_batch`
+        launch pair per group of voices and epoch).  Refused with 'shoebox': the image-source kernel stops at 4096 taps.
     filtaug: FilterAugment, None or the kind of its gain curve ('step'; 'linear' for 'filtaug_linear') - every training
         sample's mel magnitudes are multiplied by a fresh random piecewise gain curve over the mel bands inside the mel kernels,
         before any compression (`iris_magmel_gain`, `iris_wav_to_logmel_gain`: no extra launch, no extra pass; the draw is
@@ -165,6 +169,7 @@ class RunTokens:
     shoebox: bool
     filtaug: Optional[str]
     ipd: bool
+    reverb_long: bool = False
 
 
 def run_tokens(config_or_name) -> RunTokens:
@@ -181,7 +186,10 @@ def run_tokens(config_or_name) -> RunTokens:
         filter='filter' in name, stretch='stretch' in name, speed='speed' in name, reverb='reverb' in name,
         shoebox='shoebox' in name,
         filtaug=('linear' if 'filtaug_linear' in name else 'step') if 'filtaug' in name else None,
-        ipd='ipd' in name)
+        ipd='ipd' in name, reverb_long='reverb_long' in name)
+    if tokens.reverb_long and tokens.shoebox:
+        raise ValueError(f"run name {name!r} asks for both 'reverb_long' and 'shoebox': the image-source room model computes at "
+                         "most 4096 taps, name one")
     if tokens.shoebox and not tokens.reverb:
         raise ValueError(f"run name {name!r} asks for 'shoebox' without 'reverb': the token selects the room model of the "
                          "reverberation augmentation, name both")

@@ -1380,6 +1380,100 @@ def fir_pitch_launch(table: np.ndarray, channels: int, max_len: int, max_taps: i
         ptr, n, int(channels), int(max_len), int(max_taps), int(tap_pitch), stream))
 
 
+# mirrors iris_fft_fir_src (include/iris_frontend.h)
+FFT_FIR_SRC = np.dtype([("src", "<u8"), ("dst", "<u8"), ("taps", "<u8"), ("len", "<i4"), ("n_taps", "<i4"), ("ws_off", "<i8")])
+assert FFT_FIR_SRC.itemsize == 40
+FFT_FIR_MAX_TAPS = 32768   # the longest impulse response `fft_fir_batch` and a long-path mixer take (2 s at 16 kHz)
+FFT_FIR_BLOCK = 1024       # new samples per frame of the partitioned convolution; its transform has 2048 points
+
+
+def fft_fir_workspace(channels: int, length: int, n_taps: int) -> int:
+    """Bytes of workspace one record of `fft_fir_launch` needs (iris_fft_fir_workspace): channels * (ceil(length / 1024) +
+    ceil(n_taps / 1024)) spectra of 8256 bytes, a multiple of 16; 0 for a malformed record (a count <= 0, n_taps > 32768)."""
+    return int(N.lib().iris_fft_fir_workspace(int(channels), int(length), int(n_taps)))
+
+
+def fft_fir_groups(table: np.ndarray, channels: int, workspace_budget: int):
+    """Split the records of an FFT_FIR_SRC table (len and n_taps filled) into consecutive groups whose workspace stays within
+    `workspace_budget` bytes - a single record may exceed it and is then a group of its own - and fill `ws_off` per group.
+    Returns (list of (first, last + 1) index pairs, the bytes of the largest group)."""
+    need = [fft_fir_workspace(channels, int(r["len"]), int(r["n_taps"])) for r in table]
+    groups, first, used, largest = [], 0, 0, 0
+    for i, n in enumerate(need):
+        if i > first and used + n > workspace_budget:
+            groups.append((first, i))
+            first, used = i, 0
+        table["ws_off"][i] = used
+        used += n
+        largest = max(largest, used)
+    if len(need):
+        groups.append((first, len(need)))
+    return groups, largest
+
+
+def fft_fir_launch(table: np.ndarray, channels: int, max_len: int, max_taps: int, tap_pitch: int, workspace: torch.Tensor,
+                   device: torch.device, table_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Upload an FFT_FIR_SRC table (into `table_dev`, a long-lived uint8 device buffer, when given) and run
+    iris_fft_fir_batch over it on the current stream: two launches.  `workspace` is a uint8 device tensor that holds every
+    record's slice (`ws_off`); `tap_pitch` = 0 for dense tap rows.  Returns the device table (tied to the stream when it was
+    allocated here)."""
+    if not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise ValueError("fft_fir_launch: workspace must be a contiguous uint8 tensor on a ROCm device")
+    return _launch_records(table, device, table_dev, "iris_fft_fir_batch", lambda ptr, n, stream: N.lib().iris_fft_fir_batch(
+        ptr, n, int(channels), int(max_len), int(max_taps), int(tap_pitch), workspace.data_ptr(), int(workspace.numel()), stream))
+
+
+def fft_fir_batch(waves, taps, workspace_budget: int = 256 << 20):
+    """`fir_batch` for long impulse responses (iris_fft_fir_batch: a partitioned overlap-save convolution on the FFT core):
+    waves is a list of [C, L_i] float32 tensors on one ROCm device (equal C), taps as many [C, K_i] float32 tensors on it,
+    1 <= K_i <= 32768.  Returns a list of new [C, L_i] tensors, the causal convolution cut at the input length, norm-wise
+    accurate per block of 1024 outputs: |out - fp64| <= 8 u sum_p ||frame_{j-p}|| ||partition_p||, not tap
+    by tap as `fir_batch`; taps [[1.0]] give a copy within that rule, not bit for bit.  The records are run in consecutive
+    groups whose spectra fit `workspace_budget` bytes (a single larger record is a group of its own), one launch pair per
+    group: the results do not depend on the grouping.  A mismatch, an empty tap vector, K_i > 32768 or a CPU tensor is a
+    ValueError: there is no CPU fallback."""
+    waves, taps = list(waves), list(taps)
+    if len(waves) != len(taps):
+        raise ValueError(f"fft_fir_batch: {len(waves)} waveforms but {len(taps)} tap arrays")
+    if not waves:
+        return []
+    for name, group in (("waves", waves), ("taps", taps)):
+        for i, t in enumerate(group):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2):
+                what = f"{tuple(t.shape)} {t.dtype} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+                raise ValueError(f"fft_fir_batch: {name}[{i}] must be a 2-D float32 tensor on a ROCm device (there is no CPU "
+                                 f"fallback), got {what}")
+    dev, chan = waves[0].device, int(waves[0].shape[0])
+    table = np.zeros(len(waves), FFT_FIR_SRC)
+    results, keep = [], []
+    for i, (w, h) in enumerate(zip(waves, taps)):
+        if int(w.shape[0]) != chan or w.device != dev or int(w.shape[1]) < 1 or chan < 1:
+            raise ValueError(f"fft_fir_batch: waves[{i}] has shape {tuple(w.shape)} on {w.device}; expected [{chan} >= 1, "
+                             f"L >= 1] on {dev}")
+        if int(h.shape[0]) != chan or h.device != dev:
+            raise ValueError(f"fft_fir_batch: taps[{i}] has shape {tuple(h.shape)} on {h.device} for a waveform of {chan} "
+                             f"channel(s) on {dev}: one row of taps per channel")
+        if int(h.shape[1]) < 1:
+            raise ValueError(f"fft_fir_batch: taps[{i}] is empty (an impulse response has at least its direct tap)")
+        if int(h.shape[1]) > FFT_FIR_MAX_TAPS:
+            raise ValueError(f"fft_fir_batch: taps[{i}] has {int(h.shape[1])} taps per channel (> {FFT_FIR_MAX_TAPS})")
+        if int(w.shape[1]) > 2 ** 31 - 1 - 2 * FFT_FIR_BLOCK:
+            raise ValueError(f"fft_fir_batch: waves[{i}] has {int(w.shape[1])} samples (> 2^31 - 1 - 2048)")
+        w, h = w.contiguous(), h.contiguous()
+        o = torch.empty_like(w)
+        table[i] = (w.data_ptr(), o.data_ptr(), h.data_ptr(), int(w.shape[1]), int(h.shape[1]), 0)
+        results.append(o)
+        keep += [w, h]
+    groups, largest = fft_fir_groups(table, chan, int(workspace_budget))
+    workspace = torch.empty(largest, dtype=torch.uint8, device=dev)
+    for a, b in groups:
+        part = table[a:b]
+        fft_fir_launch(part, chan, int(part["len"].max()), int(part["n_taps"].max()), 0, workspace, dev)
+    for t in keep + [workspace]:   # (a contiguous copy made above, and the spectra, must outlive the kernels)
+        t.record_stream(torch.cuda.current_stream(dev))
+    return results
+
+
 # mirrors iris_ism_src (include/iris_frontend.h)
 ISM_MAX_CHAN = 8      # microphones per record (IRIS_ISM_MAX_CHAN)
 ISM_SRC = np.dtype([("dst", "<u8"), ("room", "<f8", (3,)), ("src", "<f8", (3,)), ("beta", "<f8"), ("n_taps", "<i4"),

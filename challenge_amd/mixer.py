@@ -172,6 +172,10 @@ class _ReverbAug:
     geometry: Optional[list] = None            # shoebox: the `transforms.draw_shoebox` dicts (+ rt60) of the latest draw
     ism_table: Optional[np.ndarray] = None     # shoebox: ISM_SRC records, dst (the tap buffers) filled once
     ism_table_dev: Optional[torch.Tensor] = None   # shoebox: long-lived device copy of `ism_table`
+    max_taps: int = _fe.FIR_MAX_TAPS           # the tap buffers' row pitch; above FIR_MAX_TAPS the mixer is on the long path
+    pool: Optional[list] = None                # measured responses (`transforms.load_rirs`) a plain `rereverb()` draws from
+    groups: Optional[list] = None              # long path: (first, last + 1) voice ranges, one `iris_fft_fir_batch` each
+    workspace: Optional[torch.Tensor] = None   # long path: the spectra of the largest group, allocated once
 
 
 def _check_reverb_range(rt60_lo: float, rt60_hi: float, drr_lo: float, drr_hi: float) -> None:
@@ -662,7 +666,8 @@ class WaveMixer(DeviceMixer):
 
     # -- reverberation of the voice corpus ------------------------------------------------
     def enable_reverb(self, rt60_lo: float = 0.1, rt60_hi: float = 0.4, drr_lo: float = -3.0, drr_hi: float = 12.0,
-                      model: str = "noise") -> None:
+                      model: str = "noise", max_taps: int = _fe.FIR_MAX_TAPS, rirs=None,
+                      workspace_budget: int = 256 << 20) -> None:
         """Keep a reverberated copy of every voice beside the original and mix from the copies: `rereverb()` then convolves the
         whole voice corpus with fresh synthetic room impulse responses (`transforms.synth_rir`: rt60 ~ U[rt60_lo, rt60_hi)
         seconds, direct-to-reverberant ratio ~ U[drr_lo, drr_hi) dB per voice) in one launch (`iris_fir_batch`; Ko et al. 2017,
@@ -680,21 +685,55 @@ class WaveMixer(DeviceMixer):
         resident tap buffers): both channels hear the same room, so the inter-channel delay and level of a voice are those of
         its geometry, where the "noise" model draws unrelated responses per channel.  The `drr_*` bounds are unused in this
         model: the direct-to-reverberant ratio follows from the geometry.  The direct sound of the nearest microphone sits at
-        tap 16 (1 ms, far below one hop), so the dry labels stay valid.  At most 8 channels."""
+        tap 16 (1 ms, far below one hop), so the dry labels stay valid.  At most 8 channels.
+        max_taps (default 4096: everything above, bit for bit) in 4097 .. 32768 selects the LONG path: the tap buffers are
+        [C, max_taps], `synth_rir` follows the decay up to max_taps, and `rereverb` runs the partitioned FFT convolution
+        (`iris_fft_fir_batch`) over EVERY voice, short responses included - a mixer uses one engine, so its results do not
+        depend on which voices drew short rooms.  The voices are split once, here, into consecutive groups whose spectra fit
+        `workspace_budget` bytes at max_taps (one launch pair per group) and the workspace of the largest group is allocated
+        once.  On this path the copies under the identity response equal the originals within the convolution's norm-wise
+        rule, not bit for bit.  The shoebox model stops at 4096 taps and is refused on the long path.  With
+        tails of a second, the policy above - a silent gap stays labelled silent although the room rings into it - matters
+        more than it did at a quarter of a second.
+        rirs: a list of measured responses [C, K <= max_taps] (`transforms.load_rirs`); a `rereverb()` without arguments then
+        draws one of them per voice, uniformly, from the mixer's generator instead of synthesising."""
         _check_reverb_range(rt60_lo, rt60_hi, drr_lo, drr_hi)
         if model not in ("noise", "shoebox"):
             raise ValueError(f"enable_reverb: model = {model!r}; 'noise' (synth_rir) or 'shoebox' (image-source rooms)")
+        max_taps = int(max_taps)
+        if not _fe.FIR_MAX_TAPS <= max_taps <= _fe.FFT_FIR_MAX_TAPS:
+            raise ValueError(f"enable_reverb: max_taps = {max_taps} is outside {_fe.FIR_MAX_TAPS} (the direct form) .. "
+                             f"{_fe.FFT_FIR_MAX_TAPS} (the partitioned FFT convolution)")
+        long_path = max_taps > _fe.FIR_MAX_TAPS
+        if long_path and model == "shoebox":
+            raise ValueError(f"enable_reverb: the shoebox model computes at most {_fe.FIR_MAX_TAPS} taps; max_taps = {max_taps} "
+                             "needs model = 'noise' or measured responses")
+        if rirs is not None:
+            if model == "shoebox":
+                raise ValueError("enable_reverb: measured responses (rirs=) replace the room model; drop model = 'shoebox'")
+            rirs = [np.ascontiguousarray(np.asarray(h, np.float32)) for h in rirs]
+            if not rirs:
+                raise ValueError("enable_reverb: rirs is empty")
+            for i, h in enumerate(rirs):
+                if h.ndim != 2 or h.shape[0] != self.channels or not 1 <= h.shape[1] <= max_taps:
+                    raise ValueError(f"enable_reverb: rirs[{i}] has shape {h.shape}; expected [{self.channels}, 1 <= K <= {max_taps}]")
         if self._aug is not None:
             raise RuntimeError("enable_reverb was already called on this mixer" if isinstance(self._aug, _ReverbAug) else
                                "enable_speed was already called on this mixer (a mixer holds one voice augmentation)")
         dev, orig = self.device, list(self.voices)
         bufs = [torch.zeros_like(v) for v in orig]
-        taps = [torch.zeros((self.channels, _fe.FIR_MAX_TAPS), device=dev, dtype=torch.float32) for _ in orig]
-        table = np.zeros(len(orig), _fe.FIR_SRC)
+        taps = [torch.zeros((self.channels, max_taps), device=dev, dtype=torch.float32) for _ in orig]
+        table = np.zeros(len(orig), _fe.FFT_FIR_SRC if long_path else _fe.FIR_SRC)
         table["src"], table["dst"] = [v.data_ptr() for v in orig], [b.data_ptr() for b in bufs]
         table["taps"], table["len"] = [t.data_ptr() for t in taps], self._v_L
         self._aug = _ReverbAug((float(rt60_lo), float(rt60_hi)), (float(drr_lo), float(drr_hi)), orig, bufs, taps, table,
-                               torch.empty(max(table.nbytes, 1), dtype=torch.uint8, device=dev), model=model)
+                               torch.empty(max(table.nbytes, 1), dtype=torch.uint8, device=dev), model=model,
+                               max_taps=max_taps, pool=rirs)
+        if long_path:
+            # the groups and every voice's slice are laid out for max_taps: whatever response a voice draws later fits
+            table["n_taps"] = max_taps
+            self._aug.groups, largest = _fe.fft_fir_groups(table, self.channels, int(workspace_budget))
+            self._aug.workspace = torch.empty(max(largest, 16), dtype=torch.uint8, device=dev)
         if model == "shoebox":
             if self.channels > _fe.ISM_MAX_CHAN:
                 self._aug = None
@@ -712,7 +751,8 @@ class WaveMixer(DeviceMixer):
         """Reverberate every ORIGINAL voice anew into its buffer: per voice rt60 ~ U[rt60_lo, rt60_hi) and drr_db ~
         U[drr_lo, drr_hi) from the mixer's own NumPy generator and a `transforms.synth_rir` of them (or the given `rirs`, one
         [C, K_i <= 4096] array per voice), uploaded into the resident tap buffers, then ONE `iris_fir_batch` launch over the
-        whole voice corpus.  Lengths, frame counts and the frame-activity vectors (the labels) do not change: see
+        whole voice corpus (on the long path of `enable_reverb(max_taps > 4096)`: K_i <= max_taps and one `iris_fft_fir_batch`
+        launch pair per group of voices; with `enable_reverb(rirs=)` the responses are drawn from that list).  Lengths, frame counts and the frame-activity vectors (the labels) do not change: see
         `enable_reverb`.  Call it outside any graph capture.  Backgrounds and noises are not reverberated.  Returns the list
         of impulse responses used.
         Shoebox model with rirs = None: rt60 ~ U[rt60_lo, rt60_hi) and a `transforms.draw_shoebox` per voice from the mixer's
@@ -741,21 +781,30 @@ class WaveMixer(DeviceMixer):
             aug.geometry = geometry
             aug.rirs = [t[:, :int(k)] for t, k in zip(aug.taps, aug.ism_table["n_taps"])]
             return aug.rirs
+        if rirs is None and aug.pool is not None:
+            rirs = [aug.pool[int(i)] for i in self.rng.integers(0, len(aug.pool), n_voice)]
         if rirs is None:
             rirs = []
             for _ in range(n_voice):
                 rt60, drr_db = self.rng.uniform(*aug.rt60), self.rng.uniform(*aug.drr)
-                rirs.append(_tr.synth_rir(self.rng, chan, rt60, drr_db, max_taps=_fe.FIR_MAX_TAPS))
+                rirs.append(_tr.synth_rir(self.rng, chan, rt60, drr_db, max_taps=aug.max_taps))
         rirs = [np.ascontiguousarray(np.asarray(h, np.float32)) for h in rirs]
         if len(rirs) != n_voice:
             raise ValueError(f"rereverb: {len(rirs)} impulse responses for {n_voice} voices")
         for i, h in enumerate(rirs):
-            if h.ndim != 2 or h.shape[0] != chan or not 1 <= h.shape[1] <= _fe.FIR_MAX_TAPS:
-                raise ValueError(f"rereverb: rirs[{i}] has shape {h.shape}; expected [{chan}, 1 <= K <= {_fe.FIR_MAX_TAPS}]")
+            if h.ndim != 2 or h.shape[0] != chan or not 1 <= h.shape[1] <= aug.max_taps:
+                raise ValueError(f"rereverb: rirs[{i}] has shape {h.shape}; expected [{chan}, 1 <= K <= {aug.max_taps}]")
         for h, buf in zip(rirs, aug.taps):
             buf.view(-1)[:h.size].copy_(torch.from_numpy(h.reshape(-1)), non_blocking=True)
         aug.table["n_taps"] = [h.shape[1] for h in rirs]
-        if n_voice:
+        if aug.groups is not None:
+            # the long path: every voice, short responses included, through the partitioned FFT convolution, group by group
+            # (the groups' tables sit one after the other in the resident device table)
+            for a, b in aug.groups:
+                part = aug.table[a:b]
+                _fe.fft_fir_launch(part, chan, int(part["len"].max()), int(part["n_taps"].max()), 0, aug.workspace, self.device,
+                                   aug.table_dev[a * part.itemsize:b * part.itemsize])
+        elif n_voice:
             _fe.fir_launch(aug.table, chan, int(self._v_L.max()), int(aug.table["n_taps"].max()), self.device, aug.table_dev)
         aug.rirs = rirs
         return rirs

@@ -153,6 +153,11 @@ class ARGS:
                '(recordings.load_recordings: resampled to 16 kHz, scaled as load_wav scales a file) - random windows, drawn and '
                'gathered on the device (iris_crop_draw, iris_crop_windows), labelled from --recordings_answer; the rest of the '
                'batch is synthetic as before.  The validation set is unchanged.  Not part of the run name')
+        a('--rirs', type=str, default=None, metavar='DIR',
+          help="--online_stft only, with a 'reverb' token in --name.  Reverberate the training voices with the measured room "
+               "impulse responses DIR/*.wav (transforms.load_rirs: resampled to 16 kHz, trimmed to the direct sound, cut at "
+               "16384 taps = 1.024 s, unit norm) instead of synthetic ones: one drawn per voice and epoch, through the "
+               "partitioned FFT convolution (iris_fft_fir_batch).  Refused with 'shoebox'.  Not part of the run name")
         a('--recordings_answer', type=str, default=None, metavar='FILE',
           help="the recordings' events: a JSON in sample_answer.json's schema whose 'task2_answer' has an entry per wav of "
                "--recordings (default: DIR/answer.json)")
@@ -165,6 +170,14 @@ class ARGS:
         monitor = getattr(config, 'checkpoint_monitor', None)
         if monitor is not None and monitor not in row_names(config):
             raise ValueError(f"--checkpoint_monitor {monitor!r}: the rows of this run will hold {row_names(config)}")
+        if getattr(config, 'rirs', None) is not None:
+            if not config.online_stft:
+                raise ValueError("--rirs reverberates the waveform corpus and needs the waveform path: add --online_stft")
+            tokens = _du.run_tokens(config)
+            if not tokens.reverb:
+                raise ValueError(f"--rirs needs a 'reverb' token in --name (got {tokens.name!r}): the responses feed that augmentation")
+            if tokens.shoebox:
+                raise ValueError(f"--rirs with 'shoebox' in --name {tokens.name!r}: measured responses replace the room model, name one")
         if getattr(config, 'recordings', None) is not None:
             if not config.online_stft:
                 raise ValueError("--recordings cuts waveform windows and needs the waveform path: add --online_stft")
@@ -184,6 +197,8 @@ class ARGS:
 # ---------------------------------------------------------------------------
 # dataset assembly                                            sj_train.py:74-130
 # ---------------------------------------------------------------------------
+RIR_MAX_TAPS = 16384   # tap buffers of a 'reverb_long' run and of --rirs: 1.024 s at 16 kHz (the longest synthetic response, rt60 = 1 s
+                       # followed down to -40 dB, is 10667 taps)
 def complex_to_mel(n_mels: int, num_spectrogram_bins: int = 257, sample_rate: float = 16000, **kwargs):
     """complex_to_magphase + magphase_to_mel as ONE kernel (sj_train.py:119-120 maps them
     one after the other; the phase computed by the first is discarded by the second)."""
@@ -525,7 +540,8 @@ def wave_features(plan, compression, do_minmax, wav, t_bands=None, f_bands=None,
 
 
 def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=None, seed=None, n_fft=512, hop=256,
-                      sample_rate=16000, device_draw=False, spec_sources=None, recordings=None, recordings_share=0.5):
+                      sample_rate=16000, device_draw=False, spec_sources=None, recordings=None, recordings_share=0.5,
+                      rirs=None):
     """`make_device_dataset` from WAVEFORMS (waveform-domain variant): the corpora
     stay resident in HBM as [chan, L_i] waveforms, `WaveMixer` mixes a batch before the STFT (which is linear), and
     the fused kernel takes it from there - STFT, SpecAugment / `stft_filter` bands, mel, min-max, log in one pass;
@@ -553,12 +569,22 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
     voice-corpus augmentations 'speed' / 'reverb' ('shoebox') touch the synthetic part only.  At recordings_share == 1.0 no mixer
     is built and no synthetic corpus is loaded (`dataset.mixer` is None).  `dataset.recordings` is the sampler (None without).
     ValueError: a share outside (0, 1], a sampler of another n_frame / hop, recordings whose channel count differs from the
-    synthetic corpus's, 'ipd' with mono recordings - each before the device is touched."""
+    synthetic corpus's, 'ipd' with mono recordings - each before the device is touched.
+    'reverb_long' in the name: the 'reverb' augmentation with rt60 ~ U[0.2, 1.0) s and tap buffers of RIR_MAX_TAPS = 16384 on the
+    partitioned FFT convolution (`WaveMixer.enable_reverb(max_taps=16384)`).  rirs: measured room responses, a list of
+    [corpus channels, K <= 16384] arrays (`transforms.load_rirs`): a training set's 'reverb' then draws one of them per voice
+    and epoch instead of synthesising, on the same long path.  ValueError without a 'reverb' token or with 'shoebox', before
+    anything is loaded; validation sets ignore them as they ignore the token."""
     from .mixer import WaveMixer
     if spec_sources is not None and sources is not None:
         raise ValueError("make_wave_dataset: give `sources` (waveforms) or `spec_sources` (spectra), not both")
     tokens = _du.run_tokens(config)
     _du.check_builder(tokens, 'make_wave_dataset')
+    if rirs is not None and not tokens.reverb:
+        raise ValueError(f"make_wave_dataset: measured room responses (rirs=) need a 'reverb' token in the run name {tokens.name!r}")
+    if rirs is not None and tokens.shoebox:
+        raise ValueError(f"make_wave_dataset: run name {tokens.name!r} asks for 'shoebox' rooms; measured responses (rirs=) replace "
+                         "the room model, name one")
     sampler, n_rec = None, 0
     if recordings is not None:
         from .recordings import RecordingSampler, _channels_of
@@ -622,7 +648,12 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
         respeed = mixer.respeed
         respeed()
     if training and tokens.reverb and mixer is not None:
-        mixer.enable_reverb(model="shoebox" if tokens.shoebox else "noise")
+        if tokens.reverb_long or rirs is not None:
+            # long rooms (rt60 up to 1 s: 10667 taps, none truncated) and measured responses: the partitioned FFT convolution
+            ranges = dict(rt60_lo=0.2, rt60_hi=1.0) if tokens.reverb_long else {}
+            mixer.enable_reverb(max_taps=RIR_MAX_TAPS, rirs=rirs, **ranges)
+        else:
+            mixer.enable_reverb(model="shoebox" if tokens.shoebox else "noise")
         rereverb = mixer.rereverb
         rereverb()
 
@@ -852,9 +883,13 @@ def main(argv=None):
             if dd:
                 recordings.enable_device_draw(3000 + rank)
         synthetic_part = recordings is None or config.recordings_share < 1.0
+        rirs = None
+        if config.rirs is not None:   # loaded once per rank (the corpora are stereo); files up to 1.024 s are kept whole
+            from .transforms import load_rirs
+            rirs = load_rirs(config.rirs, 2, max_taps=RIR_MAX_TAPS)
         train_set = make_wave_dataset(config, training=True, device=device, seed=1000 + rank, device_draw=dd,
                                       spec_sources=spec_sources(True) if synthetic_part else None, recordings=recordings,
-                                      recordings_share=config.recordings_share)
+                                      recordings_share=config.recordings_share, rirs=rirs)
         test_set = make_wave_dataset(config, training=False, device=device, seed=2000 + rank, device_draw=dd,
                                      spec_sources=spec_sources(False))
     elif device.type == 'cuda' and not config.per_sample_pipeline:

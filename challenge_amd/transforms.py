@@ -414,6 +414,65 @@ def reverb(wav: torch.Tensor, rir) -> torch.Tensor:
     return _fe.fir_batch([wav], [rir])[0]
 
 
+def reverb_fft(wav: torch.Tensor, rir) -> torch.Tensor:
+    """`reverb` for long responses: the same causal convolution cut at the input length, run as a partitioned overlap-save
+    convolution on the FFT core (`frontend.fft_fir_batch`, iris_fft_fir_batch: two launches), `rir` [chan, taps <= 32768]
+    (2 s at 16 kHz).  Accurate norm-wise per block of 1024 outputs, not tap by tap: an identity response
+    copies the waveform within that rule, not bit for bit.  Returns a new tensor of the input's shape.  CPU waveforms raise:
+    there is no CPU fallback."""
+    if not (isinstance(wav, torch.Tensor) and wav.is_cuda):
+        raise ValueError("reverb_fft: the waveform must be a float32 tensor on a ROCm device (there is no CPU fallback)")
+    if not isinstance(rir, torch.Tensor):
+        rir = torch.as_tensor(np.ascontiguousarray(np.asarray(rir, np.float32))).to(wav.device)
+    if wav.dim() == 1:
+        return _fe.fft_fir_batch([wav.unsqueeze(0)], [rir.reshape(1, -1)])[0][0]
+    return _fe.fft_fir_batch([wav], [rir])[0]
+
+
+def load_rirs(rir_dir: str, channels: int, sample_rate: int = 16000, max_taps: int = 16384) -> list:
+    """Measured room impulse responses for `WaveMixer.enable_reverb(rirs=)`: sorted(glob(rir_dir/*.wav)) read by
+    `data_utils.read_wav_file` as a list of float32 [channels, K_i <= max_taps] arrays.  A file at another rate is brought to
+    `sample_rate` by `frontend.resample` (that needs a ROCm device; files at `sample_rate` never touch one).  Per file: the
+    samples before max(0, i0 - 16) are dropped, i0 = the earliest channel's peak index (the direct sound then sits within
+    the first millisecond and the delay between the channels is kept); the response is cut at `max_taps`; all channels are
+    scaled by ONE factor so that the loudest channel has unit L2 norm (the level difference between the channels is kept; no
+    rms scaling as for recordings).  A mono file is copied to every channel.  A file with another channel count, a
+    directory without *.wav, or a response that is all zeros is a ValueError."""
+    import os
+    from glob import glob
+
+    from .data_utils import read_wav_file
+    channels, max_taps = int(channels), int(max_taps)
+    if channels < 1 or max_taps < 1:
+        raise ValueError(f"load_rirs: channels = {channels} and max_taps = {max_taps} must be positive")
+    paths = sorted(glob(os.path.join(rir_dir, "*.wav")))
+    if not paths:
+        raise ValueError(f"load_rirs: no *.wav in {rir_dir!r}")
+    rirs = []
+    for path in paths:
+        data, sr = read_wav_file(path)
+        if data.shape[0] not in (1, channels):
+            raise ValueError(f"load_rirs: {path!r} has {data.shape[0]} channels; expected 1 or {channels}")
+        if data.shape[1] < 1:
+            raise ValueError(f"load_rirs: {path!r} is empty")
+        if int(sr) != int(sample_rate):
+            if not torch.cuda.is_available():
+                raise RuntimeError(f"load_rirs: {path!r} is at {sr} Hz; resampling to {sample_rate} Hz needs a ROCm device")
+            data = _fe.resample(torch.from_numpy(np.ascontiguousarray(data, np.float32)).to("cuda"), int(sr), int(sample_rate)).cpu().numpy()
+        h = np.asarray(data, np.float64)
+        if h.shape[0] == 1:
+            h = np.repeat(h, channels, axis=0)
+        if not np.any(h):
+            raise ValueError(f"load_rirs: {path!r} is all zeros")
+        i0 = int(np.abs(h).argmax(axis=1).min())
+        h = h[:, max(0, i0 - 16):][:, :max_taps]
+        norm = float(np.sqrt((h * h).sum(axis=1)).max())
+        if not norm > 0:
+            raise ValueError(f"load_rirs: {path!r} is all zeros within its first {max_taps} taps")
+        rirs.append(np.ascontiguousarray((h / norm).astype(np.float32)))
+    return rirs
+
+
 def synth_rir(rng: np.random.Generator, channels: int, rt60: float, drr_db: float = 0.0, sample_rate: int = 16000,
               floor_db: float = -40.0, max_taps: int = 4096) -> np.ndarray:
     """A synthetic room impulse response [channels, K] float32, built on the host in float64: the exponentially decaying

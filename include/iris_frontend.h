@@ -1040,6 +1040,41 @@ int iris_fir_batch(const void* table_dev, int n_src, int channels, int max_len, 
 int iris_fir_batch_pitch(const void* table_dev, int n_src, int channels, int max_len, int max_taps, int tap_pitch, void* stream);
 
 /*
+ * The same convolution for LONG impulse responses (a hall rings for a second and more: 16000+ taps at 16 kHz), as a uniformly
+ * partitioned overlap-save convolution on the FFT core: block B = 1024 new samples, transform N = 2048, n_taps up to
+ * IRIS_FFT_FIR_MAX_TAPS = 32768 (2 s at 16 kHz).  Per record src, dst, taps as for iris_fir_batch, the same definition
+ *     y[c, m] = sum_{k < n_taps, k <= m} taps[c, k] * x[c, m - k]      for 0 <= m < len
+ * and `ws_off`, the byte offset (a multiple of 16) of the record's own slice of `workspace`: iris_fft_fir_workspace(channels,
+ * len, n_taps) = channels * (ceil(len / B) + ceil(n_taps / B)) * 8256 bytes (0 for channels, len or n_taps <= 0 or n_taps >
+ * 32768), the spectra of its input frames x[(j - 1) B, (j + 1) B) and of its tap partitions taps[p B, (p + 1) B).  The slices
+ * of the records of one call must not overlap.  Two launches on `stream`: the spectra (one wave per frame), then per output
+ * block j the products summed over the partitions in ascending p in registers, one inverse transform and the store of
+ * y[j B, min((j + 1) B, len)).  Floats of dst beyond channels * len are not written; rows need no alignment.
+ * An FFT convolution is not bounded tap by tap: against the float64 evaluation the bound is norm-wise per output block,
+ *     |y - ref| <= 8 u R[c, m],   u = 2^-24,   R[c, m] = sum_{p <= j} ||frame_{j - p}||_2 ||partition_p||_2,   j = m / B
+ * (DESIGN.md K2f).  An all-zero input gives exactly 0.  A record with a NULL pointer, len <= 0, n_taps <= 0, len > max_len,
+ * n_taps > max_taps, or a slice that is misaligned or does not fit `workspace_bytes` is skipped (nothing written).
+ *   tap_pitch  floats between the rows of a record's taps; 0: the rows are n_taps apart (iris_fir_batch_pitch's meaning)
+ * Checked before any HIP call (IRIS_E_INVALID): n_src < 0, channels <= 0, tap_pitch < 0, and with n_src > 0 a NULL table,
+ * max_len <= 0, max_taps <= 0, 0 < tap_pitch < max_taps, a NULL or misaligned workspace or one below the smallest record's
+ * need; IRIS_E_UNSUPPORTED: n_src > 65535, channels > 65535, max_taps > 32768.  n_src == 0 returns 0 and launches nothing.
+ * No atomics, no synchronisation: bitwise reproducible, a record's result does not depend on the records around it, and
+ * both launches are capturable - except that the FIRST call on a device uploads the transform's twiddles (built on the host
+ * in double); make that call outside any capture.  Runs on the current HIP device.
+ */
+#define IRIS_FFT_FIR_MAX_TAPS 32768
+typedef struct {
+    const float* src;    /* DEVICE [channels, len] */
+    float*       dst;    /* DEVICE [channels, len]; must not overlap src */
+    const float* taps;   /* DEVICE [channels, tap_pitch or n_taps] */
+    int32_t      len, n_taps;
+    int64_t      ws_off; /* byte offset of the record's slice of the workspace, a multiple of 16 */
+} iris_fft_fir_src;
+long long iris_fft_fir_workspace(int channels, int len, int n_taps);
+int iris_fft_fir_batch(const void* table_dev, int n_src, int channels, int max_len, int max_taps, int tap_pitch, void* workspace,
+                       long long workspace_bytes, void* stream);
+
+/*
  * Shoebox room simulation (Allen & Berkley, JASA 1979: the image-source method, as pyroomacoustics and gpuRIR compute it): the
  * room impulse responses of a RAGGED BATCH of voices, each with its own room, source, microphones, wall reflection coefficient
  * and tap count, in one launch.  All microphones of a record sit in the same room with the same source, so every reflection
