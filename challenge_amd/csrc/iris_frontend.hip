@@ -31,8 +31,10 @@
 //   k_curves.h       the validation score histogram per (class, label): integer counts behind ROC-AUC / average precision / best F1
 //   decode_core.h    the event decoder's arithmetic (overlap-add average, smoothing, dilation, run boundaries), written once
 //   k_detect.h       window predictions of many files -> smoothed, thresholded event lists (two launches)
-//   k_tune.h         the same decoder (decode_core.h) at every point of a settings grid, scored against ground truth: event and match counts
-//                    per (grid point, file, class) in two launches
+//   k_hmm.h          the opt-in other decoder: a two-state HMM per class, exact integer Viterbi as a (max, +) scan along time (two
+//                    launches; shares step 1 and the run search with k_detect.h)
+//   k_tune.h         k_detect.h's decoder (decode_core.h) at every point of a settings grid, scored against ground truth: event and match
+//                    counts per (grid point, file, class) in two launches
 //   k_pcen.h         per-channel energy normalisation: a chunked scan of the IIR smoother along time, then the compression
 //                    (host scalars, or per-band parameters from a device array: the trainable layer's forward)
 //   k_pcen_grad.h    the trainable layer's backward: gradient with respect to the per-band parameters, two launches, no atomics
@@ -78,6 +80,7 @@
 #include "k_curves.h"
 #include "decode_core.h"
 #include "k_detect.h"
+#include "k_hmm.h"
 #include "k_tune.h"
 #include "k_pcen.h"
 #include "k_pcen_grad.h"

@@ -3,6 +3,7 @@
     python -m challenge_amd.detect --name <run name> [--p] [--path DIR] [--wav_dir .] [--out answer.json]
                                    [--overlap_hop 512] [--score ANSWER.json]
                                    [--tune ANSWER.json --decoder_out decoder.json] [--decoder decoder.json]
+                                   [--decoder_kind pool|hmm]
 
 `detect` runs a trained model over wav files (or in-memory recordings) and returns, per file, the events it finds in the
 forms of the reference's helpers: frame events (Challenge_Metric.get_start_end_frame), the (class, middle second) rows
@@ -28,7 +29,24 @@ point, file, class), the predicted events and those get_er's greedy rule matches
 csrc/k_tune.h, and one copy back); get_er is a sum of per-class terms, so `choose_settings` picks each class's setting on its
 own and that choice minimises the mean ER over every per-class combination of grid points.  `DecoderSettings` carries the
 result to `decode_events` / `detect` (`settings=`) and to the command line (`--tune`, `--decoder`).  Settings chosen on the
-recordings they are then scored on flatter the score: tune on other recordings."""
+recordings they are then scored on flatter the score: tune on other recordings.
+
+The pooling rule widens every event by about a second on each side, merges whatever lies within two seconds and cannot weigh
+the evidence inside a short event or gap.  `decode_events_hmm` is the opt-in alternative (`HmmSettings` as `settings=`,
+`--decoder_kind hmm`): a two-state HMM per class decoded with Viterbi on integer scores - on GPU tensors the
+iris_decode_events_hmm launches (csrc/k_hmm.h) and one copy back, on CPU tensors the sequential restatement below, to which the
+kernel is EQUAL (integers: the order of its scans cannot matter).  For file f, class k, frames t < T:
+  1. p[t]: step 1 above.
+  2. e[t], int32: b = clamp(floor(p[t] * 1024.0f), 0, 1023) (exact in fp32; below 0, above 1 and +-inf clamp),
+     e[t] = lut[b] - bias_k; a NaN p[t] gives -2^20.  Default lut[i] = rint(256 ln(c / (1 - c))), c = (i + 0.5) / 1024, in
+     float64 on the host (`hmm_lut`): log-odds in units of 1/256 nat, in [-1952, 1952].  bias_k = rint(256 ln(thr / (1 - thr)))
+     of the class's threshold (its fp32 value, in (0, 1)): 0 at 0.5.  Any int32 table with entries in [-2^15, 2^15] may be passed.
+  3. Viterbi, int64, with the class's event cost C = rint(256 cost_nats) in [0, 2^19]: V0 = 0, V1 = -2^60; for t = 0 .. T - 1,
+     from the values before frame t: b0[t] = (V1 > V0), b1[t] = !(V0 - C > V1), then V0' = max(V0, V1),
+     V1' = e[t] + max(V1, V0 - C); s[T - 1] = (V1 > V0), s[t - 1] = s[t] ? b1[t] : b0[t].  Ties keep the state (stay off, stay
+     on, end off).  s maximises sum_{t: s[t] = 1} e[t] - C * (runs of s); a NaN frame is always off.
+  4. the maximal runs of s as (first, last) frames.
+`tune_hmm` chooses (threshold, cost) per class on labelled recordings over `hmm_grid()`, with choose_settings' arithmetic."""
 from __future__ import annotations
 
 import json
@@ -521,27 +539,281 @@ def choose_settings(n_pred, matched, n_gt, grid, names: Optional[Sequence[str]] 
     minimise it over every per-class combination of grid points.  A file without ground truth is refused (get_er divides by
     its length)."""
     pts = _grid_points(grid)
+    score, index, mean_er = _choose_per_class("choose_settings", n_pred, matched, n_gt, len(pts), names)
+    settings = DecoderSettings([pts[i][0] for i in index], [pts[i][1] for i in index], [pts[i][2] for i in index],
+                               grid=pts, score=score.tolist())
+    ref = (_f32(THRESHOLD), AVG_POOL, MAX_POOL)
+    er_ref = mean_er((pts.index(ref),) * len(index)) if ref in pts else None
+    return Tuning(settings, er_ref, mean_er(index), index)
+
+
+def _choose_per_class(who: str, n_pred, matched, n_gt, n_points: int, names: Optional[Sequence[str]] = None):
+    """choose_settings' arithmetic, whatever a grid point is: (score [G, K] float64, the chosen point of each class, and
+    mean_er(points per class) -> the mean over the files of get_er at those points)."""
     n_pred, matched, n_gt = (np.asarray(x, np.int64) for x in (n_pred, matched, n_gt))
     g, f, k = n_pred.shape
-    if matched.shape != (g, f, k) or n_gt.shape != (f, k) or g != len(pts) or f < 1:
-        raise ValueError(f"choose_settings: n_pred {n_pred.shape}, matched {matched.shape}, n_gt {n_gt.shape}, {len(pts)} grid points")
+    if matched.shape != (g, f, k) or n_gt.shape != (f, k) or g != n_points or f < 1:
+        raise ValueError(f"{who}: n_pred {n_pred.shape}, matched {matched.shape}, n_gt {n_gt.shape}, {n_points} grid points")
     total = n_gt.sum(1)
     if (total == 0).any():
         i = int(np.flatnonzero(total == 0)[0])
-        raise ValueError(f"choose_settings: file {names[i] if names is not None else i} has no ground-truth events "
+        raise ValueError(f"{who}: file {names[i] if names is not None else i} has no ground-truth events "
                          f"(get_er divides by their number)")
     score = ((n_pred + n_gt[None] - 2 * matched).astype(np.float64) / total.astype(np.float64)[None, :, None]).sum(1)   # [G, K]
     index = tuple(int(i) for i in np.argmin(score, axis=0))       # argmin: the first of equal minima
-    settings = DecoderSettings([pts[i][0] for i in index], [pts[i][1] for i in index], [pts[i][2] for i in index],
-                               grid=pts, score=score.tolist())
 
     def mean_er(idx):
         idx, cls = np.asarray(idx), np.arange(k)
         return float(np.mean([er_from_counts(n_pred[idx, i, cls], matched[idx, i, cls], n_gt[i]) for i in range(f)]))
 
-    ref = (_f32(THRESHOLD), AVG_POOL, MAX_POOL)
-    er_ref = mean_er((pts.index(ref),) * k) if ref in pts else None
-    return Tuning(settings, er_ref, mean_er(index), index)
+    return score, index, mean_er
+
+
+# ---------------------------------------------------------------------------
+# the HMM decoder: integer Viterbi smoothing (csrc/k_hmm.h)
+# ---------------------------------------------------------------------------
+HMM_BUCKETS = 1024
+HMM_UNIT = 256                     # scores and costs are in units of 1 / 256 nat
+HMM_NAN_SCORE = -(1 << 20)
+HMM_START = -(1 << 60)
+HMM_MAX_COST_NATS = 2048.0         # C <= 2^19 < 2^20: a NaN frame is always off
+HMM_MAX_LUT = 1 << 15
+HMM_THRESHOLD, HMM_COST = 0.5, 8.0
+
+HmmPoint = Tuple[float, float]     # (threshold as its fp32 value, event cost in nats)
+
+
+def hmm_lut() -> np.ndarray:
+    """The default score table: lut[i] = rint(256 ln(c / (1 - c))) at the bucket centre c = (i + 0.5) / 1024, in float64."""
+    c = (np.arange(HMM_BUCKETS, dtype=np.float64) + 0.5) / HMM_BUCKETS
+    return np.rint(HMM_UNIT * np.log(c / (1.0 - c))).astype(np.int32)
+
+
+def _hmm_points(grid) -> List[HmmPoint]:
+    pts = [(_f32(t), float(c)) for t, c in grid]
+    if not pts:
+        raise ValueError("hmm grid: no points")
+    for t, c in pts:
+        if not 0.0 < t < 1.0:
+            raise ValueError(f"hmm settings: threshold {t!r} must lie in (0, 1)")
+        if not 0.0 <= c <= HMM_MAX_COST_NATS:
+            raise ValueError(f"hmm settings: cost {c!r} nats must lie in [0, {HMM_MAX_COST_NATS:g}]")
+    return pts
+
+
+def hmm_grid(thresholds=(0.3, 0.4, 0.5, 0.6, 0.7), costs=(0.0, 2.0, 4.0, 8.0, 16.0, 32.0, 64.0, 128.0)) -> List[HmmPoint]:
+    """The default grid: the default point (0.5, 8.0) first, so that a tie keeps it, then thresholds x costs (threshold slowest)."""
+    return _hmm_points([(HMM_THRESHOLD, HMM_COST)] + [(t, c) for t in thresholds for c in costs])
+
+
+@dataclass
+class HmmSettings:
+    """One (threshold, event cost in nats) per class for decode_events_hmm, with - when tune_hmm chose them - the grid and the
+    score table [G][K] they were chosen from.  Thresholds are kept as fp32 values; the decoder sees them as the integers
+    `bias()` and the costs as `cost_units()`."""
+    threshold: Tuple[float, ...]
+    cost: Tuple[float, ...]
+    grid: Optional[List[HmmPoint]] = field(default=None, compare=False)
+    score: Optional[List[List[float]]] = field(default=None, compare=False)
+
+    def __post_init__(self):
+        self.threshold = tuple(_f32(t) for t in self.threshold)
+        self.cost = tuple(float(c) for c in self.cost)
+        if not (len(self.threshold) == len(self.cost) >= 1):
+            raise ValueError(f"HmmSettings: {len(self.threshold)} thresholds, {len(self.cost)} costs")
+        _hmm_points(self.points())
+
+    @property
+    def n_classes(self) -> int:
+        return len(self.threshold)
+
+    def points(self) -> List[HmmPoint]:
+        return list(zip(self.threshold, self.cost))
+
+    def bias(self) -> np.ndarray:
+        """rint(256 ln(thr / (1 - thr))) per class, int32: 0 at 0.5."""
+        t = np.asarray(self.threshold, np.float64)
+        return np.rint(HMM_UNIT * np.log(t / (1.0 - t))).astype(np.int32)
+
+    def cost_units(self) -> np.ndarray:
+        """rint(256 * cost) per class, int32 in [0, 2^19]."""
+        return np.rint(HMM_UNIT * np.asarray(self.cost, np.float64)).astype(np.int32)
+
+    @classmethod
+    def default(cls, n_classes: int) -> "HmmSettings":
+        return cls((HMM_THRESHOLD,) * n_classes, (HMM_COST,) * n_classes)
+
+    def save(self, path: str) -> None:
+        doc = {"kind": "hmm", "threshold": list(self.threshold), "cost": list(self.cost),
+               "grid": None if self.grid is None else [list(g) for g in self.grid],
+               "score": None if self.score is None else [list(map(float, r)) for r in self.score]}
+        with open(path, 'w') as f:
+            json.dump(doc, f, indent=1)
+
+    @classmethod
+    def load(cls, path: str) -> "HmmSettings":
+        with open(path) as f:
+            doc = json.load(f)
+        if doc.get("kind") != "hmm":
+            raise ValueError(f"HmmSettings.load: {path} holds no \"kind\": \"hmm\" settings")
+        grid = doc.get("grid")
+        return cls(doc["threshold"], doc["cost"], None if grid is None else _hmm_points(grid), doc.get("score"))
+
+
+def load_settings(path: str):
+    """Decoder settings of either kind from `path`: HmmSettings where the file says "kind": "hmm", DecoderSettings where it
+    names no kind."""
+    with open(path) as f:
+        kind = json.load(f).get("kind")
+    if kind is None:
+        return DecoderSettings.load(path)
+    if kind == "hmm":
+        return HmmSettings.load(path)
+    raise ValueError(f"load_settings: {path}: unknown decoder kind {kind!r}")
+
+
+def _hmm_table(lut) -> np.ndarray:
+    if lut is None:
+        return hmm_lut()
+    raw = np.asarray(lut.cpu() if torch.is_tensor(lut) else lut)
+    tab = raw.astype(np.int64)
+    if tab.shape != (HMM_BUCKETS,) or not np.array_equal(tab, raw) or np.abs(tab).max() > HMM_MAX_LUT:
+        raise ValueError(f"decode_events_hmm: lut must hold {HMM_BUCKETS} integers in [-{HMM_MAX_LUT}, {HMM_MAX_LUT}]")
+    return tab.astype(np.int32)
+
+
+def _hmm_scores_host(p: torch.Tensor, lut: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """Step 2 without the bias: (lut[bucket] [T, K] int64, the NaN frames [T, K])."""
+    x = p.numpy()
+    nan = np.isnan(x)
+    with np.errstate(invalid='ignore', over='ignore'):
+        b = np.clip(np.floor(x * np.float32(HMM_BUCKETS)), 0, HMM_BUCKETS - 1)      # fp32; +-inf clamp
+    return lut.astype(np.int64)[np.where(nan, 0, b).astype(np.int64)], nan
+
+
+def _viterbi_host(e: np.ndarray, cost: np.ndarray) -> np.ndarray:
+    """Step 3, frame by frame as defined, for the K classes of one file side by side: e [T, K] int64 (T >= 1), cost [K] int64
+    -> s [T, K] bool."""
+    t_len, k = e.shape
+    v0, v1 = np.zeros(k, np.int64), np.full(k, HMM_START, np.int64)
+    b0, b1 = np.empty((t_len, k), bool), np.empty((t_len, k), bool)
+    for t in range(t_len):
+        a = v0 - cost
+        b0[t] = v1 > v0
+        b1[t] = ~(a > v1)
+        v0, v1 = np.maximum(v0, v1), e[t] + np.maximum(v1, a)
+    s = np.empty((t_len, k), bool)
+    s[t_len - 1] = v1 > v0
+    for t in range(t_len - 1, 0, -1):
+        s[t - 1] = np.where(s[t], b1[t], b0[t])
+    return s
+
+
+def _runs_of(s: np.ndarray) -> Tuple[np.ndarray, ...]:
+    """Step 4: per class the [n, 2] int64 (first, last) runs of s [T, K]."""
+    out = []
+    for c in range(s.shape[1]):
+        e = np.diff(np.concatenate([[0], s[:, c].astype(np.int8), [0]]))
+        out.append(np.stack([np.flatnonzero(e == 1), np.flatnonzero(e == -1) - 1], 1).astype(np.int64))
+    return tuple(out)
+
+
+def launch_decode_hmm(preds: torch.Tensor, layout: DecodeLayout, meta: torch.Tensor, lut: torch.Tensor, work: torch.Tensor,
+                      bits: torch.Tensor, out: torch.Tensor, n_frame: int, overlap_hop: int, settings: HmmSettings) -> None:
+    """The iris_decode_events_hmm launches on the current stream into `out` (no host sync: capturable once the buffers
+    exist).  meta, bits and out are DecodeLayout.buffers'; lut is the int32 [1024] score table on the device; work holds
+    >= 2 * layout.n_words int64 words."""
+    f = len(layout.frame_lens)
+    if not (preds.is_cuda and preds.dtype == torch.float32 and preds.is_contiguous() and preds.dim() == 3):
+        raise ValueError("launch_decode_hmm: preds must be a contiguous fp32 GPU tensor [windows, n_out, K]")
+    if not isinstance(settings, HmmSettings) or settings.n_classes != layout.k or preds.shape[2] != layout.k:
+        raise ValueError(f"launch_decode_hmm: HmmSettings and preds for the layout's {layout.k} classes are needed")
+    for name, t, n in (("meta", meta, 2 * f + 1), ("out", out, layout.out_len), ("lut", lut, HMM_BUCKETS)):
+        if t.dtype != torch.int32 or t.device != preds.device or t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"launch_decode_hmm: {name} must be a contiguous int32 [{n}] tensor on {preds.device}")
+    for name, t, n in (("bits", bits, layout.n_words), ("work", work, 2 * layout.n_words)):
+        if t.dtype != torch.int64 or t.device != preds.device or t.numel() < max(n, 1) or not t.is_contiguous():
+            raise ValueError(f"launch_decode_hmm: {name} must be a contiguous int64 tensor of >= {n} words on {preds.device}")
+    wo_h, fl_h = layout.win_off, layout.frame_lens
+    bias, cost = settings.bias(), settings.cost_units()
+    ptr = meta.data_ptr()
+    N.check(N.lib().iris_decode_events_hmm(preds.data_ptr(), ptr, ptr + 4 * (f + 1), wo_h.ctypes.data, fl_h.ctypes.data, f,
+                                           int(n_frame), int(overlap_hop), preds.shape[1], preds.shape[2], lut.data_ptr(),
+                                           bias.ctypes.data, cost.ctypes.data, work.data_ptr(), bits.data_ptr(),
+                                           out.data_ptr() + 4 * f * layout.k, out.data_ptr(),
+                                           torch.cuda.current_stream(preds.device).cuda_stream), "iris_decode_events_hmm")
+
+
+def _hmm_decoder(preds: torch.Tensor, win_off, frame_lens, n_frame: int, overlap_hop: int, lut=None):
+    """run(settings) -> events for one set of window predictions: what does not depend on the settings (the buffers on a GPU;
+    the overlap-add and the table look-up on the CPU) is done once, so a grid of settings costs one decode each."""
+    wo = np.asarray(win_off.cpu() if torch.is_tensor(win_off) else win_off, dtype=np.int64).reshape(-1)
+    fl = np.asarray(frame_lens.cpu() if torch.is_tensor(frame_lens) else frame_lens, dtype=np.int64).reshape(-1)
+    _check(tuple(preds.shape), wo, fl, int(n_frame), int(overlap_hop), AVG_POOL, MAX_POOL)
+    tab = _hmm_table(lut)
+    p = preds.detach().to(torch.float32).contiguous()
+    k = p.shape[2]
+
+    def checked(settings):
+        if not isinstance(settings, HmmSettings):
+            raise ValueError(f"decode_events_hmm: settings must be HmmSettings, got {type(settings).__name__}")
+        if settings.n_classes != k:
+            raise ValueError(f"decode_events_hmm: settings for {settings.n_classes} classes, preds have {k}")
+        return settings
+
+    if p.is_cuda:
+        layout = DecodeLayout(wo, fl, k)
+        meta, bits, out = layout.buffers(p.device)
+        work = torch.empty(max(2 * layout.n_words, 1), dtype=torch.int64, device=p.device)
+        lut_dev = torch.from_numpy(tab).to(p.device)
+
+        def run(settings):
+            launch_decode_hmm(p, layout, meta, lut_dev, work, bits, out, n_frame, overlap_hop, checked(settings))
+            return layout.parse(out.cpu().numpy())
+        return run
+
+    scores = [_hmm_scores_host(_overlap_add_host(p, int(wo[i]), int(wo[i + 1] - wo[i]), int(fl[i]), int(n_frame),
+                                                 int(overlap_hop)), tab) if fl[i] > 0 else None for i in range(len(fl))]
+
+    def run_host(settings):
+        bias = checked(settings).bias().astype(np.int64)
+        cost = settings.cost_units().astype(np.int64)
+        res = []
+        for sc in scores:
+            if sc is None:
+                res.append(tuple(np.zeros((0, 2), np.int64) for _ in range(k)))
+                continue
+            e = np.where(sc[1], HMM_NAN_SCORE, sc[0] - bias[None, :])
+            res.append(_runs_of(_viterbi_host(e, cost)))
+        return res
+    return run_host
+
+
+def decode_events_hmm(preds: torch.Tensor, win_off, frame_lens, n_frame: int, overlap_hop: int, settings: HmmSettings,
+                      lut=None) -> List[Tuple[np.ndarray, ...]]:
+    """decode_events' inputs and outputs through the HMM decoder (module doc; csrc/k_hmm.h): per class a two-state HMM on integer
+    log-odds scores, decoded with Viterbi.  `settings`: per-class HmmSettings; `lut`: 1024 integer scores, one per probability
+    bucket (default hmm_lut()).  GPU tensors: the iris_decode_events_hmm launches and one copy back; CPU tensors: the
+    sequential restatement.  The two are equal, not close: everything after the bucket is integer arithmetic."""
+    return _hmm_decoder(preds, win_off, frame_lens, n_frame, overlap_hop, lut)(settings)
+
+
+@dataclass
+class HmmTuning:
+    settings: HmmSettings
+    score: List[List[float]]               # [G][K]: sum over the files of the class's ER term at each grid point
+    mean_er_first: float                   # mean over the files of get_er with every class at the first grid point
+    mean_er_chosen: float
+    index: Tuple[int, ...]                 # the chosen grid point of each class
+
+
+def choose_hmm_settings(n_pred, matched, n_gt, grid, names: Optional[Sequence[str]] = None) -> HmmTuning:
+    """choose_settings for a grid of (threshold, cost) points: per class the point with the smallest ER term, ties to the
+    earliest."""
+    pts = _hmm_points(grid)
+    score, index, mean_er = _choose_per_class("choose_hmm_settings", n_pred, matched, n_gt, len(pts), names)
+    settings = HmmSettings([pts[i][0] for i in index], [pts[i][1] for i in index], grid=pts, score=score.tolist())
+    return HmmTuning(settings, score.tolist(), mean_er((0,) * len(index)), mean_er(index), index)
 
 
 # ---------------------------------------------------------------------------
@@ -627,21 +899,23 @@ def _group_preds(model, group, batch_size: int) -> Tuple[torch.Tensor, np.ndarra
 
 @torch.no_grad()
 def detect(model, wavs_or_paths: Sequence, config, overlap_hop: int = 512, batch_size: int = 32, sample_rate: int = SR,
-           device=None, max_windows: int = 1024, settings: Optional[DecoderSettings] = None) -> List[Detection]:
+           device=None, max_windows: int = 1024, settings=None) -> List[Detection]:
     """Events of `model` in each recording: a wav path, a (name, [chan, samples] array[, sample rate]) tuple or a bare array
     (named by its position).  Files are handled in groups of at most `max_windows` windows (a longer file forms a group of
     its own); each window's prediction does not depend on the grouping.  `settings`: per-class decoder settings (default: the
-    reference's constants for every class)."""
+    reference's constants for every class) - DecoderSettings for the pooling decoder, HmmSettings for the HMM decoder."""
     results: List[Detection] = []
     for group in _groups(model, wavs_or_paths, config, overlap_hop, sample_rate, device, max_windows):
         results.extend(_detect_group(model, group, config, overlap_hop, batch_size, settings))
     return results
 
 
-def _detect_group(model, group, config, overlap_hop: int, batch_size: int,
-                  settings: Optional[DecoderSettings] = None) -> List[Detection]:
+def _detect_group(model, group, config, overlap_hop: int, batch_size: int, settings=None) -> List[Detection]:
     preds, win_off = _group_preds(model, group, batch_size)
-    events = decode_events(preds, win_off, [t for _, t, _ in group], config.n_frame, overlap_hop, settings=settings)
+    if isinstance(settings, HmmSettings):
+        events = decode_events_hmm(preds, win_off, [t for _, t, _ in group], config.n_frame, overlap_hop, settings)
+    else:
+        events = decode_events(preds, win_off, [t for _, t, _ in group], config.n_frame, overlap_hop, settings=settings)
     out = []
     for (name, t_len, _), ev in zip(group, events):
         metric = M.output_to_metric(HOP, SR)(*ev)
@@ -675,6 +949,42 @@ def tune_decoder(model, wavs_or_paths: Sequence, answer, config, grid=None, over
     return choose_settings(n_pred, matched, n_gt, pts, names)
 
 
+@torch.no_grad()
+def tune_hmm(model, wavs_or_paths: Sequence, answer, config, grid=None, overlap_hop: int = 512, batch_size: int = 32,
+             sample_rate: int = SR, device=None, max_windows: int = 1024, lut=None) -> HmmTuning:
+    """Per-class HmmSettings for `model`, chosen on labelled recordings as tune_decoder chooses DecoderSettings: group by
+    group, each grid point (threshold, cost) is one decode_events_hmm run with every class at that point; its events are
+    counted against `answer` by get_er's rule within the class, and the count tables of all groups end in
+    choose_hmm_settings.  Tune on recordings other than those the settings are scored on."""
+    if isinstance(answer, (str, os.PathLike)):
+        with open(answer) as f:
+            answer = json.load(f)['task2_answer']
+    pts = hmm_grid() if grid is None else _hmm_points(grid)
+    names, tables = [], []
+    for group in _groups(model, wavs_or_paths, config, overlap_hop, sample_rate, device, max_windows):
+        missing = [n for n, _, _ in group if n not in answer]
+        if missing:
+            raise ValueError(f"tune_hmm: no ground truth for {missing[0]}")
+        preds, win_off = _group_preds(model, group, batch_size)
+        f, k = len(group), int(preds.shape[2])
+        gt_rows, gt_off = _gt_table([answer[n] for n, _, _ in group], f, k)
+        run = _hmm_decoder(preds, win_off, [t for _, t, _ in group], config.n_frame, overlap_hop, lut)
+        n_pred, matched = (np.zeros((len(pts), f, k), np.int64) for _ in range(2))
+        for g, pt in enumerate(pts):
+            for i, ev in enumerate(run(HmmSettings((pt[0],) * k, (pt[1],) * k))):
+                for c in range(k):
+                    q = i * k + c
+                    n_pred[g, i, c] = len(ev[c])
+                    matched[g, i, c] = _greedy_matches(gt_rows[gt_off[q]:gt_off[q + 1]],
+                                                       [_middle_second(s, e) for s, e in ev[c]])
+        tables.append((n_pred, matched, np.diff(gt_off.astype(np.int64)).reshape(f, k)))
+        names += [n for n, _, _ in group]
+    if not tables:
+        raise ValueError("tune_hmm: no recordings")
+    n_pred, matched, n_gt = (np.concatenate([t[i] for t in tables], axis=ax) for i, ax in ((0, 1), (1, 1), (2, 0)))
+    return choose_hmm_settings(n_pred, matched, n_gt, pts, names)
+
+
 def answer_rows(det: Detection) -> List[List[int]]:
     """[[class, start_s, end_s], ...]: classes in order, times ascending."""
     return [[c, int(s), int(e)] for c, rows in enumerate(det.answer) for s, e in np.asarray(rows).reshape(-1, 2)]
@@ -702,7 +1012,11 @@ def main(argv=None):
                              help='answer file to choose per-class decoder settings on (the wavs of --wav_dir); they are then applied: the '
                                   'front end and the model run over every recording twice, once to tune and once to detect')
     config.args.add_argument('--decoder_out', type=str, default='decoder.json', help='where --tune writes the settings')
-    config.args.add_argument('--decoder', type=str, default=None, help='decoder settings written by --tune, to apply')
+    config.args.add_argument('--decoder', type=str, default=None,
+                             help='decoder settings written by --tune, to apply (either kind: the file names its own)')
+    config.args.add_argument('--decoder_kind', type=str, default='pool', choices=['pool', 'hmm'],
+                             help="which decoder --tune tunes: the reference's pooling rule or the HMM (Viterbi) decoder; with "
+                                  "'hmm' and neither --tune nor --decoder, the HMM decoder runs at its defaults")
     config = config.get(argv)
     if config.p:
         parse_name(config)
@@ -710,13 +1024,21 @@ def main(argv=None):
         raise ValueError("--tune chooses the decoder settings and --decoder loads them: give one of the two")
     model = load_model(config, config.path)
     paths = sorted(glob(os.path.join(config.wav_dir, '*.wav')))
-    settings = DecoderSettings.load(config.decoder) if config.decoder else None
-    if config.tune:
+    settings = load_settings(config.decoder) if config.decoder else None
+    if config.tune and config.decoder_kind == 'hmm':
+        tuned = tune_hmm(model, paths, config.tune, config, overlap_hop=config.overlap_hop)
+        settings = tuned.settings
+        settings.save(config.decoder_out)
+        print(f"hmm decoder settings (threshold, cost in nats) per class {settings.points()} -> {config.decoder_out}")
+        print(f"MEAN ER default {tuned.mean_er_first!r} chosen {tuned.mean_er_chosen!r} (on the tuning recordings)")
+    elif config.tune:
         tuned = tune_decoder(model, paths, config.tune, config, overlap_hop=config.overlap_hop)
         settings = tuned.settings
         settings.save(config.decoder_out)
         print(f"decoder settings (threshold, avg_pool, max_pool) per class {settings.points()} -> {config.decoder_out}")
         print(f"MEAN ER reference {tuned.mean_er_reference!r} chosen {tuned.mean_er_chosen!r} (on the tuning recordings)")
+    if settings is None and config.decoder_kind == 'hmm':
+        settings = HmmSettings.default(config.n_classes)
     results = detect(model, paths, config, overlap_hop=config.overlap_hop, settings=settings)
     write_answer(results, config.out)
     print(f"{len(results)} files, {sum(len(d.metric) for d in results)} events -> {config.out}")

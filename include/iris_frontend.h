@@ -524,6 +524,40 @@ int iris_decode_sweep(const float* preds, const int* win_off, const int* frame_l
                       void* stream);
 
 /*
+ * The other decoder for the same window predictions: a two-state (off / on) HMM per class, decoded with Viterbi on integer
+ * scores.  Where iris_decode_events widens and merges by a fixed morphological rule, this one keeps an event only if its
+ * accumulated log-odds pay the class's event cost, and bridges a gap only if the gap's evidence against the event is weaker than
+ * the price of a second event.  Opt-in; two launches, capturable.
+ *   preds, win_off, frame_len, win_off_host, frame_len_host, n_files, n_frame, overlap_hop, n_out, n_classes, bits, ev, n_ev: as
+ *         for iris_decode_events (the same layouts of bits, ev and n_ev)
+ *   lut   [1024] int32, DEVICE: the score of each probability bucket, entries in [-2^15, 2^15].  The default table is
+ *         lut[i] = rint(256 ln(c / (1 - c))), c = (i + 0.5) / 1024, computed by the caller in float64: log-odds in units of
+ *         1/256 nat, in [-1952, 1952], lut[511] = -1, lut[512] = 1.  The device evaluates no logarithm
+ *   bias  [K] int32, HOST: rint(256 ln(thr / (1 - thr))) of the class's threshold thr in (0, 1); 0 at 0.5; |bias| <= 2^20
+ *   cost  [K] int32, HOST: the class's event cost C in [0, 2^19], rint(256 * nats)
+ *   work  workspace of iris_decode_hmm_workspace_len = 2 K sum_f ceil(T_f / 64) uint64 words (the back-pointers), DEVICE
+ * For file f, class k, frame t < T_f:
+ *   1. p[t]: the overlap-add average of iris_decode_events (the same fp32 summation order)
+ *   2. e[t], int32: b = clamp(floor(p[t] * 1024.0f), 0, 1023) - the multiply is exact in fp32; values below 0, above 1 and
+ *      +-inf clamp - and e[t] = lut[b] - bias[k]; a NaN p[t] gives e[t] = -2^20
+ *   3. Viterbi, int64: V0 = 0, V1 = -2^60; for t = 0 .. T_f - 1, from the values before frame t,
+ *         b0[t] = (V1 > V0),  b1[t] = !(V0 - C > V1),  then  V0' = max(V0, V1),  V1' = e[t] + max(V1, V0 - C);
+ *      at the end s[T_f - 1] = (V1 > V0) and s[t - 1] = s[t] ? b1[t] : b0[t].  Ties keep the state: stay off, stay on, end off.
+ *      s maximises sum_{t: s[t] = 1} e[t] - C * (number of runs of s); since C <= 2^19 < 2^20 a NaN frame is always off
+ *   4. events: the maximal runs of s as (first, last) frame pairs
+ * No floating point after step 2's bucket.  The kernel cuts time into chunks, one per lane, and combines them with scans of
+ * (max, +) 2 x 2 integer matrices and of maps on {0, 1}: both are exactly associative, so the result EQUALS the sequential
+ * definition above whatever the order of the scans.  Deterministic: plain stores, no atomics.
+ * IRIS_E_INVALID: NULL pointers (lut and work included), a cost outside [0, 2^19], |bias| > 2^20, and what iris_decode_events
+ * refuses; IRIS_E_UNSUPPORTED: K > 16.  All refused before any launch.
+ */
+long long iris_decode_hmm_workspace_len(const int* frame_len_host, int n_files, int n_classes);
+int iris_decode_events_hmm(const float* preds, const int* win_off, const int* frame_len, const int* win_off_host,
+                           const int* frame_len_host, int n_files, int n_frame, int overlap_hop, int n_out, int n_classes,
+                           const int* lut, const int* bias, const int* cost, unsigned long long* work,
+                           unsigned long long* bits, int* ev, int* n_ev, void* stream);
+
+/*
  * Inference epilogue of ConvMPBlock's Conv2D + BatchNormalization + ReLU (+ MaxPool2D 2x2 'same'), sj_train.py:191-201,
  * once the eval-mode BatchNorm is folded into the convolution (sj_train.fold_batchnorm): the convolution itself stays
  * MIOpen (PyTorch-ROCm, per north_star); these replace the separate bias-add, ReLU and pooling passes over its output.
