@@ -104,6 +104,7 @@ struct iris_plan {
     int* d_band_lo;   // [M] first non-zero bin of each band (magmel)
     int* d_band_len;  // [M]
     float* d_mel;     // [F][M] dense (magmel)
+    float* d_wnorm;   // [M] 1 / (2 sum_k W[k][m]) (0 for an all-zero band), built in double (k_whiten.h)
     int* d_bin_band;  // [F] magmel streaming kernel: first band fed by each bin (-1 none)
     float* d_bin_w;   // [F][2] its two weights
     int tri_ok, tri_f_lo, tri_f_hi;  // filterbank is triangular-sparse (<= 2 adjacent bands per bin)

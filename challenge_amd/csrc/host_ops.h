@@ -225,6 +225,83 @@ extern "C" int iris_spec_ipd(iris_plan* p, const float* spec, float* out, int ba
     return IRIS_OK;
 }
 
+// the checks iris_spec_whiten_factors and iris_spec_whiten share (k_whiten.h); every one happens before the first HIP call
+static int check_whiten(const iris_plan* p, const float* spec, const float* factors, int batch, int n_frames, int is_magphase,
+                        int block, const char* who) {
+    if (!p || !spec || !factors) return fail(IRIS_E_INVALID, "%s: NULL argument", who);
+    if (batch <= 0 || n_frames <= 0) return fail(IRIS_E_INVALID, "%s: batch=%d n_frames=%d", who, batch, n_frames);
+    if (block < 1) return fail(IRIS_E_INVALID, "%s: block=%d must be at least 1 frame", who, block);
+    if (p->channels != 2) return fail(IRIS_E_UNSUPPORTED, "%s: the plan has %d channel(s); the covariance is that of a stereo pair", who, p->channels);
+    if (is_magphase) return fail(IRIS_E_UNSUPPORTED, "%s: magnitude / phase input; a complex spectrum (re0, re1, im0, im1) is expected", who);
+    if (batch > 65535) return fail(IRIS_E_UNSUPPORTED, "%s: batch %d > 65535", who, batch);
+    if ((reinterpret_cast<uintptr_t>(spec) & 15) || (reinterpret_cast<uintptr_t>(factors) & 15))
+        return fail(IRIS_E_INVALID, "%s: spec and factors must be 16-byte aligned", who);
+    return IRIS_OK;
+}
+
+// iris_spec_whiten_factors: the per-(sample, bin, block) whitening factors of a stereo complex spectrum (k_whiten.h, pass 1)
+extern "C" int iris_spec_whiten_factors(iris_plan* p, const float* spec, float* factors, int batch, int n_frames, int is_magphase,
+                                        int block, double loading, void* stream) {
+    const char* who = "iris_spec_whiten_factors";
+    int rc;
+    if ((rc = check_whiten(p, spec, factors, batch, n_frames, is_magphase, block, who))) return rc;
+    if (!std::isfinite(loading) || loading <= 0.) return fail(IRIS_E_INVALID, "%s: loading=%g must be finite and positive", who, loading);
+    DeviceGuard guard(p->device);
+    WhitenFactorArgs a;
+    a.spec = spec;
+    a.fac = factors;
+    a.loading = loading;
+    a.B = batch;
+    a.F = p->n_bins;
+    a.T = n_frames;
+    a.block = std::min(block, n_frames);
+    a.J = (n_frames + a.block - 1) / a.block;
+    a.log2g = 0;
+    while (a.log2g < 6 && (4 << a.log2g) < a.block) ++a.log2g;  // G = a quarter of the power of two >= block, 1 ... 64
+    const int per_wave = 64 >> a.log2g;
+    a.n_waves = (long long)batch * p->n_bins * ((a.J + per_wave - 1) / per_wave);
+    const long long blocks = (a.n_waves + 3) / 4;
+    if (blocks > 0x7fffffffLL) return fail(IRIS_E_UNSUPPORTED, "%s: %lld workgroups exceed the grid limit", who, blocks);
+    k_whiten_factors<<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(a);
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+
+// iris_spec_whiten: the whitened mel-band energy from the spectrum and its factors (k_whiten.h, pass 2)
+extern "C" int iris_spec_whiten(iris_plan* p, const float* spec, const float* factors, float* out, int batch, int n_frames,
+                                int is_magphase, int block, int log, const int32_t* t_bands, int n_tb, const int32_t* f_bands,
+                                int n_fb, void* stream) {
+    const char* who = "iris_spec_whiten";
+    int rc;
+    if (!out) return fail(IRIS_E_INVALID, "%s: NULL argument", who);
+    if ((rc = check_whiten(p, spec, factors, batch, n_frames, is_magphase, block, who))) return rc;
+    if (reinterpret_cast<uintptr_t>(out) & 3) return fail(IRIS_E_INVALID, "%s: out must be 4-byte aligned", who);
+    if ((rc = check_bands(t_bands, n_tb, who)) || (rc = check_bands(f_bands, n_fb, who))) return rc;
+    DeviceGuard guard(p->device);
+    WhitenArgs a;
+    a.spec = spec;
+    a.fac = factors;
+    a.out = out;
+    a.w = p->d_mel;
+    a.wnorm = p->d_wnorm;
+    a.band_lo = p->d_band_lo;
+    a.band_len = p->d_band_len;
+    a.t_bands = n_tb ? t_bands : nullptr;
+    a.n_tb = n_tb;
+    a.f_bands = n_fb ? f_bands : nullptr;
+    a.n_fb = n_fb;
+    a.B = batch;
+    a.F = p->n_bins;
+    a.T = n_frames;
+    a.M = p->n_mel;
+    a.block = std::min(block, n_frames);
+    a.J = (n_frames + a.block - 1) / a.block;
+    a.log = log ? 1 : 0;
+    k_spec_whiten<<<dim3((n_frames + 63) / 64, batch), 256, 0, (hipStream_t)stream>>>(a);
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+
 extern "C" size_t iris_minmax_log_workspace(int n_rows, size_t row_len) {
     return n_rows > 0 ? 2 * (size_t)n_rows * n_chunks_of(row_len) : 0;
 }

@@ -321,7 +321,7 @@ extern "C" int iris_plan_create(iris_plan** out, int device, int n_fft, int hop,
     p->d_band_lo = p->d_band_len = p->d_fband_lo = nullptr;
     p->d_bin_band = nullptr;
     p->d_bin_w = nullptr;
-    p->d_wband = p->d_mel = p->d_ws = nullptr;
+    p->d_wband = p->d_mel = p->d_ws = p->d_wnorm = nullptr;
     p->d_wfrag = nullptr;
     p->d_tile_ks = nullptr;
     p->mfma_ok = p->mfma_kb = p->mel_precision = 0;
@@ -378,6 +378,13 @@ extern "C" int iris_plan_create(iris_plan** out, int device, int n_fft, int hop,
         }
         p->max_band_len = std::max(p->max_band_len, len[m]);
         p->k_need = std::max(p->k_need, lo[m] + len[m]);
+    }
+    // the whitened channel's band normalisation (k_whiten.h): 1 / (2 sum_k W[k][m]), summed and inverted in double
+    std::vector<float> wnorm(n_mel, 0.f);
+    for (int m = 0; m < n_mel; ++m) {
+        double sum = 0.;
+        for (int f = 0; f < n_bins; ++f) sum += (double)p->mel[(size_t)f * n_mel + m];
+        if (sum != 0.) wnorm[m] = (float)(1.0 / (2.0 * sum));
     }
     // streaming magmel tables: valid when every bin's non-zeros sit in <= 2 adjacent bands and
     // the first band index never decreases with the bin (true for triangular filterbanks)
@@ -536,6 +543,7 @@ extern "C" int iris_plan_create(iris_plan** out, int device, int n_fft, int hop,
         (rc = upload(&p->d_fband_lo, flo)) || (rc = upload(&p->d_wband, wband)) ||
         (rc = upload(&p->d_bin_band, bin_band)) || (rc = upload(&p->d_bin_w, bin_w)) ||
         (rc = upload(&p->d_mel, p->mel)) ||
+        (rc = upload(&p->d_wnorm, wnorm)) ||
         (p->mfma_ok && ((rc = upload((_Float16**)&p->d_wfrag, wfrag)) || (rc = upload(&p->d_tile_ks, tile_ks))))) {
         iris_plan_destroy(p);
         return rc;
@@ -678,6 +686,7 @@ extern "C" int iris_plan_destroy(iris_plan* p) {
     (void)hipFree(p->d_bin_w);
     (void)hipFree(p->d_wband);
     (void)hipFree(p->d_mel);
+    (void)hipFree(p->d_wnorm);
     (void)hipFree(p->d_wfrag);
     (void)hipFree(p->d_tile_ks);
     (void)hipFree(p->d_ws);

@@ -13,6 +13,7 @@
 //   k_istft.h        inverse STFT of a ragged set of spectrograms in that layout (pickled spectrum corpora -> waveforms), one launch
 //   k_magmel.h       spectrum -> mel
 //   k_ipd.h         stereo spectrum -> mel-band inter-channel phase difference (cos, sin), its own streaming kernel (opt-in)
+//   k_whiten.h      stereo spectrum -> spatially whitened mel-band energy x^H (R + d I)^-1 x, two launches (opt-in)
 //   k_elementwise.h  min-max / log, normalize, magnitude-phase, mask, adaptive gradient clipping
 //   k_mix.h          batched sample synthesis (merge_complex_specs)
 //   k_draw.h         the random half of a batch drawn on the device (source table, SpecAugment bands)
@@ -58,6 +59,7 @@
 #include "k_istft.h"
 #include "k_magmel.h"
 #include "k_ipd.h"
+#include "k_whiten.h"
 #include "k_elementwise.h"
 #include "host_plan.h"
 #include "k_ism.h"

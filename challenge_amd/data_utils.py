@@ -159,6 +159,14 @@ class RunTokens:
         `inference.features_for_eval` appends the same two channels, and the model's first layer takes
         `model_in_channels(config)`.  Stereo only: n_chan must be 2 and the corpora stereo.  Refused with 'pcen_learn' (the
         trainable PCEN layer would have to skip the two phase channels); it goes with every other token.
+    whiten: the spatially whitened energy channel, two-microphone noise nulling.  A FEATURE like 'ipd': the batched datasets
+        append ONE channel, last (mel0, mel1, then the 'ipd' pair if named, then this one), on training and validation sets
+        alike - ln(e + 1e-8) of the mel-band average e of x^H (R + d I)^-1 x (`transforms.mel_whiten`, `FrontendPlan.whiten`),
+        with R the 2x2 inter-channel covariance of the clip's n_frame frames of the same mixed spectrum 'ipd' reads.  The
+        batch's SpecAugment / 'filter' bands act on its output only (the covariance does not see them), and min-max, log,
+        PCEN and the FilterAugment gain never touch it (the definition is invariant to a band gain).
+        `inference.features_for_eval` appends the same channel with blocks of n_frame frames over the whole recording.
+        Stereo only, refused with 'pcen_learn' (as 'ipd') and by `make_dataset`; it goes with every other token.
     A name without a token takes no code path of that token."""
     name: str
     compression: str
@@ -170,11 +178,12 @@ class RunTokens:
     filtaug: Optional[str]
     ipd: bool
     reverb_long: bool = False
+    whiten: bool = False
 
 
 def run_tokens(config_or_name) -> RunTokens:
     """The tokens of a run name, given the name or a config (whose `name` may be missing or None).  Raises the refusals that
-    the name alone decides and, given a config, 'ipd' at n_chan != 2."""
+    the name alone decides and, given a config, 'ipd' or 'whiten' at n_chan != 2."""
     config = None if config_or_name is None or isinstance(config_or_name, str) else config_or_name
     name = (config_or_name if config is None else getattr(config, 'name', '')) or ''
     pcen, nominmax = 'pcen' in name, 'nominmax' in name
@@ -186,7 +195,7 @@ def run_tokens(config_or_name) -> RunTokens:
         filter='filter' in name, stretch='stretch' in name, speed='speed' in name, reverb='reverb' in name,
         shoebox='shoebox' in name,
         filtaug=('linear' if 'filtaug_linear' in name else 'step') if 'filtaug' in name else None,
-        ipd='ipd' in name, reverb_long='reverb_long' in name)
+        ipd='ipd' in name, reverb_long='reverb_long' in name, whiten='whiten' in name)
     if tokens.reverb_long and tokens.shoebox:
         raise ValueError(f"run name {name!r} asks for both 'reverb_long' and 'shoebox': the image-source room model computes at "
                          "most 4096 taps, name one")
@@ -199,6 +208,12 @@ def run_tokens(config_or_name) -> RunTokens:
     if tokens.ipd and tokens.compression == 'pcen_learn':
         raise ValueError(f"run name {name!r} asks for both 'ipd' and 'pcen_learn': the trainable PCEN layer would have to skip "
                          "the two phase channels, which is not supported yet; name one (the fixed 'pcen' goes with 'ipd')")
+    if tokens.whiten and config is not None and config.n_chan != 2:
+        raise ValueError(f"run name {name!r} asks for 'whiten' at n_chan = {config.n_chan}: the inter-channel covariance is "
+                         "that of a stereo pair, n_chan must be 2")
+    if tokens.whiten and tokens.compression == 'pcen_learn':
+        raise ValueError(f"run name {name!r} asks for both 'whiten' and 'pcen_learn': the trainable PCEN layer would have to skip "
+                         "the whitened channel, which is not supported yet; name one (the fixed 'pcen' goes with 'whiten')")
     return tokens
 
 
@@ -232,10 +247,14 @@ BUILDER_REFUSALS = {
 
 def check_builder(tokens: RunTokens, builder: str) -> None:
     """ValueError if `builder` (a key of BUILDER_REFUSALS) does not honour a token of the name, or - a mixer holds one voice
-    augmentation - if the name asks it for both 'speed' and 'reverb'."""
+    augmentation - if the name asks it for both 'speed' and 'reverb'.  'whiten' is honoured by the two batched builders
+    and refused by `make_dataset` here (the table keeps the rows it has)."""
     for token, reason in BUILDER_REFUSALS[builder].items():
         if reason is not None and getattr(tokens, token):
             raise ValueError(f"run name {tokens.name!r} asks for {token!r}: {reason}")
+    if tokens.whiten and builder == 'make_dataset':
+        raise ValueError(f"run name {tokens.name!r} asks for 'whiten': the whitened channel is computed on whole batches "
+                         "(make_device_dataset, make_wave_dataset); the per-sample host pipeline has no such stage")
     if tokens.speed and tokens.reverb:
         raise ValueError(f"run name {tokens.name!r} asks for both 'speed' and 'reverb': the two cannot be combined yet (a "
                          "mixer holds one voice augmentation), name one")
@@ -247,8 +266,10 @@ def feature_compression(name: str) -> str:
 
 
 def model_in_channels(config) -> int:
-    """Channels of the model's input: n_chan, plus the two (cos, sin) phase channels of an 'ipd' run name."""
-    return config.n_chan + 2 if run_tokens(config).ipd else config.n_chan
+    """Channels of the model's input: n_chan, plus the two (cos, sin) phase channels of an 'ipd' run name, plus the whitened
+    energy channel of a 'whiten' one (in this order)."""
+    tokens = run_tokens(config)
+    return config.n_chan + 2 * tokens.ipd + tokens.whiten
 
 
 class FilterAugmentDraw:

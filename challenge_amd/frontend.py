@@ -7,6 +7,7 @@ must be float32, contiguous and on a ROCm device -- there is no CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import threading
 import weakref
@@ -322,6 +323,67 @@ class FrontendPlan:
             rc = N.lib().iris_spec_ipd(self._handle, spec.data_ptr(), out.data_ptr(), b, t, 0, tbp, ntb, fbp, nfb,
                                        _stream_ptr(self.device))
         N.check(rc, "iris_spec_ipd")
+        return out
+
+    def _whiten_args(self, spec, block, what):
+        """The checked spectrum and block length of `whiten_factors` / `whiten`: (spec, B, T, block, J)."""
+        spec = _require_device_f32(spec, "spec")
+        if self.channels != 2:
+            raise ValueError(f"{what}: the plan has {self.channels} channel(s); the covariance is that of a stereo pair")
+        if spec.dim() != 4 or spec.shape[1] != self.n_bins or spec.shape[3] != 4:
+            raise ValueError(f"spec must be [B, {self.n_bins}, T, 4], got {tuple(spec.shape)}")
+        if spec.data_ptr() % 16:
+            spec = spec.clone()   # (a view at an odd offset: the kernels load 16 bytes per bin)
+        b, t = int(spec.shape[0]), int(spec.shape[2])
+        block = t if block is None else int(block)
+        if block < 1:
+            raise ValueError(f"{what}: block = {block} must be at least 1 frame")
+        block = max(min(block, t), 1)
+        return spec, b, t, block, (t + block - 1) // block
+
+    def whiten_factors(self, spec: torch.Tensor, block: Optional[int] = None, loading: float = 1e-2) -> torch.Tensor:
+        """Stereo complex spec [B,F,T,4] = (re0, re1, im0, im1) -> the whitening factors [B,F,J,4] = (a, b, Re c, Im c) of every
+        (sample, bin, block of `block` frames; None: all T frames, J = ceil(T / block)): the inverted Cholesky factor of the
+        block's 2x2 inter-channel covariance R + d I, d = loading (r00 + r11) / 2 (`iris_spec_whiten_factors`: accumulated and
+        factorised in double; `transforms.mel_whiten` states the definition).  No bands: the covariance never sees them."""
+        spec, b, t, block, j = self._whiten_args(spec, block, "whiten_factors")
+        loading = float(loading)
+        if not (math.isfinite(loading) and loading > 0):
+            raise ValueError(f"whiten_factors: loading = {loading} must be finite and positive")
+        fac = torch.empty((b, self.n_bins, j, 4), dtype=torch.float32, device=spec.device)
+        if b == 0 or t == 0:
+            return fac
+        with self._lock, torch.cuda.device(self.device):
+            rc = N.lib().iris_spec_whiten_factors(self._handle, spec.data_ptr(), fac.data_ptr(), b, t, 0, block, loading,
+                                                  _stream_ptr(self.device))
+        N.check(rc, "iris_spec_whiten_factors")
+        return fac
+
+    def whiten(self, spec: torch.Tensor, block: Optional[int] = None, loading: float = 1e-2, log: bool = True,
+               t_bands=None, f_bands=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Stereo complex spec [B,F,T,4] -> the spatially whitened mel-band energy [B,M,T]: x^H (R + d I)^-1 x per bin, with R
+        the covariance of the frame's block (`whiten_factors`), averaged over the mel bands with weights W[k,m] / (2 sum_k
+        W[k,m]); `log`: ln(e + 1e-8), `log_on_mel`'s form (two launches: `iris_spec_whiten_factors`, `iris_spec_whiten`;
+        `transforms.mel_whiten` states the definition).  t_bands / f_bands act on the OUTPUT only - a masked frame gives e = 0,
+        a masked bin adds nothing to its bands' sums - and neither the covariance nor the normalisation sees them: unlike
+        `ipd` and `magmel`, whose bands zero the spectrum first (that would change R).  `out`: a contiguous float32 [B,M,T]
+        device tensor to write into."""
+        spec, b, t, block, _ = self._whiten_args(spec, block, "whiten")
+        if out is None:
+            out = torch.empty((b, self.n_mel, t), dtype=torch.float32, device=spec.device)
+        else:
+            if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+                    and tuple(out.shape) == (b, self.n_mel, t) and out.device == spec.device and out.data_ptr() % 4 == 0):
+                raise ValueError(f"out must be a contiguous, 4-byte aligned float32 tensor {(b, self.n_mel, t)} on {spec.device}")
+        tb, tbp, ntb = _bands_arg(t_bands, b, spec.device, "t_bands")
+        fb, fbp, nfb = _bands_arg(f_bands, b, spec.device, "f_bands")
+        fac = self.whiten_factors(spec, block, loading)
+        if b == 0 or t == 0:
+            return out
+        with self._lock, torch.cuda.device(self.device):
+            rc = N.lib().iris_spec_whiten(self._handle, spec.data_ptr(), fac.data_ptr(), out.data_ptr(), b, t, 0, block,
+                                          1 if log else 0, tbp, ntb, fbp, nfb, _stream_ptr(self.device))
+        N.check(rc, "iris_spec_whiten")
         return out
 
     def wav_to_logmel(self, wav: torch.Tensor, minmax: bool = True, log: bool = True,

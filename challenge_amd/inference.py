@@ -73,7 +73,12 @@ def features_for_eval(spec: torch.Tensor, config) -> torch.Tensor:
     into windows (training applies it per clip: see data_utils.pcen_on_mel).  A 'pcen_learn' run name returns the raw mel
     magnitudes: the trainable PCEN layer is inside the model and runs per window, which is what training saw per clip.
     An 'ipd' run name returns [M, T, 4]: the same two channels, then the (cos, sin) phase channels (`transforms.mel_ipd`) of
-    the filtered spectrum, uncompressed (per-frame quantities: cutting windows later does not change them)."""
+    the filtered spectrum, uncompressed (per-frame quantities: cutting windows later does not change them).
+    A 'whiten' run name appends one more channel, last: ln(e + 1e-8) of the spatially whitened energy (`transforms.mel_whiten`)
+    of the filtered spectrum, the covariance taken over consecutive blocks of config.n_frame frames of the WHOLE recording from
+    frame 0.  With the default `overlap_hop == n_frame` every evaluation window is exactly one block, which is what training
+    saw per clip; with another hop the windows straddle blocks and a window's frames are whitened by the covariances of the
+    two blocks it overlaps (as PCEN's smoother runs over the whole recording: see data_utils.pcen_on_mel)."""
     tokens = D.run_tokens(config)
     inputs = spec
     if config.n_chan == 1:
@@ -85,6 +90,8 @@ def features_for_eval(spec: torch.Tensor, config) -> torch.Tensor:
     inputs = D.stft_filter(int(round(256 * 1000 / 16000)))(inputs)
     if tokens.ipd and inputs.shape[-1] != 4:
         raise ValueError(f"run name {config.name!r} asks for 'ipd' but the recording has {inputs.shape[-1] // 2} channel(s)")
+    if tokens.whiten and inputs.shape[-1] != 4:
+        raise ValueError(f"run name {config.name!r} asks for 'whiten' but the recording has {inputs.shape[-1] // 2} channel(s)")
     to_mel = T.magphase_to_mel(config.n_mels, inputs.shape[0])
     mel = to_mel(T.complex_to_magphase(inputs))
     if tokens.compression == 'pcen':
@@ -93,6 +100,8 @@ def features_for_eval(spec: torch.Tensor, config) -> torch.Tensor:
         mel = D.log_on_mel(D.minmax(mel))   # unbatched: per-mel-row min-max (the reference's behaviour)
     if tokens.ipd:
         mel = torch.cat([mel, T.mel_ipd(inputs, to_mel.mel_matrix)], dim=-1)
+    if tokens.whiten:
+        mel = torch.cat([mel, T.mel_whiten(inputs, to_mel.mel_matrix, config.n_frame).unsqueeze(-1)], dim=-1)
     return mel
 
 

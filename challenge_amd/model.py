@@ -229,7 +229,7 @@ class CustomModel(nn.Module):
         # (registered first; models of other names have no such submodule and the state_dict keys they always had)
         from .data_utils import model_in_channels, run_tokens   # (the parse refuses 'ipd' at n_chan != 2 or with 'pcen_learn')
         self.pcen = PCEN(config.n_mels) if run_tokens(config).compression == 'pcen_learn' else None
-        blocks = [ConvMPBlock(model_in_channels(config), 2, fsize, BN=True)]   # n_chan, + the two phase channels of an 'ipd' name
+        blocks = [ConvMPBlock(model_in_channels(config), 2, fsize, BN=True)]   # n_chan, + the two phase channels of an 'ipd' name, + the whitened channel of a 'whiten' name
         cin, width = fsize, config.n_frame // 2
         for i in range(1, 5):
             if config.model_type == 'vad' and config.v == 6:
@@ -270,7 +270,7 @@ class CustomModel(nn.Module):
         object.__setattr__(self, '_generation', 0)
 
     def forward(self, x):
-        """x: [B, n_mels, n_frame, n_chan] (the reference's channels-last input; n_chan + 2 for an 'ipd' run name)."""
+        """x: [B, n_mels, n_frame, n_chan] (the reference's channels-last input; `data_utils.model_in_channels`: + 2 for an 'ipd' run name, + 1 for a 'whiten' one)."""
         global _NBT_PENDING
         if SW.ZERO_POOL and not _IN_STEP[0] and self.training and x.is_cuda and torch.is_grad_enabled():
             # a training-mode pass outside train_step (a custom loop, a test's grads()): it is its own "step" for the zero pool,

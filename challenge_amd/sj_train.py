@@ -239,7 +239,15 @@ def complex_to_mel(n_mels: int, num_spectrogram_bins: int = 257, sample_rate: fl
             return _tr.mel_ipd(x, to_mel.mel_matrix, t_bands, f_bands)
         return _plan(x).ipd(x.float(), t_bands=t_bands, f_bands=f_bands)
 
+    def _whiten(x, block, t_bands=None, f_bands=None):
+        """The whitened energy channel ln(e + 1e-8) [B, n_mels, T] of the same stereo spectrum with the same mel matrix, the
+        bands acting on its output (`transforms.mel_whiten`; on a ROCm tensor `FrontendPlan.whiten` of this closure's plan)."""
+        if not x.is_cuda or n_fft not in (256, 512, 1024, 2048):
+            return _tr.mel_whiten(x, to_mel.mel_matrix, block, t_bands=t_bands, f_bands=f_bands)
+        return _plan(x).whiten(x.float(), block, t_bands=t_bands, f_bands=f_bands)
+
     _complex_to_mel.ipd = _ipd
+    _complex_to_mel.whiten = _whiten
     return _complex_to_mel
 
 
@@ -349,7 +357,7 @@ class BatchDraws:
     - the bands of SpecAugment (`augment`, data_utils.py:58-61: 6 time masks, 1 frequency mask per sample) on training sets,
       and behind them the `stft_filter` band (data_utils.py:126-136: bins 1..k) of a 'filter' name on every set; None
       where there is nothing to mask.  device_draw: one `iris_augment_draw` launch into long-lived device tensors (the filter
-      band included), else NumPy on the host - uploaded here, once for both kernels that read them, on an 'ipd' run;
+      band included), else NumPy on the host - uploaded here, once for all kernels that read them, on an 'ipd' / 'whiten' run;
     - the gains [B, n_mels] of a 'filtaug' name on training sets (`FilterAugmentDraw`), else None.
     A validation set draws neither SpecAugment bands nor gains."""
 
@@ -357,7 +365,7 @@ class BatchDraws:
         key = 0 if seed is None else seed
         self.training, self.device, self.n_bins = training, device, n_bins
         self.filter_bins = _FILTER_BINS if tokens.filter else 0
-        self.upload = tokens.ipd
+        self.upload = tokens.ipd or tokens.whiten
         self.rng = np.random.default_rng(None if seed is None else seed + 1)
         self.band_draw = _du.DeviceAugmentDraw(device, key + 1, self.filter_bins) if device_draw and training else None
         self.gain_draw = None
@@ -403,13 +411,18 @@ def make_device_dataset(config, training=True, n_classes=3, sources=None, device
     host only enqueues launches.
     Of the run-name tokens (`data_utils.RunTokens`) this builder honours 'stretch', 'filtaug' and 'ipd' and refuses 'speed'
     and 'reverb' (`data_utils.BUILDER_REFUSALS`).  With 'ipd' x is [B, n_mels, n_frame, 4]: one more launch
-    (`FrontendPlan.ipd`) over the same mixed spectrum; the corpora must be stereo."""
+    (`FrontendPlan.ipd`) over the same mixed spectrum; the corpora must be stereo.  'whiten' (`check_builder` honours it here)
+    appends one channel behind those, ln(e + 1e-8) of the spatially whitened energy of the same spectrum with the clip as one
+    block (`FrontendPlan.whiten`, two more launches), the batch's bands acting on its output; stereo corpora as well."""
     from .mixer import DeviceMixer
     tokens = _du.run_tokens(config)
     _du.check_builder(tokens, 'make_device_dataset')
     backgrounds, voices, labels, noises = _load_sources(config, training, n_classes, sources)
     if config.model_type == 'se' and config.v == 9:
         raise NotImplementedError("model_type 'se' is outside the accelerated path (SURVEY.md section 2)")
+    if tokens.whiten and int(np.asarray(backgrounds[0]).shape[-1]) != 4:   # (before the device is touched)
+        raise ValueError(f"run name {config.name!r} asks for 'whiten' but the corpus has {int(np.asarray(backgrounds[0]).shape[-1]) // 2} "
+                         "channel(s): the inter-channel covariance needs stereo corpora")
     mixer = DeviceMixer(backgrounds, voices, labels, noises, n_frame=config.n_frame, max_voices=config.max_voices,
                         max_noises=config.max_noises, n_classes=n_classes, device=device, snr=config.snr,
                         min_ratio=1, seed=seed)
@@ -446,6 +459,8 @@ def make_device_dataset(config, training=True, n_classes=3, sources=None, device
                 mel, y = compress(mel, y)   # (called as `Dataset.map` calls a stage)
             if tokens.ipd:   # the phase channels: neither compressed nor gained
                 mel = torch.cat([mel, to_mel.ipd(x, tb, fb)], dim=-1)
+            if tokens.whiten:   # the whitened channel, last: the clip is one block; neither compressed nor gained
+                mel = torch.cat([mel, to_mel.whiten(x, config.n_frame, tb, fb).unsqueeze(-1)], dim=-1)
             yield mel, y
 
     dataset = _label_tail(Dataset.from_generator(gen), config, compressed=True)
@@ -521,21 +536,28 @@ def waves_from_specs(sources, n_fft=512, hop=256, device=None):
     return waves
 
 
-def wave_features(plan, compression, do_minmax, wav, t_bands=None, f_bands=None, mel_gain=None, out=None, ipd=False):
+def wave_features(plan, compression, do_minmax, wav, t_bands=None, f_bands=None, mel_gain=None, out=None, ipd=False, whiten=0):
     """The features [B, M, T, C] of the waveforms `wav` [B, C, L] on `plan`, one body for `make_wave_dataset` and
     `WaveFrontend`: compression 'log' is ONE launch of the fused kernel (STFT, bands, mel, gains, min-max if `do_minmax`,
     log); 'mel' the same launch stopping at the (gained) mel magnitudes; 'pcen' that, then `frontend.pcen` in place (a
     second launch).  `out` (optional) receives these channels.  ipd: the batch's spectrum is materialised as well (`iris_stft`)
     and the two phase channels (`FrontendPlan.ipd`) under the same bands, neither compressed nor gained, are appended - two
-    more launches and a `torch.cat`: deliberately NOT fused into the hot kernel.  Capturable into a hipGraph in every form."""
+    more launches and a `torch.cat`: deliberately NOT fused into the hot kernel.  whiten (a block length in frames, 0: off):
+    the whitened energy channel ln(e + 1e-8) (`FrontendPlan.whiten`, two launches) of that same materialised spectrum - made
+    once when both are asked for - is appended last, the bands acting on its output.  Capturable into a hipGraph in every form."""
     if compression == 'log':
         mel = plan.wav_to_logmel(wav, minmax=do_minmax, log=True, t_bands=t_bands, f_bands=f_bands, out=out, mel_gain=mel_gain)
     else:
         mel = plan.wav_to_logmel(wav, minmax=False, log=False, t_bands=t_bands, f_bands=f_bands, out=out, mel_gain=mel_gain)
         if compression == 'pcen':
             mel = _fe.pcen(mel, out=mel)
-    if ipd:
-        return torch.cat([mel, plan.ipd(plan.stft(wav), t_bands=t_bands, f_bands=f_bands)], dim=-1)
+    if ipd or whiten:
+        spec, extra = plan.stft(wav), []
+        if ipd:
+            extra.append(plan.ipd(spec, t_bands=t_bands, f_bands=f_bands))
+        if whiten:
+            extra.append(plan.whiten(spec, whiten, t_bands=t_bands, f_bands=f_bands).unsqueeze(-1))
+        return torch.cat([mel, *extra], dim=-1)
     return mel
 
 
@@ -557,7 +579,8 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
     the device (`iris_mix_draw`, `iris_augment_draw`), as in `make_device_dataset`.
     Of the run-name tokens (`data_utils.RunTokens`) this builder honours 'speed', 'reverb' (with 'shoebox'), 'filtaug' and
     'ipd' and refuses 'stretch', and 'speed' beside 'reverb' (`data_utils.BUILDER_REFUSALS`).  With 'ipd' x is
-    [B, n_mels, n_frame, 4] (`wave_features`); the corpora must be stereo.
+    [B, n_mels, n_frame, 4] (`wave_features`); the corpora must be stereo.  'whiten' (`check_builder` honours it here) appends
+    the whitened energy channel behind those, the clip as one block; stereo corpora and recordings as well.
     spec_sources: the same tuple as SPECTRA ([F, T_i, 2C], integer labels), e.g. the pickled corpora - converted once here by
     `waves_from_specs` at this n_fft / hop and used as `sources` (giving both is a ValueError).
     recordings: a `recordings.RecordingSampler` (built for this n_frame and hop), or a (waves, events) pair - what
@@ -600,6 +623,9 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
         if tokens.ipd and rec_chan != 2:
             raise ValueError(f"run name {config.name!r} asks for 'ipd' but the recordings have {rec_chan} channel(s): the "
                              "inter-channel phase difference needs stereo recordings")
+        if tokens.whiten and rec_chan != 2:
+            raise ValueError(f"run name {config.name!r} asks for 'whiten' but the recordings have {rec_chan} channel(s): the "
+                             "inter-channel covariance needs stereo recordings")
         if float(recordings_share) < 1.0:
             corpus_chan = 2 if sources is None else int(sources[0][0].shape[0])
             if spec_sources is not None:
@@ -616,6 +642,11 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
         raise NotImplementedError("make_wave_dataset: n_chan 1 (mono sum) or 2; the augmenting channel maps mix spectra")
     mixer = None
     if sampler is None or float(recordings_share) < 1.0:
+        if tokens.whiten and (sources is not None or spec_sources is not None):   # (before the device is touched)
+            corpus_chan = int(spec_sources[0][0].shape[2]) // 2 if spec_sources is not None else int(sources[0][0].shape[0])
+            if corpus_chan != 2:
+                raise ValueError(f"run name {config.name!r} asks for 'whiten' but the corpus has {corpus_chan} channel(s): the "
+                                 "inter-channel covariance needs stereo corpora")
         if spec_sources is not None:
             sources = waves_from_specs(spec_sources, n_fft, hop, device)
         if sources is None:
@@ -681,7 +712,8 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
             if config.n_chan == 1 and wav.shape[1] == 2:
                 wav = wav[:, :1] + wav[:, 1:]            # true down-mix (NOT the reference's broadcast mono_chan: see docstring)
             tb, fb, gain = draws(int(wav.shape[0]), config.n_frame, config.n_mels)
-            yield wave_features(plan, compression, do_minmax, wav.contiguous(), tb, fb, gain, None, tokens.ipd), y
+            yield wave_features(plan, compression, do_minmax, wav.contiguous(), tb, fb, gain, None, tokens.ipd,
+                                config.n_frame if tokens.whiten else 0), y
 
     dataset = _label_tail(Dataset.from_generator(gen), config, compressed=True)
     dataset.mixer = mixer   # (for inspection: the resident corpus, its draws and - 'speed' / 'reverb' runs - the current voices)

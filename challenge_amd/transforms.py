@@ -261,27 +261,14 @@ def mel_ipd(spec: torch.Tensor, mel_matrix, t_bands=None, f_bands=None) -> torch
                          f"{tuple(spec.shape)} and {w.shape}")
     b = int(x.shape[0])
     if x.is_cuda:
-        key = (x.device.index, w.shape, w.tobytes())
-        plan = _IPD_PLANS.get(key)
-        if plan is None or plan.max_batch < b:
-            n_fft = 2 * (w.shape[0] - 1)
-            if n_fft in (256, 512, 1024, 2048):
-                plan = _fe.FrontendPlan(n_fft, None, w.shape[1], 16000, 2, max(b, 1), n_fft, x.device, mel_matrix=w)
-            else:
-                plan = _fe.FrontendPlan.mel_only(w.shape[1], w.shape[0], 2, max(b, 1), x.device, w)
-            _IPD_PLANS[key] = plan
-        out = plan.ipd(x.float(), t_bands=t_bands, f_bands=f_bands)
+        out = _stereo_plan(x, w).ipd(x.float(), t_bands=t_bands, f_bands=f_bands)
     else:
         if not torch.is_floating_point(x):
             x = x.float()
         for bands, n, shape in ((t_bands, x.shape[2], (b, 1, -1, 1)), (f_bands, x.shape[1], (b, -1, 1, 1))):
             if bands is None:
                 continue
-            bd = torch.as_tensor(bands).to(torch.int64)
-            if bd.dim() != 3 or bd.shape[0] != b or bd.shape[2] != 2:
-                raise ValueError(f"mel_ipd: bands must have shape [batch={b}, n, 2], got {tuple(bd.shape)}")
-            idx = torch.arange(n)[None, None, :]
-            hit = ((idx >= bd[:, :, :1]) & (idx < bd[:, :, :1] + bd[:, :, 1:])).any(dim=1)   # [B, n]
+            hit = _band_hits(bands, b, n, "mel_ipd")
             x = torch.where(hit.reshape(shape), torch.zeros((), dtype=x.dtype), x)
         re0, re1, im0, im1 = x.unbind(-1)
         re = re0 * re1 + im0 * im1
@@ -295,6 +282,104 @@ def mel_ipd(spec: torch.Tensor, mel_matrix, t_bands=None, f_bands=None) -> torch
 
 
 _IPD_PLANS = {}
+
+
+def _stereo_plan(x: torch.Tensor, w: np.ndarray):
+    """The cached stereo `FrontendPlan` of `mel_ipd` / `mel_whiten` for the device of `x`, its batch and the mel matrix `w`."""
+    b = int(x.shape[0])
+    key = (x.device.index, w.shape, w.tobytes())
+    plan = _IPD_PLANS.get(key)
+    if plan is None or plan.max_batch < b:
+        n_fft = 2 * (w.shape[0] - 1)
+        if n_fft in (256, 512, 1024, 2048):
+            plan = _fe.FrontendPlan(n_fft, None, w.shape[1], 16000, 2, max(b, 1), n_fft, x.device, mel_matrix=w)
+        else:
+            plan = _fe.FrontendPlan.mel_only(w.shape[1], w.shape[0], 2, max(b, 1), x.device, w)
+        _IPD_PLANS[key] = plan
+    return plan
+
+
+def _band_hits(bands, b: int, n: int, who: str) -> torch.Tensor:
+    """bool [B, n]: which of the n indices lie inside one of a sample's (offset, size) bands [B, k, 2]."""
+    bd = torch.as_tensor(bands).to(torch.int64).cpu()
+    if bd.dim() != 3 or bd.shape[0] != b or bd.shape[2] != 2:
+        raise ValueError(f"{who}: bands must have shape [batch={b}, n, 2], got {tuple(bd.shape)}")
+    idx = torch.arange(n)[None, None, :]
+    return ((idx >= bd[:, :, :1]) & (idx < bd[:, :, :1] + bd[:, :, 1:])).any(dim=1)
+
+
+WHITEN_LOADING = 1e-2
+
+
+def mel_whiten(spec: torch.Tensor, mel_matrix, block=None, loading: float = WHITEN_LOADING, log: bool = True,
+               t_bands=None, f_bands=None) -> torch.Tensor:
+    """Spatially whitened mel-band energy: the two-microphone adaptive-matched-filter statistic x^H (R + d I)^-1 x.  spec: a
+    STEREO complex spectrum [B, F, T, 4] (or [F, T, 4]) with last axis (re0, re1, im0, im1); mel_matrix W [F, M].  Frames are
+    grouped into consecutive blocks of `block` frames from frame 0 (None: all T; the last block may be shorter).  Per sample,
+    bin and block, over the block's n frames (unmasked):
+        r00 = mean |X0|^2,  r11 = mean |X1|^2,  r10 = mean X1 conj(X0),  d = loading (r00 + r11) / 2
+        d == 0 (a silent block): a = b = c = 0
+        else l00 = sqrt(r00 + d),  l10 = r10 / l00,  l11 = sqrt(r11 + d - |l10|^2),  a = 1 / l00,  b = 1 / l11,  c = l10 / l00
+    per frame z0 = a X0, z1 = b (X1 - c X0), q = |z0|^2 + |z1|^2, and per band
+        e[m, t] = wnorm[m] sum_k W[k, m] q[k, t],   wnorm[m] = 1 / (2 sum_k W[k, m])   (0 for an all-zero band)
+    Returns e [B, M, T], or ln(e + 1e-8) with `log` (`log_on_mel`'s form).  A frame that holds only the coherent source which
+    dominates R scores about 2 per bin however loud that source is (e about 1); energy from another direction stands out by
+    up to 1 / (1 - coherence).  The mean of e over a block lies in (0, 1], zero frames and silent blocks give exactly 0, and
+    scaling a bin leaves e unchanged (a power of two: the same bits), so a band gain never reaches this channel.
+    t_bands / f_bands ([B, n, 2] (offset, size), optional) act on the OUTPUT only: a frame inside a time band gives e = 0, a
+    bin inside a frequency band adds nothing to the sum, and neither the covariance nor wnorm sees the bands - unlike
+    `mel_ipd`, which zeroes the spectrum first (here that would change R).  On a ROCm tensor this is two HIP launches
+    (`FrontendPlan.whiten`); on a CPU tensor the torch restatement below, in spec's dtype."""
+    w = np.ascontiguousarray(mel_matrix, np.float32)
+    x = spec if spec.dim() == 4 else spec.unsqueeze(0)
+    if x.dim() != 4 or x.shape[-1] != 4 or w.ndim != 2 or x.shape[1] != w.shape[0]:
+        raise ValueError(f"mel_whiten: spec must be [B, F, T, 4] (a stereo complex spectrum) and mel_matrix [F, M]; got "
+                         f"{tuple(spec.shape)} and {w.shape}")
+    b, f, t = (int(v) for v in x.shape[:3])
+    blk = t if block is None else int(block)
+    if blk < 1:
+        raise ValueError(f"mel_whiten: block = {blk} must be at least 1 frame")
+    if not (np.isfinite(loading) and loading > 0):
+        raise ValueError(f"mel_whiten: loading = {loading} must be finite and positive")
+    if x.is_cuda:
+        out = _stereo_plan(x, w).whiten(x.float(), blk, loading, log, t_bands, f_bands)
+        return out if spec.dim() == 4 else out[0]
+    if not torch.is_floating_point(x):
+        x = x.float()
+    blk = max(min(blk, t), 1)
+    j = (t + blk - 1) // blk
+    count = torch.full((j,), blk, dtype=x.dtype)
+    if j:
+        count[-1] = t - (j - 1) * blk
+
+    def block_mean(v):
+        return torch.nn.functional.pad(v, (0, j * blk - t)).reshape(b, f, j, blk).sum(-1) / count
+
+    def per_frame(v):
+        return v.repeat_interleave(blk, dim=-1)[..., :t]
+
+    re0, re1, im0, im1 = x.unbind(-1)
+    r00, r11 = block_mean(re0 * re0 + im0 * im0), block_mean(re1 * re1 + im1 * im1)
+    r_re, r_im = block_mean(re1 * re0 + im1 * im0), block_mean(im1 * re0 - re1 * im0)   # X1 conj(X0)
+    d = loading * (r00 + r11) / 2
+    silent, one, zero = d == 0, torch.ones((), dtype=x.dtype), torch.zeros((), dtype=x.dtype)
+    l00 = torch.sqrt(torch.where(silent, one, r00 + d))
+    l_re, l_im = r_re / l00, r_im / l00
+    l11 = torch.sqrt(torch.where(silent, one, r11 + d - (l_re * l_re + l_im * l_im)))
+    fa, fb, c_re, c_im = (per_frame(torch.where(silent, zero, v)) for v in (1 / l00, 1 / l11, l_re / l00, l_im / l00))
+    z0_re, z0_im = fa * re0, fa * im0
+    z1_re, z1_im = fb * (re1 - (c_re * re0 - c_im * im0)), fb * (im1 - (c_re * im0 + c_im * re0))
+    q = z0_re * z0_re + z0_im * z0_im + z1_re * z1_re + z1_im * z1_im
+    if f_bands is not None:
+        q = torch.where(_band_hits(f_bands, b, f, "mel_whiten")[:, :, None], zero, q)
+    wsum = w.astype(np.float64).sum(axis=0)
+    wnorm = np.divide(0.5, wsum, out=np.zeros_like(wsum), where=wsum != 0)
+    out = torch.einsum('bft,fm->bmt', q, torch.from_numpy(w).to(x.dtype)) * torch.from_numpy(wnorm).to(x.dtype)[None, :, None]
+    if t_bands is not None:
+        out = torch.where(_band_hits(t_bands, b, t, "mel_whiten")[:, None, :], zero, out)
+    if log:
+        out = torch.log(out + 1e-8)
+    return out if spec.dim() == 4 else out[0]
 
 
 def log_magphase(specs: torch.Tensor, labels=None, n_chan: int = 2):

@@ -244,6 +244,43 @@ int iris_spec_ipd(iris_plan* plan, const float* spec, float* out, int batch, int
                   const int32_t* f_bands, int n_f_bands, void* stream);
 
 /*
+ * Spatially whitened mel-band energy (opt-in feature; its own two kernels, k_whiten.h - the mel kernels are untouched): the
+ * two-microphone adaptive-matched-filter statistic x^H (R + d I)^-1 x, which stays near 2 for a frame that holds only the
+ * coherent interferer dominating R, however loud, and rises for energy from any other direction.
+ * spec: a STEREO complex spectrum [batch, n_bins, n_frames, 4] = (re0, re1, im0, im1), as for iris_spec_ipd.  Frames are
+ * grouped into J = ceil(n_frames / block) consecutive blocks of `block` frames from frame 0 (block > n_frames counts as
+ * n_frames; the last block may be shorter).
+ *
+ * iris_spec_whiten_factors: per (sample, bin, block), over the block's n frames,
+ *     r00 = mean |X0|^2,  r11 = mean |X1|^2,  r10 = mean X1 conj(X0),  d = loading (r00 + r11) / 2
+ *     d == 0 (a silent block): a = b = c = 0
+ *     else l00 = sqrt(r00 + d),  l10 = r10 / l00,  l11 = sqrt(r11 + d - |l10|^2),  a = 1 / l00,  b = 1 / l11,  c = l10 / l00
+ * (the Cholesky factor of R + d I, inverted), accumulated and factorised in double and written as (a, b, Re c, Im c) fp32 into
+ * factors [batch, n_bins, J, 4] (caller-provided, 16-byte aligned).  Each of a, b and |c| is within 4 * 2^-24 relative of the
+ * float64 form from the same fp32 spectrum.
+ *
+ * iris_spec_whiten: out [batch, n_mel, n_frames] fp32,
+ *     z0 = a X0,  z1 = b (X1 - c X0),  q = |z0|^2 + |z1|^2,  e[m, t] = wnorm[m] sum_k W[k, m] q[k, t]
+ * with W the plan's mel matrix (any matrix) and wnorm[m] = 1 / (2 sum_k W[k, m]) (0 for an all-zero band); log != 0 writes
+ * ln(e + 1e-8).  The mean of e over a block lies in (0, 1]; zero frames and silent blocks give exactly 0; scaling a bin
+ * leaves e unchanged (by a power of two: the same bits).  fp32 error of e against the float64 form from the same fp32
+ * spectrum: at most (n_m + 16) 2^-24 A[m, t], A = wnorm[m] sum_k W[k, m] (|z0|^2 + ((|X1| + |c| |X0|) b)^2), n_m = non-zero
+ * weights of band m.  t_bands / f_bands ([batch, n, 2] (offset, size)) act on the OUTPUT only: a frame inside a time band gives
+ * e = 0, a bin inside a frequency band adds nothing to the sum; neither the covariance nor wnorm sees them (unlike
+ * iris_spec_ipd, which zeroes the spectrum first: that would change R).
+ *
+ * Refused before any HIP call: NULL pointers (the factor buffer included), empty shapes, block < 1, loading not finite or
+ * <= 0, a bands pointer / count mismatch, spec or factors not 16-byte aligned (IRIS_E_INVALID); a plan whose channel count is
+ * not 2, is_magphase != 0 (IRIS_E_UNSUPPORTED).  One launch each on `stream`, no workspace, no atomics, fixed summation
+ * orders: bitwise reproducible, independent of the batch a sample sits in, capturable.
+ */
+int iris_spec_whiten_factors(iris_plan* plan, const float* spec, float* factors, int batch, int n_frames,
+                             int is_magphase, int block, double loading, void* stream);
+int iris_spec_whiten(iris_plan* plan, const float* spec, const float* factors, float* out, int batch, int n_frames,
+                     int is_magphase, int block, int log, const int32_t* t_bands, int n_t_bands,
+                     const int32_t* f_bands, int n_f_bands, void* stream);
+
+/*
  * minmax + log_on_mel (data_utils.py:37-55; fused twin trainer.py:63-77),
  * in place on x[n_rows, row_len]: per row (x - min) / max(max - min, eps_div)
  * when do_minmax, then ln(x + eps_log) when do_log.  A batched [B,M,T,C] tensor
