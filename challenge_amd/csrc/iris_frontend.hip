@@ -80,6 +80,7 @@
 #include "k_agc_optim.h"
 #include "k_metrics.h"
 #include "k_curves.h"
+#include "k_sedeval.h"
 #include "decode_core.h"
 #include "k_detect.h"
 #include "k_hmm.h"

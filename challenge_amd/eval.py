@@ -1,12 +1,16 @@
 """Drop-in counterpart of the reference's eval.py: score a trained model against sample_answer.json.
 
     python -m challenge_amd.eval --name <run name> [--p] [--path DIR] [--verbose True] [--curves OUT.json [--curve_bins 1024]]
+                                [--sed_eval OUT.json [--sed_thresholds 0.5]]
 
 loads <path>/<name>.pt (this package's checkpoint) - or, for a model trained with the reference, its Keras weights as
 <path>/<name>.npz (scripts/dump_keras_weights.py) - and runs metrics.evaluate on the *.wav files of the working directory.
 `--curves OUT.json` also writes the threshold-free numbers of the files' frame posteriors against the answer's frame labels
 (metrics.ScoreHistogram.compute: ROC-AUC, average precision, best F1 and its threshold, calibration error per class, with the
 macro values) as JSON.
+`--sed_eval OUT.json` writes the segment- and event-based measures of sed_eval / DCASE (metrics.SedEval.compute: 1 s segments;
+200 ms onset collar, offset collar max(200 ms, 50 % of the event); greedy matching per class) of the same posteriors and labels
+at every threshold of `--sed_thresholds`, a comma list (default 0.5).
 `--p` parses model / v / n_mels / n_chan / n_frame out of the run name as eval.py:51-62 does."""
 from __future__ import annotations
 
@@ -83,6 +87,12 @@ def build_args():
                              help='also write ROC-AUC / average precision / best F1 per class and their macro values, from the score '
                                   'histogram of the frame posteriors, to this file')
     config.args.add_argument('--curve_bins', type=int, default=1024)
+    from .sj_train import _sed_thresholds
+    config.args.add_argument('--sed_eval', type=str, default=None, metavar='OUT.json',
+                             help='also write segment-based F1 / ER and event-based F1 / ER (metrics.SedEval) of the frame posteriors '
+                                  'at every threshold of --sed_thresholds to this file')
+    config.args.add_argument('--sed_thresholds', type=_sed_thresholds, default=(0.5,), metavar='THRESHOLDS',
+                             help='comma list of up to 16 increasing thresholds for --sed_eval (default 0.5)')
     return config
 
 
@@ -91,13 +101,18 @@ def main(argv=None):
     if config.p:
         parse_name(config)
     model = load_model(config, config.path)
-    if not config.curves:
+    if not config.curves and not config.sed_eval:
         return evaluate(config, model, verbose=config.verbose)
-    from .metrics import ScoreHistogram
-    hist = ScoreHistogram(3, config.curve_bins)
-    scores = evaluate(config, model, verbose=config.verbose, curves=hist)
-    with open(config.curves, 'w') as f:
-        json.dump(hist.compute(), f, indent=1)
+    from .metrics import ScoreHistogram, SedEval
+    hist = ScoreHistogram(3, config.curve_bins) if config.curves else None
+    sed = SedEval(3, config.sed_thresholds or (0.5,)) if config.sed_eval else None
+    scores = evaluate(config, model, verbose=config.verbose, curves=hist, sed=sed)
+    if hist is not None:
+        with open(config.curves, 'w') as f:
+            json.dump(hist.compute(), f, indent=1)
+    if sed is not None:
+        with open(config.sed_eval, 'w') as f:
+            json.dump(sed.compute(), f, indent=1)
     return scores
 
 

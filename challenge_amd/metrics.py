@@ -391,6 +391,271 @@ def score_curves(bins=1024):
     return _ScoreCurves(bins)
 
 
+# ---------------------------------------------------------------------------
+# segment- and event-based detection measures (Mesaros, Heittola & Virtanen 2016; no counterpart in the reference)
+# ---------------------------------------------------------------------------
+SED_MAX_THRESHOLDS, SED_MAX_CLASSES, SED_MAX_FRAMES = 16, 16, 1 << 20
+
+
+def check_sed_params(thresholds=(0.5,), segment=1.0, collar=0.2, offset_pct=50, sr=16000, hop=256):
+    """-> (thresholds as a tuple of fp32 values, hop, seg_samples, collar_samples, offset_pct), or ValueError: what
+    iris_sed_counts refuses, refused alike for both paths."""
+    try:
+        thr = tuple(float(np.float32(h)) for h in thresholds)
+    except TypeError:
+        raise ValueError(f"sed_eval: thresholds must be a sequence of numbers, got {thresholds!r}") from None
+    if not 1 <= len(thr) <= SED_MAX_THRESHOLDS:
+        raise ValueError(f"sed_eval: 1 .. {SED_MAX_THRESHOLDS} thresholds, got {len(thr)}")
+    if not all(np.isfinite(h) for h in thr) or any(b <= a for a, b in zip(thr, thr[1:])):
+        raise ValueError(f"sed_eval: thresholds must be finite and strictly increasing (as fp32), got {thresholds!r}")
+    if int(offset_pct) != offset_pct or not 0 <= int(offset_pct) <= 100:
+        raise ValueError(f"sed_eval: offset_pct must be an integer in [0, 100], got {offset_pct!r}")
+    hop_i, seg_samples, collar_samples = int(hop), int(round(segment * sr)), int(round(collar * sr))
+    if hop_i != hop or hop_i < 1 or seg_samples < hop_i or collar_samples < 0 or max(seg_samples, collar_samples, hop_i) >= 2 ** 31:
+        raise ValueError(f"sed_eval: hop {hop!r} (an integer >= 1), segment {segment!r} s = {seg_samples} samples (>= hop), collar "
+                         f"{collar!r} s = {collar_samples} samples (>= 0)")
+    return thr, hop_i, seg_samples, collar_samples, int(offset_pct)
+
+
+def _greedy_matches(ref_on, ref_off, pred_on, pred_off, collar_samples, offset_pct) -> int:
+    """Matches of one row's events (onsets / offsets in samples, in time order): every reference event takes the earliest free
+    predicted event within both collars."""
+    taken = [False] * len(pred_on)
+    lo = n = 0
+    for on_r, off_r in zip(ref_on, ref_off):
+        tol = max(100 * collar_samples, offset_pct * (off_r - on_r))
+        while lo < len(pred_on) and (taken[lo] or pred_on[lo] < on_r - collar_samples):
+            lo += 1
+        for q in range(lo, len(pred_on)):
+            if pred_on[q] > on_r + collar_samples:
+                break
+            if not taken[q] and 100 * abs(pred_off[q] - off_r) <= tol:
+                taken[q] = True
+                n += 1
+                break
+    return n
+
+
+def sed_counts_host(y_true: torch.Tensor, y_pred: torch.Tensor, thresholds=(0.5,), segment=1.0, collar=0.2, offset_pct=50,
+                    sr=16000, hop=256) -> torch.Tensor:
+    """The counts [n_thr, K + 1, 6] (int64, on the host) of one batch [B, T, K]: rows k < K hold (seg_tp, seg_fp, seg_fn, ev_tp,
+    ev_fp, ev_fn), row K holds (S, D, I, n_segments, 0, 0) - the CPU path of `SedEval.update` and the rule iris_sed_counts
+    restates (include/iris_frontend.h).  Activities, segments and run ends are torch ops on the tensors' device; the events then
+    go to the host in one copy and are matched there, row by row."""
+    thr, hop, seg_samples, collar_samples, offset_pct = check_sed_params(thresholds, segment, collar, offset_pct, sr, hop)
+    yt = y_true.detach().to(torch.float32)
+    yp = y_pred.detach().to(torch.float32)
+    dev = yp.device
+    b, t, k = yp.shape
+    n = len(thr)
+    levels = torch.tensor(thr, dtype=torch.float32, device=dev)
+    act = torch.cat([(yt >= 0.5)[None], yp[None] >= levels[:, None, None, None]])          # [1 + n, B, T, K]; NaN: False
+    seg = (torch.arange(t, device=dev, dtype=torch.int64) * hop) // seg_samples
+    n_seg = ((t - 1) * hop) // seg_samples + 1
+    seg_act = torch.zeros(1 + n, b, n_seg, k, dtype=torch.int32, device=dev).index_add_(2, seg, act.to(torch.int32)) > 0
+    ref, pred = seg_act[:1], seg_act[1:]
+    out = torch.zeros(n, k + 1, 6, dtype=torch.int64, device=dev)
+    out[:, :k, 0] = (ref & pred).sum((1, 2))
+    out[:, :k, 1] = (~ref & pred).sum((1, 2))
+    out[:, :k, 2] = (ref & ~pred).sum((1, 2))
+    n_fn, n_fp = (ref & ~pred).sum(-1), (~ref & pred).sum(-1)                               # [n, B, n_seg]
+    out[:, k, 0] = torch.minimum(n_fn, n_fp).sum((1, 2))
+    out[:, k, 1] = (n_fn - n_fp).clamp(min=0).sum((1, 2))
+    out[:, k, 2] = (n_fp - n_fn).clamp(min=0).sum((1, 2))
+    out[:, k, 3] = b * n_seg
+    rows = act.permute(0, 1, 3, 2)                                                          # [1 + n, B, K, T]
+    starts, ends = _runs(rows.reshape(1 + n, b * k, t))                                     # (list, row, frame), sorted alike
+    row_id = (starts[:, 0] * (b * k) + starts[:, 1]).cpu().numpy()
+    on = (starts[:, 2] * hop).cpu().tolist()
+    off = ((ends[:, 2] + 1) * hop).cpu().tolist()
+    edge = np.searchsorted(row_id, np.arange((1 + n) * b * k + 1)).tolist()                 # events of (list, row): edge[i] .. edge[i + 1]
+    ev = np.zeros((n, k, 3), np.int64)
+    for r in range(b * k):
+        r0, r1 = edge[r], edge[r + 1]
+        for j in range(n):
+            p0, p1 = edge[(1 + j) * b * k + r], edge[(1 + j) * b * k + r + 1]
+            tp = _greedy_matches(on[r0:r1], off[r0:r1], on[p0:p1], off[p0:p1], collar_samples, offset_pct) if r1 > r0 and p1 > p0 else 0
+            ev[j, r % k] += (tp, p1 - p0 - tp, r1 - r0 - tp)
+    out = out.cpu()
+    out[:, :k, 3:] = torch.from_numpy(ev)
+    return out
+
+
+def _ratio(num, den) -> float:
+    return num / den if den else float('nan')
+
+
+def _prf(tp, fp, fn) -> tuple:
+    return _ratio(tp, tp + fp), _ratio(tp, tp + fn), _ratio(2 * tp, 2 * tp + fp + fn)
+
+
+def sed_metrics(counts, thresholds) -> dict:
+    """Host arithmetic on the counts [n_thr, K + 1, 6] of `SedEval` (integers: NumPy or a tensor; one rank's or the sum over
+    ranks), float64, a zero denominator giving NaN as in `curve_metrics`.  Returns {'thresholds', 'per_threshold': one dict per
+    threshold, 'best_event_f1_threshold', 'best_segment_f1_threshold' (the first threshold with the largest micro F1; NaN if
+    none is defined)}.  Each per-threshold dict holds
+      'segment': micro 'f1' = 2 TP / (2 TP + FP + FN) over the classes with 'precision' and 'recall', 'macro_f1' (the mean over
+                 the classes where F1 is defined), 'er' = (S + D + I) / Nref with Nref = sum_k (seg_tp + seg_fn) and its parts
+                 'substitution_rate', 'deletion_rate', 'insertion_rate', the integers 'n_ref' and 'n_segments', and 'per_class'
+                 {'f1', 'precision', 'recall': [K values]};
+      'event':   micro 'f1', 'precision', 'recall', 'macro_f1', 'er' = (FN + FP) / n_ref, the integers 'n_ref', 'n_pred', and
+                 'per_class' likewise.  Classes are scored independently: no substitutions across classes at event level."""
+    c = np.asarray(counts.detach().cpu() if torch.is_tensor(counts) else counts)
+    if c.ndim != 3 or c.shape[1] < 2 or c.shape[2] != 6 or not np.issubdtype(c.dtype, np.integer) or c.shape[0] != len(thresholds):
+        raise ValueError(f"sed_metrics: integer counts [n_thr = {len(thresholds)}, K + 1, 6], got {c.dtype} {tuple(c.shape)}")
+    k = c.shape[1] - 1
+    per_thr = []
+    for j in range(c.shape[0]):
+        v = [[int(x) for x in row] for row in c[j]]
+        res = {}
+        for name, o in (('segment', 0), ('event', 3)):
+            cls = [_prf(v[i][o], v[i][o + 1], v[i][o + 2]) for i in range(k)]
+            tp, fp, fn = (sum(v[i][o + d] for i in range(k)) for d in range(3))
+            prec, rec, f1 = _prf(tp, fp, fn)
+            res[name] = {'f1': f1, 'precision': prec, 'recall': rec, 'macro_f1': _nanmean([x[2] for x in cls]), 'n_ref': tp + fn,
+                         'per_class': {'precision': [x[0] for x in cls], 'recall': [x[1] for x in cls], 'f1': [x[2] for x in cls]}}
+            if name == 'segment':
+                s, d, i, n_segments = v[k][:4]
+                res[name].update(er=_ratio(s + d + i, tp + fn), substitution_rate=_ratio(s, tp + fn), deletion_rate=_ratio(d, tp + fn),
+                                 insertion_rate=_ratio(i, tp + fn), n_segments=n_segments)
+            else:
+                res[name].update(er=_ratio(fn + fp, tp + fn), n_pred=tp + fp)
+        per_thr.append(res)
+
+    def best(kind):
+        vals = [r[kind]['f1'] for r in per_thr]
+        kept = [x for x in vals if x == x]
+        return float(thresholds[vals.index(max(kept))]) if kept else float('nan')
+    return {'thresholds': [float(h) for h in thresholds], 'per_threshold': per_thr, 'best_event_f1_threshold': best('event'),
+            'best_segment_f1_threshold': best('segment')}
+
+
+class SedEval:
+    """Segment-based (1 s segments: ER, F1) and event-based (200 ms onset collar, offset collar max(200 ms, 50 % of the event):
+    F1, ER) detection counts of everything `update` has seen, at every threshold of `thresholds`: int64 [n_thr, K + 1, 6], one
+    state per device (as `ScoreHistogram`).  On GPU tensors an update is iris_sed_counts - two launches on the current stream,
+    integer adds, no host sync; its workspace is cached per device and stream and grows - on CPU tensors `sed_counts_host`, the same rule.
+    Event matching is greedy in time order and per class (sed_metrics has the ratios)."""
+
+    def __init__(self, n_classes: int, thresholds=(0.5,), segment=1.0, collar=0.2, offset_pct=50, sr=16000, hop=256):
+        self.n_classes = int(n_classes)
+        if not 1 <= self.n_classes <= SED_MAX_CLASSES:
+            raise ValueError(f"SedEval: n_classes in [1, {SED_MAX_CLASSES}], got {n_classes}")
+        self.thresholds, self.hop, self.seg_samples, self.collar_samples, self.offset_pct = \
+            check_sed_params(thresholds, segment, collar, offset_pct, sr, hop)
+        self._host_args = dict(thresholds=self.thresholds, segment=segment, collar=collar, offset_pct=offset_pct, sr=sr, hop=hop)
+        self._levels = (N.C.c_float * len(self.thresholds))(*self.thresholds)
+        self.states: Dict[torch.device, torch.Tensor] = {}
+        self._workspaces: Dict[tuple, torch.Tensor] = {}
+        self._retired: List[torch.Tensor] = []
+
+    def _device(self, device) -> torch.device:
+        device = torch.device(device)
+        if device.type == 'cuda' and device.index is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        return device
+
+    def state(self, device) -> torch.Tensor:
+        device = self._device(device)
+        if device not in self.states:
+            self.states[device] = torch.zeros(len(self.thresholds), self.n_classes + 1, 6, dtype=torch.int64, device=device)
+        return self.states[device]
+
+    def _workspace(self, device, stream: int, n_bytes: int) -> torch.Tensor:
+        """The workspace of (device, stream), at least n_bytes: the launches of one stream are ordered, those of two streams get
+        a workspace each.  A larger one replaces it; the old one is kept while this object lives (launches or a captured graph
+        may still hold its address)."""
+        ws = self._workspaces.get((device, stream))
+        if ws is None or ws.numel() * 4 < n_bytes:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("SedEval.update: the first call for a shape must be eager (warm up before the capture)")
+            if ws is not None:
+                self._retired.append(ws)
+            ws = self._workspaces[(device, stream)] = torch.empty((n_bytes + 3) // 4, dtype=torch.int32, device=device)
+        return ws
+
+    @torch.no_grad()
+    def update(self, y_true: torch.Tensor, y_pred: torch.Tensor) -> None:
+        y_true, y_pred = _first(y_true), _first(y_pred)
+        if y_true.dim() != 3 or y_pred.dim() != 3 or y_true.shape != y_pred.shape:
+            raise ValueError(f"SedEval.update: y_true and y_pred [B, T, K] at the same frame rate, got {tuple(y_true.shape)} "
+                             f"/ {tuple(y_pred.shape)}")
+        if y_pred.shape[2] != self.n_classes:
+            raise ValueError(f"SedEval.update: {y_pred.shape[2]} classes, made for {self.n_classes}")
+        if not (y_true.is_floating_point() and y_pred.is_floating_point()):
+            raise ValueError(f"SedEval.update: floating-point tensors, got {y_true.dtype} / {y_pred.dtype}")
+        if y_true.device != y_pred.device:
+            raise ValueError(f"SedEval.update: y_true on {y_true.device}, y_pred on {y_pred.device}")
+        if y_pred.numel() == 0:
+            return
+        b, t, k = y_pred.shape
+        if t > SED_MAX_FRAMES or b * t > 2 ** 31 - 1:
+            raise ValueError(f"SedEval.update: T {t} (<= 2^20) and B * T {b * t} (<= 2^31 - 1)")
+        st = self.state(y_pred.device)
+        if not y_pred.is_cuda:
+            st += sed_counts_host(y_true, y_pred, **self._host_args)
+            return
+        yt = y_true.detach().to(torch.float32).contiguous()
+        yp = y_pred.detach().to(torch.float32).contiguous()
+        n_bytes = int(N.lib().iris_sed_workspace_bytes(b, t, k, len(self.thresholds), self.hop, self.seg_samples))
+        if n_bytes <= 0:
+            N.check(-1, "iris_sed_workspace_bytes")
+        stream = torch.cuda.current_stream(yp.device).cuda_stream
+        ws = self._workspace(self._device(yp.device), stream, n_bytes)
+        N.check(N.lib().iris_sed_counts(yt.data_ptr(), yp.data_ptr(), b, t, k, self._levels, len(self.thresholds), self.hop,
+                                        self.seg_samples, self.collar_samples, self.offset_pct, ws.data_ptr(), ws.numel() * 4,
+                                        st.data_ptr(), stream), "iris_sed_counts")
+
+    def reset(self) -> None:
+        for s in self.states.values():
+            s.zero_()
+
+    def counts(self) -> torch.Tensor:
+        """The counts on the host, summed over this object's devices."""
+        out = torch.zeros(len(self.thresholds), self.n_classes + 1, 6, dtype=torch.int64)
+        for s in self.states.values():
+            out += s.cpu()
+        return out
+
+    def compute(self) -> dict:
+        return sed_metrics(self.counts(), self.thresholds)
+
+
+SED_NAMES = ('seg_f1', 'seg_er', 'event_f1')   # what `MetricSet.sed_values` adds to a row; `fit` MAXIMISES the two F1, minimises seg_er
+
+
+class _SedEvalMetric:
+    """sed_eval(thresholds, ...): the compiled metric behind val_seg_f1 / val_seg_er / val_event_f1.  A `MetricSet` feeds its
+    `SedEval` in the 'val' phase only and returns no per-step value for it; the state is made by the first batch (its class count)."""
+
+    def __init__(self, thresholds=(0.5,), segment=1.0, collar=0.2, offset_pct=50, sr=16000, hop=256):
+        self.kwargs = dict(thresholds=check_sed_params(thresholds, segment, collar, offset_pct, sr, hop)[0], segment=segment,
+                           collar=collar, offset_pct=offset_pct, sr=sr, hop=hop)
+        self.sed: Optional[SedEval] = None
+        self.__name__ = 'sed_eval'
+
+    def update(self, y_true, y_pred) -> None:
+        y_pred = _first(y_pred)
+        if self.sed is None:
+            self.sed = SedEval(y_pred.shape[-1], **self.kwargs)
+        self.sed.update(y_true, y_pred)
+
+    def reset(self) -> None:
+        if self.sed is not None:
+            self.sed.reset()
+
+    def __call__(self, y_true, y_pred):
+        raise TypeError("sed_eval() has no per-batch value: compile it (model.compile(metrics=[...])) and read "
+                        "MetricSet.sed_values after the validation pass")
+
+
+def sed_eval(thresholds=(0.5,), segment=1.0, collar=0.2, offset_pct=50, sr=16000, hop=256):
+    """A metric for `compile(metrics=[...])`: segment-based F1 / ER and event-based F1 of the validation pass at the FIRST
+    threshold of the list, from on-device integer counts (`fit` logs val_seg_f1, val_seg_er, val_event_f1).  `hop` is the hop of
+    the frames the metric sees - the model's output frames - in samples."""
+    return _SedEvalMetric(thresholds, segment, collar, offset_pct, sr, hop)
+
+
 def _is_cos(m):
     return m is cos_sim or m is _cos_sim_metric
 
@@ -405,7 +670,8 @@ class MetricSet:
     adds to the epoch accumulator of its phase ('train' / 'val'): fp64 [5] = sum er, sum cos, sum f1, clips, batches - zeroed by
     `reset`, read once per epoch by `fit` (Keras' means: per-clip metrics weighted by clips, the scalar F1 by batches).
     A score_curves() in the list (at most one) is fed in the 'val' phase only - one more launch, iris_score_hist - and read with
-    `curve_values`; a 'train'-phase call launches nothing for it, so the captured training step is what it is without it."""
+    `curve_values`; a 'train'-phase call launches nothing for it, so the captured training step is what it is without it.
+    A sed_eval() in the list (at most one) likewise: 'val' phase only - two more launches, iris_sed_counts - read with `sed_values`."""
 
     def __init__(self, metrics):
         self.metrics = list(metrics)
@@ -416,7 +682,11 @@ class MetricSet:
         if len(curves) > 1:
             raise ValueError("MetricSet: at most one score_curves() in a metric list")
         self.curves = curves[0] if curves else None   # fed in the 'val' phase only; no per-step value
-        fused = {id(self.er), id(self.f1), id(self.curves)}
+        seds = [m for m in self.metrics if isinstance(m, _SedEvalMetric)]
+        if len(seds) > 1:
+            raise ValueError("MetricSet: at most one sed_eval() in a metric list")
+        self.sed = seds[0] if seds else None          # likewise
+        fused = {id(self.er), id(self.f1), id(self.curves), id(self.sed)}
         self.others = [m for m in self.metrics if id(m) not in fused and not _is_cos(m)]
         self.names = [metric_name(m) for m in self.metrics]
         dup = sorted({n for n in self.names if self.names.count(n) > 1})
@@ -441,6 +711,8 @@ class MetricSet:
                 a.zero_()
         if self.curves is not None and phase in (None, 'val'):
             self.curves.reset()
+        if self.sed is not None and phase in (None, 'val'):
+            self.sed.reset()
 
     @torch.no_grad()
     def __call__(self, y_true, y_pred, phase: str = 'train') -> Dict[str, torch.Tensor]:
@@ -477,7 +749,29 @@ class MetricSet:
             res[metric_name(m)] = m(y_true, y_pred)
         if self.curves is not None and phase == 'val':   # one iris_score_hist launch on a GPU; the train phase launches nothing
             self.curves.update(y_true, y_pred)
+        if self.sed is not None and phase == 'val':      # two iris_sed_counts launches on a GPU; the train phase launches nothing
+            self.sed.update(y_true, y_pred)
         return {n: res[n] for n in self.names if n in res}
+
+    def sed_values(self, prefix: str = '', all_reduce: bool = False) -> Dict[str, float]:
+        """Row entries of a compiled sed_eval(): {prefix + 'seg_f1', 'seg_er', 'event_f1'} - segment-based micro F1 and ER,
+        event-based micro F1, at the FIRST threshold of its list - from the validation counts, summed over the ranks first with
+        `all_reduce` (int64 SUM: exact, every rank gets the same values), in one copy to the host.  Every rank must have seen a
+        validation batch, or none."""
+        if self.sed is None:
+            return {}
+        sed = self.sed.sed
+        if sed is None or not sed.states:
+            return {prefix + n: float('nan') for n in SED_NAMES}
+        states = list(sed.states.values())
+        total = states[0].clone() if all_reduce or len(states) > 1 else states[0]
+        for s in states[1:]:
+            total += s.to(total.device)
+        if all_reduce:
+            torch.distributed.all_reduce(total)
+        first = sed_metrics(total.cpu(), sed.thresholds)['per_threshold'][0]
+        return {prefix + 'seg_f1': first['segment']['f1'], prefix + 'seg_er': first['segment']['er'],
+                prefix + 'event_f1': first['event']['f1']}
 
     def curve_values(self, prefix: str = '', all_reduce: bool = False) -> Dict[str, float]:
         """Row entries of a compiled score_curves(): {prefix + 'auc', 'map', 'best_f1'} (macro means) from the validation
@@ -589,11 +883,13 @@ def output_to_metric(hop, sr):
 # challenge score                                              metrics.py:14-87
 # ---------------------------------------------------------------------------
 def evaluate(config, model, overlap_hop=512, verbose: bool = False, *, wav_dir: str = '.',
-             answer_path: str = 'sample_answer.json', device=None, curves: Optional["ScoreHistogram"] = None):
+             answer_path: str = 'sample_answer.json', device=None, curves: Optional["ScoreHistogram"] = None,
+             sed: Optional["SedEval"] = None):
     """Per-file ER of `model` on sorted(glob(wav_dir/*.wav)) against answer_path's 'task2_answer' (metrics.py:31-87): the
     frame decisions of inference.predict_frames (smoothed, >= 0.5), then get_start_end_frame -> output_to_metric -> get_er.
     `curves`: a ScoreHistogram that is also fed every file's frame posteriors (the smoothed probabilities, before the 0.5
-    decision) against the `second2frame` labels of the file's answer; the decisions and the scores are what they are without it."""
+    decision) against the `second2frame` labels of the file's answer; the decisions and the scores are what they are without it.
+    `sed`: a SedEval (made for 3 classes at hop 256) fed the same two tensors, one [1, T, K] update per file."""
     from . import data_utils as D
     from .inference import features_for_eval, predict_frames
     with open(answer_path) as f:
@@ -606,13 +902,16 @@ def evaluate(config, model, overlap_hop=512, verbose: bool = False, *, wav_dir: 
     for path in sorted(glob(os.path.join(wav_dir, '*.wav'))):
         spec = D.load_wav(path, device)
         name = os.path.basename(path)[:-4]
-        if curves is None:
+        if curves is None and sed is None:
             preds = predict_frames(model, features_for_eval(spec, config), config, overlap_hop)
         else:
             from .eval import second2frame
             post = predict_frames(model, features_for_eval(spec, config), config, overlap_hop, threshold=False)
             labels = second2frame(answer_gt[name], post.shape[0], sr / hop).to(post.device)
-            curves.update(labels[None], post.to(torch.float32)[None])
+            if curves is not None:
+                curves.update(labels[None], post.to(torch.float32)[None])
+            if sed is not None:
+                sed.update(labels[None], post.to(torch.float32)[None])
             preds = (post >= 0.5).to(torch.float32)   # (predict_frames' own decision)
         cls0, cls1, cls2 = metric.get_start_end_frame(preds.cpu().numpy())
         predict = output_to_metric(hop, sr)(cls0, cls1, cls2)

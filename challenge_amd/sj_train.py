@@ -46,6 +46,26 @@ def _curve_bins(text):
         raise argparse.ArgumentTypeError(str(exc))
 
 
+def _sed_thresholds(text):
+    """--sed_eval: '' (off) or a comma list of strictly increasing thresholds metrics.sed_eval takes."""
+    from .metrics import check_sed_params
+    if not text.strip():
+        return ()
+    try:
+        return check_sed_params(tuple(float(h) for h in text.split(',')))[0]
+    except ValueError as exc:
+        raise argparse.ArgumentTypeError(str(exc))
+
+
+def output_hop(config) -> int:
+    """Samples per OUTPUT frame of the model: the STFT hop of 256 times the label down-sampling of its version (make_dataset)."""
+    if config.v in label_downsample_model:
+        return 256 * 32
+    if config.v == 5:
+        return 256 * (config.n_frame // (config.n_frame * 256 // 16000))
+    return 256
+
+
 def row_names(config) -> list:
     """The entries `main`'s `fit` rows hold besides epoch / lr / time for these flags: what --checkpoint_monitor may name."""
     names = ['loss']
@@ -55,6 +75,9 @@ def row_names(config) -> list:
     if getattr(config, 'curves', 0):
         from .metrics import CURVE_NAMES
         val += ['val_' + n for n in CURVE_NAMES]
+    if getattr(config, 'sed_eval', ()):
+        from .metrics import SED_NAMES
+        val += ['val_' + n for n in SED_NAMES]
     ema = ['val_ema_' + n[len('val_'):] for n in val] if getattr(config, 'ema', 0) else []
     return names + val + ema
 
@@ -64,7 +87,7 @@ class ARGS:
     equivalent for (synthetic data, device, distributed launch)."""
 
     def __init__(self, trainer_flags: bool = True) -> None:
-        """trainer_flags=False: without the flags that only `main` here reads (--curves, --checkpoint_monitor,
+        """trainer_flags=False: without the flags that only `main` here reads (--curves, --sed_eval, --checkpoint_monitor,
         --recordings*), for a tool that extends this parser with flags of its own (`eval`, whose --curves names a file)."""
         self.args = argparse.ArgumentParser()
         a = self.args.add_argument
@@ -145,9 +168,14 @@ class ARGS:
           help='log the threshold-free validation numbers val_auc (macro ROC-AUC), val_map (macro average precision) and '
                'val_best_f1 (best frame F1 over thresholds) from an on-device score histogram with BINS bins (a power of two in '
                '[16, 4096]; metrics.score_curves, one more launch per validation batch); 0 (default): off.  Not part of the run name')
+        a('--sed_eval', type=_sed_thresholds, default=(), metavar='THRESHOLDS',
+          help='log the detection measures of sed_eval / DCASE on the validation pass - val_seg_f1, val_seg_er (1 s segments), '
+               'val_event_f1 (200 ms onset collar, offset collar max(200 ms, 50 %% of the event)) at the FIRST threshold of this comma '
+               'list of up to 16 increasing thresholds, e.g. 0.5 - from on-device integer counts (metrics.sed_eval, two more launches '
+               'per validation batch); empty (default): off.  Not part of the run name')
         a('--checkpoint_monitor', type=str, default=None, metavar='NAME',
-          help="the row entry the checkpoint follows, e.g. val_map (auc / map / best_f1 are maximised, everything else "
-               "minimised); default: val_er with --metrics reference, else val_loss")
+          help="the row entry the checkpoint follows, e.g. val_map or val_event_f1 (auc / map / best_f1 / seg_f1 / event_f1 are "
+               "maximised, everything else minimised); default: val_er with --metrics reference, else val_loss")
         a('--recordings', type=str, default=None, metavar='DIR',
           help='--online_stft only.  Cut a share of every training batch from the labelled recordings DIR/*.wav '
                '(recordings.load_recordings: resampled to 16 kHz, scaled as load_wav scales a file) - random windows, drawn and '
@@ -864,6 +892,9 @@ def main(argv=None):
     if config.curves:   # with --metrics none the only metric
         from .metrics import score_curves
         metrics = (metrics or []) + [score_curves(config.curves)]
+    if config.sed_eval:
+        from .metrics import sed_eval
+        metrics = (metrics or []) + [sed_eval(config.sed_eval, hop=output_hop(config))]
     if config.checkpoint_monitor is not None:
         monitor = config.checkpoint_monitor
     ema = None
@@ -877,6 +908,9 @@ def main(argv=None):
         if config.curves:   # (and a histogram of its own)
             from .metrics import score_curves
             own = (own or []) + [score_curves(config.curves)]
+        if config.sed_eval:   # (and counts of its own)
+            from .metrics import sed_eval
+            own = (own or []) + [sed_eval(config.sed_eval, hop=output_hop(config))]
         ema.compile(loss, metrics=own)
     model.compile(opt, loss, clipvalue=None if config.no_clipvalue_after_agc else config.clipvalue,
                   ddp=wrap_ddp(model, device, world), metrics=metrics, ema=ema)

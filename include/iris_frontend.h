@@ -499,6 +499,35 @@ int iris_score_hist(const float* y_true, const float* y_pred, int batch, int n_t
                     long long* counts, void* stream);
 
 /*
+ * Segment- and event-based detection counts of one batch (Mesaros, Heittola & Virtanen 2016: the measures sed_eval reports) at
+ * n_thr thresholds, TWO launches on `stream`, capturable, no host synchronisation and no allocation; ratios are host arithmetic.
+ *   y_true, y_pred [B, T, K] fp32 contiguous, DEVICE, at the same frame rate; 1 <= K <= 16, T <= 2^20, B * T <= 2^31 - 1.
+ *   thresholds     [n_thr] fp32, HOST, finite and strictly increasing, 1 <= n_thr <= 16 (read before the launches).
+ *   Label activity is y_true >= 0.5f, predicted activity at threshold h is y_pred >= h in fp32; a NaN is inactive.
+ *   Segments: frame f of a clip lies in segment (f * hop) / seg_samples (segments restart with every clip; a partial last one
+ *     counts); a class is active in a segment if any of its frames is.  Per (threshold, class) tp / fp / fn over all segments;
+ *     per (threshold, segment) with Nfn / Nfp the classes active in the labels / the prediction only: S = min(Nfn, Nfp),
+ *     D = max(0, Nfn - Nfp), I = max(0, Nfp - Nfn).
+ *   Events: maximal runs [s, e] of active frames of one (clip, class) row (a run open at the end closes at T - 1); onset s * hop,
+ *     offset (e + 1) * hop, length (e + 1 - s) * hop samples, 64-bit.  A predicted event p may match a reference event r of its
+ *     row if |on_p - on_r| <= collar_samples and 100 |off_p - off_r| <= max(100 collar_samples, offset_pct * len_r).  Reference
+ *     events in time order each take the earliest still free predicted event that may match them (greedy, not an optimal
+ *     assignment).  ev_tp the matches, ev_fp = n_pred - ev_tp, ev_fn = n_ref - ev_tp; classes are scored independently.
+ *   counts         [n_thr][K + 1][6] int64, DEVICE, CUMULATIVE (the caller zeroes it): rows k < K hold (seg_tp, seg_fp, seg_fn,
+ *                  ev_tp, ev_fp, ev_fn), row K holds (S, D, I, n_segments, 0, 0).
+ *   workspace      DEVICE, 4-byte aligned, at least iris_sed_workspace_bytes(...) bytes (0 for a shape that is refused); its
+ *                  contents are scratch, rewritten by every call: calls that share one must be ordered on one stream.
+ * Integer adds only: independent of the order, bitwise reproducible, and the counts of several ranks sum exactly.
+ * Refused before any HIP call: NULL pointers, B / T / K < 1, n_thr outside [1, 16], thresholds not finite or not increasing,
+ * hop < 1, seg_samples < hop, collar_samples < 0, offset_pct outside [0, 100], a misaligned or too small workspace (INVALID);
+ * K > 16, T > 2^20, B * T > 2^31 - 1 (UNSUPPORTED).
+ */
+long long iris_sed_workspace_bytes(int batch, int n_time, int n_classes, int n_thr, int hop, int seg_samples);
+int iris_sed_counts(const float* y_true, const float* y_pred, int batch, int n_time, int n_classes, const float* thresholds,
+                    int n_thr, int hop, int seg_samples, int collar_samples, int offset_pct, void* workspace,
+                    size_t workspace_bytes, long long* counts, void* stream);
+
+/*
  * Window predictions of F files -> event lists (metrics.py:56-81 from the model's outputs on, then get_start_end_frame,
  * metrics.py:111-137), two launches, capturable:
  *   preds      [W_total, n_out, K] fp32, DEVICE: the model's outputs for every window of every file, file after file
