@@ -1375,8 +1375,99 @@ def speed_perturb_batch(waves, rates):
     return results
 
 
+# mirrors iris_gate_rec (include/iris_frontend.h)
+GATE_REC = np.dtype([("src", "<u8"), ("dst", "<u8"), ("mask", "<u8"), ("energy", "<u8"), ("len", "<i4"), ("reserved", "<i4")])
+assert GATE_REC.itemsize == 40
+GATE_MAX_FRAMES = 131072   # IRIS_GATE_MAX_FRAMES: frames per record (35 minutes at hop 256 and 16 kHz)
+_LAUNCH_RECORDS = 65535    # records per launch (a grid dimension)
+
+
+def gate_ratio(range_db: float) -> float:
+    """10^(-range_db / 10) in double, for range_db in (0, 200]: the share of a clip's peak frame energy below which a frame is
+    silent."""
+    range_db = float(range_db)
+    if not 0.0 < range_db <= 200.0:
+        raise ValueError(f"activity gate: range_db = {range_db} is outside (0, 200]")
+    return 10.0 ** (-range_db / 10.0)
+
+
+def check_gate_settings(hop, range_db, floor, min_gap, min_event, hang) -> None:
+    """ValueError for gate settings outside their ranges (host only: nothing touches the device)."""
+    gate_ratio(range_db)
+    for name, value, low in (("hop", hop, 1), ("min_gap", min_gap, 0), ("min_event", min_event, 1), ("hang", hang, 0)):
+        if int(value) != value or not low <= int(value) <= 2 ** 31 - 1:
+            raise ValueError(f"activity gate: {name} = {value!r} must be an integer >= {low}")
+    if not float(floor) >= 0.0:
+        raise ValueError(f"activity gate: floor = {floor!r} must be >= 0")
+
+
+def activity_gate_launch(table: np.ndarray, channels: int, hop: int, min_gap: int, min_event: int, hang: int, ratio: float,
+                         floor: float, max_len: int, device: torch.device, table_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Upload a GATE_REC table (into `table_dev`, a long-lived uint8 device buffer, when given) and run iris_activity_gate over
+    it on the current stream: three launches.  Returns the device table (tied to the stream when it was allocated here)."""
+    return _launch_records(table, device, table_dev, "iris_activity_gate", lambda ptr, n, stream: N.lib().iris_activity_gate(
+        ptr, n, int(channels), int(hop), int(min_gap), int(min_event), int(hang), float(ratio), float(floor), int(max_len), stream))
+
+
+def activity_gate_batch(waves, hop: int = 256, range_db: float = 40.0, floor: float = 0.0, min_gap: int = 12, min_event: int = 6,
+                        hang: int = 1, out=None):
+    """Gate a ragged batch of waveforms (iris_activity_gate, three launches per 65535 records): waves is a list of [C, L_i]
+    float32 tensors on one ROCm device (equal C).  Per waveform, with T = 1 + L // hop frames and frame t owning the samples s
+    with min((s + hop // 2) // hop, T - 1) == t: the frame energies E (sum of squares over channels and samples, in double);
+    m0 = E >= max(max(E) * 10^(-range_db / 10), floor) and E > 0; runs of zeros of at most `min_gap` frames between ones are
+    closed, runs of ones shorter than `min_event` dropped, and what is left widened by `hang` frames a side.  Returns (gated,
+    masks, energies): lists of [C, L_i] float32 (the samples of active frames bit for bit, +0.0 elsewhere), uint8 [T_i] and
+    float64 [T_i] tensors (views of one buffer per kind).  out: a list of contiguous [C, L_i] float32 tensors on the device
+    that receive the gated waveforms; out=waves gates in place (every energy is read before anything is written).  The
+    defaults (40 dB under the clip's loudest frame, 12 / 6 / 1 frames of 16 ms) are choices, not measurements.  At most 131072
+    frames per waveform.  CPU tensors raise: there is no CPU fallback."""
+    waves = list(waves)
+    check_gate_settings(hop, range_db, floor, min_gap, min_event, hang)
+    ratio, hop = gate_ratio(range_db), int(hop)
+    if out is not None and len(out) != len(waves):
+        raise ValueError(f"activity_gate_batch: {len(waves)} waveforms but {len(out)} outputs")
+    if not waves:
+        return [], [], []
+    if out is not None:   # (an output must be the caller's own memory: no contiguous copy is made of it)
+        for i, (o, w) in enumerate(zip(out, waves)):
+            if not (isinstance(o, torch.Tensor) and o.is_cuda and o.dtype == torch.float32 and o.is_contiguous()
+                    and isinstance(w, torch.Tensor) and o.shape == w.shape and o.device == w.device):
+                raise ValueError(f"activity_gate_batch: out[{i}] must be a contiguous float32 tensor of waves[{i}]'s shape on its device")
+    waves = [_require_device_f32(w, f"waves[{i}]") for i, w in enumerate(waves)]
+    dev = waves[0].device
+    if waves[0].dim() != 2:
+        raise ValueError("activity_gate_batch: every waveform must be [chan, samples]")
+    chan = int(waves[0].shape[0])
+    for i, w in enumerate(waves):
+        if w.dim() != 2 or int(w.shape[0]) != chan or w.device != dev or int(w.shape[1]) < 1 or chan < 1:
+            raise ValueError(f"activity_gate_batch: waves[{i}] has shape {tuple(w.shape)} on {w.device}; expected "
+                             f"[{chan} >= 1, L >= 1] on {dev}")
+        if int(w.shape[1]) > 2 ** 31 - 1 or 1 + int(w.shape[1]) // hop > GATE_MAX_FRAMES:
+            raise ValueError(f"activity_gate_batch: waves[{i}] has {int(w.shape[1])} samples: {1 + int(w.shape[1]) // hop} frames at "
+                             f"hop {hop} (> {GATE_MAX_FRAMES})")
+    lens = np.array([int(w.shape[1]) for w in waves], np.int64)
+    frames = 1 + lens // hop
+    masks = list(torch.empty(int(frames.sum()), dtype=torch.uint8, device=dev).split(frames.tolist()))
+    energies = list(torch.empty(int(frames.sum()), dtype=torch.float64, device=dev).split(frames.tolist()))
+    if out is None:
+        flat = torch.empty(int(lens.sum()) * chan, dtype=torch.float32, device=dev)
+        gated = [g.view(chan, -1) for g in flat.split((lens * chan).tolist())]
+    else:
+        gated = list(out)
+    table = np.zeros(len(waves), GATE_REC)
+    table["src"], table["dst"] = [w.data_ptr() for w in waves], [g.data_ptr() for g in gated]
+    table["mask"], table["energy"] = [m.data_ptr() for m in masks], [e.data_ptr() for e in energies]
+    table["len"] = lens
+    for first in range(0, len(waves), _LAUNCH_RECORDS):
+        part = table[first:first + _LAUNCH_RECORDS]
+        activity_gate_launch(part, chan, hop, min_gap, min_event, hang, ratio, floor, int(part["len"].max()), dev)
+    for w in waves:   # (a contiguous copy made above must outlive the kernels)
+        w.record_stream(torch.cuda.current_stream(dev))
+    return gated, masks, energies
+
+
 # mirrors iris_fir_src (include/iris_frontend.h)
-FIR_SRC = np.dtype([("src", "<u8"), ("dst", "<u8"), ("taps", "<u8"), ("len", "<i4"), ("n_taps", "<i4")])
+FIR_SRC =np.dtype([("src", "<u8"), ("dst", "<u8"), ("taps", "<u8"), ("len", "<i4"), ("n_taps", "<i4")])
 assert FIR_SRC.itemsize == 32
 FIR_MAX_TAPS = 4096   # the longest impulse response `fir_batch` and the mixers take (a quarter of a second at 16 kHz)
 

@@ -136,10 +136,23 @@ class ARGS:
         a('--online_stft', action='store_true',
           help='keep (synthetic) waveform corpora on the device, mix them before the STFT (WaveMixer) and run the '
                'fused HIP frontend on line instead of mixing pre-computed spectra (make_wave_dataset)')
-        a('--wave_corpus', type=str, default='synthetic', choices=['synthetic', 'pickles'],
+        a('--wave_corpus', type=str, default='synthetic', choices=['synthetic', 'pickles', 'wavs'],
           help="--online_stft only.  'synthetic' (default): synthetic waveform corpora.  'pickles': the pickled SPECTRUM corpora "
                "(or their --synthetic stand-ins) are inverted to waveforms once at start-up (waves_from_specs: one iris_istft "
-               "launch per corpus list) and mixed from there")
+               "launch per corpus list) and mixed from there.  'wavs': folders of wav files under --corpus_dir "
+               "(corpus.load_wav_corpus), the voices passed through the activity gate")
+        a('--corpus_dir', type=str, default=None, metavar='ROOT',
+          help="--online_stft --wave_corpus wavs only.  ROOT/train and ROOT/test each hold backgrounds/*.wav and voices/<class>/*.wav "
+               "(classes 0, 1, 2); ROOT/train/noises/*.wav is optional and serves both.  Resampled to 16 kHz and scaled as load_wav "
+               "scales a file.  Not part of the run name")
+        a('--gate_range_db', type=float, default=40.0, metavar='DB',
+          help='the activity gate of the voices of --corpus_dir (iris_activity_gate): a frame of 256 samples is speech when its '
+               'energy is within DB of the loudest frame of its clip; the samples of the other frames become exact zeros, which is '
+               'what the mixer labels as silence (default 40; a choice, not a measurement)')
+        a('--gate_min_gap', type=int, default=12, metavar='FRAMES', help='pauses of up to FRAMES frames inside speech stay active (default 12)')
+        a('--gate_min_event', type=int, default=6, metavar='FRAMES', help='bursts shorter than FRAMES frames are dropped (default 6)')
+        a('--gate_hang', type=int, default=1, metavar='FRAMES', help='what is left is widened by FRAMES frames a side (default 1)')
+        a('--no_gate', action='store_true', help='--corpus_dir holds voices that are already zeroed outside speech: do not gate them')
         a('--per_sample_pipeline', action='store_true',
           help='build samples one at a time with the tf.data-shaped graph (make_dataset) instead of the '
                'batched on-device synthesis (make_device_dataset), which is the default on a GPU')
@@ -198,6 +211,17 @@ class ARGS:
         monitor = getattr(config, 'checkpoint_monitor', None)
         if monitor is not None and monitor not in row_names(config):
             raise ValueError(f"--checkpoint_monitor {monitor!r}: the rows of this run will hold {row_names(config)}")
+        if config.wave_corpus == 'wavs' or config.corpus_dir is not None:
+            if config.corpus_dir is None:
+                raise ValueError("--wave_corpus wavs needs --corpus_dir ROOT (ROOT/train and ROOT/test: backgrounds/*.wav, "
+                                 "voices/<class>/*.wav)")
+            if config.wave_corpus != 'wavs':
+                raise ValueError(f"--corpus_dir {config.corpus_dir!r} is read by --wave_corpus wavs only (got --wave_corpus "
+                                 f"{config.wave_corpus})")
+            if not config.online_stft:
+                raise ValueError("--wave_corpus wavs --corpus_dir mixes waveforms and needs the waveform path: add --online_stft")
+            if not config.no_gate:   # (the gate's ranges, before any file is read)
+                _fe.check_gate_settings(256, config.gate_range_db, 0.0, config.gate_min_gap, config.gate_min_event, config.gate_hang)
         if getattr(config, 'rirs', None) is not None:
             if not config.online_stft:
                 raise ValueError("--rirs reverberates the waveform corpus and needs the waveform path: add --online_stft")
@@ -953,11 +977,23 @@ def main(argv=None):
         if config.rirs is not None:   # loaded once per rank (the corpora are stereo); files up to 1.024 s are kept whole
             from .transforms import load_rirs
             rirs = load_rirs(config.rirs, 2, max_taps=RIR_MAX_TAPS)
+        def wav_sources(split, wanted=True):
+            """--wave_corpus wavs: ROOT/<split> as waveforms, the voices gated (each rank loads for itself)."""
+            if config.wave_corpus != 'wavs' or not wanted:
+                return None
+            from .corpus import GateSettings, load_wav_corpus
+            gate = None if config.no_gate else GateSettings(range_db=config.gate_range_db, min_gap=config.gate_min_gap,
+                                                            min_event=config.gate_min_event, hang=config.gate_hang)
+            *sources, report = load_wav_corpus(config.corpus_dir, split, device, 3, gate)
+            if rank == 0:
+                print('corpus', report)
+            return tuple(sources)
         train_set = make_wave_dataset(config, training=True, device=device, seed=1000 + rank, device_draw=dd,
+                                      sources=wav_sources('train', synthetic_part),
                                       spec_sources=spec_sources(True) if synthetic_part else None, recordings=recordings,
                                       recordings_share=config.recordings_share, rirs=rirs)
         test_set = make_wave_dataset(config, training=False, device=device, seed=2000 + rank, device_draw=dd,
-                                     spec_sources=spec_sources(False))
+                                     sources=wav_sources('test'), spec_sources=spec_sources(False))
     elif device.type == 'cuda' and not config.per_sample_pipeline:
         # corpora resident in HBM, whole batches synthesised on the device (each rank draws its own stream)
         dd = not config.host_draws

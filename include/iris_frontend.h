@@ -1108,6 +1108,44 @@ int iris_mix_wave_frame_active_batch(const void* table_dev, int n_src, int chann
                                      const void* active_ptrs_dev, int max_frames, void* stream);
 
 /*
+ * Activity gate of a waveform corpus: per frame, is the voice speaking?  The samples of the other frames become exact zeros,
+ * so that the mixers' label rule (iris_mix_wave_frame_active: a frame is active when any sample under its window is non-zero)
+ * means something on clips that hold no exact zeros of their own.  A RAGGED BATCH of waveforms in three launches.
+ * Per record: src DEVICE [channels, len] fp32 (contiguous, len >= 1), and with h2 = hop / 2, T = 1 + len / hop (the mixers'
+ * frame count) and owner(s) = min((s + h2) / hop, T - 1):
+ *   1. E[t] = sum_c sum_{s: owner(s) = t} (double)x[c, s]^2, accumulated in double (the products are exact); a frame that
+ *      owns no sample has E = 0.  The order of the sum does not depend on the record's address.
+ *   2. P = the maximum of the E[t] that are not NaN, 0 if there are none; thr = max(P * ratio, floor);
+ *      m0[t] = (E[t] >= thr) && (E[t] > 0).  Comparisons are false on NaN; +inf follows IEEE.
+ *   3. close: every maximal run of zeros of m0 of length <= min_gap with a one on both sides becomes ones (m1)
+ *   4. drop:  every maximal run of ones of m1 shorter than min_event becomes zeros (m2)
+ *   5. hang:  m[t] = OR of m2[u] over |u - t| <= hang, clipped to [0, T)
+ *   6. dst[c, s] = src[c, s] bit for bit where m[owner(s)] is set, +0.0f elsewhere
+ * Outputs per record: dst DEVICE [channels, len] (floats beyond are not written), mask DEVICE uint8 [T] (m), energy DEVICE
+ * double [T] (E; 8-byte aligned).  dst == src gates in place: every energy is read before anything is written.  Otherwise
+ * the buffers of a record, and of different records, must not overlap.  Rows need no alignment.
+ *   ratio    10^(-range_db / 10), formed in double by the caller: in (0, 1)
+ *   floor    an absolute energy below which no frame is active: >= 0
+ *   max_len  the largest len of the table (it sizes the grids): a record with len <= 0, len > max_len or a NULL pointer is
+ *            skipped (nothing written) - the table lives on the device and cannot be checked here without a synchronisation
+ * Frames per record: at most IRIS_GATE_MAX_FRAMES = 131072 (the masks of steps 2 - 5 are bit words in LDS), checked here
+ * through max_len (IRIS_E_UNSUPPORTED), as is n > 65535.  Checked before any HIP call (IRIS_E_INVALID): a NULL table, n <= 0,
+ * channels <= 0, hop < 1, min_gap < 0, min_event < 1, hang < 0, ratio outside (0, 1), floor < 0 or NaN, max_len <= 0.
+ * Three launches on `stream`; no workspace, no atomics, no synchronisation: capturable, bitwise reproducible, and a record's
+ * result does not depend on the records around it.  Runs on the current HIP device.
+ */
+#define IRIS_GATE_MAX_FRAMES 131072
+typedef struct {
+    const float* src;      /* DEVICE [channels, len] */
+    float*       dst;      /* DEVICE [channels, len]; may be src */
+    uint8_t*     mask;     /* DEVICE [1 + len / hop] */
+    double*      energy;   /* DEVICE [1 + len / hop] */
+    int32_t      len, reserved;
+} iris_gate_rec;
+int iris_activity_gate(const void* table_dev, int n, int channels, int hop, int min_gap, int min_event, int hang, double ratio,
+                       double floor, int max_len, void* stream);
+
+/*
  * Reverberation of waveforms (Ko et al., ICASSP 2017; Kaldi's reverberate_data_dir): a RAGGED BATCH of waveforms, each channel
  * convolved with its own impulse response, in one launch - a direct-form FIR in fp32.
  * Per record: src DEVICE [channels, len] fp32, taps DEVICE [channels, n_taps] fp32, dst DEVICE [channels, len] (contiguous;
