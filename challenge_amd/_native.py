@@ -54,6 +54,8 @@ SIGNATURES = {
     "iris_score_hist": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "iris_sed_workspace_bytes": (C.c_longlong, [_i, _i, _i, _i, _i, _i]),
     "iris_sed_counts": (_i, [_vp, _vp, _i, _i, _i, _fp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    "iris_psds_workspace_bytes": (C.c_longlong, [_i, _i, _i, _i]),
+    "iris_psds_counts": (_i, [_vp, _vp, _i, _i, _i, _fp, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "iris_decode_events": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "iris_decode_sweep": (_i, [_vp] * 5 + [_i] * 5 + [_vp] * 6 + [_i] + [_vp] * 3 + [_i, _i] + [_vp] * 4),
     "iris_decode_hmm_workspace_len": (C.c_longlong, [_vp, _i, _i]),

@@ -30,6 +30,7 @@
 //   k_conv_wino_wrw.h  the same layers' weight gradient as Winograd F(2x2, 3x3) on the fp32 matrix cores (training)
 //   k_metrics.h      the training metrics er_score / cos_sim / F1 counts of a batch in one launch
 //   k_curves.h       the validation score histogram per (class, label): integer counts behind ROC-AUC / average precision / best F1
+//   k_psds.h         intersection-based detection counts at up to 64 thresholds behind the polyphonic sound detection score (two launches)
 //   decode_core.h    the event decoder's arithmetic (overlap-add average, smoothing, dilation, run boundaries), written once
 //   k_detect.h       window predictions of many files -> smoothed, thresholded event lists (two launches)
 //   k_hmm.h          the opt-in other decoder: a two-state HMM per class, exact integer Viterbi as a (max, +) scan along time (two
@@ -83,6 +84,7 @@
 #include "k_metrics.h"
 #include "k_curves.h"
 #include "k_sedeval.h"
+#include "k_psds.h"
 #include "decode_core.h"
 #include "k_detect.h"
 #include "k_hmm.h"

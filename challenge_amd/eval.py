@@ -1,7 +1,7 @@
 """Drop-in counterpart of the reference's eval.py: score a trained model against sample_answer.json.
 
     python -m challenge_amd.eval --name <run name> [--p] [--path DIR] [--verbose True] [--curves OUT.json [--curve_bins 1024]]
-                                [--sed_eval OUT.json [--sed_thresholds 0.5]]
+                                [--sed_eval OUT.json [--sed_thresholds 0.5]] [--psds OUT.json [--psds_scenario 1,2]]
 
 loads <path>/<name>.pt (this package's checkpoint) - or, for a model trained with the reference, its Keras weights as
 <path>/<name>.npz (scripts/dump_keras_weights.py) - and runs metrics.evaluate on the *.wav files of the working directory.
@@ -11,6 +11,8 @@ macro values) as JSON.
 `--sed_eval OUT.json` writes the segment- and event-based measures of sed_eval / DCASE (metrics.SedEval.compute: 1 s segments;
 200 ms onset collar, offset collar max(200 ms, 50 % of the event); greedy matching per class) of the same posteriors and labels
 at every threshold of `--sed_thresholds`, a comma list (default 0.5).
+`--psds OUT.json` writes the polyphonic sound detection score (metrics.Psds.compute: intersection criteria, 50 thresholds) of the
+same posteriors and labels under every scenario of `--psds_scenario`, a comma list of 1 and 2 (default both), as {scenario: result}.
 `--p` parses model / v / n_mels / n_chan / n_frame out of the run name as eval.py:51-62 does."""
 from __future__ import annotations
 
@@ -76,6 +78,17 @@ def load_model(config, path: str = '', device=None):
     return model
 
 
+class _PsdsFanOut:
+    """One criteria set per launch: two scenarios are two Psds objects, fed the same tensors."""
+
+    def __init__(self, scored):
+        self.scored = scored
+
+    def update(self, y_true, y_pred):
+        for p in self.scored:
+            p.update(y_true, y_pred)
+
+
 def build_args():
     """The trainer's flags (the model is described by them) plus this tool's own."""
     from .sj_train import ARGS
@@ -93,7 +106,23 @@ def build_args():
                                   'at every threshold of --sed_thresholds to this file')
     config.args.add_argument('--sed_thresholds', type=_sed_thresholds, default=(0.5,), metavar='THRESHOLDS',
                              help='comma list of up to 16 increasing thresholds for --sed_eval (default 0.5)')
+    config.args.add_argument('--psds', type=str, default=None, metavar='OUT.json',
+                             help='also write the polyphonic sound detection score (metrics.Psds) of the frame posteriors under every '
+                                  'scenario of --psds_scenario to this file')
+    config.args.add_argument('--psds_scenario', type=_psds_scenarios, default=(1, 2), metavar='SCENARIOS',
+                             help='comma list of DCASE scenarios (1, 2) for --psds (default 1,2)')
     return config
+
+
+def _psds_scenarios(text):
+    import argparse
+    try:
+        out = tuple(int(v) for v in text.split(','))
+    except ValueError:
+        out = ()
+    if not out or any(v not in (1, 2) for v in out) or len(set(out)) != len(out):
+        raise argparse.ArgumentTypeError(f"--psds_scenario: a comma list of distinct scenarios out of 1, 2, got {text!r}")
+    return out
 
 
 def main(argv=None):
@@ -101,18 +130,22 @@ def main(argv=None):
     if config.p:
         parse_name(config)
     model = load_model(config, config.path)
-    if not config.curves and not config.sed_eval:
+    if not config.curves and not config.sed_eval and not config.psds:
         return evaluate(config, model, verbose=config.verbose)
-    from .metrics import ScoreHistogram, SedEval
+    from .metrics import Psds, ScoreHistogram, SedEval
     hist = ScoreHistogram(3, config.curve_bins) if config.curves else None
     sed = SedEval(3, config.sed_thresholds or (0.5,)) if config.sed_eval else None
-    scores = evaluate(config, model, verbose=config.verbose, curves=hist, sed=sed)
+    scored = [Psds(3, sc) for sc in config.psds_scenario] if config.psds else []
+    scores = evaluate(config, model, verbose=config.verbose, curves=hist, sed=sed, psds=_PsdsFanOut(scored) if scored else None)
     if hist is not None:
         with open(config.curves, 'w') as f:
             json.dump(hist.compute(), f, indent=1)
     if sed is not None:
         with open(config.sed_eval, 'w') as f:
             json.dump(sed.compute(), f, indent=1)
+    if scored:
+        with open(config.psds, 'w') as f:
+            json.dump({str(sc): p.compute() for sc, p in zip(config.psds_scenario, scored)}, f, indent=1)
     return scores
 
 

@@ -412,8 +412,8 @@ def graph_step_possible(model: "CustomModel") -> bool:
 
 def monitor_maximised(name: Optional[str]) -> bool:
     """Is a row entry better when LARGER?  The threshold-free validation numbers of a compiled score_curves() - 'auc', 'map',
-    'best_f1' behind 'val_' / 'val_ema_' - are, and so are 'seg_f1' and 'event_f1' of a compiled sed_eval(); every other name
-    (losses, er, seg_er, ...) keeps Keras' mode min."""
+    'best_f1' behind 'val_' / 'val_ema_' - are, and so are 'seg_f1' and 'event_f1' of a compiled sed_eval() and 'psds' of a compiled
+    psds(); every other name (losses, er, seg_er, ...) keeps Keras' mode min."""
     if not name:
         return False
     for prefix in ('val_ema_', 'val_'):
@@ -421,7 +421,7 @@ def monitor_maximised(name: Optional[str]) -> bool:
             name = name[len(prefix):]
             break
     from .metrics import CURVE_NAMES
-    return name in CURVE_NAMES or name in ('seg_f1', 'event_f1')   # (a compiled sed_eval(): its 'seg_er' is minimised)
+    return name in CURVE_NAMES or name in ('seg_f1', 'event_f1', 'psds')   # (a compiled sed_eval(): its 'seg_er' is minimised)
 
 
 def fit(model: CustomModel, train_set, epochs, steps_per_epoch, validation_data=None, validation_steps=16,
@@ -450,7 +450,8 @@ def fit(model: CustomModel, train_set, epochs, steps_per_epoch, validation_data=
     pass, from the validation histogram summed over the ranks; a `checkpoint_monitor` with such a name is MAXIMISED (strictly
     larger saves), and so is the EMA's twin of it.
     A compiled metrics.sed_eval() adds 'val_seg_f1', 'val_seg_er', 'val_event_f1' (and their 'val_ema_' twins) in the same way, from
-    the validation counts summed over the ranks; as monitors the two F1 are maximised, seg_er is minimised."""
+    the validation counts summed over the ranks; as monitors the two F1 are maximised, seg_er is minimised.
+    A compiled metrics.psds() adds 'val_psds' (and 'val_ema_psds') likewise; as a monitor it is maximised."""
     best, bad, history = math.inf, 0, []
     ckpt_sign = -1.0 if monitor_maximised(checkpoint_monitor) else 1.0   # best_ckpt / best_ema hold sign * value: smaller is better
     best_ckpt = math.inf
@@ -566,6 +567,8 @@ def fit(model: CustomModel, train_set, epochs, steps_per_epoch, validation_data=
                     row.update(ms.curve_values('val_', all_reduce=coll))
                 if ms.sed is not None:
                     row.update(ms.sed_values('val_', all_reduce=coll))
+                if ms.psds is not None:
+                    row.update(ms.psds_values('val_', all_reduce=coll))
             if ema is not None:   # the second pass: the averaged weights under the live model's BatchNorm statistics
                 ema.copy_buffers(model)
                 ems = ema.module._metrics
@@ -589,6 +592,8 @@ def fit(model: CustomModel, train_set, epochs, steps_per_epoch, validation_data=
                         row.update(ems.curve_values('val_ema_', all_reduce=coll))
                     if ems.sed is not None:
                         row.update(ems.sed_values('val_ema_', all_reduce=coll))
+                    if ems.psds is not None:
+                        row.update(ems.psds_values('val_ema_', all_reduce=coll))
         history.append(row)
         if swa is not None:
             swa.on_epoch_end(epoch, model)

@@ -17,6 +17,7 @@ The scoring helpers run on the host, once per file."""
 from __future__ import annotations
 
 import json
+import math
 import os
 from glob import glob
 from typing import Dict, List, Optional
@@ -656,6 +657,300 @@ def sed_eval(thresholds=(0.5,), segment=1.0, collar=0.2, offset_pct=50, sr=16000
     return _SedEvalMetric(thresholds, segment, collar, offset_pct, sr, hop)
 
 
+# ---------------------------------------------------------------------------
+# polyphonic sound detection score (Bilen et al., ICASSP 2020; no counterpart in the reference)
+# ---------------------------------------------------------------------------
+PSDS_MAX_THRESHOLDS, PSDS_MAX_CLASSES, PSDS_MAX_FRAMES = 64, 16, 1 << 20
+PSDS_SCENARIOS = {   # the two DCASE Task 4 settings
+    1: dict(dtc_pct=70, gtc_pct=70, cttc_pct=None, alpha_ct=0.0, alpha_st=1.0),
+    2: dict(dtc_pct=10, gtc_pct=10, cttc_pct=30, alpha_ct=0.5, alpha_st=1.0),
+}
+
+
+def psds_default_thresholds() -> tuple:
+    return tuple(float(h) for h in np.linspace(0.01, 0.99, 50).astype(np.float32))
+
+
+def check_psds_params(thresholds=None, dtc_pct=70, gtc_pct=70, cttc_pct=None):
+    """-> (thresholds as a tuple of fp32 values, dtc_pct, gtc_pct, cttc_pct or None), or ValueError: what iris_psds_counts
+    refuses, refused alike for both paths.  `thresholds` None: the 50 values of np.linspace(0.01, 0.99, 50) as fp32; `cttc_pct`
+    None (or 0, as in the C ABI): no cross-triggers are counted."""
+    if thresholds is None:
+        thresholds = psds_default_thresholds()
+    try:
+        thr = tuple(float(np.float32(h)) for h in thresholds)
+    except TypeError:
+        raise ValueError(f"psds: thresholds must be a sequence of numbers, got {thresholds!r}") from None
+    if not 1 <= len(thr) <= PSDS_MAX_THRESHOLDS:
+        raise ValueError(f"psds: 1 .. {PSDS_MAX_THRESHOLDS} thresholds, got {len(thr)}")
+    if not all(np.isfinite(h) for h in thr) or any(b <= a for a, b in zip(thr, thr[1:])):
+        raise ValueError(f"psds: thresholds must be finite and strictly increasing (as fp32), got {thresholds!r}")
+    for name, v in (('dtc_pct', dtc_pct), ('gtc_pct', gtc_pct)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= 100:
+            raise ValueError(f"psds: {name} must be an integer in [1, 100], got {v!r}")
+    if cttc_pct is not None and (isinstance(cttc_pct, bool) or not isinstance(cttc_pct, (int, np.integer)) or not 0 <= int(cttc_pct) <= 100):
+        raise ValueError(f"psds: cttc_pct must be None or an integer in [1, 100], got {cttc_pct!r}")
+    return thr, int(dtc_pct), int(gtc_pct), (int(cttc_pct) or None) if cttc_pct is not None else None
+
+
+def _psds_frames_column(k: int) -> int:
+    """The column of row 0 of the totals plane that holds n_frames: K - for K = 1, where that is the gt_frames column, 2."""
+    return k if k > 1 else 2
+
+
+def psds_counts_host(y_true: torch.Tensor, y_pred: torch.Tensor, thresholds=None, dtc_pct=70, gtc_pct=70, cttc_pct=None) -> torch.Tensor:
+    """The counts [n_thr + 1, K, K + 2] (int64, on the host) of one batch [B, T, K] in the layout of include/iris_frontend.h
+    (iris_psds_counts): plane j, row c holds TP in column c, the cross-triggers on class k in column k != c, FP in column K and
+    the detections in column K + 1; the last plane holds n_gt, gt_frames per class and n_frames.  The CPU path of `Psds.update`
+    and the rule the kernel restates: torch ops on the tensors' device, threshold after threshold, and one copy to the host."""
+    thr, dtc, gtc, cttc = check_psds_params(thresholds, dtc_pct, gtc_pct, cttc_pct)
+    yt = y_true.detach().to(torch.float32)
+    yp = y_pred.detach().to(torch.float32)
+    dev = yp.device
+    b, t, k = yp.shape
+    n = len(thr)
+    out = torch.zeros(n + 1, k, k + 2, dtype=torch.int64, device=dev)
+    ref = (yt >= 0.5).permute(0, 2, 1)                                                # [B, K, T]; NaN: False
+    lab = torch.nn.functional.pad(ref.to(torch.int64).cumsum(-1), (1, 0))             # lab[..., x]: active label frames before x
+    gs, ge = _runs(ref)
+    g_b, g_k, g_s, g_e = gs[:, 0], gs[:, 1], gs[:, 2], ge[:, 2] + 1
+    out[n, :, 0] = torch.bincount(g_k, minlength=k)
+    out[n, :, 1] = ref.sum((0, 2))
+    out[n, 0, _psds_frames_column(k)] = b * t
+    classes = torch.arange(k, device=dev)
+    levels = torch.tensor(thr, dtype=torch.float32, device=dev)
+    for j in range(n):
+        ds, de = _runs((yp >= levels[j]).permute(0, 2, 1))
+        d_b, d_c, d_s, d_e = ds[:, 0], ds[:, 1], ds[:, 2], de[:, 2] + 1
+        length = d_e - d_s
+        inter = lab[d_b, :, d_e] - lab[d_b, :, d_s]                                   # [N, K]: I_k(d)
+        passes = 100 * inter.gather(1, d_c[:, None])[:, 0] >= dtc * length
+        out[j, :, k + 1] = torch.bincount(d_c, minlength=k)
+        out[j, :, k] = torch.bincount(d_c[~passes], minlength=k)
+        if cttc:
+            ct = ~passes[:, None] & (100 * inter >= cttc * length[:, None]) & (classes[None] != d_c[:, None])
+            out[j, :, :k] = torch.bincount((d_c[:, None] * k + classes[None])[ct], minlength=k * k).view(k, k)
+        edge = torch.zeros(b, k, t + 1, dtype=torch.int64, device=dev)               # + 1 at a passing start, - 1 at its end
+        one = torch.ones((), dtype=torch.int64, device=dev)
+        edge.index_put_((d_b[passes], d_c[passes], d_s[passes]), one, accumulate=True)
+        edge.index_put_((d_b[passes], d_c[passes], d_e[passes]), -one, accumulate=True)
+        cover = torch.nn.functional.pad(edge.cumsum(-1)[..., :t].cumsum(-1), (1, 0))  # passing frames before x
+        tp = 100 * (cover[g_b, g_k, g_e] - cover[g_b, g_k, g_s]) >= gtc * (g_e - g_s)
+        out[j, classes, classes] = torch.bincount(g_k[tp], minlength=k)
+    return out.cpu()
+
+
+def _step_curve(points):
+    """[(eFPR, TPR)] -> (x, y): sorted by eFPR, the largest TPR among equal eFPR, the running maximum of TPR."""
+    best = {}
+    for x, y in points:
+        best[x] = max(y, best.get(x, 0.0))
+    xs, ys, top = [], [], 0.0
+    for x in sorted(best):
+        top = max(top, best[x])
+        xs.append(x)
+        ys.append(top)
+    return xs, ys
+
+
+def _step_value(xs, ys, x) -> float:
+    """The step function held from the left: the value of the last point at or before x, 0 before the first."""
+    i = int(np.searchsorted(np.asarray(xs, np.float64), x, side='right'))
+    return ys[i - 1] if i else 0.0
+
+
+def psds_metrics(counts, thresholds, hop=256, sr=16000, alpha_ct=0.0, alpha_st=1.0, e_max=100.0) -> dict:
+    """Host arithmetic on the counts [n_thr + 1, K, K + 2] of `Psds` (integers: NumPy or a tensor; one rank's or the sum over
+    ranks), float64; one frame is hop / sr seconds.  Per class c with ground truth and per threshold: TPR = TP / n_gt[c],
+    FPR = FP per hour of audio, CTR[c][k] = CT[c][k] per hour of label activity of class k (classes k != c with activity),
+    eFPR = FPR + alpha_ct * mean_k CTR[c][k].  The class's curve is the points (eFPR, TPR) sorted by eFPR, the largest TPR among
+    equal eFPR, the running maximum, read as a step function held from the left (0 before the first point);
+    eTPR(x) = mean over the scored classes - alpha_st * their population standard deviation, not clipped; 'psds' is its mean
+    over [0, e_max], summed exactly over the union of the breakpoints.  Classes without ground truth are left out
+    ('classes_without_gt'); with none left the score is NaN.  Also: 'curves' {class: {'efpr', 'tpr'}}, 'tpr_at_e_max' (NaN for a
+    class left out), 'cross_triggers' {'threshold': the one nearest 0.5, 'matrix': CT[c][k] there}, and the totals."""
+    c = np.asarray(counts.detach().cpu() if torch.is_tensor(counts) else counts)
+    n = len(thresholds)
+    if c.ndim != 3 or c.shape[0] != n + 1 or c.shape[2] != c.shape[1] + 2 or not np.issubdtype(c.dtype, np.integer):
+        raise ValueError(f"psds_metrics: integer counts [n_thr + 1 = {n + 1}, K, K + 2], got {c.dtype} {tuple(c.shape)}")
+    if not (e_max > 0 and np.isfinite(e_max)) or hop < 1 or sr <= 0:
+        raise ValueError(f"psds_metrics: e_max {e_max!r} (> 0), hop {hop!r} (>= 1), sr {sr!r} (> 0)")
+    k = c.shape[1]
+    n_gt = [int(c[n, i, 0]) for i in range(k)]
+    gt_frames = [int(c[n, i, 1]) for i in range(k)]
+    n_frames = int(c[n, 0, _psds_frames_column(k)])
+
+    def hours(frames):
+        return frames * hop / sr / 3600.0
+    curves, scored = {}, [i for i in range(k) if n_gt[i] > 0]
+    for i in scored:
+        others = [o for o in range(k) if o != i and gt_frames[o] > 0]
+        points = []
+        for j in range(n):
+            efpr = int(c[j, i, k]) / hours(n_frames)
+            if others:
+                efpr += alpha_ct * sum(int(c[j, i, o]) / hours(gt_frames[o]) for o in others) / len(others)
+            points.append((efpr, int(c[j, i, i]) / n_gt[i]))
+        curves[i] = _step_curve(points)
+    if scored:
+        knots = sorted({0.0, float(e_max)} | {x for xs, _ in curves.values() for x in xs if 0.0 < x < e_max})
+        parts = []
+        for lo, hi in zip(knots, knots[1:]):
+            v = np.asarray([_step_value(*curves[i], lo) for i in scored], np.float64)
+            parts.append((float(v.mean()) - alpha_st * float(v.std())) * (hi - lo))
+        score = math.fsum(parts) / float(e_max)
+    else:
+        score = float('nan')
+    near = int(np.argmin([abs(float(h) - 0.5) for h in thresholds]))
+    return {'psds': score, 'thresholds': [float(h) for h in thresholds], 'alpha_ct': float(alpha_ct), 'alpha_st': float(alpha_st),
+            'e_max': float(e_max), 'classes_scored': scored, 'classes_without_gt': [i for i in range(k) if n_gt[i] == 0],
+            'curves': {i: {'efpr': list(xs), 'tpr': list(ys)} for i, (xs, ys) in curves.items()},
+            'tpr_at_e_max': [_step_value(*curves[i], float(e_max)) if i in curves else float('nan') for i in range(k)],
+            'cross_triggers': {'threshold': float(thresholds[near]),
+                               'matrix': [[int(c[near, i, o]) if o != i else 0 for o in range(k)] for i in range(k)]},
+            'n_gt': n_gt, 'gt_frames': gt_frames, 'n_frames': n_frames}
+
+
+class Psds:
+    """Intersection-based detection counts of everything `update` has seen at every threshold (default: 50 from 0.01 to 0.99),
+    under one criteria set - scenario 1 or 2 of DCASE Task 4 (PSDS_SCENARIOS), or a dict with dtc_pct, gtc_pct, cttc_pct and
+    optionally alpha_ct, alpha_st: int64 [n_thr + 1, K, K + 2], one state per device (as `SedEval`).  On GPU tensors an update is
+    iris_psds_counts - two launches on the current stream, integer adds, no host sync; its workspace is cached per device and
+    stream and grows - on CPU tensors `psds_counts_host`, the same rule.  `compute` is `psds_metrics` on the counts."""
+
+    def __init__(self, n_classes: int, scenario=1, thresholds=None, sr=16000, hop=256, e_max=100.0):
+        self.n_classes = int(n_classes)
+        if not 1 <= self.n_classes <= PSDS_MAX_CLASSES:
+            raise ValueError(f"Psds: n_classes in [1, {PSDS_MAX_CLASSES}], got {n_classes}")
+        if isinstance(scenario, dict):
+            unknown = set(scenario) - {'dtc_pct', 'gtc_pct', 'cttc_pct', 'alpha_ct', 'alpha_st'}
+            if unknown or not {'dtc_pct', 'gtc_pct'} <= set(scenario):
+                raise ValueError(f"Psds: a scenario dict holds dtc_pct, gtc_pct and optionally cttc_pct, alpha_ct, alpha_st, got {scenario!r}")
+            sc = dict(cttc_pct=None, alpha_ct=0.0, alpha_st=1.0)
+            sc.update(scenario)
+        elif scenario in PSDS_SCENARIOS and not isinstance(scenario, bool):
+            sc = dict(PSDS_SCENARIOS[scenario])
+        else:
+            raise ValueError(f"Psds: scenario 1, 2 or a dict, got {scenario!r}")
+        self.thresholds, self.dtc_pct, self.gtc_pct, self.cttc_pct = \
+            check_psds_params(thresholds, sc['dtc_pct'], sc['gtc_pct'], sc['cttc_pct'])
+        self.alpha_ct, self.alpha_st = float(sc['alpha_ct']), float(sc['alpha_st'])
+        if int(hop) != hop or hop < 1 or not sr > 0 or not (e_max > 0 and np.isfinite(e_max)):
+            raise ValueError(f"Psds: hop {hop!r} (an integer >= 1), sr {sr!r} (> 0), e_max {e_max!r} (> 0)")
+        self.hop, self.sr, self.e_max = int(hop), sr, float(e_max)
+        self._levels = (N.C.c_float * len(self.thresholds))(*self.thresholds)
+        self.states: Dict[torch.device, torch.Tensor] = {}
+        self._workspaces: Dict[tuple, torch.Tensor] = {}
+        self._retired: List[torch.Tensor] = []
+
+    def _device(self, device) -> torch.device:
+        device = torch.device(device)
+        if device.type == 'cuda' and device.index is None:
+            device = torch.device('cuda', torch.cuda.current_device())
+        return device
+
+    def _shape(self) -> tuple:
+        return len(self.thresholds) + 1, self.n_classes, self.n_classes + 2
+
+    def state(self, device) -> torch.Tensor:
+        device = self._device(device)
+        if device not in self.states:
+            self.states[device] = torch.zeros(*self._shape(), dtype=torch.int64, device=device)
+        return self.states[device]
+
+    def _workspace(self, device, stream: int, n_bytes: int) -> torch.Tensor:
+        """As `SedEval._workspace`: one per (device, stream), growing, the outgrown ones kept alive; 8-byte words."""
+        ws = self._workspaces.get((device, stream))
+        if ws is None or ws.numel() * 8 < n_bytes:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("Psds.update: the first call for a shape must be eager (warm up before the capture)")
+            if ws is not None:
+                self._retired.append(ws)
+            ws = self._workspaces[(device, stream)] = torch.empty((n_bytes + 7) // 8, dtype=torch.int64, device=device)
+        return ws
+
+    @torch.no_grad()
+    def update(self, y_true: torch.Tensor, y_pred: torch.Tensor) -> None:
+        y_true, y_pred = _first(y_true), _first(y_pred)
+        if y_true.dim() != 3 or y_pred.dim() != 3 or y_true.shape != y_pred.shape:
+            raise ValueError(f"Psds.update: y_true and y_pred [B, T, K] at the same frame rate, got {tuple(y_true.shape)} "
+                             f"/ {tuple(y_pred.shape)}")
+        if y_pred.shape[2] != self.n_classes:
+            raise ValueError(f"Psds.update: {y_pred.shape[2]} classes, made for {self.n_classes}")
+        if not (y_true.is_floating_point() and y_pred.is_floating_point()):
+            raise ValueError(f"Psds.update: floating-point tensors, got {y_true.dtype} / {y_pred.dtype}")
+        if y_true.device != y_pred.device:
+            raise ValueError(f"Psds.update: y_true on {y_true.device}, y_pred on {y_pred.device}")
+        if y_pred.numel() == 0:
+            return
+        b, t, k = y_pred.shape
+        if t > PSDS_MAX_FRAMES or b * t > 2 ** 31 - 1:
+            raise ValueError(f"Psds.update: T {t} (<= 2^20) and B * T {b * t} (<= 2^31 - 1)")
+        st = self.state(y_pred.device)
+        if not y_pred.is_cuda:
+            st += psds_counts_host(y_true, y_pred, self.thresholds, self.dtc_pct, self.gtc_pct, self.cttc_pct)
+            return
+        yt = y_true.detach().to(torch.float32).contiguous()
+        yp = y_pred.detach().to(torch.float32).contiguous()
+        n_bytes = int(N.lib().iris_psds_workspace_bytes(b, t, k, len(self.thresholds)))
+        if n_bytes <= 0:
+            N.check(-1, "iris_psds_workspace_bytes")
+        stream = torch.cuda.current_stream(yp.device).cuda_stream
+        ws = self._workspace(self._device(yp.device), stream, n_bytes)
+        N.check(N.lib().iris_psds_counts(yt.data_ptr(), yp.data_ptr(), b, t, k, self._levels, len(self.thresholds), self.dtc_pct,
+                                         self.gtc_pct, self.cttc_pct or 0, ws.data_ptr(), ws.numel() * 8, st.data_ptr(), stream),
+                "iris_psds_counts")
+
+    def reset(self) -> None:
+        for s in self.states.values():
+            s.zero_()
+
+    def counts(self) -> torch.Tensor:
+        """The counts on the host, summed over this object's devices."""
+        out = torch.zeros(*self._shape(), dtype=torch.int64)
+        for s in self.states.values():
+            out += s.cpu()
+        return out
+
+    def metrics(self, counts) -> dict:
+        return psds_metrics(counts, self.thresholds, self.hop, self.sr, self.alpha_ct, self.alpha_st, self.e_max)
+
+    def compute(self) -> dict:
+        return self.metrics(self.counts())
+
+
+class _PsdsMetric:
+    """psds(scenario, ...): the compiled metric behind val_psds.  A `MetricSet` feeds its `Psds` in the 'val' phase only and
+    returns no per-step value for it; the state is made by the first batch (its class count)."""
+
+    def __init__(self, scenario=1, thresholds=None, sr=16000, hop=256, e_max=100.0):
+        Psds(1, scenario, thresholds, sr, hop, e_max)   # (refuses bad arguments now, not at the first validation batch)
+        self.kwargs = dict(scenario=scenario, thresholds=thresholds, sr=sr, hop=hop, e_max=e_max)
+        self.psds: Optional[Psds] = None
+        self.__name__ = 'psds'
+
+    def update(self, y_true, y_pred) -> None:
+        y_pred = _first(y_pred)
+        if self.psds is None:
+            self.psds = Psds(y_pred.shape[-1], **self.kwargs)
+        self.psds.update(y_true, y_pred)
+
+    def reset(self) -> None:
+        if self.psds is not None:
+            self.psds.reset()
+
+    def __call__(self, y_true, y_pred):
+        raise TypeError("psds() has no per-batch value: compile it (model.compile(metrics=[...])) and read "
+                        "MetricSet.psds_values after the validation pass")
+
+
+def psds(scenario=1, thresholds=None, sr=16000, hop=256, e_max=100.0):
+    """A metric for `compile(metrics=[...])`: the polyphonic sound detection score of the validation pass under DCASE scenario
+    1 or 2 (or a criteria dict, see `Psds`), from on-device integer counts at 50 thresholds (`fit` logs val_psds).  `hop` is the
+    hop of the frames the metric sees - the model's output frames - in samples."""
+    return _PsdsMetric(scenario, thresholds, sr, hop, e_max)
+
+
 def _is_cos(m):
     return m is cos_sim or m is _cos_sim_metric
 
@@ -671,7 +966,8 @@ class MetricSet:
     `reset`, read once per epoch by `fit` (Keras' means: per-clip metrics weighted by clips, the scalar F1 by batches).
     A score_curves() in the list (at most one) is fed in the 'val' phase only - one more launch, iris_score_hist - and read with
     `curve_values`; a 'train'-phase call launches nothing for it, so the captured training step is what it is without it.
-    A sed_eval() in the list (at most one) likewise: 'val' phase only - two more launches, iris_sed_counts - read with `sed_values`."""
+    A sed_eval() in the list (at most one) likewise: 'val' phase only - two more launches, iris_sed_counts - read with `sed_values`.
+    A psds() in the list (at most one) likewise: 'val' phase only - two more launches, iris_psds_counts - read with `psds_values`."""
 
     def __init__(self, metrics):
         self.metrics = list(metrics)
@@ -686,7 +982,11 @@ class MetricSet:
         if len(seds) > 1:
             raise ValueError("MetricSet: at most one sed_eval() in a metric list")
         self.sed = seds[0] if seds else None          # likewise
-        fused = {id(self.er), id(self.f1), id(self.curves), id(self.sed)}
+        scores = [m for m in self.metrics if isinstance(m, _PsdsMetric)]
+        if len(scores) > 1:
+            raise ValueError("MetricSet: at most one psds() in a metric list")
+        self.psds = scores[0] if scores else None     # likewise
+        fused = {id(self.er), id(self.f1), id(self.curves), id(self.sed), id(self.psds)}
         self.others = [m for m in self.metrics if id(m) not in fused and not _is_cos(m)]
         self.names = [metric_name(m) for m in self.metrics]
         dup = sorted({n for n in self.names if self.names.count(n) > 1})
@@ -713,6 +1013,8 @@ class MetricSet:
             self.curves.reset()
         if self.sed is not None and phase in (None, 'val'):
             self.sed.reset()
+        if self.psds is not None and phase in (None, 'val'):
+            self.psds.reset()
 
     @torch.no_grad()
     def __call__(self, y_true, y_pred, phase: str = 'train') -> Dict[str, torch.Tensor]:
@@ -751,7 +1053,26 @@ class MetricSet:
             self.curves.update(y_true, y_pred)
         if self.sed is not None and phase == 'val':      # two iris_sed_counts launches on a GPU; the train phase launches nothing
             self.sed.update(y_true, y_pred)
+        if self.psds is not None and phase == 'val':     # two iris_psds_counts launches on a GPU; the train phase launches nothing
+            self.psds.update(y_true, y_pred)
         return {n: res[n] for n in self.names if n in res}
+
+    def psds_values(self, prefix: str = '', all_reduce: bool = False) -> Dict[str, float]:
+        """Row entry of a compiled psds(): {prefix + 'psds'} from the validation counts, summed over the ranks first with
+        `all_reduce` (a clone, int64 SUM: exact, every rank gets the same value), in one copy to the host.  Every rank must have
+        seen a validation batch, or none."""
+        if self.psds is None:
+            return {}
+        score = self.psds.psds
+        if score is None or not score.states:
+            return {prefix + 'psds': float('nan')}
+        states = list(score.states.values())
+        total = states[0].clone() if all_reduce or len(states) > 1 else states[0]
+        for s in states[1:]:
+            total += s.to(total.device)
+        if all_reduce:
+            torch.distributed.all_reduce(total)
+        return {prefix + 'psds': score.metrics(total.cpu())['psds']}
 
     def sed_values(self, prefix: str = '', all_reduce: bool = False) -> Dict[str, float]:
         """Row entries of a compiled sed_eval(): {prefix + 'seg_f1', 'seg_er', 'event_f1'} - segment-based micro F1 and ER,
@@ -884,12 +1205,13 @@ def output_to_metric(hop, sr):
 # ---------------------------------------------------------------------------
 def evaluate(config, model, overlap_hop=512, verbose: bool = False, *, wav_dir: str = '.',
              answer_path: str = 'sample_answer.json', device=None, curves: Optional["ScoreHistogram"] = None,
-             sed: Optional["SedEval"] = None):
+             sed: Optional["SedEval"] = None, psds: Optional["Psds"] = None):
     """Per-file ER of `model` on sorted(glob(wav_dir/*.wav)) against answer_path's 'task2_answer' (metrics.py:31-87): the
     frame decisions of inference.predict_frames (smoothed, >= 0.5), then get_start_end_frame -> output_to_metric -> get_er.
     `curves`: a ScoreHistogram that is also fed every file's frame posteriors (the smoothed probabilities, before the 0.5
     decision) against the `second2frame` labels of the file's answer; the decisions and the scores are what they are without it.
-    `sed`: a SedEval (made for 3 classes at hop 256) fed the same two tensors, one [1, T, K] update per file."""
+    `sed`: a SedEval (made for 3 classes at hop 256) fed the same two tensors, one [1, T, K] update per file.
+    `psds`: a Psds (made for 3 classes at hop 256) likewise."""
     from . import data_utils as D
     from .inference import features_for_eval, predict_frames
     with open(answer_path) as f:
@@ -902,7 +1224,7 @@ def evaluate(config, model, overlap_hop=512, verbose: bool = False, *, wav_dir: 
     for path in sorted(glob(os.path.join(wav_dir, '*.wav'))):
         spec = D.load_wav(path, device)
         name = os.path.basename(path)[:-4]
-        if curves is None and sed is None:
+        if curves is None and sed is None and psds is None:
             preds = predict_frames(model, features_for_eval(spec, config), config, overlap_hop)
         else:
             from .eval import second2frame
@@ -912,6 +1234,8 @@ def evaluate(config, model, overlap_hop=512, verbose: bool = False, *, wav_dir: 
                 curves.update(labels[None], post.to(torch.float32)[None])
             if sed is not None:
                 sed.update(labels[None], post.to(torch.float32)[None])
+            if psds is not None:
+                psds.update(labels[None], post.to(torch.float32)[None])
             preds = (post >= 0.5).to(torch.float32)   # (predict_frames' own decision)
         cls0, cls1, cls2 = metric.get_start_end_frame(preds.cpu().numpy())
         predict = output_to_metric(hop, sr)(cls0, cls1, cls2)

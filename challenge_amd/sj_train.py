@@ -78,6 +78,8 @@ def row_names(config) -> list:
     if getattr(config, 'sed_eval', ()):
         from .metrics import SED_NAMES
         val += ['val_' + n for n in SED_NAMES]
+    if getattr(config, 'psds', 0):
+        val += ['val_psds']
     ema = ['val_ema_' + n[len('val_'):] for n in val] if getattr(config, 'ema', 0) else []
     return names + val + ema
 
@@ -87,7 +89,7 @@ class ARGS:
     equivalent for (synthetic data, device, distributed launch)."""
 
     def __init__(self, trainer_flags: bool = True) -> None:
-        """trainer_flags=False: without the flags that only `main` here reads (--curves, --sed_eval, --checkpoint_monitor,
+        """trainer_flags=False: without the flags that only `main` here reads (--curves, --sed_eval, --psds, --checkpoint_monitor,
         --recordings*), for a tool that extends this parser with flags of its own (`eval`, whose --curves names a file)."""
         self.args = argparse.ArgumentParser()
         a = self.args.add_argument
@@ -186,8 +188,13 @@ class ARGS:
                'val_event_f1 (200 ms onset collar, offset collar max(200 ms, 50 %% of the event)) at the FIRST threshold of this comma '
                'list of up to 16 increasing thresholds, e.g. 0.5 - from on-device integer counts (metrics.sed_eval, two more launches '
                'per validation batch); empty (default): off.  Not part of the run name')
+        a('--psds', type=int, default=0, choices=[0, 1, 2], metavar='SCENARIO',
+          help='log val_psds, the polyphonic sound detection score (Bilen et al. 2020) of the validation pass under DCASE scenario 1 '
+               '(DTC / GTC 0.7, no cross-triggers) or 2 (DTC / GTC 0.1, CTTC 0.3, alpha_ct 0.5), alpha_st 1, over 50 thresholds - from '
+               'on-device integer counts (metrics.psds, two more launches per validation batch); 0 (default): off.  Not part of the '
+               'run name')
         a('--checkpoint_monitor', type=str, default=None, metavar='NAME',
-          help="the row entry the checkpoint follows, e.g. val_map or val_event_f1 (auc / map / best_f1 / seg_f1 / event_f1 are "
+          help="the row entry the checkpoint follows, e.g. val_map or val_event_f1 (auc / map / best_f1 / seg_f1 / event_f1 / psds are "
                "maximised, everything else minimised); default: val_er with --metrics reference, else val_loss")
         a('--recordings', type=str, default=None, metavar='DIR',
           help='--online_stft only.  Cut a share of every training batch from the labelled recordings DIR/*.wav '
@@ -919,6 +926,9 @@ def main(argv=None):
     if config.sed_eval:
         from .metrics import sed_eval
         metrics = (metrics or []) + [sed_eval(config.sed_eval, hop=output_hop(config))]
+    if config.psds:
+        from .metrics import psds
+        metrics = (metrics or []) + [psds(config.psds, hop=output_hop(config))]
     if config.checkpoint_monitor is not None:
         monitor = config.checkpoint_monitor
     ema = None
@@ -935,6 +945,9 @@ def main(argv=None):
         if config.sed_eval:   # (and counts of its own)
             from .metrics import sed_eval
             own = (own or []) + [sed_eval(config.sed_eval, hop=output_hop(config))]
+        if config.psds:   # (likewise)
+            from .metrics import psds
+            own = (own or []) + [psds(config.psds, hop=output_hop(config))]
         ema.compile(loss, metrics=own)
     model.compile(opt, loss, clipvalue=None if config.no_clipvalue_after_agc else config.clipvalue,
                   ddp=wrap_ddp(model, device, world), metrics=metrics, ema=ema)

@@ -528,6 +528,41 @@ int iris_sed_counts(const float* y_true, const float* y_pred, int batch, int n_t
                     size_t workspace_bytes, long long* counts, void* stream);
 
 /*
+ * Intersection-based detection counts of one batch behind the polyphonic sound detection score (PSDS: Bilen et al., ICASSP 2020)
+ * at n_thr thresholds, TWO launches on `stream`, capturable, no host synchronisation and no allocation; the rates, the curves and
+ * the area are host arithmetic.  All arithmetic is integer; products are formed in 64 bits.
+ *   y_true, y_pred [B, T, K] fp32 contiguous, DEVICE, at the same frame rate; 1 <= K <= 16, T <= 2^20, B * T <= 2^31 - 1.
+ *   thresholds     [n_thr] fp32, HOST, finite and strictly increasing, 1 <= n_thr <= 64 (read before the launches).
+ *   dtc_pct, gtc_pct in [1, 100]; cttc_pct in [1, 100], or 0 for none (no cross-triggers are counted).
+ *   Label activity is y_true >= 0.5f, predicted activity at threshold h is y_pred >= h in fp32; a NaN is inactive.
+ *   Events are the maximal runs [s, e) of active frames of one (clip, class) row; a run open at the row's end closes at T; the
+ *     length is e - s frames.  Events are not joined across calls.
+ *   For clip b, threshold j, class c and a detection d (a run of class c at h_j) let I_k(d) be the number of frames of d in
+ *     which label k of that clip is active (the sum of |d ∩ g| over the ground-truth events g of class k).
+ *     d PASSES if 100 I_c(d) >= dtc_pct len(d).  Otherwise FP[j][c] += 1, and for every class k != c, if cttc_pct is given and
+ *     100 I_k(d) >= cttc_pct len(d), CT[j][c][k] += 1 (a failing detection is a false positive whether or not it is also a
+ *     cross-trigger).  n_det[j][c] counts every detection.
+ *     A ground-truth event g of class c is a true positive at j, TP[j][c] += 1, if 100 cov(g) >= gtc_pct len(g), cov(g) being
+ *     the number of frames of g inside passing detections of class c at h_j in that clip.
+ *   counts         [n_thr + 1][K][K + 2] int64, DEVICE, CUMULATIVE (the caller zeroes it).
+ *                  Plane j < n_thr, row c: column c holds TP[j][c], column k != c (k < K) holds CT[j][c][k], column K holds
+ *                  FP[j][c], column K + 1 holds n_det[j][c].
+ *                  Plane n_thr, the threshold-independent totals: row k holds n_gt[k] (ground-truth events) in column 0 and
+ *                  gt_frames[k] (active label frames) in column 1; row 0 holds n_frames (B * T summed over the calls) in column
+ *                  K - for K = 1, where that is the gt_frames column, in column 2.  Every other entry of the plane stays 0.
+ *   workspace      DEVICE, 8-byte aligned, at least iris_psds_workspace_bytes(...) bytes (0 for a shape that is refused); its
+ *                  contents are scratch, rewritten by every call: calls that share one must be ordered on one stream.
+ * Integer adds only: independent of the order, bitwise reproducible, and the counts of several ranks sum exactly.
+ * Refused before any HIP call: NULL pointers, B / T / K / n_thr < 1, thresholds not finite or not increasing, dtc_pct or gtc_pct
+ * outside [1, 100], cttc_pct outside [0, 100], a misaligned or too small workspace (INVALID); K > 16, n_thr > 64, T > 2^20,
+ * B * T > 2^31 - 1 (UNSUPPORTED).
+ */
+long long iris_psds_workspace_bytes(int batch, int n_time, int n_classes, int n_thr);
+int iris_psds_counts(const float* y_true, const float* y_pred, int batch, int n_time, int n_classes, const float* thresholds,
+                     int n_thr, int dtc_pct, int gtc_pct, int cttc_pct /* 0: none */, void* workspace, size_t workspace_bytes,
+                     long long* counts, void* stream);
+
+/*
  * Window predictions of F files -> event lists (metrics.py:56-81 from the model's outputs on, then get_start_end_frame,
  * metrics.py:111-137), two launches, capturable:
  *   preds      [W_total, n_out, K] fp32, DEVICE: the model's outputs for every window of every file, file after file
