@@ -77,6 +77,7 @@ SIGNATURES = {
     "iris_speed_len": (C.c_longlong, [C.c_longlong, C.c_double]),
     "iris_speed_perturb": (_i, [_vp, _i, _i, _i, _vp]),
     "iris_mix_wave_frame_active_batch": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),
+    "iris_flyby": (_i, [_vp, _i, _i, _i, _vp]),
     "iris_activity_gate": (_i, [_vp, _i, _i, _i, _i, _i, _i, C.c_double, C.c_double, _i, _vp]),
     "iris_fir_batch": (_i, [_vp, _i, _i, _i, _i, _vp]),
     "iris_fir_batch_pitch": (_i, [_vp, _i, _i, _i, _i, _i, _vp]),

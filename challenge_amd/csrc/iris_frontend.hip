@@ -44,6 +44,9 @@
 //                    chunked scan modulo 2 pi
 //   k_speed.h        speed perturbation: a batched band-limited resampler over a ragged set of waveforms, each at its own
 //                    real-valued rate, and the frame activity of the results, one launch each
+//   k_flyby.h        fly-by augmentation: a static source heard by a moving array - a time-varying fractional delay per channel
+//                    (Doppler, inter-channel delay), spreading level and one ground reflection over a ragged set of waveforms,
+//                    one launch
 //   k_gate.h         activity gate of a waveform corpus: frame energies in double, the mask (threshold, close, drop, hang) and
 //                    the gated copy of a ragged set of waveforms, one launch each
 //   k_fir.h          reverberation: a batched direct-form FIR over a ragged set of waveforms, each channel with its own taps,
@@ -93,6 +96,7 @@
 #include "k_pcen_grad.h"
 #include "k_vocoder.h"
 #include "k_speed.h"
+#include "k_flyby.h"
 #include "k_gate.h"
 #include "k_fir.h"
 #include "k_fft_fir.h"

@@ -147,6 +147,14 @@ class RunTokens:
         U[0.2, 1.0) s followed down to -40 dB without truncation - up to 10667 taps in [C, 16384] tap buffers - through the
         partitioned FFT convolution (`enable_reverb(rt60_lo=0.2, rt60_hi=1.0, max_taps=16384)`: one `iris_fft_fir_batch`
         launch pair per group of voices and epoch).  Refused with 'shoebox': the image-source kernel stops at 4096 taps.
+    flyby: the fly-by augmentation of the voice corpus, on training sets of `make_wave_dataset`, at creation and again every
+        config.steps_per_epoch batches - every voice as a moving microphone array hears it: one random level pass per voice
+        (`transforms.draw_flyby`: altitude ~ U[5, 30) m, speed ~ U[0, 15) m/s, any heading, closest approach ~ U[0, 20) m at a
+        time inside the voice, ground reflection ~ U[0, 0.6); choices, not measurements), per channel the time-varying delay of
+        its microphone, the spreading level and one ground reflection (`WaveMixer.enable_flyby` / `reflyby`: one `iris_flyby`
+        and one `iris_mix_wave_frame_active_batch` launch; the labels follow the delayed voice).  A mixer holds one voice
+        augmentation: refused with 'speed' or 'reverb', and by the two other builders.  It goes with every other token, with
+        recordings and with a corpus of wav files; validation sets, backgrounds and noises are never touched.
     filtaug: FilterAugment, None or the kind of its gain curve ('step'; 'linear' for 'filtaug_linear') - every training
         sample's mel magnitudes are multiplied by a fresh random piecewise gain curve over the mel bands inside the mel kernels,
         before any compression (`iris_magmel_gain`, `iris_wav_to_logmel_gain`: no extra launch, no extra pass; the draw is
@@ -178,6 +186,7 @@ class RunTokens:
     filtaug: Optional[str]
     ipd: bool
     reverb_long: bool = False
+    flyby: bool = False
     whiten: bool = False
 
 
@@ -195,7 +204,11 @@ def run_tokens(config_or_name) -> RunTokens:
         filter='filter' in name, stretch='stretch' in name, speed='speed' in name, reverb='reverb' in name,
         shoebox='shoebox' in name,
         filtaug=('linear' if 'filtaug_linear' in name else 'step') if 'filtaug' in name else None,
-        ipd='ipd' in name, reverb_long='reverb_long' in name, whiten='whiten' in name)
+        ipd='ipd' in name, reverb_long='reverb_long' in name, flyby='flyby' in name, whiten='whiten' in name)
+    for other in ('speed', 'reverb'):
+        if tokens.flyby and getattr(tokens, other):
+            raise ValueError(f"run name {name!r} asks for both 'flyby' and {other!r}: the two cannot be combined yet (a mixer "
+                             "holds one voice augmentation), name one")
     if tokens.reverb_long and tokens.shoebox:
         raise ValueError(f"run name {name!r} asks for both 'reverb_long' and 'shoebox': the image-source room model computes at "
                          "most 4096 taps, name one")
@@ -248,13 +261,18 @@ BUILDER_REFUSALS = {
 def check_builder(tokens: RunTokens, builder: str) -> None:
     """ValueError if `builder` (a key of BUILDER_REFUSALS) does not honour a token of the name, or - a mixer holds one voice
     augmentation - if the name asks it for both 'speed' and 'reverb'.  'whiten' is honoured by the two batched builders
-    and refused by `make_dataset` here (the table keeps the rows it has)."""
+    and refused by `make_dataset` here (the table keeps the rows it has); 'flyby' is honoured by `make_wave_dataset` alone, here
+    as well."""
     for token, reason in BUILDER_REFUSALS[builder].items():
         if reason is not None and getattr(tokens, token):
             raise ValueError(f"run name {tokens.name!r} asks for {token!r}: {reason}")
     if tokens.whiten and builder == 'make_dataset':
         raise ValueError(f"run name {tokens.name!r} asks for 'whiten': the whitened channel is computed on whole batches "
                          "(make_device_dataset, make_wave_dataset); the per-sample host pipeline has no such stage")
+    if tokens.flyby and builder != 'make_wave_dataset':
+        raise ValueError(f"run name {tokens.name!r} asks for 'flyby': the fly-by runs on the resident waveform corpus "
+                         f"(make_wave_dataset); " + ("the per-sample host pipeline has no such stage" if builder == 'make_dataset'
+                                                     else "a spectrum corpus has no waveform to delay"))
     if tokens.speed and tokens.reverb:
         raise ValueError(f"run name {tokens.name!r} asks for both 'speed' and 'reverb': the two cannot be combined yet (a "
                          "mixer holds one voice augmentation), name one")

@@ -1734,6 +1734,108 @@ def shoebox_rir_batch(rooms, sources, mics, betas, n_taps, normalize: bool = Tru
     return [b[:, :int(k)] for b, k in zip(out, table["n_taps"])]
 
 
+# mirrors iris_flyby_src (include/iris_frontend.h)
+FLYBY_MAX_CHAN = ISM_MAX_CHAN   # microphones per record (IRIS_FLYBY_MAX_CHAN)
+FLYBY_SRC = np.dtype([("src", "<u8"), ("dst", "<u8"), ("len", "<i4"), ("n_paths", "<i4"), ("p0", "<f8", (3,)), ("v", "<f8", (3,)),
+                      ("z_s", "<f8"), ("beta", "<f8"), ("r_ref", "<f8"), ("mic", "<f8", (FLYBY_MAX_CHAN, 3))])
+assert FLYBY_SRC.itemsize == 96 + 24 * FLYBY_MAX_CHAN
+FLYBY_FS = 16000.0              # the sample rate iris_flyby is written for
+
+
+def flyby_r_ref(p0, v, z_s: float, mics, length: int) -> float:
+    """The reference distance of a flight: the smallest distance between the source (0, 0, z_s) and any microphone
+    p0 + v t + mics[c] over t in [0, (length - 1) / 16000], in closed form - per microphone the squared distance is a
+    quadratic in t, whose vertex is clamped to the interval.  Delays and gains of `iris_flyby` are measured against it."""
+    p0, v, mics = np.asarray(p0, np.float64), np.asarray(v, np.float64), np.asarray(mics, np.float64).reshape(-1, 3)
+    t_end = (int(length) - 1) / FLYBY_FS
+    vv = float(v[0] * v[0] + v[1] * v[1] + v[2] * v[2])
+    best = np.inf
+    for m in mics:
+        q = p0 + m
+        q[2] -= float(z_s)
+        t = 0.0 if vv == 0.0 else min(max(-float(q[0] * v[0] + q[1] * v[1] + q[2] * v[2]) / vv, 0.0), t_end)
+        dx, dy, dz = q[0] + v[0] * t, q[1] + v[1] * t, q[2] + v[2] * t
+        best = min(best, float(np.sqrt(dx * dx + dy * dy + dz * dz)))
+    return best
+
+
+def flyby_records(geometry, lengths, channels: int) -> np.ndarray:
+    """The FLYBY_SRC table (src / dst left 0) of one flight per voice: geometry[i] is a dict of p0 [3], v [3] (metres, metres per
+    second), z_s, beta and mics [channels, 3] (offsets from the array centre) - what `transforms.draw_flyby` returns - or None
+    for the identity record (n_paths 0: a copy); lengths[i] the voice's samples per channel.  beta == 0 packs one path, exactly;
+    r_ref is `flyby_r_ref` of the flight.  ValueError: a length below 1, 1 <= channels <= 8 violated, a shape that does not fit,
+    a value that is not finite, z_s < 0, beta outside [0, 1), |v| >= 343 m/s, a flight that touches the source (r_ref = 0)."""
+    geometry, lengths, channels = list(geometry), [int(n) for n in lengths], int(channels)
+    if len(geometry) != len(lengths):
+        raise ValueError(f"flyby_records: {len(geometry)} geometries but {len(lengths)} lengths")
+    if not 1 <= channels <= FLYBY_MAX_CHAN:
+        raise ValueError(f"flyby_records: {channels} microphones per voice; 1 .. {FLYBY_MAX_CHAN} are supported")
+    table = np.zeros(len(geometry), FLYBY_SRC)
+    for i, (g, n) in enumerate(zip(geometry, lengths)):
+        if not 1 <= n <= 2 ** 31 - 1:
+            raise ValueError(f"flyby_records: lengths[{i}] = {n} is outside 1 .. 2^31 - 1")
+        table["len"][i] = n
+        if g is None:
+            continue
+        p0, v = np.asarray(g["p0"], np.float64), np.asarray(g["v"], np.float64)
+        mics, z_s, beta = np.asarray(g["mics"], np.float64), float(g["z_s"]), float(g["beta"])
+        if p0.shape != (3,) or v.shape != (3,) or mics.shape != (channels, 3):
+            raise ValueError(f"flyby_records: geometry[{i}] has p0 {p0.shape}, v {v.shape}, mics {mics.shape}; expected [3], [3], "
+                             f"[{channels}, 3]")
+        if not (np.all(np.isfinite(p0)) and np.all(np.isfinite(v)) and np.all(np.isfinite(mics)) and np.isfinite(z_s)
+                and np.isfinite(beta)):
+            raise ValueError(f"flyby_records: geometry[{i}] holds a value that is not finite")
+        if z_s < 0 or not 0 <= beta < 1:
+            raise ValueError(f"flyby_records: geometry[{i}] has z_s = {z_s} (must be >= 0) and beta = {beta} (must be in [0, 1))")
+        if not float(np.sqrt(np.sum(v * v))) < ISM_SOUND:
+            raise ValueError(f"flyby_records: geometry[{i}] moves at {float(np.sqrt(np.sum(v * v)))} m/s, not below the sound speed")
+        r_ref = flyby_r_ref(p0, v, z_s, mics, n)
+        if not r_ref > 0:
+            raise ValueError(f"flyby_records: the flight of geometry[{i}] touches the source (reference distance {r_ref})")
+        table["n_paths"][i] = 1 if beta == 0.0 else 2
+        table["p0"][i], table["v"][i], table["z_s"][i], table["beta"][i], table["r_ref"][i] = p0, v, z_s, beta, r_ref
+        table["mic"][i, :channels] = mics
+    return table
+
+
+def flyby_launch(table: np.ndarray, chan: int, max_len: int, device: torch.device,
+                 table_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Upload a FLYBY_SRC table (into `table_dev`, a long-lived uint8 device buffer, when given) and run iris_flyby over it on
+    the current stream: one launch.  Returns the device table (tied to the stream when it was allocated here)."""
+    return _launch_records(table, device, table_dev, "iris_flyby", lambda ptr, n, stream: N.lib().iris_flyby(
+        ptr, n, int(chan), int(max_len), stream))
+
+
+def flyby_batch(waves, geometry):
+    """Fly a moving microphone array past a ragged batch of voices in ONE launch (iris_flyby): waves is a list of [C, L_i]
+    float32 tensors on one ROCm device (equal C <= 8, sampled at 16 kHz), geometry as many flights (`flyby_records`; None: a
+    copy).  Returns a list of new [C, L_i] tensors: channel c is row c of the source under the time-varying delay and
+    spherical-spreading gain of microphone c, plus the ground reflection at beta > 0 - the Doppler shift, the moving
+    inter-channel delay and the level swell of a pass; what arrives later than the buffer is cut.  |out - fp64| <= 4 u cut
+    sum_p |g_p| sum |x| over the support.  CPU tensors raise: there is no CPU fallback."""
+    waves, geometry = list(waves), list(geometry)
+    if len(waves) != len(geometry):
+        raise ValueError(f"flyby_batch: {len(waves)} waveforms but {len(geometry)} geometries")
+    if not waves:
+        return []
+    waves = [_require_device_f32(w, f"waves[{i}]") for i, w in enumerate(waves)]
+    dev = waves[0].device
+    if waves[0].dim() != 2:
+        raise ValueError("flyby_batch: every waveform must be [chan, samples]")
+    chan = int(waves[0].shape[0])
+    for i, w in enumerate(waves):
+        if w.dim() != 2 or int(w.shape[0]) != chan or w.device != dev or int(w.shape[1]) < 1 or chan < 1:
+            raise ValueError(f"flyby_batch: waves[{i}] has shape {tuple(w.shape)} on {w.device}; expected [{chan} >= 1, L >= 1] on "
+                             f"{dev}")
+    table = flyby_records(geometry, [int(w.shape[1]) for w in waves], chan)
+    results = [torch.empty_like(w) for w in waves]
+    table["src"], table["dst"] = [w.data_ptr() for w in waves], [o.data_ptr() for o in results]
+    flyby_launch(table, chan, int(table["len"].max()), dev)
+    for w in waves:   # (a contiguous copy made above must outlive the kernel)
+        w.record_stream(torch.cuda.current_stream(dev))
+    return results
+
+
 # mirrors iris_istft_src (include/iris_frontend.h)
 ISTFT_SRC =np.dtype([("src", "<u8"), ("dst", "<u8"), ("n_frames", "<i4"), ("len_out", "<i4")])
 assert ISTFT_SRC.itemsize == 24

@@ -103,7 +103,8 @@ def _enable_voice_aug(mixer, word: str, lo: float, hi: float) -> None:
     and fill them at rate 1.  The range is checked before `mixer` is touched."""
     _check_rate_range(word, lo, hi)
     if mixer._aug is not None:
-        raise RuntimeError(f"enable_{word} was already called on this mixer")
+        raise RuntimeError(f"enable_{word} was already called on this mixer" if isinstance(mixer._aug, _VoiceAug) else
+                           f"{_aug_name(mixer._aug)} was already called on this mixer (a mixer holds one voice augmentation)")
     dev = mixer.device
     dtype, f_in, _ = mixer._aug_record
     orig = list(mixer.voices)
@@ -176,6 +177,26 @@ class _ReverbAug:
     pool: Optional[list] = None                # measured responses (`transforms.load_rirs`) a plain `rereverb()` draws from
     groups: Optional[list] = None              # long path: (first, last + 1) voice ranges, one `iris_fft_fir_batch` each
     workspace: Optional[torch.Tensor] = None   # long path: the spectra of the largest group, allocated once
+
+
+@dataclass
+class _FlybyAug:
+    """The voice corpus under `WaveMixer.enable_flyby` (it takes the mixer's one `_aug` slot): the originals, their never-moving
+    copies and activity vectors, the launch table and the resident table of the activity pass."""
+    ranges: dict                    # `transforms.draw_flyby`'s keyword arguments of a plain `reflyby()`
+    orig: list                      # the voices as given (device tensors [C, L_i])
+    bufs: list                      # one [C, L_i] buffer per voice: what the mixer reads
+    acts: list                      # its frame-activity vector, recomputed from the buffer by every `reflyby`
+    table: np.ndarray               # FLYBY_SRC records, src / dst / len filled once
+    table_dev: torch.Tensor         # long-lived device copy of `table`, uploaded by every `reflyby`
+    act_table_dev: torch.Tensor     # SPEED_SRC records of `iris_mix_wave_frame_active_batch` (dst / len_out), uploaded once
+    act_ptr_dev: torch.Tensor       # device array of the `acts` addresses
+    geometry: Optional[list] = None   # the flights of the latest `reflyby` (None per voice: the identity)
+
+
+def _aug_name(aug) -> str:
+    """The enable call whose state sits in a mixer's `_aug` slot."""
+    return "enable_flyby" if isinstance(aug, _FlybyAug) else "enable_reverb" if isinstance(aug, _ReverbAug) else "enable_speed"
 
 
 def _check_reverb_range(rt60_lo: float, rt60_hi: float, drr_lo: float, drr_hi: float) -> None:
@@ -520,6 +541,10 @@ class DeviceMixer:
         raise NotImplementedError("DeviceMixer.enable_reverb: a spectrum corpus has no waveform to convolve (reverberation "
                                   "works on waveforms: use WaveMixer; this corpus has enable_stretch)")
 
+    def enable_flyby(self, **ranges) -> None:
+        raise NotImplementedError("DeviceMixer.enable_flyby: a spectrum corpus has no waveform to delay (the fly-by works on "
+                                  "waveforms: use WaveMixer; this corpus has enable_stretch)")
+
     def _draw_on_device(self, batch: int):
         """(table_d [batch * stride, 48 B], first_d [batch + 1], n_srcs) written by iris_mix_draw on the current stream."""
         dd, dev = self._dd, self.device
@@ -719,7 +744,7 @@ class WaveMixer(DeviceMixer):
                     raise ValueError(f"enable_reverb: rirs[{i}] has shape {h.shape}; expected [{self.channels}, 1 <= K <= {max_taps}]")
         if self._aug is not None:
             raise RuntimeError("enable_reverb was already called on this mixer" if isinstance(self._aug, _ReverbAug) else
-                               "enable_speed was already called on this mixer (a mixer holds one voice augmentation)")
+                               f"{_aug_name(self._aug)} was already called on this mixer (a mixer holds one voice augmentation)")
         dev, orig = self.device, list(self.voices)
         bufs = [torch.zeros_like(v) for v in orig]
         taps = [torch.zeros((self.channels, max_taps), device=dev, dtype=torch.float32) for _ in orig]
@@ -808,6 +833,73 @@ class WaveMixer(DeviceMixer):
             _fe.fir_launch(aug.table, chan, int(self._v_L.max()), int(aug.table["n_taps"].max()), self.device, aug.table_dev)
         aug.rirs = rirs
         return rirs
+
+    # -- fly-by of the voice corpus ---------------------------------------------------------
+    def enable_flyby(self, **ranges) -> None:
+        """Keep a copy of every voice as a moving microphone array hears it beside the original and mix from the copies:
+        `reflyby()` then flies the array past every voice anew - one random level pass per voice (`transforms.draw_flyby`, whose
+        keyword arguments `ranges` are: mic_spacing, altitude, speed, miss, z_s, beta) - in one launch (`iris_flyby`): per
+        channel the time-varying delay of its microphone (Doppler shift, a moving inter-channel delay), the level that swells
+        and fades with the distance, and one ground reflection.  The voices are taken to be sampled at 16 kHz.  One [C, L_i]
+        buffer and one frame-activity vector per voice are allocated here and never move: the pointer tables (and the
+        device-side corpus of `enable_device_draw`, in either call order) are switched to them once, so a captured `mix`
+        replayed after a `reflyby` reads the new contents through unchanged addresses.  The copies are filled here through
+        identity records: until the first `reflyby` the mixer mixes bit-identically to one on which this was never called.
+        Lengths and frame counts do not move - what arrives later than a voice's buffer is cut, as the reverberation's tail
+        is.  Backgrounds and noises are left alone: they carry no labels.  A mixer holds one voice augmentation: this after
+        `enable_speed` / `enable_reverb` (or the other way round) raises.  At most 8 channels.  The ranges are choices, not
+        measurements of any corpus; no accuracy claim is made for the augmentation."""
+        _tr.draw_flyby(np.random.default_rng(0), self.channels, 1.0, **ranges)   # (the ranges are checked before the mixer is touched)
+        if self._aug is not None:
+            raise RuntimeError("enable_flyby was already called on this mixer" if isinstance(self._aug, _FlybyAug) else
+                               f"{_aug_name(self._aug)} was already called on this mixer (a mixer holds one voice augmentation)")
+        dev, orig = self.device, list(self.voices)
+        bufs = [torch.zeros_like(v) for v in orig]
+        acts = [torch.zeros_like(a) for a in self.voice_active]
+        table = _fe.flyby_records([None] * len(orig), self._v_L, self.channels)
+        table["src"], table["dst"] = [v.data_ptr() for v in orig], [b.data_ptr() for b in bufs]
+        act_table = np.zeros(len(orig), _fe.SPEED_SRC)   # only dst / len_out are read by the activity pass
+        act_table["dst"], act_table["len_out"] = table["dst"], self._v_L
+        i64 = lambda a: torch.from_numpy(np.asarray(a).astype(np.int64)).to(dev)  # noqa: E731
+        v_act = np.array([a.data_ptr() for a in acts], np.uint64)
+        self._aug = _FlybyAug(dict(ranges), orig, bufs, acts, table, torch.empty(max(table.nbytes, 1), dtype=torch.uint8, device=dev),
+                              torch.from_numpy(act_table.view(np.uint8).reshape(-1).copy()).to(dev), i64(v_act))
+        self.voices, self.voice_active = bufs, acts
+        self._v_ptr, self._v_act = np.array([b.data_ptr() for b in bufs], np.uint64), v_act
+        if self._dd is not None:
+            self._dd["voice_arrays"]["src"].copy_(torch.from_numpy(self._v_ptr.astype(np.int64)))
+            self._dd["voice_arrays"]["act"].copy_(torch.from_numpy(self._v_act.astype(np.int64)))
+        self.reflyby([None] * len(orig))
+
+    def reflyby(self, geometry=None) -> list:
+        """Fly the array past every ORIGINAL voice anew, into its buffer: one `transforms.draw_flyby` per voice from the mixer's
+        own NumPy generator, over the voice's own duration (or the given `geometry`, one dict per voice; None: the identity),
+        packed by `frontend.flyby_records` and uploaded into the resident table, then ONE `iris_flyby` launch over the whole
+        voice corpus and ONE `iris_mix_wave_frame_active_batch` launch for the frame activity of the results: the labels follow
+        the delayed voice, and a silent tail stays exactly zero.  Lengths, frame counts and addresses do not change.  Call it
+        outside any graph capture.  Backgrounds and noises are left alone.  Returns the list of flights used."""
+        aug = getattr(self, "_aug", None)
+        if not isinstance(aug, _FlybyAug):
+            raise RuntimeError("reflyby needs enable_flyby() first")
+        n_voice, chan = len(aug.orig), self.channels
+        if geometry is None:
+            geometry = [_tr.draw_flyby(self.rng, chan, int(n) / _fe.FLYBY_FS, **aug.ranges) for n in self._v_L]
+        geometry = list(geometry)
+        if len(geometry) != n_voice:
+            raise ValueError(f"reflyby: {len(geometry)} flights for {n_voice} voices")
+        records = _fe.flyby_records(geometry, self._v_L, chan)
+        for f in ("n_paths", "p0", "v", "z_s", "beta", "r_ref", "mic"):
+            aug.table[f] = records[f]
+        if n_voice:
+            max_len = int(self._v_L.max())
+            _fe.flyby_launch(aug.table, chan, max_len, self.device, aug.table_dev)
+            with torch.cuda.device(self.device):
+                rc = N.lib().iris_mix_wave_frame_active_batch(aug.act_table_dev.data_ptr(), n_voice, chan, self.n_fft, self.hop,
+                                                              aug.act_ptr_dev.data_ptr(), 1 + max_len // self.hop,
+                                                              C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+            N.check(rc, "iris_mix_wave_frame_active_batch")
+        aug.geometry = geometry
+        return geometry
 
     def mix(self, batch: int, draws=None):
         """One batch of (waveforms [B, C, (n_frame - 1) * hop], labels [B, max_voices, n_frame, n_classes])."""

@@ -639,7 +639,9 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
     Of the run-name tokens (`data_utils.RunTokens`) this builder honours 'speed', 'reverb' (with 'shoebox'), 'filtaug' and
     'ipd' and refuses 'stretch', and 'speed' beside 'reverb' (`data_utils.BUILDER_REFUSALS`).  With 'ipd' x is
     [B, n_mels, n_frame, 4] (`wave_features`); the corpora must be stereo.  'whiten' (`check_builder` honours it here) appends
-    the whitened energy channel behind those, the clip as one block; stereo corpora and recordings as well.
+    the whitened energy channel behind those, the clip as one block; stereo corpora and recordings as well.  'flyby'
+    (`check_builder` honours it here alone): the training voices as a moving microphone array hears them, redrawn every epoch
+    (`WaveMixer.enable_flyby` / `reflyby`); it touches the synthetic part only, as 'speed' / 'reverb' do, and is refused beside either.
     spec_sources: the same tuple as SPECTRA ([F, T_i, 2C], integer labels), e.g. the pickled corpora - converted once here by
     `waves_from_specs` at this n_fft / hop and used as `sources` (giving both is a ValueError).
     recordings: a `recordings.RecordingSampler` (built for this n_frame and hop), or a (waves, events) pair - what
@@ -732,7 +734,11 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
         mixer.enable_device_draw(0 if seed is None else seed)
     draws = BatchDraws(tokens, training, dev, seed, device_draw, plan.n_bins)
     # the voice corpus is augmented anew now and once per epoch (the validation set never is)
-    respeed = rereverb = None
+    respeed = rereverb = reflyby = None
+    if training and tokens.flyby and mixer is not None:
+        mixer.enable_flyby()
+        reflyby = mixer.reflyby
+        reflyby()
     if training and tokens.speed and mixer is not None:
         mixer.enable_speed()
         respeed = mixer.respeed
@@ -764,7 +770,7 @@ def make_wave_dataset(config, training=True, n_classes=3, sources=None, device=N
     batch = synthetic if sampler is None else mixed
 
     def gen():
-        reaugment = _every_epoch(respeed or rereverb, config.steps_per_epoch)
+        reaugment = _every_epoch(respeed or rereverb or reflyby, config.steps_per_epoch)
         while True:
             reaugment()
             wav, y = batch(config.batch_size)

@@ -652,6 +652,58 @@ def draw_shoebox(rng: np.random.Generator, channels: int, rt60: float, mic_spaci
     raise ValueError(f"draw_shoebox: no source at least {margin} m from the array in {tries} tries")
 
 
+def _flyby_range(name: str, rng_, lo_min: float, lo_open: bool = False):
+    """(lo, hi) of a `draw_flyby` range: finite, lo_min <= lo <= hi (lo_min < lo with lo_open)."""
+    try:
+        lo, hi = (float(x) for x in rng_)
+    except (TypeError, ValueError):
+        raise ValueError(f"draw_flyby: {name} = {rng_!r} must be a (lo, hi) pair") from None
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo <= hi and (lo > lo_min if lo_open else lo >= lo_min)):
+        raise ValueError(f"draw_flyby: {name} = ({lo}, {hi}) must be finite with {lo_min} {'<' if lo_open else '<='} lo <= hi")
+    return lo, hi
+
+
+def draw_flyby(rng: np.random.Generator, channels: int, seconds: float, mic_spacing: float = 0.1, altitude=(5.0, 30.0),
+               speed=(0.0, 15.0), miss=(0.0, 20.0), z_s: float = 1.5, beta=(0.0, 0.6)) -> dict:
+    """One random fly-by on the host: a dict of p0 [3] (the array centre at t = 0), v [3] (float64, metres and metres per
+    second), z_s, beta and mics [channels, 3] (offsets from the centre) - what `frontend.flyby_records` packs.  The source stands
+    at (0, 0, z_s) on the ground plane z = 0.  Level flight at an altitude ~ U[altitude) with speed ~ U[speed) on a heading ~
+    U[0, 2 pi) that passes the source at a horizontal distance ~ U[miss) at a time ~ U[0, seconds); ground reflection coefficient
+    ~ U[beta) (drawn in this order).  The microphones sit on a line along x, `mic_spacing` apart and centred, as `draw_shoebox`
+    places them; the array does not rotate.  With hi == lo a range is that value.  These ranges are defaults of the augmentation
+    - a small drone over a standing person - not measurements of any corpus.  ValueError: channels outside 1 .. 8, seconds,
+    mic_spacing or z_s negative or not finite, a range that is not a finite (lo <= hi) pair, an altitude that does not stay above
+    z_s, a speed range outside [0, 343), a miss distance below 0, beta outside [0, 1)."""
+    channels, seconds, mic_spacing, z_s = int(channels), float(seconds), float(mic_spacing), float(z_s)
+    if not 1 <= channels <= _fe.FLYBY_MAX_CHAN:
+        raise ValueError(f"draw_flyby: channels = {channels}; 1 .. {_fe.FLYBY_MAX_CHAN} microphones are supported")
+    if not (np.isfinite(seconds) and np.isfinite(mic_spacing) and np.isfinite(z_s) and seconds >= 0 and mic_spacing >= 0 and z_s >= 0):
+        raise ValueError(f"draw_flyby: seconds = {seconds}, mic_spacing = {mic_spacing} and z_s = {z_s} must be finite and >= 0")
+    altitude, speed = _flyby_range("altitude", altitude, z_s, lo_open=True), _flyby_range("speed", speed, 0.0)
+    miss, beta = _flyby_range("miss", miss, 0.0), _flyby_range("beta", beta, 0.0)
+    if not speed[1] < _fe.ISM_SOUND:
+        raise ValueError(f"draw_flyby: speed = {speed} must stay below the sound speed {_fe.ISM_SOUND} m/s")
+    if beta[0] >= 1.0 or beta[1] > 1.0:
+        raise ValueError(f"draw_flyby: beta = {beta} must stay inside [0, 1)")
+    h, s, heading = rng.uniform(*altitude), rng.uniform(*speed), rng.uniform(0.0, 2.0 * np.pi)
+    b, t_c, refl = rng.uniform(*miss), rng.uniform(0.0, seconds), rng.uniform(*beta)
+    v = np.array([s * np.cos(heading), s * np.sin(heading), 0.0])
+    closest = np.array([-b * np.sin(heading), b * np.cos(heading), h])   # the centre at t_c: abeam of the source
+    mics = np.zeros((channels, 3))
+    mics[:, 0] = mic_spacing * (np.arange(channels) - 0.5 * (channels - 1))
+    return {"p0": closest - v * t_c, "v": v, "z_s": z_s, "beta": float(refl), "mics": mics}
+
+
+def flyby(wav: torch.Tensor, geometry: dict) -> torch.Tensor:
+    """The fly-by of one [chan, samples] (or [samples]) float32 voice at 16 kHz on a ROCm device as ONE HIP launch
+    (`frontend.flyby_batch`, iris_flyby): every channel under the time-varying delay and spreading gain of its microphone of
+    `geometry` (a `draw_flyby` dict), plus the ground reflection.  Returns a new tensor of the input's shape.  CPU tensors
+    raise: there is no CPU fallback."""
+    if isinstance(wav, torch.Tensor) and wav.dim() == 1:
+        return _fe.flyby_batch([wav.unsqueeze(0)], [geometry])[0][0]
+    return _fe.flyby_batch([wav], [geometry])[0]
+
+
 def shoebox_rir(room, source, mics, rt60: float, device, n_taps=None, normalize: bool = True, sample_rate: int = 16000) -> torch.Tensor:
     """One shoebox room impulse response [chan, K] float32 on a ROCm `device` as ONE HIP launch (`frontend.shoebox_rir_batch`,
     iris_ism_rir): the image-source method for the room (L_x, L_y, L_z), the `source` and the microphones `mics` [chan, 3], the

@@ -1292,6 +1292,44 @@ int iris_ism_rir(const iris_ism_src* table_host, const void* table_dev, int n_sr
                  double sample_rate, int normalize, void* stream);
 
 /*
+ * Fly-by augmentation: a static source heard by a MOVING microphone array - the time-varying delay per channel (Doppler shift
+ * and a changing inter-channel delay), the spherical-spreading level and one ground reflection - for a RAGGED BATCH of
+ * waveforms, each with its own flight, in one launch.  The sample rate is 16 kHz, the sound speed 343 m/s.
+ * Per record: src DEVICE [channels, len] fp32, dst DEVICE [channels, len] fp32 (output channel ch is made from row ch of the
+ * source; what arrives later than the buffer is cut).  Ground plane z = 0, source at (0, 0, z_s), array centre p(t) = p0 + v t
+ * with t = n / 16000, microphone ch at p(t) + mic[ch].  Paths: p = 0 direct (a_0 = 1), p = 1 - only with n_paths == 2 - the
+ * image source (0, 0, -z_s) with a_1 = beta.  With d_p(n) the distance from the microphone at sample n to the (image) source:
+ *     pos_p(n) = n - (d_p(n) - r_ref) * (16000 / 343),       g_p(n) = a_p * r_ref / d_p(n),
+ *     y[ch, n] = sum_p g_p(n) * sum_s x[ch, s] * cut * w(cut * (s - pos_p(n))),      cut = 0.99 / (1 + |v| / 343),
+ *     w(t)     = sinc(pi t) * cos^2(pi t / 12)  for |t| < 6, else 0,     x[ch, s] = 0 outside [0, len)
+ * - the window of iris_speed_perturb at a position that moves with the flight; one cut per record is alias-safe for the whole
+ * clip, because d pos / d n <= 1 + |v| / 343.  r_ref is the caller's reference distance (the smallest direct distance of the
+ * flight: delay 0 and gain 1 at the nearest point).  d, pos, floor(pos) and the fraction are formed in double (dx, dy, dz by one
+ * fma each, d^2 by two more); the fraction and the gain are rounded once, the taps (sinf / cosf per tap), the sum in ascending s
+ * (an fma per tap) and y = fma(g_1, sum_1, g_0 * sum_0) are fp32: a fixed operation sequence per value that depends neither on
+ * the tile nor on the staging.  Against the float64 evaluation |y - ref| <= 4 u S, u = 2^-24, S = cut * sum_p |g_p| * (sum of
+ * |x[ch, s]| over the support).  An output sample whose whole support is zero input is exactly 0.  n_paths == 0 copies the
+ * source bit for bit (the geometry is not read).
+ * A record with a NULL pointer, len <= 0, len > max_len, n_paths outside 0 .. 2 or - at n_paths > 0 - a non-finite p0, v, z_s,
+ * beta, r_ref or microphone, r_ref <= 0 or |v| >= 343 is skipped (nothing written): the table lives on the device and cannot be
+ * checked here without a synchronisation.  src and dst must not overlap.
+ * Checked before any HIP call (IRIS_E_INVALID): n_src < 0, channels <= 0, NULL table with n_src > 0, max_len <= 0;
+ * IRIS_E_UNSUPPORTED: channels > IRIS_FLYBY_MAX_CHAN, n_src > 65535.  n_src == 0 returns 0 and launches nothing.
+ * One launch on `stream`; no workspace, no atomics, no synchronisation: capturable, bitwise reproducible, and a record's
+ * result does not depend on the records around it.  Runs on the current HIP device.
+ */
+#define IRIS_FLYBY_MAX_CHAN 8
+typedef struct {
+    const float* src;                      /* DEVICE [channels, len] */
+    float*  dst;                           /* DEVICE [channels, len] */
+    int32_t len, n_paths;                  /* n_paths: 0 the identity, 1 direct, 2 direct + ground reflection */
+    double  p0[3], v[3];                   /* the array centre at t = 0 (m) and its velocity (m / s) */
+    double  z_s, beta, r_ref;              /* source height, ground reflection coefficient, reference distance */
+    double  mic[IRIS_FLYBY_MAX_CHAN][3];   /* offsets from the array centre; the first `channels` rows are read */
+} iris_flyby_src;
+int iris_flyby(const void* table_dev, int n_src, int channels, int max_len, void* stream);
+
+/*
  * Inverse STFT of a RAGGED BATCH of complex spectrograms in the reference layout, in one launch: the inverse of iris_stft /
  * load_wav's Spectrogram(n_fft, power = None), i.e. torch.istft(n_fft, hop, window = periodic Hann, center = True, onesided,
  * normalized = False, length = len_out).  n_fft, hop, the channel count C and the constants come from the plan.
