@@ -302,6 +302,87 @@ extern "C" int iris_spec_whiten(iris_plan* p, const float* spec, const float* fa
     return IRIS_OK;
 }
 
+// iris_locate_events: the noise-whitened steered response of E events over a lag grid (k_locate.h, two launches); every check
+// happens before the first HIP call.  events_host is the host's copy of the device table: what is checked here.
+extern "C" int iris_locate_events(iris_plan* p, const float* spec, const float* factors, int n_blocks, const int32_t* events_dev,
+                                  const int32_t* events_host, int n_events, int batch, int n_frames, int block, int k_lo, int k_hi,
+                                  int max_lag, int q, double* workspace, size_t workspace_bytes, double* curve, int64_t* n_terms,
+                                  void* stream) {
+    const char* who = "iris_locate_events";
+    if (!p || !spec) return fail(IRIS_E_INVALID, "%s: NULL argument", who);
+    if (batch <= 0 || n_frames <= 0 || n_events < 0)
+        return fail(IRIS_E_INVALID, "%s: batch=%d n_frames=%d n_events=%d", who, batch, n_frames, n_events);
+    if (n_frames > (1 << 30)) return fail(IRIS_E_UNSUPPORTED, "%s: n_frames=%d > 2^30", who, n_frames);
+    if (reinterpret_cast<uintptr_t>(spec) & 15) return fail(IRIS_E_INVALID, "%s: spec must be 16-byte aligned", who);
+    if (k_lo < 0 || k_lo >= k_hi) return fail(IRIS_E_INVALID, "%s: bins [%d, %d) must be a non-empty range from 0 up", who, k_lo, k_hi);
+    if (q < 1 || max_lag < 0) return fail(IRIS_E_INVALID, "%s: q=%d must be >= 1 and max_lag=%d >= 0", who, q, max_lag);
+    if (q > 65536) return fail(IRIS_E_UNSUPPORTED, "%s: q=%d > 65536", who, q);
+    if (2LL * max_lag + 1 > kLocateMaxLags)
+        return fail(IRIS_E_UNSUPPORTED, "%s: %lld lags exceed the limit of %d", who, 2LL * max_lag + 1, kLocateMaxLags);
+    if (factors) {
+        if (block < 1) return fail(IRIS_E_INVALID, "%s: block=%d must be at least 1 frame", who, block);
+        if (reinterpret_cast<uintptr_t>(factors) & 15) return fail(IRIS_E_INVALID, "%s: factors must be 16-byte aligned", who);
+        block = std::min(block, n_frames);
+        if (n_blocks != (n_frames + block - 1) / block)
+            return fail(IRIS_E_INVALID, "%s: factors of %d block(s), but %d frames in blocks of %d make %d", who, n_blocks, n_frames,
+                        block, (n_frames + block - 1) / block);
+    } else {
+        block = n_frames;  // the identity: one block
+        n_blocks = 1;
+    }
+    if (n_events > 0 && (!events_dev || !events_host || !workspace || !curve || !n_terms)) return fail(IRIS_E_INVALID, "%s: NULL argument", who);
+    if ((reinterpret_cast<uintptr_t>(events_dev) & 3) || (reinterpret_cast<uintptr_t>(workspace) & 7) ||
+        (reinterpret_cast<uintptr_t>(curve) & 7) || (reinterpret_cast<uintptr_t>(n_terms) & 7))
+        return fail(IRIS_E_INVALID, "%s: the event table must be 4-byte, workspace, curve and n_terms 8-byte aligned", who);
+    long long n_seg = 0;
+    for (int e = 0; e < n_events; ++e) {
+        const int32_t* r = events_host + 4 * (size_t)e;
+        if (r[0] < 0 || r[0] >= batch) return fail(IRIS_E_INVALID, "%s: event %d names sample %d of %d", who, e, r[0], batch);
+        if (r[1] < 0 || r[1] > r[2] || r[2] >= n_frames)
+            return fail(IRIS_E_INVALID, "%s: event %d spans frames %d .. %d of %d", who, e, r[1], r[2], n_frames);
+        if (r[3] != n_seg) return fail(IRIS_E_INVALID, "%s: event %d starts at segment %d, expected %lld", who, e, r[3], n_seg);
+        n_seg += r[2] / block - r[1] / block + 1;
+        if (n_seg > 0x7fffffffLL) return fail(IRIS_E_UNSUPPORTED, "%s: more than 2^31 - 1 segments", who);
+    }
+    // (the plan is read only now: everything above is checked without it)
+    if (p->channels != 2) return fail(IRIS_E_UNSUPPORTED, "%s: the plan has %d channel(s); the delay is that of a stereo pair", who, p->channels);
+    if (p->n_bins < 2) return fail(IRIS_E_UNSUPPORTED, "%s: a plan of %d bin(s)", who, p->n_bins);
+    if (k_hi > p->n_bins) return fail(IRIS_E_INVALID, "%s: bins [%d, %d) leave [0, %d]", who, k_lo, k_hi, p->n_bins);
+    if (n_events == 0) return IRIS_OK;  // nothing to do, no launch
+    const int nk = k_hi - k_lo, lags = 2 * max_lag + 1;
+    const long long mom_waves = n_seg * nk, scan_waves = (long long)n_events * lags;
+    if (workspace_bytes / 32 < (size_t)mom_waves)
+        return fail(IRIS_E_CAPACITY, "%s: workspace of %zu bytes, %lld needed", who, workspace_bytes, 32 * mom_waves);
+    if ((mom_waves + 3) / 4 > 0x7fffffffLL || (scan_waves + 3) / 4 > 0x7fffffffLL)
+        return fail(IRIS_E_UNSUPPORTED, "%s: %lld / %lld waves exceed the grid limit", who, mom_waves, scan_waves);
+    DeviceGuard guard(p->device);
+    LocateArgs a;
+    a.spec = spec;
+    a.fac = factors;
+    a.events = events_dev;
+    a.mom = workspace;
+    a.curve = curve;
+    a.n_terms = reinterpret_cast<long long*>(n_terms);
+    a.B = batch;
+    a.F = p->n_bins;
+    a.T = n_frames;
+    a.J = n_blocks;
+    a.block = block;
+    a.E = n_events;
+    a.S = (int)n_seg;
+    a.k_lo = k_lo;
+    a.nk = nk;
+    a.N = max_lag;
+    a.q = q;
+    a.L = lags;
+    a.period = 2LL * (p->n_bins - 1) * q;  // n_fft q (a mel-only plan carries no n_fft)
+    k_locate_moments<<<dim3((unsigned)((mom_waves + 3) / 4)), 256, 0, (hipStream_t)stream>>>(a);
+    HIP_TRY(hipGetLastError());
+    k_locate_scan<<<dim3((unsigned)((scan_waves + 3) / 4)), 256, 0, (hipStream_t)stream>>>(a);
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+
 extern "C" size_t iris_minmax_log_workspace(int n_rows, size_t row_len) {
     return n_rows > 0 ? 2 * (size_t)n_rows * n_chunks_of(row_len) : 0;
 }

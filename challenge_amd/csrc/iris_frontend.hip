@@ -14,6 +14,8 @@
 //   k_magmel.h       spectrum -> mel
 //   k_ipd.h         stereo spectrum -> mel-band inter-channel phase difference (cos, sin), its own streaming kernel (opt-in)
 //   k_whiten.h      stereo spectrum -> spatially whitened mel-band energy x^H (R + d I)^-1 x, two launches (opt-in)
+//   k_locate.h      stereo spectrum + whitening factors + events -> the noise-whitened steered response over a lag grid: which
+//                    inter-channel delay, hence bearing, fits each detected event (two launches, double)
 //   k_elementwise.h  min-max / log, normalize, magnitude-phase, mask, adaptive gradient clipping
 //   k_mix.h          batched sample synthesis (merge_complex_specs)
 //   k_draw.h         the random half of a batch drawn on the device (source table, SpecAugment bands)
@@ -66,6 +68,7 @@
 #include "k_magmel.h"
 #include "k_ipd.h"
 #include "k_whiten.h"
+#include "k_locate.h"
 #include "k_elementwise.h"
 #include "host_plan.h"
 #include "k_ism.h"

@@ -3,7 +3,7 @@
     python -m challenge_amd.detect --name <run name> [--p] [--path DIR] [--wav_dir .] [--out answer.json]
                                    [--overlap_hop 512] [--score ANSWER.json]
                                    [--tune ANSWER.json --decoder_out decoder.json] [--decoder decoder.json]
-                                   [--decoder_kind pool|hmm]
+                                   [--decoder_kind pool|hmm] [--locate [--mic_spacing M] --locate_out FILE.json]
 
 `detect` runs a trained model over wav files (or in-memory recordings) and returns, per file, the events it finds in the
 forms of the reference's helpers: frame events (Challenge_Metric.get_start_end_frame), the (class, middle second) rows
@@ -826,6 +826,58 @@ class Detection:
     events: Tuple[np.ndarray, ...]     # per class [n, 2] int64 (first, last) frames   (get_start_end_frame)
     metric: np.ndarray                 # [N, 2] int32 (class, middle second)             (output_to_metric)
     answer: Tuple[np.ndarray, ...]     # per class [n, 2] int32 (start s, end s)        (get_start_end_time)
+    location: Optional[Tuple[np.ndarray, ...]] = None   # per class [n, 4] float64 (tdoa, bearing, score, contrast), row for
+                                                        # row with `events`; None unless `detect` was given `locate=`
+
+
+@dataclass
+class LocateSettings:
+    """How `detect(..., locate=)` localises every detected event (`transforms.locate_events` states the definition):
+    mic_spacing in metres between the two microphones (on a line along x, as `transforms.draw_shoebox` places them); block: the
+    frames per noise-covariance block (None: config.n_frame); loading: the covariance's diagonal loading; q: lag steps per
+    sample; f_lo_hz .. f_hi_hz: the band whose bins are steered (250 Hz is the cut `stft_filter` applies in evaluation: bin 16
+    at n_fft 1024, bin 8 at load_wav's 512); noise: 'block' (whitened by the block covariance) or 'identity' (the plain
+    steered response: finds the loudest direction); sound_speed in m/s; max_lag: lag steps either way (None: the array's
+    aperture, ceil(mic_spacing / sound_speed * 16000 * q))."""
+    mic_spacing: float = 0.1
+    block: Optional[int] = None
+    loading: float = 1e-2
+    q: int = 8
+    f_lo_hz: float = 250.0
+    f_hi_hz: float = 8000.0
+    noise: str = "block"
+    sound_speed: float = 343.0
+    max_lag: Optional[int] = None
+
+    def __post_init__(self):
+        from .frontend import LOCATE_MAX_LAGS
+        for name in ("mic_spacing", "loading", "sound_speed"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not (np.isfinite(v) and v > 0):
+                raise ValueError(f"LocateSettings: {name} = {v!r} must be a positive finite number")
+        if isinstance(self.q, bool) or not isinstance(self.q, (int, np.integer)) or not 1 <= self.q <= 65536:
+            raise ValueError(f"LocateSettings: q = {self.q!r} must be an integer in 1 .. 65536")
+        if self.block is not None and (isinstance(self.block, bool) or not isinstance(self.block, (int, np.integer)) or self.block < 1):
+            raise ValueError(f"LocateSettings: block = {self.block!r} must be None or a positive number of frames")
+        if self.noise not in ("block", "identity"):
+            raise ValueError(f"LocateSettings: noise = {self.noise!r} must be 'block' or 'identity'")
+        lo, hi = self.f_lo_hz, self.f_hi_hz
+        if not (isinstance(lo, (int, float)) and isinstance(hi, (int, float)) and np.isfinite(lo) and np.isfinite(hi) and 0 <= lo < hi):
+            raise ValueError(f"LocateSettings: f_lo_hz = {lo!r}, f_hi_hz = {hi!r} must be finite with 0 <= f_lo_hz < f_hi_hz")
+        if self.max_lag is None:
+            self.max_lag = int(np.ceil(self.mic_spacing / self.sound_speed * SR * self.q))
+        if isinstance(self.max_lag, bool) or not isinstance(self.max_lag, (int, np.integer)) or not 0 <= 2 * self.max_lag + 1 <= LOCATE_MAX_LAGS:
+            raise ValueError(f"LocateSettings: max_lag = {self.max_lag!r} must be an integer in 0 .. {(LOCATE_MAX_LAGS - 1) // 2} "
+                             f"steps of 1 / q sample")
+
+    def bins(self, n_bins: int) -> Tuple[int, int]:
+        """[k_lo, k_hi) of f_lo_hz .. f_hi_hz (inclusive) on a spectrum of n_bins bins at 16 kHz, n_fft = 2 (n_bins - 1)."""
+        n_fft = 2 * (int(n_bins) - 1)
+        k_lo = int(np.ceil(self.f_lo_hz * n_fft / SR))
+        k_hi = min(int(n_bins), int(np.floor(self.f_hi_hz * n_fft / SR)) + 1)
+        if not 0 <= k_lo < k_hi:
+            raise ValueError(f"LocateSettings: {self.f_lo_hz} .. {self.f_hi_hz} Hz holds no bin of a {n_bins}-bin spectrum at {SR} Hz")
+        return k_lo, k_hi
 
 
 class _FromEvents(M.Challenge_Metric):
@@ -869,14 +921,20 @@ def _predict(model, windows: torch.Tensor, batch_size: int) -> torch.Tensor:
     return torch.cat([model(windows[i:i + batch_size]) for i in range(0, windows.shape[0], batch_size)])
 
 
-def _groups(model, wavs_or_paths: Sequence, config, overlap_hop: int, sample_rate: int, device, max_windows: int):
+def _groups(model, wavs_or_paths: Sequence, config, overlap_hop: int, sample_rate: int, device, max_windows: int,
+            spectra: Optional[list] = None):
     """The front end of `detect`: yields groups [(name, frames, windows [W, M, n_frame, C])] of at most `max_windows` windows
-    (a longer file forms a group of its own)."""
+    (a longer file forms a group of its own).  spectra: a list that holds, while a group is out, the [F, T, 4] load_wav
+    spectra of that group's files in order, kept on the device (localisation reads them); a recording that is not stereo is
+    then a ValueError."""
     dev = _model_device(model, device)
     group, n_group = [], 0
     for name, path, wav, sr in _items(wavs_or_paths, sample_rate):
         spec = D.load_wav(path, dev) if path is not None else D.load_wav_array(wav, sr, dev)
+        if spectra is not None and spec.shape[-1] != 4:
+            raise ValueError(f"detect: locate= needs stereo recordings; {name} has {spec.shape[-1] // 2} channel(s)")
         feats = features_for_eval(spec, config)
+        kept = spec if spectra is not None else None
         del spec
         t_len = int(feats.shape[-2])
         windows = frame(feats, config.n_frame, overlap_hop, pad_end=True, axis=-2)   # [M, W, n_frame, C']
@@ -884,7 +942,11 @@ def _groups(model, wavs_or_paths: Sequence, config, overlap_hop: int, sample_rat
         if group and n_group + windows.shape[0] > max_windows:
             yield group
             group, n_group = [], 0
+            if spectra is not None:
+                del spectra[:]
         group.append((name, t_len, windows))
+        if spectra is not None:
+            spectra.append(kept)
         n_group += windows.shape[0]
     if group:
         yield group
@@ -899,27 +961,75 @@ def _group_preds(model, group, batch_size: int) -> Tuple[torch.Tensor, np.ndarra
 
 @torch.no_grad()
 def detect(model, wavs_or_paths: Sequence, config, overlap_hop: int = 512, batch_size: int = 32, sample_rate: int = SR,
-           device=None, max_windows: int = 1024, settings=None) -> List[Detection]:
+           device=None, max_windows: int = 1024, settings=None, locate: Optional[LocateSettings] = None) -> List[Detection]:
     """Events of `model` in each recording: a wav path, a (name, [chan, samples] array[, sample rate]) tuple or a bare array
     (named by its position).  Files are handled in groups of at most `max_windows` windows (a longer file forms a group of
     its own); each window's prediction does not depend on the grouping.  `settings`: per-class decoder settings (default: the
-    reference's constants for every class) - DecoderSettings for the pooling decoder, HmmSettings for the HMM decoder."""
+    reference's constants for every class) - DecoderSettings for the pooling decoder, HmmSettings for the HMM decoder.
+    `locate`: LocateSettings - every detected event is also localised (`Detection.location`: per class [n, 4] float64 (tdoa in
+    samples, bearing in degrees from broadside towards microphone 1, score, contrast), row for row with `events`) by the
+    noise-whitened steered response over the event's frames of the recording's own load_wav spectrum, whatever the run name's
+    features: per file the `whiten_factors` launch, per group one `FrontendPlan.locate` call.  The recordings must be stereo
+    (ValueError) and on a ROCm device.  It costs memory: the spectra of a group stay on the device until the group is decoded,
+    16 bytes x F x T per file, and once more, padded to the longest file, for the group's call.  Without `locate` nothing
+    changes and `location` is None."""
+    if locate is not None and not isinstance(locate, LocateSettings):
+        raise ValueError(f"detect: locate must be a LocateSettings, got {type(locate).__name__}")
     results: List[Detection] = []
-    for group in _groups(model, wavs_or_paths, config, overlap_hop, sample_rate, device, max_windows):
-        results.extend(_detect_group(model, group, config, overlap_hop, batch_size, settings))
+    spectra = [] if locate is not None else None
+    for group in _groups(model, wavs_or_paths, config, overlap_hop, sample_rate, device, max_windows, spectra):
+        results.extend(_detect_group(model, group, config, overlap_hop, batch_size, settings, locate, spectra))
     return results
 
 
-def _detect_group(model, group, config, overlap_hop: int, batch_size: int, settings=None) -> List[Detection]:
+def _locate_group(spectra, events, config, locate: LocateSettings) -> List[Tuple[np.ndarray, ...]]:
+    """`Detection.location` of every file of a group: spectra[i] the file's [F, T_i, 4] spectrum, events[i] its per-class frame
+    events.  The factors are each file's own (its last block may be short); the spectra and factors are padded to the longest
+    file - blocks start at frame 0, so the padding changes no block an event touches - and ONE `locate` call serves the
+    group.  The rows equal `transforms.locate_events` of the file alone, bit for bit."""
+    from . import transforms as T
+    rows = [(i, int(f0), int(f1)) for i, ev in enumerate(events) for cls in ev for f0, f1 in np.asarray(cls).reshape(-1, 2)]
+    out = np.zeros((0, 4), np.float64)
+    if rows:
+        n, f, t_max = len(spectra), int(spectra[0].shape[0]), max(int(sp.shape[1]) for sp in spectra)
+        block = config.n_frame if locate.block is None else int(locate.block)
+        k_lo, k_hi = locate.bins(f)
+        spec = spectra[0].float().unsqueeze(0).contiguous() if n == 1 else torch.zeros((n, f, t_max, 4), dtype=torch.float32,
+                                                                                       device=spectra[0].device)
+        plan, fac = T._locate_plan(spec), None
+        if n > 1:
+            for i, sp in enumerate(spectra):
+                spec[i, :, :sp.shape[1]] = sp
+        if locate.noise == "block":
+            blk = max(min(block, t_max), 1)
+            fac = torch.zeros((n, f, (t_max + blk - 1) // blk, 4), dtype=torch.float32, device=spec.device)
+            for i, sp in enumerate(spectra):
+                own = plan.whiten_factors(sp.float().unsqueeze(0).contiguous(), block, locate.loading)
+                fac[i, :, :own.shape[2]] = own[0]
+        curve, n_terms = plan.locate(spec, np.asarray(rows, np.int32), fac, block, k_lo, k_hi, locate.max_lag, locate.q)
+        out = T.locate_peak(curve, n_terms, locate.q, locate.mic_spacing, float(SR), locate.sound_speed)
+    res, at = [], 0
+    for ev in events:
+        per_class = []
+        for cls in ev:
+            per_class.append(out[at:at + len(cls)].copy())
+            at += len(cls)
+        res.append(tuple(per_class))
+    return res
+
+
+def _detect_group(model, group, config, overlap_hop: int, batch_size: int, settings=None, locate=None,
+                  spectra=None) -> List[Detection]:
     preds, win_off = _group_preds(model, group, batch_size)
     if isinstance(settings, HmmSettings):
         events = decode_events_hmm(preds, win_off, [t for _, t, _ in group], config.n_frame, overlap_hop, settings)
     else:
         events = decode_events(preds, win_off, [t for _, t, _ in group], config.n_frame, overlap_hop, settings=settings)
+    where = _locate_group(spectra, events, config, locate) if locate is not None else [None] * len(group)
     out = []
-    for (name, t_len, _), ev in zip(group, events):
+    for (name, t_len, _), ev, loc in zip(group, events, where):
         metric = M.output_to_metric(HOP, SR)(*ev)
-        out.append(Detection(name, t_len, ev, metric, _FromEvents(ev).get_start_end_time(None)))
+        out.append(Detection(name, t_len, ev, metric, _FromEvents(ev).get_start_end_time(None), loc))
     return out
 
 
@@ -998,6 +1108,27 @@ def write_answer(results: Sequence[Detection], path: str) -> dict:
     return answer
 
 
+def location_rows(det: Detection) -> list:
+    """[[class, first_frame, last_frame, tdoa, bearing, score, contrast], ...]: classes in order, events in `det.events`' order;
+    NaN (an event nothing contributed to) as None."""
+    if det.location is None:
+        raise ValueError(f"{det.name}: no location - run detect(..., locate=LocateSettings())")
+    rows = []
+    for c, (ev, loc) in enumerate(zip(det.events, det.location)):
+        for (f0, f1), v in zip(np.asarray(ev).reshape(-1, 2), np.asarray(loc, np.float64).reshape(-1, 4)):
+            rows.append([c, int(f0), int(f1)] + [None if np.isnan(x) else float(x) for x in v])
+    return rows
+
+
+def write_locations(results: Sequence[Detection], path: str) -> dict:
+    """{"task2_location": {name: [[class, first_frame, last_frame, tdoa, bearing, score, contrast], ...]}}: where every event
+    of `detect(..., locate=)` comes from (NaN is written as null)."""
+    where = {"task2_location": {d.name: location_rows(d) for d in results}}
+    with open(path, 'w') as f:
+        json.dump(where, f, indent=4, allow_nan=False)
+    return where
+
+
 def main(argv=None):
     from .eval import load_model, parse_name
     from .sj_train import ARGS
@@ -1017,6 +1148,11 @@ def main(argv=None):
     config.args.add_argument('--decoder_kind', type=str, default='pool', choices=['pool', 'hmm'],
                              help="which decoder --tune tunes: the reference's pooling rule or the HMM (Viterbi) decoder; with "
                                   "'hmm' and neither --tune nor --decoder, the HMM decoder runs at its defaults")
+    config.args.add_argument('--locate', action='store_true',
+                             help='also localise every detected event (stereo recordings): the noise-whitened steered response, '
+                                  'written to --locate_out')
+    config.args.add_argument('--mic_spacing', type=float, default=0.1, help='metres between the two microphones (--locate)')
+    config.args.add_argument('--locate_out', type=str, default='location.json', help='where --locate writes the locations')
     config = config.get(argv)
     if config.p:
         parse_name(config)
@@ -1039,9 +1175,13 @@ def main(argv=None):
         print(f"MEAN ER reference {tuned.mean_er_reference!r} chosen {tuned.mean_er_chosen!r} (on the tuning recordings)")
     if settings is None and config.decoder_kind == 'hmm':
         settings = HmmSettings.default(config.n_classes)
-    results = detect(model, paths, config, overlap_hop=config.overlap_hop, settings=settings)
+    locate = LocateSettings(mic_spacing=config.mic_spacing) if config.locate else None
+    results = detect(model, paths, config, overlap_hop=config.overlap_hop, settings=settings, locate=locate)
     write_answer(results, config.out)
     print(f"{len(results)} files, {sum(len(d.metric) for d in results)} events -> {config.out}")
+    if locate is not None:
+        write_locations(results, config.locate_out)
+        print(f"locations (tdoa in samples, bearing in degrees, score, contrast) -> {config.locate_out}")
     if config.score:
         with open(config.score) as f:
             gt = json.load(f)['task2_answer']

@@ -386,6 +386,61 @@ class FrontendPlan:
         N.check(rc, "iris_spec_whiten")
         return out
 
+    def locate(self, spec: torch.Tensor, events, fac: Optional[torch.Tensor] = None, block: Optional[int] = None, k_lo: int = 0,
+               k_hi: Optional[int] = None, max_lag: int = 40, q: int = 8) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Stereo complex spec [B,F,T,4] and events int32 [E,3] = (sample, first frame, last frame; frames inclusive) -> the
+        noise-whitened steered response curve [E, 2 max_lag + 1] float64 over the lags -max_lag .. max_lag in steps of 1 / q
+        sample and bins [k_lo, k_hi) (None: F), and n_terms [E] int64, both on the device (`iris_locate_events`, two launches;
+        `transforms.locate_events` states the definition).  fac: the factors [B,F,J,4] `whiten_factors` returns for `block`
+        (None: all T frames); fac=None: a = b = 1, c = 0 and one block, the plain power-weighted steered response (`block` is
+        then not used).  Every check happens before a launch: ValueError."""
+        spec = _require_device_f32(spec, "spec")
+        if self.channels != 2:
+            raise ValueError(f"locate: the plan has {self.channels} channel(s); the delay is that of a stereo pair")
+        if spec.dim() != 4 or spec.shape[1] != self.n_bins or spec.shape[3] != 4:
+            raise ValueError(f"spec must be [B, {self.n_bins}, T, 4], got {tuple(spec.shape)}")
+        if spec.data_ptr() % 16:
+            spec = spec.clone()   # (a view at an odd offset: the kernels load 16 bytes per bin)
+        b, t = int(spec.shape[0]), int(spec.shape[2])
+        k_hi = self.n_bins if k_hi is None else int(k_hi)
+        k_lo, max_lag, q = int(k_lo), int(max_lag), int(q)
+        if not 0 <= k_lo < k_hi <= self.n_bins:
+            raise ValueError(f"locate: bins [{k_lo}, {k_hi}) must be a non-empty range inside [0, {self.n_bins}]")
+        if q < 1 or max_lag < 0 or 2 * max_lag + 1 > LOCATE_MAX_LAGS:
+            raise ValueError(f"locate: q = {q} must be >= 1 and max_lag = {max_lag} in 0 .. {(LOCATE_MAX_LAGS - 1) // 2}")
+        if fac is None:
+            block, j = max(t, 1), 1
+        else:
+            fac = _require_device_f32(fac, "fac")
+            block = t if block is None else int(block)
+            if block < 1:
+                raise ValueError(f"locate: block = {block} must be at least 1 frame")
+            block = max(min(block, t), 1)
+            j = (t + block - 1) // block
+            if tuple(fac.shape) != (b, self.n_bins, j, 4) or fac.device != spec.device:
+                raise ValueError(f"locate: fac must be [{b}, {self.n_bins}, {j}, 4] on {spec.device} for blocks of {block} frames, "
+                                 f"got {tuple(fac.shape)} on {fac.device}")
+            if fac.data_ptr() % 16:
+                fac = fac.clone()
+        table = locate_table(events, block, t, b)
+        e, lags = int(table.shape[0]), 2 * max_lag + 1
+        curve = torch.empty((e, lags), dtype=torch.float64, device=spec.device)
+        n_terms = torch.empty((e,), dtype=torch.int64, device=spec.device)
+        if e == 0:
+            return curve, n_terms
+        n_seg = int(table[-1, 3]) + int(table[-1, 2]) // block - int(table[-1, 1]) // block + 1
+        work = torch.empty((n_seg, k_hi - k_lo, 4), dtype=torch.float64, device=spec.device)
+        table_dev = torch.from_numpy(table).to(spec.device, non_blocking=True)
+        with self._lock, torch.cuda.device(self.device):
+            rc = N.lib().iris_locate_events(self._handle, spec.data_ptr(), None if fac is None else fac.data_ptr(), j,
+                                            table_dev.data_ptr(), table.ctypes.data, e, b, t, block, k_lo, k_hi, max_lag, q,
+                                            work.data_ptr(), work.numel() * 8, curve.data_ptr(), n_terms.data_ptr(),
+                                            _stream_ptr(self.device))
+        N.check(rc, "iris_locate_events")
+        for x in (table_dev, work):   # (allocated here: they must outlive the kernels on this stream)
+            x.record_stream(torch.cuda.current_stream(self.device))
+        return curve, n_terms
+
     def wav_to_logmel(self, wav: torch.Tensor, minmax: bool = True, log: bool = True,
                       normalize: bool = False, t_bands=None, f_bands=None,
                       out: Optional[torch.Tensor] = None, mel_gain=None) -> torch.Tensor:
@@ -1262,6 +1317,36 @@ def _launch_records(table: np.ndarray, device: torch.device, table_dev: Optional
     if table_dev is None and dev_table.numel():
         dev_table.record_stream(torch.cuda.current_stream(device))
     return dev_table
+
+
+LOCATE_MAX_LAGS = 4097    # the lag limit of iris_locate_events (include/iris_frontend.h): max_lag <= 2048
+
+
+def locate_table(events, block: int, n_frames: int, batch: int) -> np.ndarray:
+    """The int32 [E, 4] event table of iris_locate_events from events [E, 3] = (sample, first frame, last frame; inclusive):
+    column 3 is the event's first segment, the running count of the segments of the events before it - an event is cut at the
+    boundaries of blocks of `block` frames into last // block - first // block + 1 segments.  ValueError: a shape other than
+    [E, 3], values that are not integers, a sample outside [0, batch), frames outside [0, n_frames) or first > last."""
+    ev = np.asarray(events.cpu() if torch.is_tensor(events) else events)
+    if ev.size == 0:
+        return np.zeros((0, 4), np.int32)
+    if ev.ndim != 2 or ev.shape[1] != 3 or not np.issubdtype(ev.dtype, np.integer):
+        raise ValueError(f"locate: events must be integers [E, 3] = (sample, first frame, last frame), got {ev.dtype} {ev.shape}")
+    ev, block = ev.astype(np.int64), int(block)
+    if block < 1:
+        raise ValueError(f"locate: block = {block} must be at least 1 frame")
+    bad = np.flatnonzero((ev[:, 0] < 0) | (ev[:, 0] >= batch) | (ev[:, 1] < 0) | (ev[:, 1] > ev[:, 2]) | (ev[:, 2] >= n_frames))
+    if bad.size:
+        i = int(bad[0])
+        raise ValueError(f"locate: event {i} = (sample {ev[i, 0]}, frames {ev[i, 1]} .. {ev[i, 2]}) does not fit {batch} sample(s) of "
+                         f"{n_frames} frames with first <= last")
+    n_seg = ev[:, 2] // block - ev[:, 1] // block + 1
+    if int(n_seg.sum()) > 2 ** 31 - 1:
+        raise ValueError("locate: more than 2^31 - 1 segments")
+    table = np.empty((len(ev), 4), np.int32)
+    table[:, :3] = ev
+    table[:, 3] = np.concatenate([[0], np.cumsum(n_seg)[:-1]])
+    return table
 
 
 def phase_vocoder_launch(table: np.ndarray, n_bins: int, chan2: int, max_out_frames: int, device: torch.device,

@@ -382,6 +382,107 @@ def mel_whiten(spec: torch.Tensor, mel_matrix, block=None, loading: float = WHIT
     return out if spec.dim() == 4 else out[0]
 
 
+LOCATE_SOUND = _fe.ISM_SOUND   # 343 m/s, the constant of the room and fly-by simulations
+
+
+def locate_peak(curve, n_terms, q: int = 8, mic_spacing: float = 0.1, sample_rate: float = 16000.0,
+                sound_speed: float = LOCATE_SOUND) -> np.ndarray:
+    """The peak of steered-response curves [E, 2 N + 1] (lags -N .. N in steps of 1 / q sample) with their n_terms [E] ->
+    float64 [E, 4] = (tdoa, bearing, score, contrast), host arithmetic in float64:
+        i = the first argmax; for an interior i the parabola through i - 1, i, i + 1 gives the offset
+        (y[i - 1] - y[i + 1]) / (2 (y[i - 1] - 2 y[i] + y[i + 1])), clipped to +-0.5 (a zero denominator, or i at either end
+        of the grid: 0);  tdoa = (i - N + offset) / q samples, positive when channel 1 hears the event later
+        bearing = degrees(asin(clip(-tdoa sound_speed / (sample_rate mic_spacing), -1, 1))), from broadside towards
+        microphone 1 (+x, as `draw_shoebox` places it)
+        score = curve[i] / n_terms,  contrast = (curve[i] - median(curve)) / n_terms
+    n_terms == 0 (nothing contributed): tdoa and bearing NaN, score and contrast 0.  A pair cannot tell front from back: the
+    bearing is that of the cone's trace, mirrored about the microphones' axis."""
+    y = np.asarray(curve.cpu() if torch.is_tensor(curve) else curve, np.float64)
+    n_t = np.asarray(n_terms.cpu() if torch.is_tensor(n_terms) else n_terms, np.int64).reshape(-1)
+    q, mic_spacing, sample_rate, sound_speed = int(q), float(mic_spacing), float(sample_rate), float(sound_speed)
+    if y.ndim != 2 or y.shape[1] % 2 != 1 or y.shape[0] != n_t.shape[0]:
+        raise ValueError(f"locate_peak: curve must be [E, 2 N + 1] and n_terms [E], got {y.shape} and {n_t.shape}")
+    if q < 1 or not (np.isfinite(mic_spacing) and mic_spacing > 0 and np.isfinite(sample_rate) and sample_rate > 0
+                     and np.isfinite(sound_speed) and sound_speed > 0):
+        raise ValueError(f"locate_peak: q = {q} must be >= 1 and mic_spacing = {mic_spacing}, sample_rate = {sample_rate}, "
+                         f"sound_speed = {sound_speed} positive and finite")
+    n_ev, lags = y.shape
+    n = (lags - 1) // 2
+    out = np.zeros((n_ev, 4), np.float64)
+    for r in range(n_ev):
+        if n_t[r] == 0:
+            out[r, :2] = np.nan
+            continue
+        i = int(np.argmax(y[r]))
+        off = 0.0
+        if 0 < i < lags - 1:
+            den = 2.0 * (y[r, i - 1] - 2.0 * y[r, i] + y[r, i + 1])
+            if den != 0.0:
+                off = float(np.clip((y[r, i - 1] - y[r, i + 1]) / den, -0.5, 0.5))
+        tdoa = (i - n + off) / q
+        out[r, 0] = tdoa
+        out[r, 1] = np.degrees(np.arcsin(np.clip(-tdoa * sound_speed / (sample_rate * mic_spacing), -1.0, 1.0)))
+        out[r, 2] = y[r, i] / n_t[r]
+        out[r, 3] = (y[r, i] - np.median(y[r])) / n_t[r]
+    return out
+
+
+_LOCATE_PLANS = {}
+
+
+def _locate_plan(x: torch.Tensor):
+    """The cached stereo `FrontendPlan` of `locate_events` for the device of `x`, its bins and its batch."""
+    f, b = int(x.shape[1]), int(x.shape[0])
+    key = (x.device.index, f)
+    plan = _LOCATE_PLANS.get(key)
+    if plan is None or plan.max_batch < b:
+        w = np.ones((f, 1), np.float32)   # (the localisation reads no mel matrix)
+        plan = _LOCATE_PLANS[key] = _fe.FrontendPlan.mel_only(1, f, 2, max(b, 1), x.device, w)
+    return plan
+
+
+def locate_events(spec: torch.Tensor, events, block=None, loading: float = WHITEN_LOADING, noise: str = "block", k_lo: int = 0,
+                  k_hi=None, max_lag: int = 40, q: int = 8, mic_spacing: float = 0.1, sample_rate: float = 16000.0,
+                  sound_speed: float = LOCATE_SOUND) -> np.ndarray:
+    """Where each event comes from: the noise-whitened steered response of a two-microphone delay vector over the event's
+    frames, and its peak.  spec: a STEREO complex spectrum [B, F, T, 4] (or [F, T, 4]) = (re0, re1, im0, im1) on a ROCm device,
+    n_fft = 2 (F - 1); events: integers [E, 3] = (sample, first frame, last frame), frames inclusive, 0 <= first <= last < T.
+    Definition, in float64 (`tests/locate_ref.py` restates it in NumPy).  Frames are grouped into blocks of `block` frames
+    (None: all T) and (a, b, c) are `mel_whiten`'s factors of the block's inter-channel covariance with `loading`
+    (noise="block"), or a = b = 1, c = 0 with one block (noise="identity": the plain power-weighted steered response, which
+    finds the LOUDEST direction).  An event is cut at block boundaries into segments j = first // block .. last // block.  For
+    one segment and one bin k in [k_lo, k_hi) (None: F), with (a, b, c) of (sample, k, j):
+        a == 0 (a silent block): the pair contributes nothing; otherwise over the segment's frames
+        z0 = a X0,  z1 = b (X1 - c X0),  p00 = sum |z0|^2,  p11 = sum |z1|^2,  p10 = sum z1 conj(z0)
+    and for the lag n of the grid -max_lag .. max_lag (steps of 1 / q sample)
+        e = exp(-i 2 pi k n / (n_fft q))      (a positive delay: channel 1 hears the event later)
+        s0 = a,  s1 = b (e - c)               (the steering vector [1, e], whitened)
+        term = (a^2 p00 + |s1|^2 p11 + 2 a Re(conj(s1) p10)) / (a^2 + |s1|^2)        = sum_t |s^H z|^2 / (s^H s)
+    curve[E, 2 max_lag + 1] is the sum of the terms over the event's segments and bins, n_terms[E] the sum over the
+    contributing (segment, bin) pairs of the segment's frame count: under noise alone curve / n_terms is near 1.  Returns
+    `locate_peak` of the curves: float64 [E, 4] = (tdoa in samples, bearing in degrees, score, contrast).
+    The launches are `FrontendPlan.whiten_factors` (noise="block") and `FrontendPlan.locate`; there is no CPU fallback.
+    What it cannot do: a pair cannot tell front from back (the bearing is mirrored about the microphones' axis); the block
+    covariance includes the event, so an event that dominates its block partly nulls itself; and the estimate is biased
+    towards the interferer when the two delays are within about a sample of each other (with two microphones one degree of
+    freedom is left after the null)."""
+    if noise not in ("block", "identity"):
+        raise ValueError(f"locate_events: noise = {noise!r} must be 'block' or 'identity'")
+    if not isinstance(spec, torch.Tensor):
+        raise TypeError(f"spec must be a torch.Tensor, got {type(spec).__name__}")
+    x = spec if spec.dim() == 4 else spec.unsqueeze(0)
+    if x.dim() != 4 or x.shape[-1] != 4 or x.shape[1] < 2:
+        raise ValueError(f"locate_events: spec must be [B, F >= 2, T, 4] (a stereo complex spectrum), got {tuple(spec.shape)}")
+    if not x.is_cuda:
+        raise RuntimeError(f"locate_events: spec is on {x.device}: the localisation runs only as HIP kernels on a ROCm device "
+                           "(there is no CPU fallback); move the tensor to 'cuda'")
+    x = x.float().contiguous()
+    plan = _locate_plan(x)
+    fac = plan.whiten_factors(x, block, loading) if noise == "block" else None
+    curve, n_terms = plan.locate(x, events, fac, block, k_lo, k_hi, max_lag, q)
+    return locate_peak(curve, n_terms, q, mic_spacing, sample_rate, sound_speed)
+
+
 def log_magphase(specs: torch.Tensor, labels=None, n_chan: int = 2):
     """ln(x + EPSILON) on the first n_chan trailing channels, the rest passes through
     (transforms.py:80-86)."""

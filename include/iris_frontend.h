@@ -281,6 +281,39 @@ int iris_spec_whiten(iris_plan* plan, const float* spec, const float* factors, f
                      const int32_t* f_bands, int n_f_bands, void* stream);
 
 /*
+ * Event localisation (k_locate.h): the noise-whitened steered response of a two-microphone delay vector over the frames of
+ * detected events - the adaptive matched filter the whitening factors above were built for.
+ * spec: a STEREO complex spectrum [batch, n_bins, n_frames, 4] = (re0, re1, im0, im1); factors: [batch, n_bins, n_blocks, 4]
+ * = (a, b, Re c, Im c) as iris_spec_whiten_factors writes them for blocks of `block` frames (block > n_frames counts as
+ * n_frames), or NULL: a = b = 1, c = 0 and one block - the plain power-weighted steered response (`block` and `n_blocks` are
+ * then not used).  Events: int32 [n_events, 4] = (sample, first frame, last frame, first segment), frames inclusive, once on
+ * the device (events_dev, what the kernels read) and once on the host (events_host, what is checked here): an event is cut
+ * at block boundaries into the segments j = first / block .. last / block, and `first segment` is the running count of the
+ * segments of the events before it.  Lags n = -max_lag .. max_lag in steps of 1 / q sample, bins [k_lo, k_hi).
+ * Per (segment, bin k) with (a, b, c) = factors[sample, k, j], a != 0 (a == 0, a silent block, contributes nothing):
+ *     z0 = a X0,  z1 = b (X1 - c X0),  p00 = sum |z0|^2,  p11 = sum |z1|^2,  p10 = sum z1 conj(z0)   over the segment's frames
+ *     e = exp(-i 2 pi k n / (n_fft q))   (a positive delay: channel 1 hears it later),  s1 = b (e - c)
+ *     term = (a^2 p00 + |s1|^2 p11 + 2 a Re(conj(s1) p10)) / (a^2 + |s1|^2)      ( = sum_t |s^H z|^2 / (s^H s), s = [a, s1])
+ * curve [n_events, 2 max_lag + 1] double: the sum of the terms over the event's segments and bins; n_terms [n_events] int64:
+ * the sum over the contributing (segment, bin) pairs of the segment's frame count (curve / n_terms is near 1 under noise
+ * alone).  Everything is accumulated in double from the fp32 inputs; against the float64 definition from the same inputs
+ * |curve - exact| <= (n_l + n_s + 72) 2^-53 sum A, A a term's magnitude with nothing cancelled (k_locate.h), n_l =
+ * ceil(longest segment / 64), n_s = segments of the event x ceil((k_hi - k_lo) / 64).
+ * workspace: DEVICE scratch of 32 bytes x (segments of all events) x (k_hi - k_lo), 8-byte aligned.
+ * Refused before any HIP call: NULL plan or spec, empty shapes, n_events < 0, spec or factors not 16-byte aligned, block < 1
+ * or n_blocks != ceil(n_frames / block) (with factors), a bin range that is empty or leaves [0, n_bins], q < 1, max_lag < 0
+ * (IRIS_E_INVALID); a plan whose channel count is not 2, more than 4097 lags (max_lag > 2048), q > 65536, n_frames > 2^30
+ * (IRIS_E_UNSUPPORTED); then, with n_events > 0: NULL or misaligned tables and outputs, an event naming a sample outside
+ * [0, batch), frames outside [0, n_frames) or first > last, a `first segment` that is not the running count (IRIS_E_INVALID),
+ * a workspace that is too small (IRIS_E_CAPACITY).  n_events == 0 returns IRIS_OK without a launch.  Two launches on `stream`,
+ * no atomics, fixed summation orders: bitwise reproducible, and an event's row depends on no other event or sample of the call.
+ */
+int iris_locate_events(iris_plan* plan, const float* spec, const float* factors, int n_blocks, const int32_t* events_dev,
+                       const int32_t* events_host, int n_events, int batch, int n_frames, int block, int k_lo, int k_hi,
+                       int max_lag, int q, double* workspace, size_t workspace_bytes, double* curve, int64_t* n_terms,
+                       void* stream);
+
+/*
  * minmax + log_on_mel (data_utils.py:37-55; fused twin trainer.py:63-77),
  * in place on x[n_rows, row_len]: per row (x - min) / max(max - min, eps_div)
  * when do_minmax, then ln(x + eps_log) when do_log.  A batched [B,M,T,C] tensor
