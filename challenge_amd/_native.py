@@ -93,6 +93,7 @@ SIGNATURES = {
     "iris_spec_whiten_factors": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, C.c_double, _vp]),
     "iris_spec_whiten": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     "iris_locate_events": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
+    "iris_beamform_events": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "iris_filter_draw": (_i, [_i, _i, _i, _i, _i, _i, _f, _f, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "iris_crop_windows": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "iris_crop_draw": (_i, [_vp, _i, _i, C.c_uint64, _vp, _vp, _vp]),

@@ -16,6 +16,8 @@
 //   k_whiten.h      stereo spectrum -> spatially whitened mel-band energy x^H (R + d I)^-1 x, two launches (opt-in)
 //   k_locate.h      stereo spectrum + whitening factors + events -> the noise-whitened steered response over a lag grid: which
 //                    inter-channel delay, hence bearing, fits each detected event (two launches, double)
+//   k_beamform.h    stereo spectrum + whitening factors + events + delays -> the MVDR-beamformed spectrum of each event, one
+//                    [F, T_e, 2] slab per event in iris_istft's record layout (one streaming launch)
 //   k_elementwise.h  min-max / log, normalize, magnitude-phase, mask, adaptive gradient clipping
 //   k_mix.h          batched sample synthesis (merge_complex_specs)
 //   k_draw.h         the random half of a batch drawn on the device (source table, SpecAugment bands)
@@ -69,6 +71,7 @@
 #include "k_ipd.h"
 #include "k_whiten.h"
 #include "k_locate.h"
+#include "k_beamform.h"
 #include "k_elementwise.h"
 #include "host_plan.h"
 #include "k_ism.h"

@@ -4,6 +4,7 @@
                                    [--overlap_hop 512] [--score ANSWER.json]
                                    [--tune ANSWER.json --decoder_out decoder.json] [--decoder decoder.json]
                                    [--decoder_kind pool|hmm] [--locate [--mic_spacing M] --locate_out FILE.json]
+                                   [--extract DIR [--extract_context S]]    (with --locate)
 
 `detect` runs a trained model over wav files (or in-memory recordings) and returns, per file, the events it finds in the
 forms of the reference's helpers: frame events (Challenge_Metric.get_start_end_frame), the (class, middle second) rows
@@ -828,6 +829,27 @@ class Detection:
     answer: Tuple[np.ndarray, ...]     # per class [n, 2] int32 (start s, end s)        (get_start_end_time)
     location: Optional[Tuple[np.ndarray, ...]] = None   # per class [n, 4] float64 (tdoa, bearing, score, contrast), row for
                                                         # row with `events`; None unless `detect` was given `locate=`
+    audio: Optional[Tuple[List[np.ndarray], ...]] = None   # per class a list of 1-D float32 arrays, row for row with `events`: the
+                                                           # beamformed sound of each event; None unless `detect` was given `extract=`
+    audio_span: Optional[Tuple[np.ndarray, ...]] = None    # per class [n, 2] int64 (first, last) sample of the recording each clip
+                                                           # stands for (the event widened by the context)
+
+
+@dataclass
+class ExtractSettings:
+    """How `detect(..., locate=, extract=)` extracts the sound of every detected event (`transforms.extract_events` states the
+    definition): context_s, the seconds of recording kept on either side of an event (clipped to the recording).  Block,
+    loading, noise and bins are `locate`'s."""
+    context_s: float = 0.25
+
+    def __post_init__(self):
+        v = self.context_s
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not (np.isfinite(v) and v >= 0):
+            raise ValueError(f"ExtractSettings: context_s = {v!r} must be a finite number of seconds >= 0")
+
+    def frames(self, hop: int = HOP) -> int:
+        """The context in frames of `hop` samples at 16 kHz, rounded to the nearest frame."""
+        return int(round(self.context_s * SR / hop))
 
 
 @dataclass
@@ -961,7 +983,8 @@ def _group_preds(model, group, batch_size: int) -> Tuple[torch.Tensor, np.ndarra
 
 @torch.no_grad()
 def detect(model, wavs_or_paths: Sequence, config, overlap_hop: int = 512, batch_size: int = 32, sample_rate: int = SR,
-           device=None, max_windows: int = 1024, settings=None, locate: Optional[LocateSettings] = None) -> List[Detection]:
+           device=None, max_windows: int = 1024, settings=None, locate: Optional[LocateSettings] = None,
+           extract: Optional[ExtractSettings] = None) -> List[Detection]:
     """Events of `model` in each recording: a wav path, a (name, [chan, samples] array[, sample rate]) tuple or a bare array
     (named by its position).  Files are handled in groups of at most `max_windows` windows (a longer file forms a group of
     its own); each window's prediction does not depend on the grouping.  `settings`: per-class decoder settings (default: the
@@ -972,21 +995,37 @@ def detect(model, wavs_or_paths: Sequence, config, overlap_hop: int = 512, batch
     features: per file the `whiten_factors` launch, per group one `FrontendPlan.locate` call.  The recordings must be stereo
     (ValueError) and on a ROCm device.  It costs memory: the spectra of a group stay on the device until the group is decoded,
     16 bytes x F x T per file, and once more, padded to the longest file, for the group's call.  Without `locate` nothing
-    changes and `location` is None."""
+    changes and `location` is None.
+    `extract`: ExtractSettings, only with `locate` (ValueError otherwise) - every detected event's sound is also extracted
+    (`Detection.audio`: per class a list of float32 arrays, row for row with `events`; `Detection.audio_span`: per class [n, 2]
+    int64, the sample range of the recording each clip stands for): the event, widened by `context_s` a side, through the MVDR
+    beamformer steered at the event's own `location[:, 0]` with `locate`'s block, loading, noise and bins, then the inverse
+    STFT (`transforms.extract_events`), on `load_wav`'s scale (wav / (10 rms)).  It reuses the group's spectra and factors: per
+    group one `FrontendPlan.beamform` launch, one `iris_istft` launch and one copy back.  An event whose delay is NaN gives an
+    all-zero clip.  Without `extract` nothing changes and `audio` is None."""
     if locate is not None and not isinstance(locate, LocateSettings):
         raise ValueError(f"detect: locate must be a LocateSettings, got {type(locate).__name__}")
+    if extract is not None and not isinstance(extract, ExtractSettings):
+        raise ValueError(f"detect: extract must be an ExtractSettings, got {type(extract).__name__}")
+    if extract is not None and locate is None:
+        raise ValueError("detect: extract= steers every event at its own delay: it needs locate=LocateSettings(...)")
     results: List[Detection] = []
     spectra = [] if locate is not None else None
     for group in _groups(model, wavs_or_paths, config, overlap_hop, sample_rate, device, max_windows, spectra):
-        results.extend(_detect_group(model, group, config, overlap_hop, batch_size, settings, locate, spectra))
+        results.extend(_detect_group(model, group, config, overlap_hop, batch_size, settings, locate, spectra, extract))
     return results
 
 
-def _locate_group(spectra, events, config, locate: LocateSettings) -> List[Tuple[np.ndarray, ...]]:
+def _locate_group(spectra, events, config, locate: LocateSettings, extract: Optional[ExtractSettings] = None):
     """`Detection.location` of every file of a group: spectra[i] the file's [F, T_i, 4] spectrum, events[i] its per-class frame
     events.  The factors are each file's own (its last block may be short); the spectra and factors are padded to the longest
     file - blocks start at frame 0, so the padding changes no block an event touches - and ONE `locate` call serves the
-    group.  The rows equal `transforms.locate_events` of the file alone, bit for bit."""
+    group.  The rows equal `transforms.locate_events` of the file alone, bit for bit.
+    With `extract` also `Detection.audio` and `Detection.audio_span` of every file (else None each): every event, widened by
+    the context inside its OWN file's frames, goes through one `beamform` call over the same padded spectra and factors,
+    steered at the delay just found, one `iris_istft` launch and one copy back; a frame's value depends on its sample, frame,
+    bin and delay only, so the clips equal `transforms.extract_events` of the file alone, bit for bit.
+    Returns (locations, audio, spans), one entry per file."""
     from . import transforms as T
     rows = [(i, int(f0), int(f1)) for i, ev in enumerate(events) for cls in ev for f0, f1 in np.asarray(cls).reshape(-1, 2)]
     out = np.zeros((0, 4), np.float64)
@@ -1008,28 +1047,42 @@ def _locate_group(spectra, events, config, locate: LocateSettings) -> List[Tuple
                 fac[i, :, :own.shape[2]] = own[0]
         curve, n_terms = plan.locate(spec, np.asarray(rows, np.int32), fac, block, k_lo, k_hi, locate.max_lag, locate.q)
         out = T.locate_peak(curve, n_terms, locate.q, locate.mic_spacing, float(SR), locate.sound_speed)
-    res, at = [], 0
+        if extract is not None:
+            wide = T.widen_events(np.asarray(rows, np.int64), extract.frames(f - 1),
+                                  np.asarray([int(spectra[i].shape[1]) for i, _, _ in rows], np.int64))
+            _, flat = T.clips_from_slabs(plan.beamform(spec, wide, out[:, 0], fac, block, k_lo, k_hi))
+            samples = flat.cpu().numpy()                                   # the one copy back of the group
+            spans = wide[:, 1:] * (f - 1)                                  # load_wav's hop: n_fft // 2 = F - 1
+            ends = np.cumsum(spans[:, 1] - spans[:, 0])
+            clips = [samples[z - n:z].copy() for z, n in zip(ends, spans[:, 1] - spans[:, 0])]
+    res, audio, where, at = [], [], [], 0
     for ev in events:
-        per_class = []
+        per_class, per_audio, per_span = [], [], []
         for cls in ev:
             per_class.append(out[at:at + len(cls)].copy())
+            if extract is not None:
+                per_audio.append(clips[at:at + len(cls)] if rows else [])
+                per_span.append(spans[at:at + len(cls)].copy() if rows else np.zeros((0, 2), np.int64))
             at += len(cls)
         res.append(tuple(per_class))
-    return res
+        audio.append(tuple(per_audio) if extract is not None else None)
+        where.append(tuple(per_span) if extract is not None else None)
+    return res, audio, where
 
 
 def _detect_group(model, group, config, overlap_hop: int, batch_size: int, settings=None, locate=None,
-                  spectra=None) -> List[Detection]:
+                  spectra=None, extract=None) -> List[Detection]:
     preds, win_off = _group_preds(model, group, batch_size)
     if isinstance(settings, HmmSettings):
         events = decode_events_hmm(preds, win_off, [t for _, t, _ in group], config.n_frame, overlap_hop, settings)
     else:
         events = decode_events(preds, win_off, [t for _, t, _ in group], config.n_frame, overlap_hop, settings=settings)
-    where = _locate_group(spectra, events, config, locate) if locate is not None else [None] * len(group)
+    none = [None] * len(group)
+    where, audio, spans = _locate_group(spectra, events, config, locate, extract) if locate is not None else (none, none, none)
     out = []
-    for (name, t_len, _), ev, loc in zip(group, events, where):
+    for (name, t_len, _), ev, loc, clips, span in zip(group, events, where, audio, spans):
         metric = M.output_to_metric(HOP, SR)(*ev)
-        out.append(Detection(name, t_len, ev, metric, _FromEvents(ev).get_start_end_time(None), loc))
+        out.append(Detection(name, t_len, ev, metric, _FromEvents(ev).get_start_end_time(None), loc, clips, span))
     return out
 
 
@@ -1129,6 +1182,29 @@ def write_locations(results: Sequence[Detection], path: str) -> dict:
     return where
 
 
+def write_extracts(results: Sequence[Detection], out_dir: str) -> dict:
+    """Every clip of `detect(..., locate=, extract=)` as out_dir/<recording>_c<class>_<row>.wav - mono, float32, 16 kHz, on
+    load_wav's scale (the recording divided by 10 times its rms) - and out_dir/extract.json = {"task2_extract": {name: [[class,
+    row, file, start sample, end sample, tdoa, bearing], ...]}} (NaN is written as null)."""
+    from scipy.io import wavfile
+    os.makedirs(out_dir, exist_ok=True)
+    index = {}
+    for d in results:
+        if d.audio is None or d.audio_span is None or d.location is None:
+            raise ValueError(f"{d.name}: no audio - run detect(..., locate=LocateSettings(), extract=ExtractSettings())")
+        stem, rows = os.path.splitext(os.path.basename(d.name))[0], []
+        for c, (clips, spans, loc) in enumerate(zip(d.audio, d.audio_span, d.location)):
+            for r, (clip, span, v) in enumerate(zip(clips, np.asarray(spans).reshape(-1, 2), np.asarray(loc, np.float64).reshape(-1, 4))):
+                name = f"{stem}_c{c}_{r}.wav"
+                wavfile.write(os.path.join(out_dir, name), SR, np.ascontiguousarray(clip, np.float32))
+                rows.append([c, r, name, int(span[0]), int(span[1])] + [None if np.isnan(x) else float(x) for x in v[:2]])
+        index[d.name] = rows
+    index = {"task2_extract": index}
+    with open(os.path.join(out_dir, "extract.json"), 'w') as f:
+        json.dump(index, f, indent=4, allow_nan=False)
+    return index
+
+
 def main(argv=None):
     from .eval import load_model, parse_name
     from .sj_train import ARGS
@@ -1153,7 +1229,16 @@ def main(argv=None):
                                   'written to --locate_out')
     config.args.add_argument('--mic_spacing', type=float, default=0.1, help='metres between the two microphones (--locate)')
     config.args.add_argument('--locate_out', type=str, default='location.json', help='where --locate writes the locations')
+    config.args.add_argument('--extract', type=str, default=None, metavar='DIR',
+                             help='with --locate: also write the beamformed sound of every detected event to '
+                                  'DIR/<recording>_c<class>_<row>.wav (mono, float32, 16 kHz, on load_wav\'s scale: the recording '
+                                  'divided by 10 times its rms) and DIR/extract.json')
+    config.args.add_argument('--extract_context', type=float, default=0.25, metavar='S',
+                             help='seconds of recording kept on either side of an event (--extract)')
+    parser = config.args
     config = config.get(argv)
+    if config.extract is not None and not config.locate:
+        parser.error("--extract steers every event at its own delay: it needs --locate")
     if config.p:
         parse_name(config)
     if config.tune and config.decoder:
@@ -1176,12 +1261,16 @@ def main(argv=None):
     if settings is None and config.decoder_kind == 'hmm':
         settings = HmmSettings.default(config.n_classes)
     locate = LocateSettings(mic_spacing=config.mic_spacing) if config.locate else None
-    results = detect(model, paths, config, overlap_hop=config.overlap_hop, settings=settings, locate=locate)
+    extract = ExtractSettings(context_s=config.extract_context) if config.extract is not None else None
+    results = detect(model, paths, config, overlap_hop=config.overlap_hop, settings=settings, locate=locate, extract=extract)
     write_answer(results, config.out)
     print(f"{len(results)} files, {sum(len(d.metric) for d in results)} events -> {config.out}")
     if locate is not None:
         write_locations(results, config.locate_out)
         print(f"locations (tdoa in samples, bearing in degrees, score, contrast) -> {config.locate_out}")
+    if extract is not None:
+        write_extracts(results, config.extract)
+        print(f"{sum(len(c) for d in results for c in d.audio)} clips (mono float32, load_wav's scale) and extract.json -> {config.extract}")
     if config.score:
         with open(config.score) as f:
             gt = json.load(f)['task2_answer']

@@ -11,7 +11,7 @@ import math
 import os
 import threading
 import weakref
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -440,6 +440,63 @@ class FrontendPlan:
         for x in (table_dev, work):   # (allocated here: they must outlive the kernels on this stream)
             x.record_stream(torch.cuda.current_stream(self.device))
         return curve, n_terms
+
+    def beamform(self, spec: torch.Tensor, events, tdoa, fac: Optional[torch.Tensor] = None, block: Optional[int] = None,
+                 k_lo: int = 0, k_hi: Optional[int] = None) -> List[torch.Tensor]:
+        """Stereo complex spec [B,F,T,4], events int [E,3] = (sample, first frame, last frame; frames inclusive) and their
+        delays tdoa [E] (samples, float64; positive: channel 1 hears the event later - `locate_peak`'s sign) -> the list of the
+        events' MVDR-beamformed spectra, [F, T_e, 2] = (Re Y, Im Y) float32 each (T_e = last - first + 1; `iris_istft`'s record
+        layout for one channel), views of ONE flat device buffer (`iris_beamform_events`, one launch; `transforms.extract_events`
+        states the definition).  fac: the factors [B,F,J,4] `whiten_factors` returns for `block` (None: all T frames);
+        fac=None: a = b = 1, c = 0 and one block, the delay-and-sum beamformer (`block` is then not used).  Bins outside
+        [k_lo, k_hi) (None: F), silent blocks and events whose delay is not finite are exactly 0.  Every check happens before a
+        launch: ValueError."""
+        spec = _require_device_f32(spec, "spec")
+        if self.channels != 2:
+            raise ValueError(f"beamform: the plan has {self.channels} channel(s); the delay is that of a stereo pair")
+        if spec.dim() != 4 or spec.shape[1] != self.n_bins or spec.shape[3] != 4:
+            raise ValueError(f"spec must be [B, {self.n_bins}, T, 4], got {tuple(spec.shape)}")
+        if spec.data_ptr() % 16:
+            spec = spec.clone()   # (a view at an odd offset: the kernel loads 16 bytes per bin)
+        b, t = int(spec.shape[0]), int(spec.shape[2])
+        k_hi = self.n_bins if k_hi is None else int(k_hi)
+        k_lo = int(k_lo)
+        if not 0 <= k_lo < k_hi <= self.n_bins:
+            raise ValueError(f"beamform: bins [{k_lo}, {k_hi}) must be a non-empty range inside [0, {self.n_bins}]")
+        if fac is None:
+            block, j = max(t, 1), 1
+        else:
+            fac = _require_device_f32(fac, "fac")
+            block = t if block is None else int(block)
+            if block < 1:
+                raise ValueError(f"beamform: block = {block} must be at least 1 frame")
+            block = max(min(block, t), 1)
+            j = (t + block - 1) // block
+            if tuple(fac.shape) != (b, self.n_bins, j, 4) or fac.device != spec.device:
+                raise ValueError(f"beamform: fac must be [{b}, {self.n_bins}, {j}, 4] on {spec.device} for blocks of {block} frames, "
+                                 f"got {tuple(fac.shape)} on {fac.device}")
+            if fac.data_ptr() % 16:
+                fac = fac.clone()
+        table = beamform_table(events, t, b)
+        e = int(table.shape[0])
+        delays = np.ascontiguousarray(np.asarray(tdoa.cpu() if torch.is_tensor(tdoa) else tdoa, np.float64).reshape(-1))
+        if delays.shape[0] != e:
+            raise ValueError(f"beamform: {delays.shape[0]} delay(s) for {e} event(s)")
+        if e == 0:
+            return []
+        frames = (table[:, 2] - table[:, 1] + 1).astype(np.int64)
+        per = 2 * self.n_bins
+        flat = torch.empty((per * int(frames.sum()),), dtype=torch.float32, device=spec.device)
+        table_dev = torch.from_numpy(table).to(spec.device, non_blocking=True)
+        tdoa_dev = torch.from_numpy(delays).to(spec.device, non_blocking=True)
+        with self._lock, torch.cuda.device(self.device):
+            rc = N.lib().iris_beamform_events(self._handle, spec.data_ptr(), None if fac is None else fac.data_ptr(), j,
+                                              table_dev.data_ptr(), table.ctypes.data, tdoa_dev.data_ptr(), e, b, t, block, k_lo,
+                                              k_hi, flat.data_ptr(), flat.numel(), _stream_ptr(self.device))
+        N.check(rc, "iris_beamform_events")
+        for x in (table_dev, tdoa_dev, spec) + (() if fac is None else (fac,)):   # (they must outlive the kernel on this stream)
+            x.record_stream(torch.cuda.current_stream(self.device))
+        return [flat[per * int(o):per * int(o + n)].view(self.n_bins, int(n), 2) for o, n in zip(table[:, 3], frames)]
 
     def wav_to_logmel(self, wav: torch.Tensor, minmax: bool = True, log: bool = True,
                       normalize: bool = False, t_bands=None, f_bands=None,
@@ -1346,6 +1403,31 @@ def locate_table(events, block: int, n_frames: int, batch: int) -> np.ndarray:
     table = np.empty((len(ev), 4), np.int32)
     table[:, :3] = ev
     table[:, 3] = np.concatenate([[0], np.cumsum(n_seg)[:-1]])
+    return table
+
+
+def beamform_table(events, n_frames: int, batch: int) -> np.ndarray:
+    """The int32 [E, 4] event table of iris_beamform_events from events [E, 3] = (sample, first frame, last frame; inclusive):
+    column 3 is the event's first output frame, the running count of the frames of the events before it (slab e starts at
+    float 2 F x column 3).  ValueError: a shape other than [E, 3], values that are not integers, a sample outside [0, batch),
+    frames outside [0, n_frames), first > last, or more than 2^31 - 1 output frames."""
+    ev = np.asarray(events.cpu() if torch.is_tensor(events) else events)
+    if ev.size == 0:
+        return np.zeros((0, 4), np.int32)
+    if ev.ndim != 2 or ev.shape[1] != 3 or not np.issubdtype(ev.dtype, np.integer):
+        raise ValueError(f"beamform: events must be integers [E, 3] = (sample, first frame, last frame), got {ev.dtype} {ev.shape}")
+    ev = ev.astype(np.int64)
+    bad = np.flatnonzero((ev[:, 0] < 0) | (ev[:, 0] >= batch) | (ev[:, 1] < 0) | (ev[:, 1] > ev[:, 2]) | (ev[:, 2] >= n_frames))
+    if bad.size:
+        i = int(bad[0])
+        raise ValueError(f"beamform: event {i} = (sample {ev[i, 0]}, frames {ev[i, 1]} .. {ev[i, 2]}) does not fit {batch} sample(s) of "
+                         f"{n_frames} frames with first <= last")
+    frames = ev[:, 2] - ev[:, 1] + 1
+    if int(frames.sum()) > 2 ** 31 - 1:
+        raise ValueError("beamform: more than 2^31 - 1 output frames")
+    table = np.empty((len(ev), 4), np.int32)
+    table[:, :3] = ev
+    table[:, 3] = np.concatenate([[0], np.cumsum(frames)[:-1]])
     return table
 
 

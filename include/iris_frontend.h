@@ -314,6 +314,39 @@ int iris_locate_events(iris_plan* plan, const float* spec, const float* factors,
                        void* stream);
 
 /*
+ * Event extraction (k_beamform.h): the MVDR (minimum-variance distortionless-response) beamformer w = R^-1 d / (d^H R^-1 d)
+ * of a two-microphone delay vector d = [1, e], applied over the frames of detected events - the audio of an event with the
+ * interferer the whitening factors describe nulled.
+ * spec, factors, n_blocks, block, k_lo, k_hi: as for iris_locate_events (factors NULL: a = b = 1, c = 0 and one block, the
+ * delay-and-sum beamformer Y = (X0 + conj(e) X1) / 2).  Events: int32 [n_events, 4] = (sample, first frame, last frame, first
+ * output frame), frames inclusive, once on the device (events_dev, what the kernel reads) and once on the host (events_host,
+ * what is checked here); `first output frame` is the running count of the frames of the events before it.  tdoa_dev: DEVICE
+ * double [n_events], the delay of each event in samples, positive when channel 1 hears the event later (locate_peak's sign).
+ * For event e, frame t in first .. last, block j = t / block, bin k, (a, b, c) = factors[sample, k, j]:
+ *     k outside [k_lo, k_hi), a == 0 (a silent block) or tdoa not finite:  Y = 0 exactly
+ *     r = k tdoa / n_fft (double, n_fft = 2 (n_bins - 1)),  r -= rint(r),  e = cos(2 pi r) - i sin(2 pi r)
+ *     s1 = b (e - c),  den = a^2 + |s1|^2,  g1 = b conj(s1) / den,  g0 = a^2 / den - g1 c,   Y = g0 X0 + g1 X1
+ * out: slab e = [n_bins, T_e, 2] = (Re Y, Im Y) fp32, T_e = last - first + 1, at float 2 n_bins x (first output frame): the
+ * record layout of iris_istft for one channel.  g0, g1 are formed in double and rounded once to fp32; per component one
+ * product and three fmas in a fixed order.  Against the float64 definition from the same fp32 inputs, per real component,
+ * |Y - exact| <= 6 x 2^-24 A, A = |g0| |X0| + |g1| |X1| (nothing cancelled; the count is in k_beamform.h).  X1 = e X0 gives
+ * Y = X0 (distortionless).
+ * Refused before any HIP call: NULL plan or spec, empty shapes, n_events < 0, spec or factors not 16-byte aligned, block < 1
+ * or n_blocks != ceil(n_frames / block) (with factors), a bin range that is empty or leaves [0, n_bins] (IRIS_E_INVALID);
+ * n_frames > 2^30, a plan whose channel count is not 2 (IRIS_E_UNSUPPORTED); then, with n_events > 0: a NULL table, tdoa or
+ * out, a table that is not 4-byte or tdoa / out that are not 8-byte aligned, an event naming a sample outside [0, batch),
+ * frames outside [0, n_frames) or first > last, a `first output frame` that is not the running count (IRIS_E_INVALID), more
+ * than 2^31 - 1 output frames, more than 2^24 events, ceil(n_bins / 16) x ceil(longest event / 256) > 262140 (the grid;
+ * IRIS_E_UNSUPPORTED), out_floats <
+ * 2 n_bins x (frames of all events) (IRIS_E_CAPACITY).  n_events == 0 returns IRIS_OK without a launch.  One launch on
+ * `stream`, no workspace, no atomics: capturable, bitwise reproducible, and a frame's value depends on its sample, frame, bin
+ * and delay only - not on the event it sits in or on the other events of the call.
+ */
+int iris_beamform_events(iris_plan* plan, const float* spec, const float* factors, int n_blocks, const int32_t* events_dev,
+                         const int32_t* events_host, const double* tdoa_dev, int n_events, int batch, int n_frames, int block,
+                         int k_lo, int k_hi, float* out, size_t out_floats, void* stream);
+
+/*
  * minmax + log_on_mel (data_utils.py:37-55; fused twin trainer.py:63-77),
  * in place on x[n_rows, row_len]: per row (x - min) / max(max - min, eps_div)
  * when do_minmax, then ln(x + eps_log) when do_log.  A batched [B,M,T,C] tensor
