@@ -503,9 +503,15 @@ __global__ __launch_bounds__(64 * fused_waves(LOG2N, S, BANDS, HI, FUSE, MELMODE
                                 acc2 += acc3;
                                 acc = acc2.x + acc2.y;
                             } else {
+                                // a window of any length (up to all NC + 1 bins of a dense matrix): one fp32 chain over n bins
+                                // rounds n times, a random walk of ~sqrt(n / 3) u relative on same-signed terms - 1e-6 at 511
+                                // bins, which min-max then divides by the clip's RANGE (a wide band's values differ by a few
+                                // per cent only).  Accumulated in double the sum is rounded once, whatever n is.
                                 const int lo = a.band_lo[m];
+                                double acc64 = 0.;
                                 for (int i = 0; i < a.rows; ++i)
-                                    acc = fmaf(a.wband[i * a.M + m], magbuf[st][lo + i], acc);
+                                    acc64 = fma((double)a.wband[i * a.M + m], (double)magbuf[st][lo + i], acc64);
+                                acc = (float)acc64;
                             }
 #if IRIS_K_GAIN
                             const float v = (acc * keep) * gain_row[m];
