@@ -79,14 +79,18 @@ def load_model(config, path: str = '', device=None):
 
 
 class _PsdsFanOut:
-    """One criteria set per launch: two scenarios are two Psds objects, fed the same tensors."""
+    """One criteria set per launch: two scenarios are two Psds objects, fed the same tensors; `compute` is {scenario: result}."""
 
-    def __init__(self, scored):
-        self.scored = scored
+    def __init__(self, scenarios):
+        from .metrics import Psds
+        self.scored = {sc: Psds(3, sc) for sc in scenarios}
 
     def update(self, y_true, y_pred):
-        for p in self.scored:
+        for p in self.scored.values():
             p.update(y_true, y_pred)
+
+    def compute(self):
+        return {str(sc): p.compute() for sc, p in self.scored.items()}
 
 
 def build_args():
@@ -130,22 +134,18 @@ def main(argv=None):
     if config.p:
         parse_name(config)
     model = load_model(config, config.path)
-    if not config.curves and not config.sed_eval and not config.psds:
-        return evaluate(config, model, verbose=config.verbose)
-    from .metrics import Psds, ScoreHistogram, SedEval
-    hist = ScoreHistogram(3, config.curve_bins) if config.curves else None
-    sed = SedEval(3, config.sed_thresholds or (0.5,)) if config.sed_eval else None
-    scored = [Psds(3, sc) for sc in config.psds_scenario] if config.psds else []
-    scores = evaluate(config, model, verbose=config.verbose, curves=hist, sed=sed, psds=_PsdsFanOut(scored) if scored else None)
-    if hist is not None:
-        with open(config.curves, 'w') as f:
-            json.dump(hist.compute(), f, indent=1)
-    if sed is not None:
-        with open(config.sed_eval, 'w') as f:
-            json.dump(sed.compute(), f, indent=1)
-    if scored:
-        with open(config.psds, 'w') as f:
-            json.dump({str(sc): p.compute() for sc, p in zip(config.psds_scenario, scored)}, f, indent=1)
+    from .metrics import ScoreHistogram, SedEval
+    asked = {}   # `evaluate`'s keyword -> (the file to write, the counter whose compute() it holds)
+    if config.curves:
+        asked['curves'] = (config.curves, ScoreHistogram(3, config.curve_bins))
+    if config.sed_eval:
+        asked['sed'] = (config.sed_eval, SedEval(3, config.sed_thresholds or (0.5,)))
+    if config.psds:
+        asked['psds'] = (config.psds, _PsdsFanOut(config.psds_scenario))
+    scores = evaluate(config, model, verbose=config.verbose, **{key: counter for key, (_, counter) in asked.items()})
+    for path, counter in asked.values():
+        with open(path, 'w') as f:
+            json.dump(counter.compute(), f, indent=1)
     return scores
 
 

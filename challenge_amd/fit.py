@@ -411,17 +411,17 @@ def graph_step_possible(model: "CustomModel") -> bool:
 
 
 def monitor_maximised(name: Optional[str]) -> bool:
-    """Is a row entry better when LARGER?  The threshold-free validation numbers of a compiled score_curves() - 'auc', 'map',
-    'best_f1' behind 'val_' / 'val_ema_' - are, and so are 'seg_f1' and 'event_f1' of a compiled sed_eval() and 'psds' of a compiled
-    psds(); every other name (losses, er, seg_er, ...) keeps Keras' mode min."""
+    """Is a row entry better when LARGER?  The entries of the compiled count metrics behind 'val_' / 'val_ema_' are
+    (metrics.VAL_MAXIMISED: score_curves()'s, sed_eval()'s two F1, psds()'s); every other name (losses, er, seg_er, ...) keeps
+    Keras' mode min."""
     if not name:
         return False
     for prefix in ('val_ema_', 'val_'):
         if name.startswith(prefix):
             name = name[len(prefix):]
             break
-    from .metrics import CURVE_NAMES
-    return name in CURVE_NAMES or name in ('seg_f1', 'event_f1', 'psds')   # (a compiled sed_eval(): its 'seg_er' is minimised)
+    from .metrics import VAL_MAXIMISED
+    return name in VAL_MAXIMISED
 
 
 def fit(model: CustomModel, train_set, epochs, steps_per_epoch, validation_data=None, validation_steps=16,
@@ -446,12 +446,10 @@ def fit(model: CustomModel, train_set, epochs, steps_per_epoch, validation_data=
     'val_ema_loss' and the 'val_ema_*' metrics.  Everything the
     live model's row, early stopping and checkpoint depend on is computed as without it.  `ema_checkpoint_path` is written when
     'val_ema_<the checkpoint's monitor>' improves strictly.
-    A compiled metrics.score_curves() adds 'val_auc', 'val_map', 'val_best_f1' (and their 'val_ema_' twins) after the validation
-    pass, from the validation histogram summed over the ranks; a `checkpoint_monitor` with such a name is MAXIMISED (strictly
-    larger saves), and so is the EMA's twin of it.
-    A compiled metrics.sed_eval() adds 'val_seg_f1', 'val_seg_er', 'val_event_f1' (and their 'val_ema_' twins) in the same way, from
-    the validation counts summed over the ranks; as monitors the two F1 are maximised, seg_er is minimised.
-    A compiled metrics.psds() adds 'val_psds' (and 'val_ema_psds') likewise; as a monitor it is maximised."""
+    The compiled count metrics add their entries (and the 'val_ema_' twins) after the validation pass, from the validation counts
+    summed over the ranks (`MetricSet.val_values`): metrics.score_curves() 'val_auc', 'val_map', 'val_best_f1'; metrics.sed_eval()
+    'val_seg_f1', 'val_seg_er', 'val_event_f1'; metrics.psds() 'val_psds'.  A `checkpoint_monitor` with such a name is MAXIMISED
+    (strictly larger saves), and so is the EMA's twin of it - but for seg_er, which is minimised."""
     best, bad, history = math.inf, 0, []
     ckpt_sign = -1.0 if monitor_maximised(checkpoint_monitor) else 1.0   # best_ckpt / best_ema hold sign * value: smaller is better
     best_ckpt = math.inf
@@ -563,12 +561,7 @@ def fit(model: CustomModel, train_set, epochs, steps_per_epoch, validation_data=
                 host = torch.cat([vl.double().view(1), metric_sums('val', vl.device)]).tolist()
                 row['val_loss'] = host[0]
                 row.update(ms.epoch_values(host[1:], 'val_'))
-                if ms.curves is not None:
-                    row.update(ms.curve_values('val_', all_reduce=coll))
-                if ms.sed is not None:
-                    row.update(ms.sed_values('val_', all_reduce=coll))
-                if ms.psds is not None:
-                    row.update(ms.psds_values('val_', all_reduce=coll))
+                row.update(ms.val_values('val_', all_reduce=coll))
             if ema is not None:   # the second pass: the averaged weights under the live model's BatchNorm statistics
                 ema.copy_buffers(model)
                 ems = ema.module._metrics
@@ -588,12 +581,7 @@ def fit(model: CustomModel, train_set, epochs, steps_per_epoch, validation_data=
                     host = torch.cat([evl.double().view(1), acc]).tolist()
                     row['val_ema_loss'] = host[0]
                     row.update(ems.epoch_values(host[1:], 'val_ema_'))
-                    if ems.curves is not None:
-                        row.update(ems.curve_values('val_ema_', all_reduce=coll))
-                    if ems.sed is not None:
-                        row.update(ems.sed_values('val_ema_', all_reduce=coll))
-                    if ems.psds is not None:
-                        row.update(ems.psds_values('val_ema_', all_reduce=coll))
+                    row.update(ems.val_values('val_ema_', all_reduce=coll))
         history.append(row)
         if swa is not None:
             swa.on_epoch_end(epoch, model)

@@ -35,6 +35,14 @@ def _first(x):
     return x[0] if isinstance(x, tuple) else x
 
 
+def _device(device) -> torch.device:
+    """The key of a per-device state: a bare 'cuda' is the current device."""
+    device = torch.device(device)
+    if device.type == 'cuda' and device.index is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    return device
+
+
 def _pool_same_strided(y: torch.Tensor, k: int) -> torch.Tensor:
     """Keras AveragePooling1D(k, padding='same') (stride = k) on [B, T, K]: ceil(T / k) windows, the padding split floor /
     ceil before / after, each window the mean of its in-range frames summed in frame order (as the kernel sums)."""
@@ -184,7 +192,7 @@ class _F1Score:
         self.__name__ = 'f1_score'
 
     def state(self, device) -> torch.Tensor:
-        device = torch.device(device)
+        device = _device(device)
         if device not in self.states:
             self.states[device] = torch.zeros(3, dtype=torch.float64, device=device)
         return self.states[device]
@@ -211,6 +219,149 @@ def _cos_sim_metric(y_true, y_pred):
 
 
 _cos_sim_metric.__name__ = 'cos_sim'
+
+
+# ---------------------------------------------------------------------------
+# integer count states of the validation pass: what ScoreHistogram, SedEval and Psds share
+# ---------------------------------------------------------------------------
+def _workspace_query(name: str, *args) -> int:
+    """The byte count the library's query `name` gives for these arguments; what it refuses (0) is a ValueError."""
+    n_bytes = int(getattr(N.lib(), name)(*args))
+    if n_bytes <= 0:
+        N.check(-1, name)
+    return n_bytes
+
+
+class _CountState:
+    """Integer counts of everything `update` has seen: one int64 tensor of shape `_shape` per device (as `_F1Score` keeps its
+    states).  On GPU tensors an update is the subclass's launches on the current stream - integer adds: exact, independent of the
+    order, no host sync - on CPU tensors its host rule, the same arithmetic with torch ops.  A subclass checks its parameters,
+    sets `_shape`, and gives the four things that differ:
+      _host(y_true, y_pred)               the counts of one batch, on the host
+      _workspace_bytes(b, t, k)           what its launches need as scratch memory (0: none, the default)
+      _launch(yt, yp, ws, state, stream)  its iris_* call on fp32 contiguous tensors; `ws` an int64 tensor of at least that size, or None
+      metrics(counts)                     the host arithmetic on counts (one rank's or the sum over ranks)
+    MAX_CLASSES bounds n_classes; MAX_FRAMES, where set, bounds T, and B * T then stays below 2^31."""
+    MAX_CLASSES = 16
+    MAX_FRAMES = None
+
+    def __init__(self, n_classes: int):
+        self.n_classes = int(n_classes)
+        if not 1 <= self.n_classes <= self.MAX_CLASSES:
+            raise ValueError(f"{type(self).__name__}: n_classes in [1, {self.MAX_CLASSES}], got {n_classes}")
+        self.states: Dict[torch.device, torch.Tensor] = {}
+        self._workspaces: Dict[tuple, torch.Tensor] = {}
+        self._retired: List[torch.Tensor] = []
+
+    def _workspace_bytes(self, b: int, t: int, k: int) -> int:
+        return 0
+
+    def state(self, device) -> torch.Tensor:
+        device = _device(device)
+        if device not in self.states:
+            self.states[device] = torch.zeros(*self._shape, dtype=torch.int64, device=device)
+        return self.states[device]
+
+    def _workspace(self, device, stream: int, n_bytes: int) -> torch.Tensor:
+        """The workspace of (device, stream), at least n_bytes in 8-byte words: the launches of one stream are ordered, those of
+        two streams get a workspace each.  A larger one replaces it; the old one is kept while this object lives (launches or a
+        captured graph may still hold its address)."""
+        ws = self._workspaces.get((device, stream))
+        if ws is None or ws.numel() * 8 < n_bytes:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"{type(self).__name__}.update: the first call for a shape must be eager (warm up before the capture)")
+            if ws is not None:
+                self._retired.append(ws)
+            ws = self._workspaces[(device, stream)] = torch.empty((n_bytes + 7) // 8, dtype=torch.int64, device=device)
+        return ws
+
+    @torch.no_grad()
+    def update(self, y_true: torch.Tensor, y_pred: torch.Tensor) -> None:
+        name = type(self).__name__
+        y_true, y_pred = _first(y_true), _first(y_pred)
+        if y_true.dim() != 3 or y_pred.dim() != 3 or y_true.shape != y_pred.shape:
+            raise ValueError(f"{name}.update: y_true and y_pred [B, T, K] at the same frame rate, got {tuple(y_true.shape)} "
+                             f"/ {tuple(y_pred.shape)}")
+        if y_pred.shape[2] != self.n_classes:
+            raise ValueError(f"{name}.update: {y_pred.shape[2]} classes, made for {self.n_classes}")
+        if not (y_true.is_floating_point() and y_pred.is_floating_point()):
+            raise ValueError(f"{name}.update: floating-point tensors, got {y_true.dtype} / {y_pred.dtype}")
+        if y_true.device != y_pred.device:
+            raise ValueError(f"{name}.update: y_true on {y_true.device}, y_pred on {y_pred.device}")
+        if y_pred.numel() == 0:
+            return
+        b, t, k = y_pred.shape
+        if self.MAX_FRAMES and (t > self.MAX_FRAMES or b * t > 2 ** 31 - 1):
+            raise ValueError(f"{name}.update: T {t} (<= 2^{self.MAX_FRAMES.bit_length() - 1}) and B * T {b * t} (<= 2^31 - 1)")
+        st = self.state(y_pred.device)
+        if not y_pred.is_cuda:
+            st += self._host(y_true, y_pred)
+            return
+        yt = y_true.detach().to(torch.float32).contiguous()
+        yp = y_pred.detach().to(torch.float32).contiguous()
+        stream = torch.cuda.current_stream(yp.device).cuda_stream
+        n_bytes = self._workspace_bytes(b, t, k)
+        self._launch(yt, yp, self._workspace(yp.device, stream, n_bytes) if n_bytes else None, st, stream)
+
+    def reset(self) -> None:
+        for s in self.states.values():
+            s.zero_()
+
+    def counts(self) -> torch.Tensor:
+        """The counts on the host, summed over this object's devices."""
+        out = torch.zeros(*self._shape, dtype=torch.int64)
+        for s in self.states.values():
+            out += s.cpu()
+        return out
+
+    def total(self, all_reduce: bool = False) -> torch.Tensor:
+        """The counts summed over this object's devices (at least one update has made a state), on the first one's device, and
+        with `all_reduce` over the ranks (int64 SUM: exact, every rank gets the same values).  The sums are formed in a clone: the
+        live states are never modified.  The caller's `.cpu()` is the one copy to the host."""
+        states = list(self.states.values())
+        total = states[0].clone() if all_reduce or len(states) > 1 else states[0]
+        for s in states[1:]:
+            total += s.to(total.device)
+        if all_reduce:
+            torch.distributed.all_reduce(total)
+        return total
+
+    def compute(self) -> dict:
+        return self.metrics(self.counts())
+
+
+class _CompiledCounts:
+    """What score_curves(), sed_eval() and psds() return: a `_CountState` subclass behind a compiled metric.  A `MetricSet` feeds
+    it in the 'val' phase only and returns no per-step value for it; `counter` is made by the first batch (its class count).
+    `names` are the row entries it adds, `row` the function from the counter's `metrics(counts)` to their values."""
+
+    def __init__(self, name: str, cls, names: tuple, row, **kwargs):
+        cls(1, **kwargs)   # (refuses bad arguments now, not at the first validation batch)
+        self.cls, self.kwargs, self.names, self.row = cls, kwargs, names, row
+        self.counter: Optional[_CountState] = None
+        self.__name__ = name
+
+    def update(self, y_true, y_pred) -> None:
+        y_pred = _first(y_pred)
+        if self.counter is None:
+            self.counter = self.cls(y_pred.shape[-1], **self.kwargs)
+        self.counter.update(y_true, y_pred)
+
+    def reset(self) -> None:
+        if self.counter is not None:
+            self.counter.reset()
+
+    def values(self, prefix: str = '', all_reduce: bool = False) -> Dict[str, float]:
+        """{prefix + name: value} for `names` from the validation counts (NaN before the first batch), summed over the ranks first
+        with `all_reduce`, in one copy to the host.  Every rank must have seen a validation batch, or none."""
+        c = self.counter
+        if c is None or not c.states:
+            return {prefix + n: float('nan') for n in self.names}
+        return {prefix + n: v for n, v in zip(self.names, self.row(c.metrics(c.total(all_reduce).cpu())))}
+
+    def __call__(self, y_true, y_pred):
+        raise TypeError(f"{self.__name__}() has no per-batch value: compile it (model.compile(metrics=[...])) and read "
+                        "MetricSet.val_values after the validation pass")
 
 
 # ---------------------------------------------------------------------------
@@ -301,95 +452,34 @@ def curve_metrics(counts) -> dict:
             'bins': bins}
 
 
-class ScoreHistogram:
-    """The score histogram per (class, label) of everything `update` has seen: int64 [K, 2, bins + 1], one state per device (as
-    `_F1Score` keeps its states).  On GPU tensors an update is ONE iris_score_hist launch on the current stream (integer adds:
-    exact, independent of the order, no host sync); on CPU tensors `score_hist_host`, the same rule with torch ops."""
+class ScoreHistogram(_CountState):
+    """The score histogram per (class, label), a `_CountState` of int64 [K, 2, bins + 1].  On GPU tensors an update is ONE
+    iris_score_hist launch, no workspace; on CPU tensors `score_hist_host`.  `compute` is `curve_metrics` on the counts."""
+    MAX_CLASSES = CURVE_MAX_CLASSES
 
     def __init__(self, n_classes: int, bins: int = 1024):
-        self.n_classes, self.bins = int(n_classes), check_curve_bins(bins)
-        if not 1 <= self.n_classes <= CURVE_MAX_CLASSES:
-            raise ValueError(f"ScoreHistogram: n_classes in [1, {CURVE_MAX_CLASSES}], got {n_classes}")
-        self.states: Dict[torch.device, torch.Tensor] = {}
-
-    def state(self, device) -> torch.Tensor:
-        device = torch.device(device)
-        if device.type == 'cuda' and device.index is None:
-            device = torch.device('cuda', torch.cuda.current_device())
-        if device not in self.states:
-            self.states[device] = torch.zeros(self.n_classes, 2, self.bins + 1, dtype=torch.int64, device=device)
-        return self.states[device]
-
-    @torch.no_grad()
-    def update(self, y_true: torch.Tensor, y_pred: torch.Tensor) -> None:
-        y_true, y_pred = _first(y_true), _first(y_pred)
-        if y_true.dim() != 3 or y_pred.dim() != 3 or y_true.shape != y_pred.shape:
-            raise ValueError(f"ScoreHistogram.update: y_true and y_pred [B, T, K] at the same frame rate, got {tuple(y_true.shape)} "
-                             f"/ {tuple(y_pred.shape)}")
-        if y_pred.shape[2] != self.n_classes:
-            raise ValueError(f"ScoreHistogram.update: {y_pred.shape[2]} classes, made for {self.n_classes}")
-        if not (y_true.is_floating_point() and y_pred.is_floating_point()):
-            raise ValueError(f"ScoreHistogram.update: floating-point tensors, got {y_true.dtype} / {y_pred.dtype}")
-        if y_true.device != y_pred.device:
-            raise ValueError(f"ScoreHistogram.update: y_true on {y_true.device}, y_pred on {y_pred.device}")
-        if y_pred.numel() == 0:
-            return
-        st = self.state(y_pred.device)
-        if not y_pred.is_cuda:
-            st += score_hist_host(y_true, y_pred, self.bins)
-            return
-        yt = y_true.detach().to(torch.float32).contiguous()
-        yp = y_pred.detach().to(torch.float32).contiguous()
-        b, t, k = yp.shape
-        N.check(N.lib().iris_score_hist(yt.data_ptr(), yp.data_ptr(), b, t, k, self.bins, st.data_ptr(),
-                                        torch.cuda.current_stream(yp.device).cuda_stream), "iris_score_hist")
-
-    def reset(self) -> None:
-        for s in self.states.values():
-            s.zero_()
-
-    def counts(self) -> torch.Tensor:
-        """The counts on the host, summed over this object's devices."""
-        out = torch.zeros(self.n_classes, 2, self.bins + 1, dtype=torch.int64)
-        for s in self.states.values():
-            out += s.cpu()
-        return out
-
-    def compute(self) -> dict:
-        return curve_metrics(self.counts())
-
-
-CURVE_NAMES = ('auc', 'map', 'best_f1')   # what `MetricSet.curve_values` adds to a row; `fit` MAXIMISES a monitor with such a name
-
-
-class _ScoreCurves:
-    """score_curves(bins): the compiled metric behind val_auc / val_map / val_best_f1.  A `MetricSet` feeds its histogram in
-    the 'val' phase only and returns no per-step value for it; the histogram is made by the first batch (its class count)."""
-
-    def __init__(self, bins=1024):
         self.bins = check_curve_bins(bins)
-        self.hist: Optional[ScoreHistogram] = None
-        self.__name__ = 'score_curves'
+        super().__init__(n_classes)
+        self._shape = (self.n_classes, 2, self.bins + 1)
 
-    def update(self, y_true, y_pred) -> None:
-        y_pred = _first(y_pred)
-        if self.hist is None:
-            self.hist = ScoreHistogram(y_pred.shape[-1], self.bins)
-        self.hist.update(y_true, y_pred)
+    def _host(self, y_true, y_pred):
+        return score_hist_host(y_true, y_pred, self.bins)
 
-    def reset(self) -> None:
-        if self.hist is not None:
-            self.hist.reset()
+    def _launch(self, yt, yp, ws, st, stream):
+        b, t, k = yp.shape
+        N.check(N.lib().iris_score_hist(yt.data_ptr(), yp.data_ptr(), b, t, k, self.bins, st.data_ptr(), stream), "iris_score_hist")
 
-    def __call__(self, y_true, y_pred):
-        raise TypeError("score_curves() has no per-batch value: compile it (model.compile(metrics=[...])) and read "
-                        "MetricSet.curve_values after the validation pass")
+    def metrics(self, counts) -> dict:
+        return curve_metrics(counts)
+
+
+CURVE_NAMES = ('auc', 'map', 'best_f1')   # what a compiled score_curves() adds to a row (macro means); `fit` MAXIMISES such a monitor
 
 
 def score_curves(bins=1024):
     """A metric for `compile(metrics=[...])`: ROC-AUC, average precision and the best frame F1 of the validation pass, from an
     on-device score histogram with `bins` bins (`fit` logs val_auc, val_map, val_best_f1)."""
-    return _ScoreCurves(bins)
+    return _CompiledCounts('score_curves', ScoreHistogram, CURVE_NAMES, lambda m: [m[n] for n in CURVE_NAMES], bins=bins)
 
 
 # ---------------------------------------------------------------------------
@@ -531,130 +621,51 @@ def sed_metrics(counts, thresholds) -> dict:
             'best_segment_f1_threshold': best('segment')}
 
 
-class SedEval:
+class SedEval(_CountState):
     """Segment-based (1 s segments: ER, F1) and event-based (200 ms onset collar, offset collar max(200 ms, 50 % of the event):
-    F1, ER) detection counts of everything `update` has seen, at every threshold of `thresholds`: int64 [n_thr, K + 1, 6], one
-    state per device (as `ScoreHistogram`).  On GPU tensors an update is iris_sed_counts - two launches on the current stream,
-    integer adds, no host sync; its workspace is cached per device and stream and grows - on CPU tensors `sed_counts_host`, the same rule.
-    Event matching is greedy in time order and per class (sed_metrics has the ratios)."""
+    F1, ER) detection counts at every threshold of `thresholds`, a `_CountState` of int64 [n_thr, K + 1, 6].  On GPU tensors an
+    update is iris_sed_counts - two launches, with a workspace - on CPU tensors `sed_counts_host`.  Event matching is greedy in
+    time order and per class; `compute` is `sed_metrics` on the counts."""
+    MAX_CLASSES, MAX_FRAMES = SED_MAX_CLASSES, SED_MAX_FRAMES
 
     def __init__(self, n_classes: int, thresholds=(0.5,), segment=1.0, collar=0.2, offset_pct=50, sr=16000, hop=256):
-        self.n_classes = int(n_classes)
-        if not 1 <= self.n_classes <= SED_MAX_CLASSES:
-            raise ValueError(f"SedEval: n_classes in [1, {SED_MAX_CLASSES}], got {n_classes}")
+        super().__init__(n_classes)
         self.thresholds, self.hop, self.seg_samples, self.collar_samples, self.offset_pct = \
             check_sed_params(thresholds, segment, collar, offset_pct, sr, hop)
         self._host_args = dict(thresholds=self.thresholds, segment=segment, collar=collar, offset_pct=offset_pct, sr=sr, hop=hop)
         self._levels = (N.C.c_float * len(self.thresholds))(*self.thresholds)
-        self.states: Dict[torch.device, torch.Tensor] = {}
-        self._workspaces: Dict[tuple, torch.Tensor] = {}
-        self._retired: List[torch.Tensor] = []
+        self._shape = (len(self.thresholds), self.n_classes + 1, 6)
 
-    def _device(self, device) -> torch.device:
-        device = torch.device(device)
-        if device.type == 'cuda' and device.index is None:
-            device = torch.device('cuda', torch.cuda.current_device())
-        return device
+    def _host(self, y_true, y_pred):
+        return sed_counts_host(y_true, y_pred, **self._host_args)
 
-    def state(self, device) -> torch.Tensor:
-        device = self._device(device)
-        if device not in self.states:
-            self.states[device] = torch.zeros(len(self.thresholds), self.n_classes + 1, 6, dtype=torch.int64, device=device)
-        return self.states[device]
+    def _workspace_bytes(self, b, t, k):
+        return _workspace_query("iris_sed_workspace_bytes", b, t, k, len(self.thresholds), self.hop, self.seg_samples)
 
-    def _workspace(self, device, stream: int, n_bytes: int) -> torch.Tensor:
-        """The workspace of (device, stream), at least n_bytes: the launches of one stream are ordered, those of two streams get
-        a workspace each.  A larger one replaces it; the old one is kept while this object lives (launches or a captured graph
-        may still hold its address)."""
-        ws = self._workspaces.get((device, stream))
-        if ws is None or ws.numel() * 4 < n_bytes:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("SedEval.update: the first call for a shape must be eager (warm up before the capture)")
-            if ws is not None:
-                self._retired.append(ws)
-            ws = self._workspaces[(device, stream)] = torch.empty((n_bytes + 3) // 4, dtype=torch.int32, device=device)
-        return ws
-
-    @torch.no_grad()
-    def update(self, y_true: torch.Tensor, y_pred: torch.Tensor) -> None:
-        y_true, y_pred = _first(y_true), _first(y_pred)
-        if y_true.dim() != 3 or y_pred.dim() != 3 or y_true.shape != y_pred.shape:
-            raise ValueError(f"SedEval.update: y_true and y_pred [B, T, K] at the same frame rate, got {tuple(y_true.shape)} "
-                             f"/ {tuple(y_pred.shape)}")
-        if y_pred.shape[2] != self.n_classes:
-            raise ValueError(f"SedEval.update: {y_pred.shape[2]} classes, made for {self.n_classes}")
-        if not (y_true.is_floating_point() and y_pred.is_floating_point()):
-            raise ValueError(f"SedEval.update: floating-point tensors, got {y_true.dtype} / {y_pred.dtype}")
-        if y_true.device != y_pred.device:
-            raise ValueError(f"SedEval.update: y_true on {y_true.device}, y_pred on {y_pred.device}")
-        if y_pred.numel() == 0:
-            return
-        b, t, k = y_pred.shape
-        if t > SED_MAX_FRAMES or b * t > 2 ** 31 - 1:
-            raise ValueError(f"SedEval.update: T {t} (<= 2^20) and B * T {b * t} (<= 2^31 - 1)")
-        st = self.state(y_pred.device)
-        if not y_pred.is_cuda:
-            st += sed_counts_host(y_true, y_pred, **self._host_args)
-            return
-        yt = y_true.detach().to(torch.float32).contiguous()
-        yp = y_pred.detach().to(torch.float32).contiguous()
-        n_bytes = int(N.lib().iris_sed_workspace_bytes(b, t, k, len(self.thresholds), self.hop, self.seg_samples))
-        if n_bytes <= 0:
-            N.check(-1, "iris_sed_workspace_bytes")
-        stream = torch.cuda.current_stream(yp.device).cuda_stream
-        ws = self._workspace(self._device(yp.device), stream, n_bytes)
+    def _launch(self, yt, yp, ws, st, stream):
+        b, t, k = yp.shape
         N.check(N.lib().iris_sed_counts(yt.data_ptr(), yp.data_ptr(), b, t, k, self._levels, len(self.thresholds), self.hop,
-                                        self.seg_samples, self.collar_samples, self.offset_pct, ws.data_ptr(), ws.numel() * 4,
+                                        self.seg_samples, self.collar_samples, self.offset_pct, ws.data_ptr(), ws.numel() * 8,
                                         st.data_ptr(), stream), "iris_sed_counts")
 
-    def reset(self) -> None:
-        for s in self.states.values():
-            s.zero_()
-
-    def counts(self) -> torch.Tensor:
-        """The counts on the host, summed over this object's devices."""
-        out = torch.zeros(len(self.thresholds), self.n_classes + 1, 6, dtype=torch.int64)
-        for s in self.states.values():
-            out += s.cpu()
-        return out
-
-    def compute(self) -> dict:
-        return sed_metrics(self.counts(), self.thresholds)
+    def metrics(self, counts) -> dict:
+        return sed_metrics(counts, self.thresholds)
 
 
-SED_NAMES = ('seg_f1', 'seg_er', 'event_f1')   # what `MetricSet.sed_values` adds to a row; `fit` MAXIMISES the two F1, minimises seg_er
+SED_NAMES = ('seg_f1', 'seg_er', 'event_f1')   # what a compiled sed_eval() adds to a row; `fit` MAXIMISES the two F1, minimises seg_er
 
 
-class _SedEvalMetric:
-    """sed_eval(thresholds, ...): the compiled metric behind val_seg_f1 / val_seg_er / val_event_f1.  A `MetricSet` feeds its
-    `SedEval` in the 'val' phase only and returns no per-step value for it; the state is made by the first batch (its class count)."""
-
-    def __init__(self, thresholds=(0.5,), segment=1.0, collar=0.2, offset_pct=50, sr=16000, hop=256):
-        self.kwargs = dict(thresholds=check_sed_params(thresholds, segment, collar, offset_pct, sr, hop)[0], segment=segment,
-                           collar=collar, offset_pct=offset_pct, sr=sr, hop=hop)
-        self.sed: Optional[SedEval] = None
-        self.__name__ = 'sed_eval'
-
-    def update(self, y_true, y_pred) -> None:
-        y_pred = _first(y_pred)
-        if self.sed is None:
-            self.sed = SedEval(y_pred.shape[-1], **self.kwargs)
-        self.sed.update(y_true, y_pred)
-
-    def reset(self) -> None:
-        if self.sed is not None:
-            self.sed.reset()
-
-    def __call__(self, y_true, y_pred):
-        raise TypeError("sed_eval() has no per-batch value: compile it (model.compile(metrics=[...])) and read "
-                        "MetricSet.sed_values after the validation pass")
+def _sed_row(m: dict) -> list:
+    first = m['per_threshold'][0]
+    return [first['segment']['f1'], first['segment']['er'], first['event']['f1']]
 
 
 def sed_eval(thresholds=(0.5,), segment=1.0, collar=0.2, offset_pct=50, sr=16000, hop=256):
     """A metric for `compile(metrics=[...])`: segment-based F1 / ER and event-based F1 of the validation pass at the FIRST
     threshold of the list, from on-device integer counts (`fit` logs val_seg_f1, val_seg_er, val_event_f1).  `hop` is the hop of
     the frames the metric sees - the model's output frames - in samples."""
-    return _SedEvalMetric(thresholds, segment, collar, offset_pct, sr, hop)
+    return _CompiledCounts('sed_eval', SedEval, SED_NAMES, _sed_row, thresholds=thresholds, segment=segment, collar=collar,
+                           offset_pct=offset_pct, sr=sr, hop=hop)
 
 
 # ---------------------------------------------------------------------------
@@ -811,17 +822,15 @@ def psds_metrics(counts, thresholds, hop=256, sr=16000, alpha_ct=0.0, alpha_st=1
             'n_gt': n_gt, 'gt_frames': gt_frames, 'n_frames': n_frames}
 
 
-class Psds:
-    """Intersection-based detection counts of everything `update` has seen at every threshold (default: 50 from 0.01 to 0.99),
-    under one criteria set - scenario 1 or 2 of DCASE Task 4 (PSDS_SCENARIOS), or a dict with dtc_pct, gtc_pct, cttc_pct and
-    optionally alpha_ct, alpha_st: int64 [n_thr + 1, K, K + 2], one state per device (as `SedEval`).  On GPU tensors an update is
-    iris_psds_counts - two launches on the current stream, integer adds, no host sync; its workspace is cached per device and
-    stream and grows - on CPU tensors `psds_counts_host`, the same rule.  `compute` is `psds_metrics` on the counts."""
+class Psds(_CountState):
+    """Intersection-based detection counts at every threshold (default: 50 from 0.01 to 0.99) under one criteria set - scenario
+    1 or 2 of DCASE Task 4 (PSDS_SCENARIOS), or a dict with dtc_pct, gtc_pct, cttc_pct and optionally alpha_ct, alpha_st - a
+    `_CountState` of int64 [n_thr + 1, K, K + 2].  On GPU tensors an update is iris_psds_counts - two launches, with a workspace -
+    on CPU tensors `psds_counts_host`.  `compute` is `psds_metrics` on the counts."""
+    MAX_CLASSES, MAX_FRAMES = PSDS_MAX_CLASSES, PSDS_MAX_FRAMES
 
     def __init__(self, n_classes: int, scenario=1, thresholds=None, sr=16000, hop=256, e_max=100.0):
-        self.n_classes = int(n_classes)
-        if not 1 <= self.n_classes <= PSDS_MAX_CLASSES:
-            raise ValueError(f"Psds: n_classes in [1, {PSDS_MAX_CLASSES}], got {n_classes}")
+        super().__init__(n_classes)
         if isinstance(scenario, dict):
             unknown = set(scenario) - {'dtc_pct', 'gtc_pct', 'cttc_pct', 'alpha_ct', 'alpha_st'}
             if unknown or not {'dtc_pct', 'gtc_pct'} <= set(scenario):
@@ -839,116 +848,36 @@ class Psds:
             raise ValueError(f"Psds: hop {hop!r} (an integer >= 1), sr {sr!r} (> 0), e_max {e_max!r} (> 0)")
         self.hop, self.sr, self.e_max = int(hop), sr, float(e_max)
         self._levels = (N.C.c_float * len(self.thresholds))(*self.thresholds)
-        self.states: Dict[torch.device, torch.Tensor] = {}
-        self._workspaces: Dict[tuple, torch.Tensor] = {}
-        self._retired: List[torch.Tensor] = []
+        self._shape = (len(self.thresholds) + 1, self.n_classes, self.n_classes + 2)
 
-    def _device(self, device) -> torch.device:
-        device = torch.device(device)
-        if device.type == 'cuda' and device.index is None:
-            device = torch.device('cuda', torch.cuda.current_device())
-        return device
+    def _host(self, y_true, y_pred):
+        return psds_counts_host(y_true, y_pred, self.thresholds, self.dtc_pct, self.gtc_pct, self.cttc_pct)
 
-    def _shape(self) -> tuple:
-        return len(self.thresholds) + 1, self.n_classes, self.n_classes + 2
+    def _workspace_bytes(self, b, t, k):
+        return _workspace_query("iris_psds_workspace_bytes", b, t, k, len(self.thresholds))
 
-    def state(self, device) -> torch.Tensor:
-        device = self._device(device)
-        if device not in self.states:
-            self.states[device] = torch.zeros(*self._shape(), dtype=torch.int64, device=device)
-        return self.states[device]
-
-    def _workspace(self, device, stream: int, n_bytes: int) -> torch.Tensor:
-        """As `SedEval._workspace`: one per (device, stream), growing, the outgrown ones kept alive; 8-byte words."""
-        ws = self._workspaces.get((device, stream))
-        if ws is None or ws.numel() * 8 < n_bytes:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("Psds.update: the first call for a shape must be eager (warm up before the capture)")
-            if ws is not None:
-                self._retired.append(ws)
-            ws = self._workspaces[(device, stream)] = torch.empty((n_bytes + 7) // 8, dtype=torch.int64, device=device)
-        return ws
-
-    @torch.no_grad()
-    def update(self, y_true: torch.Tensor, y_pred: torch.Tensor) -> None:
-        y_true, y_pred = _first(y_true), _first(y_pred)
-        if y_true.dim() != 3 or y_pred.dim() != 3 or y_true.shape != y_pred.shape:
-            raise ValueError(f"Psds.update: y_true and y_pred [B, T, K] at the same frame rate, got {tuple(y_true.shape)} "
-                             f"/ {tuple(y_pred.shape)}")
-        if y_pred.shape[2] != self.n_classes:
-            raise ValueError(f"Psds.update: {y_pred.shape[2]} classes, made for {self.n_classes}")
-        if not (y_true.is_floating_point() and y_pred.is_floating_point()):
-            raise ValueError(f"Psds.update: floating-point tensors, got {y_true.dtype} / {y_pred.dtype}")
-        if y_true.device != y_pred.device:
-            raise ValueError(f"Psds.update: y_true on {y_true.device}, y_pred on {y_pred.device}")
-        if y_pred.numel() == 0:
-            return
-        b, t, k = y_pred.shape
-        if t > PSDS_MAX_FRAMES or b * t > 2 ** 31 - 1:
-            raise ValueError(f"Psds.update: T {t} (<= 2^20) and B * T {b * t} (<= 2^31 - 1)")
-        st = self.state(y_pred.device)
-        if not y_pred.is_cuda:
-            st += psds_counts_host(y_true, y_pred, self.thresholds, self.dtc_pct, self.gtc_pct, self.cttc_pct)
-            return
-        yt = y_true.detach().to(torch.float32).contiguous()
-        yp = y_pred.detach().to(torch.float32).contiguous()
-        n_bytes = int(N.lib().iris_psds_workspace_bytes(b, t, k, len(self.thresholds)))
-        if n_bytes <= 0:
-            N.check(-1, "iris_psds_workspace_bytes")
-        stream = torch.cuda.current_stream(yp.device).cuda_stream
-        ws = self._workspace(self._device(yp.device), stream, n_bytes)
+    def _launch(self, yt, yp, ws, st, stream):
+        b, t, k = yp.shape
         N.check(N.lib().iris_psds_counts(yt.data_ptr(), yp.data_ptr(), b, t, k, self._levels, len(self.thresholds), self.dtc_pct,
                                          self.gtc_pct, self.cttc_pct or 0, ws.data_ptr(), ws.numel() * 8, st.data_ptr(), stream),
                 "iris_psds_counts")
 
-    def reset(self) -> None:
-        for s in self.states.values():
-            s.zero_()
-
-    def counts(self) -> torch.Tensor:
-        """The counts on the host, summed over this object's devices."""
-        out = torch.zeros(*self._shape(), dtype=torch.int64)
-        for s in self.states.values():
-            out += s.cpu()
-        return out
-
     def metrics(self, counts) -> dict:
         return psds_metrics(counts, self.thresholds, self.hop, self.sr, self.alpha_ct, self.alpha_st, self.e_max)
 
-    def compute(self) -> dict:
-        return self.metrics(self.counts())
 
-
-class _PsdsMetric:
-    """psds(scenario, ...): the compiled metric behind val_psds.  A `MetricSet` feeds its `Psds` in the 'val' phase only and
-    returns no per-step value for it; the state is made by the first batch (its class count)."""
-
-    def __init__(self, scenario=1, thresholds=None, sr=16000, hop=256, e_max=100.0):
-        Psds(1, scenario, thresholds, sr, hop, e_max)   # (refuses bad arguments now, not at the first validation batch)
-        self.kwargs = dict(scenario=scenario, thresholds=thresholds, sr=sr, hop=hop, e_max=e_max)
-        self.psds: Optional[Psds] = None
-        self.__name__ = 'psds'
-
-    def update(self, y_true, y_pred) -> None:
-        y_pred = _first(y_pred)
-        if self.psds is None:
-            self.psds = Psds(y_pred.shape[-1], **self.kwargs)
-        self.psds.update(y_true, y_pred)
-
-    def reset(self) -> None:
-        if self.psds is not None:
-            self.psds.reset()
-
-    def __call__(self, y_true, y_pred):
-        raise TypeError("psds() has no per-batch value: compile it (model.compile(metrics=[...])) and read "
-                        "MetricSet.psds_values after the validation pass")
+PSDS_NAMES = ('psds',)   # what a compiled psds() adds to a row; `fit` MAXIMISES such a monitor
 
 
 def psds(scenario=1, thresholds=None, sr=16000, hop=256, e_max=100.0):
     """A metric for `compile(metrics=[...])`: the polyphonic sound detection score of the validation pass under DCASE scenario
     1 or 2 (or a criteria dict, see `Psds`), from on-device integer counts at 50 thresholds (`fit` logs val_psds).  `hop` is the
     hop of the frames the metric sees - the model's output frames - in samples."""
-    return _PsdsMetric(scenario, thresholds, sr, hop, e_max)
+    return _CompiledCounts('psds', Psds, PSDS_NAMES, lambda m: [m['psds']], scenario=scenario, thresholds=thresholds, sr=sr,
+                           hop=hop, e_max=e_max)
+
+
+VAL_MAXIMISED = tuple(n for n in CURVE_NAMES + SED_NAMES + PSDS_NAMES if n != 'seg_er')   # larger is better, but for the one error rate
 
 
 def _is_cos(m):
@@ -964,29 +893,25 @@ class MetricSet:
     iris_event_metrics launch per batch on a GPU (at most one of each kind; other callables are called as they are).  Each call
     adds to the epoch accumulator of its phase ('train' / 'val'): fp64 [5] = sum er, sum cos, sum f1, clips, batches - zeroed by
     `reset`, read once per epoch by `fit` (Keras' means: per-clip metrics weighted by clips, the scalar F1 by batches).
-    A score_curves() in the list (at most one) is fed in the 'val' phase only - one more launch, iris_score_hist - and read with
-    `curve_values`; a 'train'-phase call launches nothing for it, so the captured training step is what it is without it.
-    A sed_eval() in the list (at most one) likewise: 'val' phase only - two more launches, iris_sed_counts - read with `sed_values`.
-    A psds() in the list (at most one) likewise: 'val' phase only - two more launches, iris_psds_counts - read with `psds_values`."""
+    The count metrics score_curves(), sed_eval() and psds() (at most one of each) are fed in the 'val' phase only - the launches
+    of their counters: one, two and two more - and read with `val_values`; a 'train'-phase call launches nothing for them, so the
+    captured training step is what it is without them.  `counted` holds them in the fixed order curves, sed, psds, whatever their
+    order in the list: the order of their row entries, and the order in which every rank all-reduces their counts."""
 
     def __init__(self, metrics):
         self.metrics = list(metrics)
         self.er = next((m for m in self.metrics if isinstance(m, _ErScore)), None)
         self.f1 = next((m for m in self.metrics if isinstance(m, _F1Score)), None)
         self.cos = any(_is_cos(m) for m in self.metrics)
-        curves = [m for m in self.metrics if isinstance(m, _ScoreCurves)]
-        if len(curves) > 1:
-            raise ValueError("MetricSet: at most one score_curves() in a metric list")
-        self.curves = curves[0] if curves else None   # fed in the 'val' phase only; no per-step value
-        seds = [m for m in self.metrics if isinstance(m, _SedEvalMetric)]
-        if len(seds) > 1:
-            raise ValueError("MetricSet: at most one sed_eval() in a metric list")
-        self.sed = seds[0] if seds else None          # likewise
-        scores = [m for m in self.metrics if isinstance(m, _PsdsMetric)]
-        if len(scores) > 1:
-            raise ValueError("MetricSet: at most one psds() in a metric list")
-        self.psds = scores[0] if scores else None     # likewise
-        fused = {id(self.er), id(self.f1), id(self.curves), id(self.sed), id(self.psds)}
+        compiled = [m for m in self.metrics if isinstance(m, _CompiledCounts)]
+        self.counted: List[_CompiledCounts] = []
+        for attr, kind in (('curves', 'score_curves'), ('sed', 'sed_eval'), ('psds', 'psds')):
+            same = [m for m in compiled if m.__name__ == kind]
+            if len(same) > 1:
+                raise ValueError(f"MetricSet: at most one {kind}() in a metric list")
+            setattr(self, attr, same[0] if same else None)
+            self.counted += same
+        fused = {id(self.er), id(self.f1)} | {id(m) for m in compiled}
         self.others = [m for m in self.metrics if id(m) not in fused and not _is_cos(m)]
         self.names = [metric_name(m) for m in self.metrics]
         dup = sorted({n for n in self.names if self.names.count(n) > 1})
@@ -1009,12 +934,9 @@ class MetricSet:
         for (_, ph), a in self.accums.items():
             if phase is None or ph == phase:
                 a.zero_()
-        if self.curves is not None and phase in (None, 'val'):
-            self.curves.reset()
-        if self.sed is not None and phase in (None, 'val'):
-            self.sed.reset()
-        if self.psds is not None and phase in (None, 'val'):
-            self.psds.reset()
+        if phase in (None, 'val'):
+            for m in self.counted:
+                m.reset()
 
     @torch.no_grad()
     def __call__(self, y_true, y_pred, phase: str = 'train') -> Dict[str, torch.Tensor]:
@@ -1049,68 +971,34 @@ class MetricSet:
                                 acc.new_tensor(float(b)), acc.new_tensor(1.0)])
         for m in self.others:
             res[metric_name(m)] = m(y_true, y_pred)
-        if self.curves is not None and phase == 'val':   # one iris_score_hist launch on a GPU; the train phase launches nothing
-            self.curves.update(y_true, y_pred)
-        if self.sed is not None and phase == 'val':      # two iris_sed_counts launches on a GPU; the train phase launches nothing
-            self.sed.update(y_true, y_pred)
-        if self.psds is not None and phase == 'val':     # two iris_psds_counts launches on a GPU; the train phase launches nothing
-            self.psds.update(y_true, y_pred)
+        if phase == 'val':   # the counters' launches on a GPU; the train phase launches nothing
+            for m in self.counted:
+                m.update(y_true, y_pred)
         return {n: res[n] for n in self.names if n in res}
 
-    def psds_values(self, prefix: str = '', all_reduce: bool = False) -> Dict[str, float]:
-        """Row entry of a compiled psds(): {prefix + 'psds'} from the validation counts, summed over the ranks first with
-        `all_reduce` (a clone, int64 SUM: exact, every rank gets the same value), in one copy to the host.  Every rank must have
-        seen a validation batch, or none."""
-        if self.psds is None:
-            return {}
-        score = self.psds.psds
-        if score is None or not score.states:
-            return {prefix + 'psds': float('nan')}
-        states = list(score.states.values())
-        total = states[0].clone() if all_reduce or len(states) > 1 else states[0]
-        for s in states[1:]:
-            total += s.to(total.device)
-        if all_reduce:
-            torch.distributed.all_reduce(total)
-        return {prefix + 'psds': score.metrics(total.cpu())['psds']}
+    @staticmethod
+    def _rows(compiled, prefix: str, all_reduce: bool) -> Dict[str, float]:
+        out: Dict[str, float] = {}
+        for m in compiled:
+            if m is not None:
+                out.update(m.values(prefix, all_reduce))
+        return out
 
-    def sed_values(self, prefix: str = '', all_reduce: bool = False) -> Dict[str, float]:
-        """Row entries of a compiled sed_eval(): {prefix + 'seg_f1', 'seg_er', 'event_f1'} - segment-based micro F1 and ER,
-        event-based micro F1, at the FIRST threshold of its list - from the validation counts, summed over the ranks first with
-        `all_reduce` (int64 SUM: exact, every rank gets the same values), in one copy to the host.  Every rank must have seen a
-        validation batch, or none."""
-        if self.sed is None:
-            return {}
-        sed = self.sed.sed
-        if sed is None or not sed.states:
-            return {prefix + n: float('nan') for n in SED_NAMES}
-        states = list(sed.states.values())
-        total = states[0].clone() if all_reduce or len(states) > 1 else states[0]
-        for s in states[1:]:
-            total += s.to(total.device)
-        if all_reduce:
-            torch.distributed.all_reduce(total)
-        first = sed_metrics(total.cpu(), sed.thresholds)['per_threshold'][0]
-        return {prefix + 'seg_f1': first['segment']['f1'], prefix + 'seg_er': first['segment']['er'],
-                prefix + 'event_f1': first['event']['f1']}
+    def val_values(self, prefix: str = '', all_reduce: bool = False) -> Dict[str, float]:
+        """The row entries of the compiled count metrics (`_CompiledCounts.values`, in the order of `counted`); {} without any."""
+        return self._rows(self.counted, prefix, all_reduce)
 
     def curve_values(self, prefix: str = '', all_reduce: bool = False) -> Dict[str, float]:
-        """Row entries of a compiled score_curves(): {prefix + 'auc', 'map', 'best_f1'} (macro means) from the validation
-        histogram - summed over the ranks first with `all_reduce` (int64 SUM: exact, every rank gets the same values) - in one
-        copy to the host.  Every rank must have seen a validation batch, or none."""
-        if self.curves is None:
-            return {}
-        hist = self.curves.hist
-        if hist is None or not hist.states:
-            return {prefix + n: float('nan') for n in CURVE_NAMES}
-        states = list(hist.states.values())
-        total = states[0].clone() if all_reduce or len(states) > 1 else states[0]
-        for s in states[1:]:
-            total += s.to(total.device)
-        if all_reduce:
-            torch.distributed.all_reduce(total)
-        values = curve_metrics(total.cpu())
-        return {prefix + n: values[n] for n in CURVE_NAMES}
+        """`val_values` of the compiled score_curves() alone."""
+        return self._rows([self.curves], prefix, all_reduce)
+
+    def sed_values(self, prefix: str = '', all_reduce: bool = False) -> Dict[str, float]:
+        """`val_values` of the compiled sed_eval() alone."""
+        return self._rows([self.sed], prefix, all_reduce)
+
+    def psds_values(self, prefix: str = '', all_reduce: bool = False) -> Dict[str, float]:
+        """`val_values` of the compiled psds() alone."""
+        return self._rows([self.psds], prefix, all_reduce)
 
     def epoch_values(self, sums: torch.Tensor, prefix: str = '') -> Dict[str, float]:
         """Row entries from an accumulator's (possibly all-reduced) host values."""
@@ -1221,21 +1109,18 @@ def evaluate(config, model, overlap_hop=512, verbose: bool = False, *, wav_dir: 
     if device is None:
         device = next(model.parameters()).device if hasattr(model, 'parameters') else None
     final_score = []
+    counters = [c for c in (curves, sed, psds) if c is not None]
     for path in sorted(glob(os.path.join(wav_dir, '*.wav'))):
         spec = D.load_wav(path, device)
         name = os.path.basename(path)[:-4]
-        if curves is None and sed is None and psds is None:
+        if not counters:
             preds = predict_frames(model, features_for_eval(spec, config), config, overlap_hop)
         else:
             from .eval import second2frame
             post = predict_frames(model, features_for_eval(spec, config), config, overlap_hop, threshold=False)
             labels = second2frame(answer_gt[name], post.shape[0], sr / hop).to(post.device)
-            if curves is not None:
-                curves.update(labels[None], post.to(torch.float32)[None])
-            if sed is not None:
-                sed.update(labels[None], post.to(torch.float32)[None])
-            if psds is not None:
-                psds.update(labels[None], post.to(torch.float32)[None])
+            for counter in counters:
+                counter.update(labels[None], post.to(torch.float32)[None])
             preds = (post >= 0.5).to(torch.float32)   # (predict_frames' own decision)
         cls0, cls1, cls2 = metric.get_start_end_frame(preds.cpu().numpy())
         predict = output_to_metric(hop, sr)(cls0, cls1, cls2)

@@ -72,16 +72,22 @@ def row_names(config) -> list:
     if getattr(config, 'metrics', 'none') == 'reference':
         names += ['cos_sim', 'f1_score'] + (['er'] if config.v != 5 else [])
     val = ['val_' + n for n in names]
-    if getattr(config, 'curves', 0):
-        from .metrics import CURVE_NAMES
-        val += ['val_' + n for n in CURVE_NAMES]
-    if getattr(config, 'sed_eval', ()):
-        from .metrics import SED_NAMES
-        val += ['val_' + n for n in SED_NAMES]
-    if getattr(config, 'psds', 0):
-        val += ['val_psds']
+    from .metrics import CURVE_NAMES, PSDS_NAMES, SED_NAMES
+    for flag, added in (('curves', CURVE_NAMES), ('sed_eval', SED_NAMES), ('psds', PSDS_NAMES)):
+        if getattr(config, flag, 0):
+            val += ['val_' + n for n in added]
     ema = ['val_ema_' + n[len('val_'):] for n in val] if getattr(config, 'ema', 0) else []
     return names + val + ema
+
+
+def count_metrics(config) -> list:
+    """The compiled count metrics of --curves / --sed_eval / --psds, made anew at every call: the model and its EMA copy each
+    compile a list of their own, so the EMA's validation pass never counts into the live model's states."""
+    from .metrics import psds, score_curves, sed_eval
+    hop = output_hop(config)
+    return ([score_curves(config.curves)] if config.curves else []) \
+        + ([sed_eval(config.sed_eval, hop=hop)] if config.sed_eval else []) \
+        + ([psds(config.psds, hop=hop)] if config.psds else [])
 
 
 class ARGS:
@@ -926,15 +932,7 @@ def main(argv=None):
         monitor = 'val_er'
         if rank == 0:
             callbacks.append(eval_callback(config, NAME.replace('.h5', '.pt')))
-    if config.curves:   # with --metrics none the only metric
-        from .metrics import score_curves
-        metrics = (metrics or []) + [score_curves(config.curves)]
-    if config.sed_eval:
-        from .metrics import sed_eval
-        metrics = (metrics or []) + [sed_eval(config.sed_eval, hop=output_hop(config))]
-    if config.psds:
-        from .metrics import psds
-        metrics = (metrics or []) + [psds(config.psds, hop=output_hop(config))]
+    metrics = ((metrics or []) + count_metrics(config)) or None   # (with --metrics none the only metrics)
     if config.checkpoint_monitor is not None:
         monitor = config.checkpoint_monitor
     ema = None
@@ -945,16 +943,7 @@ def main(argv=None):
         if config.metrics == 'reference':   # fresh metric objects: the F1 counts of the EMA pass must not land in the live model's
             from .metrics import cos_sim, er_score, f1_score
             own = [cos_sim, f1_score()] + ([er_score(smoothing=False)] if config.v != 5 else [])
-        if config.curves:   # (and a histogram of its own)
-            from .metrics import score_curves
-            own = (own or []) + [score_curves(config.curves)]
-        if config.sed_eval:   # (and counts of its own)
-            from .metrics import sed_eval
-            own = (own or []) + [sed_eval(config.sed_eval, hop=output_hop(config))]
-        if config.psds:   # (likewise)
-            from .metrics import psds
-            own = (own or []) + [psds(config.psds, hop=output_hop(config))]
-        ema.compile(loss, metrics=own)
+        ema.compile(loss, metrics=((own or []) + count_metrics(config)) or None)   # (and counts of its own)
     model.compile(opt, loss, clipvalue=None if config.no_clipvalue_after_agc else config.clipvalue,
                   ddp=wrap_ddp(model, device, world), metrics=metrics, ema=ema)
     if rank == 0:

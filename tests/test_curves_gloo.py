@@ -40,8 +40,8 @@ def _worker(rank, world, port, out_dir):
     hist = S.fit(model, Dataset.from_generator(lambda: iter(tb)).repeat(), epochs=1, steps_per_epoch=1,
                  validation_data=Dataset.from_generator(lambda: iter(vb)).repeat(), validation_steps=2, rank=rank, world=world,
                  verbose=False)
-    own = curves.hist.counts()                            # this rank's shard: the all-reduce acted on a copy
-    merged = curves.hist.state('cpu').clone()
+    own = curves.counter.counts()                            # this rank's shard: the all-reduce acted on a copy
+    merged = curves.counter.state('cpu').clone()
     torch.distributed.all_reduce(merged)
     model.eval()
     with torch.no_grad():

@@ -138,11 +138,11 @@ def test_metric_set_through_test_step_equals_the_cpu_path():
         out = model.test_step(batch)
         assert 'score_curves' not in out
     ms = model._metrics
-    before = curves.hist.counts()
+    before = curves.counter.counts()
     ms(batches[0][1], torch.rand(6, 2, 3, device=dev), 'train')              # no train-phase launch: the histogram is untouched
     model.train_step(batches[0])
-    assert torch.equal(curves.hist.counts(), before) and int(before.sum()) == 2 * 6 * 2 * 3
-    assert not any(t is s for t in ms.state_tensors() for s in curves.hist.states.values())
+    assert torch.equal(curves.counter.counts(), before) and int(before.sum()) == 2 * 6 * 2 * 3
+    assert not any(t is s for t in ms.state_tensors() for s in curves.counter.states.values())
     cpu = M.ScoreHistogram(3, 64)
     for yt, yp in seen[:2]:
         cpu.update(yt, yp)
@@ -152,7 +152,7 @@ def test_metric_set_through_test_step_equals_the_cpu_path():
     ref = R.metrics(torch.cat([a for a, _ in seen[:2]]).numpy(), torch.cat([b for _, b in seen[:2]]).numpy(), 64)
     assert all(abs(vals['val_' + k] - ref[k]) <= tol(64) for k in ('auc', 'map', 'best_f1'))
     ms.reset()
-    assert int(curves.hist.counts().sum()) == 0
+    assert int(curves.counter.counts().sum()) == 0
 
 
 def test_eval_writes_the_curves_of_the_recordings(tmp_path, monkeypatch):

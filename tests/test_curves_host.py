@@ -220,20 +220,20 @@ def test_metric_set_feeds_the_histogram_in_the_val_phase_only():
     ms = M.MetricSet([M.cos_sim, curves, M.er_score(smoothing=False)])
     assert ms.curves is curves and curves not in ms.others
     out = ms(yt, yp, 'train')
-    assert set(out) == {'cos_sim', 'er'} and curves.hist is None           # nothing made, nothing counted
+    assert set(out) == {'cos_sim', 'er'} and curves.counter is None           # nothing made, nothing counted
     assert all(math.isnan(v) for v in ms.curve_values('val_').values())
     assert set(ms(yt, yp, 'val')) == {'cos_sim', 'er'}                     # no per-step value
     ms(yt, yp, 'train')
-    assert np.array_equal(curves.hist.counts().numpy(), R.counts(yt.numpy(), yp.numpy(), 64))
-    assert not any(t is s for t in ms.state_tensors() for s in curves.hist.states.values())
+    assert np.array_equal(curves.counter.counts().numpy(), R.counts(yt.numpy(), yp.numpy(), 64))
+    assert not any(t is s for t in ms.state_tensors() for s in curves.counter.states.values())
     vals = ms.curve_values('val_')
     ref = R.metrics(yt.numpy(), yp.numpy(), 64)
     assert set(vals) == {'val_auc', 'val_map', 'val_best_f1'}
     assert all(abs(vals['val_' + k] - ref[k]) <= tol(64) for k in ('auc', 'map', 'best_f1'))
     ms.reset('train')
-    assert int(curves.hist.counts().sum()) == 96
+    assert int(curves.counter.counts().sum()) == 96
     ms.reset()
-    assert int(curves.hist.counts().sum()) == 0
+    assert int(curves.counter.counts().sum()) == 0
     assert M.MetricSet([M.cos_sim]).curve_values('val_') == {}
     with pytest.raises(ValueError):
         M.MetricSet([M.score_curves(64), M.score_curves(16)])

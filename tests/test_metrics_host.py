@@ -355,6 +355,91 @@ def test_metric_names_must_be_unique():
         M.MetricSet([M.f1_score(), M.f1_score()])
 
 
+# ---------------------------------------------------------------------------
+# the count states of the validation pass: one contract for ScoreHistogram, SedEval and Psds
+# ---------------------------------------------------------------------------
+_LEVELS = (0.3, 0.6)
+COUNTERS = {   # public name -> (a fresh object for 3 classes, the class's host rule with the same parameters)
+    'ScoreHistogram': (lambda: M.ScoreHistogram(3, 16), lambda yt, yp: M.score_hist_host(yt, yp, 16)),
+    'SedEval': (lambda: M.SedEval(3, _LEVELS, hop=1600), lambda yt, yp: M.sed_counts_host(yt, yp, _LEVELS, hop=1600)),
+    'Psds': (lambda: M.Psds(3, 2, _LEVELS), lambda yt, yp: M.psds_counts_host(yt, yp, _LEVELS, dtc_pct=10, gtc_pct=10, cttc_pct=30)),
+}
+
+
+def _count_case():
+    """B = 2, T = 16, K = 3: block labels (events of 4 frames) and scores that follow them loosely."""
+    g = torch.Generator().manual_seed(3)
+    yt = (torch.rand(2, 4, 3, generator=g) < 0.5).float().repeat_interleave(4, dim=1)
+    yp = (0.6 * yt + 0.5 * torch.rand(2, 16, 3, generator=g)).clamp(0, 1)
+    return yt, yp
+
+
+@pytest.mark.parametrize("name", sorted(COUNTERS))
+def test_count_states_share_one_contract(name):
+    make, host_rule = COUNTERS[name]
+    yt, yp = _count_case()
+    want = host_rule(yt, yp)
+    assert want.dtype == torch.int64 and int(want.sum()) > 0
+    c, other = make(), make()
+    assert type(c).__name__ == name and int(c.counts().sum()) == 0 and not c.states
+    c.update(yt[:1], yp[:1])
+    c.update(yt[1:], yp[1:])                                      # two updates = one on the concatenation
+    assert torch.equal(c.counts(), want) and tuple(c.counts().shape) == tuple(want.shape)
+    assert torch.equal(c.total(), want)
+    assert int(other.counts().sum()) == 0 and not other.states    # a second object shares nothing
+    other.update(yt, yp)
+    assert torch.equal(other.counts(), want) and torch.equal(c.counts(), want)
+    bad = [(yt[0], yp[0]),                                        # rank
+           (yt, yp[:, :8]),                                       # shape
+           (yt[:, :, :2], yp[:, :, :2]),                          # class count
+           (yt.long(), yp),                                       # dtype
+           (yt.to('meta'), yp)]                                   # device
+    for a, b in bad:
+        with pytest.raises(ValueError) as exc:
+            c.update(a, b)
+        assert str(exc.value).startswith(name + ".update: "), exc.value
+        assert torch.equal(c.counts(), want)                      # the state is left untouched
+    c.update(yt[:0], yp[:0])                                      # an empty batch: nothing
+    assert torch.equal(c.counts(), want)
+    with pytest.raises(ValueError) as exc:
+        type(c)(17)
+    assert str(exc.value).startswith(name + ": n_classes")
+    c.reset()
+    assert int(c.counts().abs().sum()) == 0 and torch.equal(other.counts(), want)
+    c.update(yt, yp)
+    assert torch.equal(c.counts(), want) and c.compute() == other.compute() == c.metrics(want)
+
+
+def test_val_values_is_the_union_of_the_three_readers_in_row_order():
+    """All three count metrics compiled in REVERSE order: the rows keep curves, sed, psds."""
+    def same(a, b):
+        return list(a) == list(b) and all(x == y or (x != x and y != y) for x, y in zip(a.values(), b.values()))
+    score, sed, curves = M.psds(2, _LEVELS, hop=1600), M.sed_eval(_LEVELS, hop=1600), M.score_curves(16)
+    ms = M.MetricSet([score, M.cos_sim, sed, curves])
+    assert ms.counted == [curves, sed, score] and (ms.curves, ms.sed, ms.psds) == (curves, sed, score) and ms.others == []
+    keys = ['val_auc', 'val_map', 'val_best_f1', 'val_seg_f1', 'val_seg_er', 'val_event_f1', 'val_psds']
+    assert keys == ['val_' + n for n in M.CURVE_NAMES + M.SED_NAMES + M.PSDS_NAMES]
+    yt, yp = _count_case()
+    for _ in range(2):                                            # before the first 'val' call, and after 'train' calls: all NaN
+        vals = ms.val_values('val_')
+        assert list(vals) == keys and all(math.isnan(v) for v in vals.values())
+        assert set(ms(yt, yp, 'train')) == {'cos_sim'} and all(m.counter is None for m in ms.counted)
+    assert set(ms(yt, yp, 'val')) == {'cos_sim'}
+    vals = ms.val_values('val_')
+    union = {**ms.curve_values('val_'), **ms.sed_values('val_'), **ms.psds_values('val_')}
+    assert list(vals) == keys and same(vals, union) and any(math.isfinite(v) for v in vals.values())
+    assert vals['val_psds'] == score.counter.compute()['psds'] and vals['val_auc'] == curves.counter.compute()['auc']
+    assert vals['val_seg_er'] == sed.counter.compute()['per_threshold'][0]['segment']['er']
+    ms(yt, 1 - yp, 'train')                                       # a 'train' call counts nothing
+    assert same(ms.val_values('val_'), vals)
+    assert same(ms.val_values('val_ema_'), {'val_ema_' + k[4:]: v for k, v in vals.items()})
+    assert M.MetricSet([M.cos_sim]).val_values('val_') == {}
+    ms.reset('train')
+    assert same(ms.val_values('val_'), vals)
+    ms.reset('val')
+    assert all(int(m.counter.counts().sum()) == 0 for m in ms.counted)
+
+
 def test_main_with_reference_metrics_needs_the_answer_file(tmp_path, monkeypatch):
     monkeypatch.chdir(tmp_path)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "IRIS_FORCE_PG"):

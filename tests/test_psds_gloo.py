@@ -40,9 +40,9 @@ def _worker(rank, world, port, out_dir):
     hist = S.fit(model, Dataset.from_generator(lambda: iter(tb)).repeat(), epochs=1, steps_per_epoch=1,
                  validation_data=Dataset.from_generator(lambda: iter(vb)).repeat(), validation_steps=2, rank=rank, world=world,
                  verbose=False)
-    own = score.psds.counts()                             # this rank's shard: the all-reduce acted on a copy
+    own = score.counter.counts()                             # this rank's shard: the all-reduce acted on a copy
     values = model._metrics.psds_values('val_', all_reduce=True)
-    merged = score.psds.state('cpu').clone()
+    merged = score.counter.state('cpu').clone()
     torch.distributed.all_reduce(merged)
     model.eval()
     with torch.no_grad():

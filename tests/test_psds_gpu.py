@@ -237,10 +237,10 @@ def test_fit_with_psds_logs_a_finite_val_psds():
     batches = [(torch.randn(4, 32, 64, 1, generator=g).to(dev), (torch.rand(4, 2, 3, generator=g) > 0.5).float().to(dev)) for _ in range(2)]
     assert 'psds' not in model.test_step(batches[0])
     ms = model._metrics
-    before = score.psds.counts()
+    before = score.counter.counts()
     ms(batches[0][1], torch.rand(4, 2, 3, device=dev), 'train')                       # no train-phase launch: the state is untouched
-    assert torch.equal(score.psds.counts(), before) and int(before[50, 0, 3]) == 8    # 4 clips of 2 output frames
-    assert not any(t is s for t in ms.state_tensors() for s in score.psds.states.values())
+    assert torch.equal(score.counter.counts(), before) and int(before[50, 0, 3]) == 8    # 4 clips of 2 output frames
+    assert not any(t is s for t in ms.state_tensors() for s in score.counter.states.values())
     want = R.counts(seen[0][0].numpy(), seen[0][1].numpy(), M.psds_default_thresholds(), **SCENARIOS[2])
     assert np.array_equal(before.numpy(), want)
     value = ms.psds_values('val_')['val_psds']
@@ -248,7 +248,7 @@ def test_fit_with_psds_logs_a_finite_val_psds():
     hist = S.fit(model, Dataset.from_generator(lambda: iter(batches)).repeat(), epochs=1, steps_per_epoch=1,
                  validation_data=Dataset.from_generator(lambda: iter(batches)).repeat(), validation_steps=2, verbose=False, graph=False)
     assert math.isfinite(hist[0]['val_psds']) and -1.0 <= hist[0]['val_psds'] <= 1.0
-    assert int(score.psds.counts()[50, 0, 3]) == 16                                   # reset, then the two validation batches
+    assert int(score.counter.counts()[50, 0, 3]) == 16                                   # reset, then the two validation batches
 
 
 def test_eval_writes_the_scores_of_the_recordings(tmp_path, monkeypatch):

@@ -243,19 +243,19 @@ def test_metric_set_feeds_the_counts_in_the_val_phase_only():
     ms = M.MetricSet([M.cos_sim, score, M.er_score(smoothing=False), M.sed_eval((0.5,), hop=1600)])
     assert ms.psds is score and score not in ms.others
     out = ms(yt, yp, 'train')
-    assert set(out) == {'cos_sim', 'er'} and score.psds is None                      # nothing made, nothing counted
+    assert set(out) == {'cos_sim', 'er'} and score.counter is None                      # nothing made, nothing counted
     assert set(ms.psds_values('val_')) == {'val_psds'} and math.isnan(ms.psds_values('val_')['val_psds'])
     assert set(ms(yt, yp, 'val')) == {'cos_sim', 'er'}                               # no per-step value
     ms(yt, yp, 'train')
     want = R.counts(yt.numpy(), yp.numpy(), M.psds_default_thresholds(), **SCENARIOS[2])
-    assert np.array_equal(score.psds.counts().numpy(), want)
-    assert not any(t is s for t in ms.state_tensors() for s in score.psds.states.values())
+    assert np.array_equal(score.counter.counts().numpy(), want)
+    assert not any(t is s for t in ms.state_tensors() for s in score.counter.states.values())
     value = M.psds_metrics(want, M.psds_default_thresholds(), 1600, 16000, 0.5, 1.0)['psds']
     assert ms.psds_values('val_') == {'val_psds': value} and 0.0 <= value <= 1.0
     ms.reset('train')
-    assert int(score.psds.counts().sum()) == int(want.sum())
+    assert int(score.counter.counts().sum()) == int(want.sum())
     ms.reset()
-    assert int(score.psds.counts().sum()) == 0
+    assert int(score.counter.counts().sum()) == 0
     assert M.MetricSet([M.cos_sim]).psds_values('val_') == {}
     with pytest.raises(ValueError, match="psds"):
         M.MetricSet([M.psds(1), M.psds(2)])

@@ -40,9 +40,9 @@ def _worker(rank, world, port, out_dir):
     hist = S.fit(model, Dataset.from_generator(lambda: iter(tb)).repeat(), epochs=1, steps_per_epoch=1,
                  validation_data=Dataset.from_generator(lambda: iter(vb)).repeat(), validation_steps=2, rank=rank, world=world,
                  verbose=False)
-    own = sed.sed.counts()                                # this rank's shard: the all-reduce acted on a copy
+    own = sed.counter.counts()                                # this rank's shard: the all-reduce acted on a copy
     values = model._metrics.sed_values('val_', all_reduce=True)
-    merged = sed.sed.state('cpu').clone()
+    merged = sed.counter.state('cpu').clone()
     torch.distributed.all_reduce(merged)
     model.eval()
     with torch.no_grad():

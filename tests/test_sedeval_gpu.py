@@ -132,7 +132,13 @@ def test_state_accumulates_is_reproducible_and_resets(cases):
         other.update(gt, gp)
     other.update(gt, gp)                                                             # two streams: a workspace each
     side.synchronize()
-    assert np.array_equal(other.counts().numpy(), 2 * one)
+    assert np.array_equal(other.counts().numpy(), 2 * one) and len(other._workspaces) == 2
+    small = torch.from_numpy(yt2).to(dev), torch.from_numpy(yp2).to(dev)
+    grown = M.SedEval(3, thr)
+    grown.update(*small)
+    grown.update(gt, gp)                                                             # a larger batch: the workspace grows
+    grown.update(*small)                                                             # ... and serves the smaller one again
+    assert np.array_equal(grown.counts().numpy(), one + 2 * two) and len(grown._retired) == 1
     sed.reset()
     assert int(sed.counts().abs().sum()) == 0
     with pytest.raises(ValueError):
@@ -165,11 +171,11 @@ def test_metric_set_through_test_step_equals_the_cpu_path():
     batch = (torch.randn(2, 32, 64, 1, generator=g).to(dev), (torch.rand(2, 2, 3, generator=g) > 0.5).float().to(dev))
     assert 'sed_eval' not in model.test_step(batch)
     ms = model._metrics
-    before = sed.sed.counts()
+    before = sed.counter.counts()
     ms(batch[1], torch.rand(2, 2, 3, device=dev), 'train')                           # no train-phase launch: the state is untouched
     model.train_step(batch)
-    assert torch.equal(sed.sed.counts(), before) and int(before[0, 3, 3]) == 2    # 2 clips; a clip's 2 output frames (0 s, 0.512 s) share a segment
-    assert not any(t is s for t in ms.state_tensors() for s in sed.sed.states.values())
+    assert torch.equal(sed.counter.counts(), before) and int(before[0, 3, 3]) == 2    # 2 clips; a clip's 2 output frames (0 s, 0.512 s) share a segment
+    assert not any(t is s for t in ms.state_tensors() for s in sed.counter.states.values())
     want = M.sed_counts_host(*seen[0], thr, hop=hop)
     assert torch.equal(before, want) and np.array_equal(want.numpy(), R.counts(seen[0][0].numpy(), seen[0][1].numpy(), thr, hop=hop))
     first = M.sed_metrics(want, thr)['per_threshold'][0]
@@ -177,7 +183,7 @@ def test_metric_set_through_test_step_equals_the_cpu_path():
     for name, value in (('val_seg_f1', first['segment']['f1']), ('val_seg_er', first['segment']['er']), ('val_event_f1', first['event']['f1'])):
         assert vals[name] == value or (vals[name] != vals[name] and value != value), (name, vals, first)
     ms.reset()
-    assert int(sed.sed.counts().sum()) == 0
+    assert int(sed.counter.counts().sum()) == 0
 
 
 def test_eval_writes_the_measures_of_the_recordings(tmp_path, monkeypatch):

@@ -260,22 +260,22 @@ def test_metric_set_feeds_the_counts_in_the_val_phase_only():
     ms = M.MetricSet([M.cos_sim, sed, M.er_score(smoothing=False), M.score_curves(64)])
     assert ms.sed is sed and sed not in ms.others
     out = ms(yt, yp, 'train')
-    assert set(out) == {'cos_sim', 'er'} and sed.sed is None                        # nothing made, nothing counted
+    assert set(out) == {'cos_sim', 'er'} and sed.counter is None                        # nothing made, nothing counted
     assert set(ms.sed_values('val_')) == {'val_seg_f1', 'val_seg_er', 'val_event_f1'}
     assert all(math.isnan(v) for v in ms.sed_values('val_').values())
     assert set(ms(yt, yp, 'val')) == {'cos_sim', 'er'}                              # no per-step value
     ms(yt, yp, 'train')
     want = R.counts(yt.numpy(), yp.numpy(), (0.5, 0.7), hop=1600)
-    assert np.array_equal(sed.sed.counts().numpy(), want)
-    assert not any(t is s for t in ms.state_tensors() for s in sed.sed.states.values())
+    assert np.array_equal(sed.counter.counts().numpy(), want)
+    assert not any(t is s for t in ms.state_tensors() for s in sed.counter.states.values())
     first = M.sed_metrics(want, (0.5, 0.7))['per_threshold'][0]
     assert ms.sed_values('val_') == {'val_seg_f1': first['segment']['f1'], 'val_seg_er': first['segment']['er'],
                                      'val_event_f1': first['event']['f1']}
     assert M.SED_NAMES == ('seg_f1', 'seg_er', 'event_f1')
     ms.reset('train')
-    assert int(sed.sed.counts().sum()) == int(want.sum())
+    assert int(sed.counter.counts().sum()) == int(want.sum())
     ms.reset()
-    assert int(sed.sed.counts().sum()) == 0
+    assert int(sed.counter.counts().sum()) == 0
     assert M.MetricSet([M.cos_sim]).sed_values('val_') == {}
     with pytest.raises(ValueError, match="sed_eval"):
         M.MetricSet([M.sed_eval(), M.sed_eval((0.3,))])
