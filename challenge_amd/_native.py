@@ -91,6 +91,7 @@ SIGNATURES = {
     "iris_magmel_gain": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
     "iris_spec_ipd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     "iris_spec_whiten_factors": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, C.c_double, _vp]),
+    "iris_spec_whiten_factors_ranges": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_double, _vp]),
     "iris_spec_whiten": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp]),
     "iris_locate_events": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
     "iris_beamform_events": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),

@@ -262,7 +262,54 @@ extern "C" int iris_spec_whiten_factors(iris_plan* p, const float* spec, float* 
     a.n_waves = (long long)batch * p->n_bins * ((a.J + per_wave - 1) / per_wave);
     const long long blocks = (a.n_waves + 3) / 4;
     if (blocks > 0x7fffffffLL) return fail(IRIS_E_UNSUPPORTED, "%s: %lld workgroups exceed the grid limit", who, blocks);
-    k_whiten_factors<<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(a);
+    k_whiten_factors<false><<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(a);
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+
+// iris_spec_whiten_factors_ranges: the factors of every (sample, bin, block) from the frames a table names, without the masked
+// ones (k_whiten.h, K18).  ranges_host is the host's copy of the device table: what is checked here.  Every check that does not
+// read the plan comes first, and all of them before the first HIP call.
+extern "C" int iris_spec_whiten_factors_ranges(iris_plan* p, const float* spec, const uint8_t* mask, const int32_t* ranges_dev,
+                                               const int32_t* ranges_host, float* factors, int batch, int n_frames, int block,
+                                               double loading, void* stream) {
+    const char* who = "iris_spec_whiten_factors_ranges";
+    if (!p || !spec || !mask || !ranges_dev || !ranges_host || !factors) return fail(IRIS_E_INVALID, "%s: NULL argument", who);
+    if (batch <= 0 || n_frames <= 0) return fail(IRIS_E_INVALID, "%s: batch=%d n_frames=%d", who, batch, n_frames);
+    if (block < 1) return fail(IRIS_E_INVALID, "%s: block=%d must be at least 1 frame", who, block);
+    if (!std::isfinite(loading) || loading <= 0.) return fail(IRIS_E_INVALID, "%s: loading=%g must be finite and positive", who, loading);
+    if ((reinterpret_cast<uintptr_t>(spec) & 15) || (reinterpret_cast<uintptr_t>(factors) & 15))
+        return fail(IRIS_E_INVALID, "%s: spec and factors must be 16-byte aligned", who);
+    if (reinterpret_cast<uintptr_t>(ranges_dev) & 3) return fail(IRIS_E_INVALID, "%s: the range table must be 4-byte aligned", who);
+    if (batch > 65535) return fail(IRIS_E_UNSUPPORTED, "%s: batch %d > 65535", who, batch);
+    const int blk = std::min(block, n_frames), n_blocks = (n_frames + blk - 1) / blk;
+    for (long long i = 0; i < (long long)batch * n_blocks; ++i) {
+        const int32_t* r = ranges_host + 3 * i;
+        if (r[0] < 0 || r[0] >= r[1] || r[1] > n_frames || (r[2] != 0 && r[2] != 1))
+            return fail(IRIS_E_INVALID, "%s: sample %lld, block %lld: frames [%d, %d) of %d, use_mask=%d", who, i / n_blocks,
+                        i % n_blocks, r[0], r[1], n_frames, r[2]);
+    }
+    if (p->channels != 2) return fail(IRIS_E_UNSUPPORTED, "%s: the plan has %d channel(s); the covariance is that of a stereo pair", who, p->channels);
+    DeviceGuard guard(p->device);
+    WhitenRangeArgs a;
+    a.spec = spec;
+    a.fac = factors;
+    a.loading = loading;
+    a.B = batch;
+    a.F = p->n_bins;
+    a.T = n_frames;
+    a.block = blk;
+    a.J = n_blocks;
+    a.log2g = 0;
+    // G from `block` as passed, not cut to n_frames: a recording shorter than a block sums in the order it would in a longer batch
+    while (a.log2g < 6 && (4LL << a.log2g) < block) ++a.log2g;
+    const int per_wave = 64 >> a.log2g;
+    a.n_waves = (long long)batch * p->n_bins * ((a.J + per_wave - 1) / per_wave);
+    a.mask = mask;
+    a.ranges = ranges_dev;
+    const long long blocks = (a.n_waves + 3) / 4;
+    if (blocks > 0x7fffffffLL) return fail(IRIS_E_UNSUPPORTED, "%s: %lld workgroups exceed the grid limit", who, blocks);
+    k_whiten_factors<true><<<dim3((unsigned)blocks), 256, 0, (hipStream_t)stream>>>(a);
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
 }

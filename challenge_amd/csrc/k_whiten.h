@@ -32,6 +32,19 @@
 //      component (2), all relative to |X1| + |c| |X0|;  z1 = b y: b stored in fp32 (1) + the product (1) -> (3 + 2) 2 = 10 on
 //      |z1|^2;  the sum of the four squares: one product + three fmas (4)  ->  14 per bin;  the band sum: one fma per bin
 //      (n_m);  wnorm stored in fp32 (1) and the final product (1)  ->  (n_m + 16) u A.
+//
+// K18: k_whiten_factors<true>, the factors of a block from the frames OUTSIDE the detected events (iris_spec_whiten_factors_ranges).
+//   A host-built table names, per (sample, block), the frames [t0, t1) behind the block's covariance - the block itself or the
+//   block and up to `reach` neighbours a side, at most (2 reach + 1) block frames - and whether the byte mask [B, T] (non-zero:
+//   the frame is inside an event) applies.  The same text as pass 1 (a template flag): the same G lanes per (row, block), G a
+//   function of `block` alone, lane l taking the frames t0 + l, t0 + l + G, ... of the RANGE in frame order; the mask byte is
+//   loaded first and a masked frame's 16 bytes are never loaded (four frames a step: the four bytes in flight together, then
+//   the 16-byte loads of the frames that count, then the sums - a byte load followed by its dependent 16-byte load, frame
+//   after frame, left one load in flight and measured 1.43 x pass 1 with an empty mask); four double sums and an integer
+//   count per lane, the same xor tree, the mean = sum * (1 / count) and the factorisation in double on the group's lane 0.
+//   count == 0: a = b = c = 0.
+//   The same four fp32 roundings: a, b, |c| within 4 u of the float64 form.  use_mask == 0 over a block's own frames is pass 1,
+//   bit for bit.  One launch, no workspace, no atomics; a row depends on its own sample's spectrum, mask and table rows only.
 // ---------------------------------------------------------------------------
 constexpr float kWhitenLogEps = 1e-8f;  // log_on_mel's epsilon
 
@@ -42,6 +55,11 @@ struct WhitenFactorArgs {
     int B, F, T, J, block;
     int log2g;          // G = 1 << log2g lanes per block
     long long n_waves;  // B * F * ceil(J / (64 / G))
+};
+
+struct WhitenRangeArgs : WhitenFactorArgs {  // K18: the frames behind a block's covariance come from a table
+    const unsigned char* mask;  // [B, T], non-zero: the frame is inside an event
+    const int* ranges;          // [B, J, 3] = (t0, t1, use_mask): frames [t0, t1), without the masked ones when use_mask
 };
 
 struct WhitenArgs {
@@ -59,7 +77,9 @@ struct WhitenArgs {
     int B, F, T, M, J, block, log;
 };
 
-__global__ __launch_bounds__(256) void k_whiten_factors(const WhitenFactorArgs a) {
+// RANGES = false is K3w's pass 1; RANGES = true is K18 (the same text: the same lane mapping, sums, tree and factorisation)
+template <bool RANGES>
+__global__ __launch_bounds__(256) void k_whiten_factors(const std::conditional_t<RANGES, WhitenRangeArgs, WhitenFactorArgs> a) {
     typedef float vec4 __attribute__((ext_vector_type(4)));
     const int lane = threadIdx.x & 63;
     const long long wave = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -69,31 +89,79 @@ __global__ __launch_bounds__(256) void k_whiten_factors(const WhitenFactorArgs a
     const long long row = wave / jw;                 // b * F + f
     const int j = (int)(wave % jw) * per_wave + (lane >> a.log2g);
     const int l = lane & (G - 1);
-    const int t0 = j < a.J ? j * a.block : a.T;  // (a group past the last block reads nothing and writes nothing)
-    const int t1 = min(t0 + a.block, a.T);
+    int t0, t1;
+    [[maybe_unused]] const unsigned char* mk = nullptr;  // the sample's mask row
+    [[maybe_unused]] bool use_mask = false;              // false: every frame of the range counts
+    if constexpr (RANGES) {
+        t0 = t1 = a.T;  // (a group past the last block reads nothing and writes nothing)
+        if (j < a.J) {
+            const int* r = a.ranges + ((row / a.F) * a.J + j) * 3;
+            t0 = max(r[0], 0);
+            t1 = min(r[1], a.T);  // (the host checked the table's host copy; the clamps keep a differing device copy in bounds)
+            use_mask = r[2] != 0;
+            mk = a.mask + (row / a.F) * a.T;
+        }
+    } else {
+        t0 = j < a.J ? j * a.block : a.T;  // (a group past the last block reads nothing and writes nothing)
+        t1 = min(t0 + a.block, a.T);
+    }
     const vec4* sp = reinterpret_cast<const vec4*>(a.spec) + row * a.T;
     double s00 = 0., s11 = 0., sre = 0., sim = 0.;
-#pragma unroll 4  // (loads of four frames in flight; the sums keep their frame order)
-    for (int t = t0 + l; t < t1; t += G) {
-        const vec4 v = sp[t];
-        const double re0 = v[0], re1 = v[1], im0 = v[2], im1 = v[3];
-        s00 += re0 * re0 + im0 * im0;
-        s11 += re1 * re1 + im1 * im1;
-        sre += re1 * re0 + im1 * im0;  // X1 conj(X0)
-        sim += im1 * re0 - re1 * im0;
+    [[maybe_unused]] int cnt = 0;  // RANGES: the frames this lane summed
+// one frame into the four sums (sre + i sim: X1 conj(X0)); the one text of both kernels
+#define WHITEN_ADD_FRAME(v)                                              \
+    {                                                                    \
+        const double re0 = v[0], re1 = v[1], im0 = v[2], im1 = v[3];     \
+        s00 += re0 * re0 + im0 * im0;                                    \
+        s11 += re1 * re1 + im1 * im1;                                    \
+        sre += re1 * re0 + im1 * im0;                                    \
+        sim += im1 * re0 - re1 * im0;                                    \
     }
+    if constexpr (RANGES) {
+        // four frames a step, in three passes so that the loads of one pass are in flight together: the mask bytes first, then
+        // the 16 bytes of the frames that count (a masked frame's are never loaded), then the sums in frame order
+        constexpr int U = 4;
+        for (int t = t0 + l; t < t1; t += U * G) {
+            bool on[U];
+            vec4 v[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int tu = t + u * G;
+                const unsigned char m = mk[min(tu, t1 - 1)];  // (unconditional, so that the four are in flight together: past
+                on[u] = (tu < t1) & !(use_mask & (m != 0));    // the range the last byte again, dropped; unused when !use_mask)
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) v[u] = on[u] ? sp[t + u * G] : vec4(0.f);
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (!on[u]) continue;
+                WHITEN_ADD_FRAME(v[u]);
+                ++cnt;
+            }
+        }
+    } else {
+#pragma unroll 4  // (loads of four frames in flight; the sums keep their frame order)
+        for (int t = t0 + l; t < t1; t += G) {
+            const vec4 v = sp[t];
+            WHITEN_ADD_FRAME(v);
+        }
+    }
+#undef WHITEN_ADD_FRAME
     for (int off = G >> 1; off; off >>= 1) {  // the fixed tree: lanes of other groups never mix in (off < G)
         s00 += __shfl_xor(s00, off);
         s11 += __shfl_xor(s11, off);
         sre += __shfl_xor(sre, off);
         sim += __shfl_xor(sim, off);
+        if constexpr (RANGES) cnt += __shfl_xor(cnt, off);
     }
     if (l != 0 || j >= a.J) return;
-    const double inv_n = 1.0 / (double)(t1 - t0);
+    int n = t1 - t0;
+    if constexpr (RANGES) n = cnt;
+    const double inv_n = 1.0 / (double)n;
     const double r00 = s00 * inv_n, r11 = s11 * inv_n, rre = sre * inv_n, rim = sim * inv_n;
     const double d = a.loading * (r00 + r11) * 0.5;
     vec4 o = {0.f, 0.f, 0.f, 0.f};
-    if (d != 0.) {
+    if (d != 0. && (!RANGES || n > 0)) {  // (n == 0, a masked range without a quiet frame: NaN above; zero factors, as a silent block)
         const double fa = 1.0 / sqrt(r00 + d), fa2 = fa * fa;  // 1 / l00, 1 / l00^2
         const double l11sq = r11 + d - (rre * rre + rim * rim) * fa2;  // r11 + d - |l10|^2
         o[0] = (float)fa;

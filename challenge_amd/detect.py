@@ -833,6 +833,10 @@ class Detection:
                                                            # beamformed sound of each event; None unless `detect` was given `extract=`
     audio_span: Optional[Tuple[np.ndarray, ...]] = None    # per class [n, 2] int64 (first, last) sample of the recording each clip
                                                            # stands for (the event widened by the context)
+    noise_frames: Optional[Tuple[np.ndarray, ...]] = None  # per class [n] int64, row for row with `events`: the fewest quiet frames
+                                                           # behind any noise-covariance block the event touches, 0 where a block
+                                                           # fell back on its own frames (the event nulls itself there as under
+                                                           # noise='block'); None unless locate.noise == 'quiet'
 
 
 @dataclass
@@ -859,8 +863,12 @@ class LocateSettings:
     frames per noise-covariance block (None: config.n_frame); loading: the covariance's diagonal loading; q: lag steps per
     sample; f_lo_hz .. f_hi_hz: the band whose bins are steered (250 Hz is the cut `stft_filter` applies in evaluation: bin 16
     at n_fft 1024, bin 8 at load_wav's 512); noise: 'block' (whitened by the block covariance) or 'identity' (the plain
-    steered response: finds the loudest direction); sound_speed in m/s; max_lag: lag steps either way (None: the array's
-    aperture, ceil(mic_spacing / sound_speed * 16000 * q))."""
+    steered response: finds the loudest direction) or 'quiet' (whitened by the covariance of the frames OUTSIDE the detected
+    events: every event of any class, widened by guard_s seconds a side, is masked; a block uses its own unmasked frames if
+    there are at least min_quiet of them, else those of itself and up to `reach` neighbours a side, else - a fallback that
+    `Detection.noise_frames` reports as 0 - its own frames with the event in them; `transforms.quiet_ranges`.  guard_s = 0.1,
+    min_quiet = 32 frames (0.5 s at load_wav's hop) and reach = 1 are choices, not measurements); sound_speed in m/s; max_lag:
+    lag steps either way (None: the array's aperture, ceil(mic_spacing / sound_speed * 16000 * q))."""
     mic_spacing: float = 0.1
     block: Optional[int] = None
     loading: float = 1e-2
@@ -870,8 +878,22 @@ class LocateSettings:
     noise: str = "block"
     sound_speed: float = 343.0
     max_lag: Optional[int] = None
+    guard_s: float = 0.1
+    min_quiet: int = 32
+    reach: int = 1
+
+    def guard_frames(self, hop: int = HOP) -> int:
+        """guard_s in frames of `hop` samples at 16 kHz, rounded to the nearest frame (as `ExtractSettings.frames`)."""
+        return int(round(self.guard_s * SR / hop))
 
     def __post_init__(self):
+        v = self.guard_s
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not (np.isfinite(v) and v >= 0):
+            raise ValueError(f"LocateSettings: guard_s = {v!r} must be a finite number of seconds >= 0")
+        if isinstance(self.min_quiet, bool) or not isinstance(self.min_quiet, (int, np.integer)) or self.min_quiet < 1:
+            raise ValueError(f"LocateSettings: min_quiet = {self.min_quiet!r} must be a positive number of frames")
+        if isinstance(self.reach, bool) or not isinstance(self.reach, (int, np.integer)) or self.reach < 0:
+            raise ValueError(f"LocateSettings: reach = {self.reach!r} must be a number of blocks >= 0")
         from .frontend import LOCATE_MAX_LAGS
         for name in ("mic_spacing", "loading", "sound_speed"):
             v = getattr(self, name)
@@ -881,8 +903,8 @@ class LocateSettings:
             raise ValueError(f"LocateSettings: q = {self.q!r} must be an integer in 1 .. 65536")
         if self.block is not None and (isinstance(self.block, bool) or not isinstance(self.block, (int, np.integer)) or self.block < 1):
             raise ValueError(f"LocateSettings: block = {self.block!r} must be None or a positive number of frames")
-        if self.noise not in ("block", "identity"):
-            raise ValueError(f"LocateSettings: noise = {self.noise!r} must be 'block' or 'identity'")
+        if self.noise not in ("block", "identity", "quiet"):
+            raise ValueError(f"LocateSettings: noise = {self.noise!r} must be 'block', 'identity' or 'quiet'")
         lo, hi = self.f_lo_hz, self.f_hi_hz
         if not (isinstance(lo, (int, float)) and isinstance(hi, (int, float)) and np.isfinite(lo) and np.isfinite(hi) and 0 <= lo < hi):
             raise ValueError(f"LocateSettings: f_lo_hz = {lo!r}, f_hi_hz = {hi!r} must be finite with 0 <= f_lo_hz < f_hi_hz")
@@ -995,7 +1017,9 @@ def detect(model, wavs_or_paths: Sequence, config, overlap_hop: int = 512, batch
     features: per file the `whiten_factors` launch, per group one `FrontendPlan.locate` call.  The recordings must be stereo
     (ValueError) and on a ROCm device.  It costs memory: the spectra of a group stay on the device until the group is decoded,
     16 bytes x F x T per file, and once more, padded to the longest file, for the group's call.  Without `locate` nothing
-    changes and `location` is None.
+    changes and `location` is None.  With `LocateSettings(noise='quiet')` the covariance comes from the frames outside the
+    detected events - per group one mask, one range table and ONE `whiten_factors_ranges` launch - and `Detection.noise_frames`
+    holds, per class and row for row with `events`, the quiet frames behind each event (0: a block fell back on its own frames).
     `extract`: ExtractSettings, only with `locate` (ValueError otherwise) - every detected event's sound is also extracted
     (`Detection.audio`: per class a list of float32 arrays, row for row with `events`; `Detection.audio_span`: per class [n, 2]
     int64, the sample range of the recording each clip stands for): the event, widened by `context_s` a side, through the MVDR
@@ -1025,7 +1049,12 @@ def _locate_group(spectra, events, config, locate: LocateSettings, extract: Opti
     the context inside its OWN file's frames, goes through one `beamform` call over the same padded spectra and factors,
     steered at the delay just found, one `iris_istft` launch and one copy back; a frame's value depends on its sample, frame,
     bin and delay only, so the clips equal `transforms.extract_events` of the file alone, bit for bit.
-    Returns (locations, audio, spans), one entry per file."""
+    With locate.noise == 'quiet' the factors come from ONE `whiten_factors_ranges` launch over the padded spectra: one mask of
+    the group's events (guard_s in frames of the spectrum's hop) and one range table, every range clipped to its file's own
+    length; the lanes that share a range follow from the block length alone, so the rows still equal the file alone, bit for
+    bit.  Blocks past a file's end read zero padding: zero factors.  `Detection.noise_frames` is then the fewest quiet frames
+    behind any block an event touches (else None).
+    Returns (locations, audio, spans, noise_frames), one entry per file."""
     from . import transforms as T
     rows = [(i, int(f0), int(f1)) for i, ev in enumerate(events) for cls in ev for f0, f1 in np.asarray(cls).reshape(-1, 2)]
     out = np.zeros((0, 4), np.float64)
@@ -1045,6 +1074,10 @@ def _locate_group(spectra, events, config, locate: LocateSettings, extract: Opti
             for i, sp in enumerate(spectra):
                 own = plan.whiten_factors(sp.float().unsqueeze(0).contiguous(), block, locate.loading)
                 fac[i, :, :own.shape[2]] = own[0]
+        elif locate.noise == "quiet":   # one mask, one range table, ONE factors launch over the padded spectra
+            fac, quiet = T._quiet_factors(plan, spec, np.asarray(rows, np.int64), block, locate.loading, locate.guard_frames(f - 1),
+                                          locate.min_quiet, locate.reach, [int(sp.shape[1]) for sp in spectra])
+            behind = T.quiet_frames(rows, quiet, max(min(block, t_max), 1))
         curve, n_terms = plan.locate(spec, np.asarray(rows, np.int32), fac, block, k_lo, k_hi, locate.max_lag, locate.q)
         out = T.locate_peak(curve, n_terms, locate.q, locate.mic_spacing, float(SR), locate.sound_speed)
         if extract is not None:
@@ -1055,11 +1088,14 @@ def _locate_group(spectra, events, config, locate: LocateSettings, extract: Opti
             spans = wide[:, 1:] * (f - 1)                                  # load_wav's hop: n_fft // 2 = F - 1
             ends = np.cumsum(spans[:, 1] - spans[:, 0])
             clips = [samples[z - n:z].copy() for z, n in zip(ends, spans[:, 1] - spans[:, 0])]
-    res, audio, where, at = [], [], [], 0
+    res, audio, where, noise, at = [], [], [], [], 0
+    quiet_on = locate.noise == "quiet"
     for ev in events:
-        per_class, per_audio, per_span = [], [], []
+        per_class, per_audio, per_span, per_noise = [], [], [], []
         for cls in ev:
             per_class.append(out[at:at + len(cls)].copy())
+            if quiet_on:
+                per_noise.append(behind[at:at + len(cls)].copy() if rows else np.zeros((0,), np.int64))
             if extract is not None:
                 per_audio.append(clips[at:at + len(cls)] if rows else [])
                 per_span.append(spans[at:at + len(cls)].copy() if rows else np.zeros((0, 2), np.int64))
@@ -1067,7 +1103,8 @@ def _locate_group(spectra, events, config, locate: LocateSettings, extract: Opti
         res.append(tuple(per_class))
         audio.append(tuple(per_audio) if extract is not None else None)
         where.append(tuple(per_span) if extract is not None else None)
-    return res, audio, where
+        noise.append(tuple(per_noise) if quiet_on else None)
+    return res, audio, where, noise
 
 
 def _detect_group(model, group, config, overlap_hop: int, batch_size: int, settings=None, locate=None,
@@ -1078,11 +1115,11 @@ def _detect_group(model, group, config, overlap_hop: int, batch_size: int, setti
     else:
         events = decode_events(preds, win_off, [t for _, t, _ in group], config.n_frame, overlap_hop, settings=settings)
     none = [None] * len(group)
-    where, audio, spans = _locate_group(spectra, events, config, locate, extract) if locate is not None else (none, none, none)
+    where, audio, spans, noise = _locate_group(spectra, events, config, locate, extract) if locate is not None else (none,) * 4
     out = []
-    for (name, t_len, _), ev, loc, clips, span in zip(group, events, where, audio, spans):
+    for (name, t_len, _), ev, loc, clips, span, behind in zip(group, events, where, audio, spans, noise):
         metric = M.output_to_metric(HOP, SR)(*ev)
-        out.append(Detection(name, t_len, ev, metric, _FromEvents(ev).get_start_end_time(None), loc, clips, span))
+        out.append(Detection(name, t_len, ev, metric, _FromEvents(ev).get_start_end_time(None), loc, clips, span, behind))
     return out
 
 
@@ -1175,8 +1212,11 @@ def location_rows(det: Detection) -> list:
 
 def write_locations(results: Sequence[Detection], path: str) -> dict:
     """{"task2_location": {name: [[class, first_frame, last_frame, tdoa, bearing, score, contrast], ...]}}: where every event
-    of `detect(..., locate=)` comes from (NaN is written as null)."""
+    of `detect(..., locate=)` comes from (NaN is written as null).  Under LocateSettings(noise='quiet') also "noise_frames":
+    {name: [n, ...]}, row for row with the recording's locations: `Detection.noise_frames`, 0 where the event may null itself."""
     where = {"task2_location": {d.name: location_rows(d) for d in results}}
+    if results and all(d.noise_frames is not None for d in results):
+        where["noise_frames"] = {d.name: [int(v) for cls in d.noise_frames for v in np.asarray(cls).reshape(-1)] for d in results}
     with open(path, 'w') as f:
         json.dump(where, f, indent=4, allow_nan=False)
     return where
@@ -1229,6 +1269,16 @@ def main(argv=None):
                                   'written to --locate_out')
     config.args.add_argument('--mic_spacing', type=float, default=0.1, help='metres between the two microphones (--locate)')
     config.args.add_argument('--locate_out', type=str, default='location.json', help='where --locate writes the locations')
+    config.args.add_argument('--locate_noise', type=str, default='block', choices=['block', 'identity', 'quiet'],
+                             help="what --locate whitens with: the covariance of each block of frames, nothing (the plain steered "
+                                  "response), or 'quiet': the covariance of the frames outside the detected events, so that a "
+                                  "dominant event does not null itself (--locate_out then also lists noise_frames)")
+    config.args.add_argument('--locate_guard', type=float, default=0.1, metavar='S',
+                             help='seconds by which every event is widened before its frames are left out (--locate_noise quiet)')
+    config.args.add_argument('--locate_min_quiet', type=int, default=32, metavar='N',
+                             help='the fewest quiet frames a noise covariance is taken from (--locate_noise quiet)')
+    config.args.add_argument('--locate_reach', type=int, default=1, metavar='R',
+                             help='how many neighbouring blocks a side may lend their quiet frames (--locate_noise quiet)')
     config.args.add_argument('--extract', type=str, default=None, metavar='DIR',
                              help='with --locate: also write the beamformed sound of every detected event to '
                                   'DIR/<recording>_c<class>_<row>.wav (mono, float32, 16 kHz, on load_wav\'s scale: the recording '
@@ -1239,6 +1289,10 @@ def main(argv=None):
     config = config.get(argv)
     if config.extract is not None and not config.locate:
         parser.error("--extract steers every event at its own delay: it needs --locate")
+    # (the settings refuse bad values before the model is loaded)
+    locate = LocateSettings(mic_spacing=config.mic_spacing, noise=config.locate_noise, guard_s=config.locate_guard,
+                            min_quiet=config.locate_min_quiet, reach=config.locate_reach) if config.locate else None
+    extract = ExtractSettings(context_s=config.extract_context) if config.extract is not None else None
     if config.p:
         parse_name(config)
     if config.tune and config.decoder:
@@ -1260,8 +1314,6 @@ def main(argv=None):
         print(f"MEAN ER reference {tuned.mean_er_reference!r} chosen {tuned.mean_er_chosen!r} (on the tuning recordings)")
     if settings is None and config.decoder_kind == 'hmm':
         settings = HmmSettings.default(config.n_classes)
-    locate = LocateSettings(mic_spacing=config.mic_spacing) if config.locate else None
-    extract = ExtractSettings(context_s=config.extract_context) if config.extract is not None else None
     results = detect(model, paths, config, overlap_hop=config.overlap_hop, settings=settings, locate=locate, extract=extract)
     write_answer(results, config.out)
     print(f"{len(results)} files, {sum(len(d.metric) for d in results)} events -> {config.out}")

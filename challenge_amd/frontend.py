@@ -359,6 +359,61 @@ class FrontendPlan:
         N.check(rc, "iris_spec_whiten_factors")
         return fac
 
+    def whiten_factors_ranges(self, spec: torch.Tensor, mask, ranges, block: Optional[int] = None,
+                              loading: float = 1e-2) -> torch.Tensor:
+        """`whiten_factors` with the covariance of every (sample, block) taken over the frames a table names - the noise
+        covariance from the frames outside detected events (`iris_spec_whiten_factors_ranges`, one launch;
+        `transforms.quiet_mask` and `transforms.quiet_ranges` build the two inputs, `tests/quiet_ref.py` states the
+        definition).  mask: uint8 [B,T], non-zero where a frame is inside an event - a tensor on spec's device, or a host array
+        that is uploaded here; ranges: int32 [B,J,3] = (t0, t1, use_mask) per (sample, block), J = ceil(T / min(block, T)), on
+        the host (an array or a CPU tensor; checked and uploaded here): the means run over the frames of [t0, t1), without the
+        masked ones when use_mask is 1.  use_mask = 1 without an unmasked frame gives zero factors.  G, the lanes that share a
+        range, follows from `block` as given (None: T), not cut to T.  Returns the factors [B,F,J,4]."""
+        what = "whiten_factors_ranges"
+        given = None if block is None else int(block)
+        spec, b, t, _, j = self._whiten_args(spec, block, what)
+        given = max(t, 1) if given is None else given
+        loading = float(loading)
+        if not (math.isfinite(loading) and loading > 0):
+            raise ValueError(f"{what}: loading = {loading} must be finite and positive")
+        if isinstance(mask, torch.Tensor):
+            if mask.dtype != torch.uint8 or tuple(mask.shape) != (b, t) or mask.device != spec.device:
+                raise ValueError(f"{what}: mask must be uint8 [{b}, {t}] on {spec.device}, got {mask.dtype} {tuple(mask.shape)} on "
+                                 f"{mask.device}")
+            mask = mask.contiguous()
+        else:
+            m = np.asarray(mask)
+            if m.dtype != np.uint8 or m.shape != (b, t):
+                raise ValueError(f"{what}: mask must be uint8 [{b}, {t}], got {m.dtype} {m.shape}")
+            mask = torch.from_numpy(np.ascontiguousarray(m)).to(spec.device, non_blocking=True)
+        if isinstance(ranges, torch.Tensor):
+            if ranges.is_cuda:
+                raise ValueError(f"{what}: ranges must be on the host (it is checked there and uploaded here), got {ranges.device}")
+            ranges = ranges.numpy()
+        table = np.asarray(ranges)
+        if table.dtype != np.int32 or table.shape != (b, j, 3):
+            raise ValueError(f"{what}: ranges must be int32 [{b}, {j}, 3] = (t0, t1, use_mask) for blocks of {min(given, max(t, 1))} "
+                             f"frames, got {table.dtype} {table.shape}")
+        table = np.ascontiguousarray(table)
+        bad = np.argwhere((table[..., 0] < 0) | (table[..., 0] >= table[..., 1]) | (table[..., 1] > t)
+                          | (table[..., 2] < 0) | (table[..., 2] > 1))
+        if bad.size:
+            i, k = (int(v) for v in bad[0])
+            raise ValueError(f"{what}: sample {i}, block {k}: (t0, t1, use_mask) = {tuple(int(v) for v in table[i, k])} must hold "
+                             f"0 <= t0 < t1 <= {t} and use_mask 0 or 1")
+        fac = torch.empty((b, self.n_bins, j, 4), dtype=torch.float32, device=spec.device)
+        if b == 0 or t == 0:
+            return fac
+        table_dev = torch.from_numpy(table).to(spec.device, non_blocking=True)
+        with self._lock, torch.cuda.device(self.device):
+            rc = N.lib().iris_spec_whiten_factors_ranges(self._handle, spec.data_ptr(), mask.data_ptr(), table_dev.data_ptr(),
+                                                         table.ctypes.data, fac.data_ptr(), b, t, given, loading,
+                                                         _stream_ptr(self.device))
+        N.check(rc, "iris_spec_whiten_factors_ranges")
+        for x in (table_dev, mask):   # (they must outlive the kernel on this stream)
+            x.record_stream(torch.cuda.current_stream(self.device))
+        return fac
+
     def whiten(self, spec: torch.Tensor, block: Optional[int] = None, loading: float = 1e-2, log: bool = True,
                t_bands=None, f_bands=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Stereo complex spec [B,F,T,4] -> the spatially whitened mel-band energy [B,M,T]: x^H (R + d I)^-1 x per bin, with R

@@ -441,9 +441,113 @@ def _locate_plan(x: torch.Tensor):
     return plan
 
 
+NOISE_KINDS = ("block", "identity", "quiet")
+
+
+def _count(value, name: str, least: int) -> int:
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < least:
+        raise ValueError(f"quiet: {name} = {value!r} must be an integer >= {least}")
+    return int(value)
+
+
+def _sample_lengths(n_frames, batch=None) -> np.ndarray:
+    """One frame count per sample, int64 [B]: a sequence as it is, one count repeated `batch` times (None: once)."""
+    n = np.asarray(n_frames)
+    if n.ndim == 0:
+        n = np.repeat(n, 1 if batch is None else int(batch))
+    if n.ndim != 1 or n.size == 0 or not np.issubdtype(n.dtype, np.integer) or (n < 1).any() or \
+            (batch is not None and n.size != int(batch)):
+        raise ValueError(f"quiet: n_frames = {n_frames!r} must be a frame count >= 1, or one per sample")
+    return n.astype(np.int64)
+
+
+def quiet_mask(events, n_frames, guard: int = 0, batch=None) -> np.ndarray:
+    """The frames that do NOT count as noise: uint8 [B, T], 1 for every frame inside any event of sample b - events: integers
+    [E, 3] = (sample, first frame, last frame), frames inclusive, of any class - widened by `guard` frames a side and clipped
+    to the recording.  n_frames: one frame count per sample (B of them; T is the largest) or one count for all of `batch`
+    samples (None: one).  Frames past a sample's own end stay 0: no range of `quiet_ranges` holds them.  Host NumPy."""
+    lens, guard = _sample_lengths(n_frames, batch), _count(guard, "guard", 0)
+    mask = np.zeros((len(lens), int(lens.max())), np.uint8)
+    ev = np.asarray(events.cpu() if torch.is_tensor(events) else events)
+    if ev.size == 0:
+        return mask
+    if ev.ndim != 2 or ev.shape[1] != 3 or not np.issubdtype(ev.dtype, np.integer):
+        raise ValueError(f"quiet: events must be integers [E, 3] = (sample, first frame, last frame), got {ev.dtype} {ev.shape}")
+    ev = ev.astype(np.int64)
+    inside = (ev[:, 0] >= 0) & (ev[:, 0] < len(lens))
+    bad = np.flatnonzero(~inside | (ev[:, 1] < 0) | (ev[:, 1] > ev[:, 2]) | (ev[:, 2] >= lens[np.where(inside, ev[:, 0], 0)]))
+    if bad.size:
+        i = int(bad[0])
+        raise ValueError(f"quiet: event {i} = (sample {ev[i, 0]}, frames {ev[i, 1]} .. {ev[i, 2]}) does not fit {len(lens)} sample(s) "
+                         f"of {lens.tolist()} frames with first <= last")
+    for s, first, last in ev:
+        mask[s, max(first - guard, 0):min(last + guard, lens[s] - 1) + 1] = 1
+    return mask
+
+
+def quiet_ranges(mask, n_frames, block=None, min_quiet: int = 32, reach: int = 1):
+    """Which frames stand behind the noise covariance of every (sample, block): (ranges int32 [B, J, 3] = (t0, t1, use_mask),
+    quiet int64 [B, J]) from mask uint8 [B, T] (`quiet_mask`) and n_frames, one frame count per sample (or one for all).
+    Blocks of `block` frames from frame 0 (None, or more than T: all T), J = ceil(T / block).  For block j of a sample of T_b
+    frames and r = 0 .. reach, the first r for which [max((j - r) block, 0), min((j + r + 1) block, T_b)) holds at least
+    `min_quiet` unmasked frames gives the range, with use_mask = 1 and quiet = that count: the block's own quiet frames, else
+    those of the block and r neighbours a side.  If there is none the range is the block's own frames with use_mask = 0 and
+    quiet = 0: the block covariance, event included.  A block that starts past the sample's end gets its own (padding) frames
+    with use_mask = 0 and quiet = 0: a zero-padded spectrum gives it zero factors.  Host NumPy."""
+    m = np.asarray(mask.cpu() if torch.is_tensor(mask) else mask)
+    if m.ndim != 2 or m.dtype != np.uint8 or m.shape[1] < 1:
+        raise ValueError(f"quiet: mask must be uint8 [B, T >= 1], got {m.dtype} {m.shape}")
+    bsz, t = m.shape
+    lens = _sample_lengths(n_frames, bsz)
+    if (lens > t).any():
+        raise ValueError(f"quiet: n_frames = {lens.tolist()} exceed the mask's {t} frames")
+    min_quiet, reach = _count(min_quiet, "min_quiet", 1), _count(reach, "reach", 0)
+    blk = min(t if block is None else _count(block, "block", 1), t)
+    n_blocks = (t + blk - 1) // blk
+    ahead = np.concatenate([np.zeros((bsz, 1), np.int64), np.cumsum(m == 0, axis=1, dtype=np.int64)], axis=1)   # quiet frames before t
+    ranges, quiet = np.zeros((bsz, n_blocks, 3), np.int32), np.zeros((bsz, n_blocks), np.int64)
+    for b in range(bsz):
+        t_b = int(lens[b])
+        for j in range(n_blocks):
+            ranges[b, j] = (j * blk, min((j + 1) * blk, t_b if j * blk < t_b else t), 0)
+            if j * blk >= t_b:
+                continue
+            for r in range(reach + 1):
+                lo, hi = max((j - r) * blk, 0), min((j + r + 1) * blk, t_b)
+                n = int(ahead[b, hi] - ahead[b, lo])
+                if n >= min_quiet:
+                    ranges[b, j], quiet[b, j] = (lo, hi, 1), n
+                    break
+                if lo == 0 and hi == t_b:   # the whole recording already: a wider reach finds nothing more
+                    break
+    return ranges, quiet
+
+
+def quiet_frames(events, quiet, block) -> np.ndarray:
+    """How much noise stands behind each event: int64 [E], the fewest quiet frames (`quiet_ranges`' second result [B, J]) behind
+    any block of `block` frames the event (sample, first frame, last frame) touches; 0 when one of them fell back on its own
+    frames, event included."""
+    ev = np.asarray(events, np.int64).reshape(-1, 3)
+    quiet = np.asarray(quiet, np.int64)
+    blk = max(int(block), 1)
+    return np.asarray([quiet[s, first // blk:last // blk + 1].min() for s, first, last in ev], np.int64).reshape(-1)
+
+
+def _quiet_factors(plan, x: torch.Tensor, events, block, loading: float, guard: int, min_quiet: int, reach: int, n_frames=None):
+    """The factors of noise="quiet" for the spectrum x [B, F, T, 4] and its events: (fac [B, F, J, 4], quiet [B, J])."""
+    bsz, t = int(x.shape[0]), int(x.shape[2])
+    lens = _sample_lengths(t if n_frames is None else n_frames, bsz)
+    mask = quiet_mask(events, lens, guard)
+    if mask.shape[1] < t:   # (the longest recording is shorter than the padded spectrum)
+        mask = np.pad(mask, ((0, 0), (0, t - mask.shape[1])))
+    block = t if block is None else _count(block, "block", 1)
+    ranges, quiet = quiet_ranges(mask, lens, block, min_quiet, reach)
+    return plan.whiten_factors_ranges(x, mask, ranges, block, loading), quiet
+
+
 def locate_events(spec: torch.Tensor, events, block=None, loading: float = WHITEN_LOADING, noise: str = "block", k_lo: int = 0,
                   k_hi=None, max_lag: int = 40, q: int = 8, mic_spacing: float = 0.1, sample_rate: float = 16000.0,
-                  sound_speed: float = LOCATE_SOUND) -> np.ndarray:
+                  sound_speed: float = LOCATE_SOUND, guard: int = 0, min_quiet: int = 32, reach: int = 1) -> np.ndarray:
     """Where each event comes from: the noise-whitened steered response of a two-microphone delay vector over the event's
     frames, and its peak.  spec: a STEREO complex spectrum [B, F, T, 4] (or [F, T, 4]) = (re0, re1, im0, im1) on a ROCm device,
     n_fft = 2 (F - 1); events: integers [E, 3] = (sample, first frame, last frame), frames inclusive, 0 <= first <= last < T.
@@ -461,13 +565,18 @@ def locate_events(spec: torch.Tensor, events, block=None, loading: float = WHITE
     curve[E, 2 max_lag + 1] is the sum of the terms over the event's segments and bins, n_terms[E] the sum over the
     contributing (segment, bin) pairs of the segment's frame count: under noise alone curve / n_terms is near 1.  Returns
     `locate_peak` of the curves: float64 [E, 4] = (tdoa in samples, bearing in degrees, score, contrast).
+    noise="quiet": the covariance of a block is taken over the frames OUTSIDE the events (`tests/quiet_ref.py` restates it):
+    every frame inside any of `events`, widened by `guard` frames a side, is masked (`quiet_mask`); a block uses its own
+    unmasked frames if there are at least `min_quiet` of them, else those of itself and up to `reach` neighbours a side, else
+    - a fallback - all of its own frames, event included (`quiet_ranges`); the factors are otherwise "block"'s
+    (`FrontendPlan.whiten_factors_ranges`, one launch).  guard = 0, min_quiet = 32 and reach = 1 are choices, not measurements.
     The launches are `FrontendPlan.whiten_factors` (noise="block") and `FrontendPlan.locate`; there is no CPU fallback.
-    What it cannot do: a pair cannot tell front from back (the bearing is mirrored about the microphones' axis); the block
-    covariance includes the event, so an event that dominates its block partly nulls itself; and the estimate is biased
-    towards the interferer when the two delays are within about a sample of each other (with two microphones one degree of
-    freedom is left after the null)."""
-    if noise not in ("block", "identity"):
-        raise ValueError(f"locate_events: noise = {noise!r} must be 'block' or 'identity'")
+    What it cannot do: a pair cannot tell front from back (the bearing is mirrored about the microphones' axis); with
+    noise="block", and with noise="quiet" in a fallback block, the block covariance includes the event, so an event that
+    dominates its block partly nulls itself; and the estimate is biased towards the interferer when the two delays are within
+    about a sample of each other (with two microphones one degree of freedom is left after the null)."""
+    if noise not in NOISE_KINDS:
+        raise ValueError(f"locate_events: noise = {noise!r} must be 'block', 'identity' or 'quiet'")
     if not isinstance(spec, torch.Tensor):
         raise TypeError(f"spec must be a torch.Tensor, got {type(spec).__name__}")
     x = spec if spec.dim() == 4 else spec.unsqueeze(0)
@@ -478,7 +587,10 @@ def locate_events(spec: torch.Tensor, events, block=None, loading: float = WHITE
                            "(there is no CPU fallback); move the tensor to 'cuda'")
     x = x.float().contiguous()
     plan = _locate_plan(x)
-    fac = plan.whiten_factors(x, block, loading) if noise == "block" else None
+    if noise == "quiet":
+        fac, _ = _quiet_factors(plan, x, events, block, loading, guard, min_quiet, reach)
+    else:
+        fac = plan.whiten_factors(x, block, loading) if noise == "block" else None
     curve, n_terms = plan.locate(x, events, fac, block, k_lo, k_hi, max_lag, q)
     return locate_peak(curve, n_terms, q, mic_spacing, sample_rate, sound_speed)
 
@@ -536,7 +648,7 @@ def clips_from_slabs(slabs, hop=None):
 
 
 def extract_events(spec: torch.Tensor, events, tdoa, block=None, loading: float = WHITEN_LOADING, noise: str = "block",
-                   k_lo: int = 0, k_hi=None, context: int = 0, hop=None):
+                   k_lo: int = 0, k_hi=None, context: int = 0, hop=None, guard: int = 0, min_quiet: int = 32, reach: int = 1):
     """The sound of each event with the interferer nulled: the MVDR (minimum-variance distortionless-response) beamformer
     w = R^-1 d / (d^H R^-1 d) of a two-microphone delay vector, applied over the event's frames, and the inverse STFT of the
     result.  spec: a STEREO complex spectrum [B, F, T, 4] (or [F, T, 4]) = (re0, re1, im0, im1) on a ROCm device, n_fft =
@@ -556,11 +668,14 @@ def extract_events(spec: torch.Tensor, events, tdoa, block=None, loading: float 
     int64 [E, 2] = (first hop, last hop), the sample range of the recording the clip stands for.
     The launches are `FrontendPlan.whiten_factors` (noise="block"), `FrontendPlan.beamform` and one `iris_istft` per 65535
     events; there is no CPU fallback.
-    What it cannot do: the block covariance contains the event, so a steering error on an event that dominates its block
-    makes the beamformer null the event itself (1/8 sample on a source 10 dB above the interferer costs 3.5 dB, 10 dB when the
-    event fills 400 of the block's 512 frames; at 10 dB under the interferer the loss is under 0.1 dB)."""
-    if noise not in ("block", "identity"):
-        raise ValueError(f"extract_events: noise = {noise!r} must be 'block' or 'identity'")
+    noise="quiet" with `guard`, `min_quiet` and `reach`: the covariance from the frames outside the events, as
+    `locate_events` describes it; the mask is that of `events` as given, before the context widens them.
+    What it cannot do: with noise="block", and with noise="quiet" in a fallback block (`quiet_ranges`), the block covariance
+    contains the event, so a steering error on an event that dominates its block makes the beamformer null the event itself
+    (1/8 sample on a source 10 dB above the interferer costs 3.5 dB, 10 dB when the event fills 400 of the block's 512 frames;
+    at 10 dB under the interferer the loss is under 0.1 dB)."""
+    if noise not in NOISE_KINDS:
+        raise ValueError(f"extract_events: noise = {noise!r} must be 'block', 'identity' or 'quiet'")
     if not isinstance(spec, torch.Tensor):
         raise TypeError(f"spec must be a torch.Tensor, got {type(spec).__name__}")
     x = spec if spec.dim() == 4 else spec.unsqueeze(0)
@@ -574,7 +689,10 @@ def extract_events(spec: torch.Tensor, events, tdoa, block=None, loading: float 
     plan = _locate_plan(x)
     n_fft = 2 * (int(x.shape[1]) - 1)
     hop = n_fft // 2 if hop is None else int(hop)
-    fac = plan.whiten_factors(x, block, loading) if noise == "block" else None
+    if noise == "quiet":   # (the mask is that of the events as given, not widened by the context)
+        fac, _ = _quiet_factors(plan, x, events, block, loading, guard, min_quiet, reach)
+    else:
+        fac = plan.whiten_factors(x, block, loading) if noise == "block" else None
     slabs = plan.beamform(x, wide, tdoa, fac, block, k_lo, k_hi)
     clips, _ = clips_from_slabs(slabs, hop)
     return clips, wide[:, 1:] * hop

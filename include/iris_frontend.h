@@ -281,6 +281,30 @@ int iris_spec_whiten(iris_plan* plan, const float* spec, const float* factors, f
                      const int32_t* f_bands, int n_f_bands, void* stream);
 
 /*
+ * iris_spec_whiten_factors_ranges (k_whiten.h, K18): the same factors, with the covariance of every (sample, block) taken
+ * over the frames a table names - the noise covariance from the frames OUTSIDE detected events.
+ * mask: DEVICE bytes [batch, n_frames], non-zero where a frame is inside an event.  ranges: int32 [batch, J, 3] = (t0, t1,
+ * use_mask) per (sample, block), J = ceil(n_frames / min(block, n_frames)), once on the device (ranges_dev, what the kernel
+ * reads) and once on the host (ranges_host, what is checked here).  The means r00, r11, r10 of block j are taken over the
+ * frames t of [t0, t1) that count: with use_mask = 1 those with mask[sample, t] == 0, with use_mask = 0 all of them; the
+ * factorisation is iris_spec_whiten_factors'.  use_mask = 1 with no unmasked frame in the range: a = b = c = 0, like a
+ * silent block.  A range may lie anywhere in [0, n_frames) and have any length (the block and its neighbours).
+ * factors [batch, n_bins, J, 4] as above; each of a, b and |c| is within 4 * 2^-24 relative of the float64 form from the same
+ * fp32 spectrum.  A group of G lanes sums a range, G a function of `block` AS PASSED (a quarter of the power of two >=
+ * block, 1 .. 64; not cut to n_frames, so that a recording shorter than a block is summed in the same order when it is padded
+ * into a longer batch).  With block <= n_frames, a row (j block, min((j + 1) block, n_frames), 0) gives the bits of
+ * iris_spec_whiten_factors for that block, and so does use_mask = 1 under an all-zero mask.
+ * Refused before any HIP call: NULL pointers, empty shapes, block < 1, loading not finite or <= 0, spec or factors not 16-byte
+ * aligned, a device table that is not 4-byte aligned, a ranges_host row with t0 < 0, t0 >= t1, t1 > n_frames or use_mask
+ * outside {0, 1} (IRIS_E_INVALID); batch > 65535, a plan whose channel count is not 2 (IRIS_E_UNSUPPORTED).  One launch on
+ * `stream`, no workspace, no atomics, fixed summation orders: bitwise reproducible, independent of the batch a sample sits in,
+ * capturable.
+ */
+int iris_spec_whiten_factors_ranges(iris_plan* plan, const float* spec, const uint8_t* mask, const int32_t* ranges_dev,
+                                    const int32_t* ranges_host, float* factors, int batch, int n_frames, int block,
+                                    double loading, void* stream);
+
+/*
  * Event localisation (k_locate.h): the noise-whitened steered response of a two-microphone delay vector over the frames of
  * detected events - the adaptive matched filter the whitening factors above were built for.
  * spec: a STEREO complex spectrum [batch, n_bins, n_frames, 4] = (re0, re1, im0, im1); factors: [batch, n_bins, n_blocks, 4]
