@@ -351,11 +351,13 @@ extern "C" int iris_spec_whiten(iris_plan* p, const float* spec, const float* fa
 
 // iris_locate_events: the noise-whitened steered response of E events over a lag grid (k_locate.h, two launches); every check
 // happens before the first HIP call.  events_host is the host's copy of the device table: what is checked here.
-extern "C" int iris_locate_events(iris_plan* p, const float* spec, const float* factors, int n_blocks, const int32_t* events_dev,
-                                  const int32_t* events_host, int n_events, int batch, int n_frames, int block, int k_lo, int k_hi,
-                                  int max_lag, int q, double* workspace, size_t workspace_bytes, double* curve, int64_t* n_terms,
-                                  void* stream) {
-    const char* who = "iris_locate_events";
+// step == 0: K16, rows are the events' segments and `curve` holds one row per event.  step >= 1: K19 (k_track.h), rows are the
+// events' steps of `step` frames and `curve` (= R) and n_terms hold one row per step.
+static int locate_impl(const char* who, int step, iris_plan* p, const float* spec, const float* factors, int n_blocks,
+                       const int32_t* events_dev, const int32_t* events_host, int n_events, int batch, int n_frames, int block,
+                       int k_lo, int k_hi, int max_lag, int q, double* workspace, size_t workspace_bytes, double* curve,
+                       int64_t* n_terms, void* stream) {
+    const bool steps = step != 0;
     if (!p || !spec) return fail(IRIS_E_INVALID, "%s: NULL argument", who);
     if (batch <= 0 || n_frames <= 0 || n_events < 0)
         return fail(IRIS_E_INVALID, "%s: batch=%d n_frames=%d n_events=%d", who, batch, n_frames, n_events);
@@ -377,6 +379,9 @@ extern "C" int iris_locate_events(iris_plan* p, const float* spec, const float* 
         block = n_frames;  // the identity: one block
         n_blocks = 1;
     }
+    if (steps && (step < 1 || (n_blocks > 1 && block % step)))
+        return fail(IRIS_E_INVALID, "%s: step=%d must be at least 1 frame and divide block=%d (a step lies in one block)", who, step, block);
+    const int cut = steps ? step : block;
     if (n_events > 0 && (!events_dev || !events_host || !workspace || !curve || !n_terms)) return fail(IRIS_E_INVALID, "%s: NULL argument", who);
     if ((reinterpret_cast<uintptr_t>(events_dev) & 3) || (reinterpret_cast<uintptr_t>(workspace) & 7) ||
         (reinterpret_cast<uintptr_t>(curve) & 7) || (reinterpret_cast<uintptr_t>(n_terms) & 7))
@@ -387,9 +392,9 @@ extern "C" int iris_locate_events(iris_plan* p, const float* spec, const float* 
         if (r[0] < 0 || r[0] >= batch) return fail(IRIS_E_INVALID, "%s: event %d names sample %d of %d", who, e, r[0], batch);
         if (r[1] < 0 || r[1] > r[2] || r[2] >= n_frames)
             return fail(IRIS_E_INVALID, "%s: event %d spans frames %d .. %d of %d", who, e, r[1], r[2], n_frames);
-        if (r[3] != n_seg) return fail(IRIS_E_INVALID, "%s: event %d starts at segment %d, expected %lld", who, e, r[3], n_seg);
-        n_seg += r[2] / block - r[1] / block + 1;
-        if (n_seg > 0x7fffffffLL) return fail(IRIS_E_UNSUPPORTED, "%s: more than 2^31 - 1 segments", who);
+        if (r[3] != n_seg) return fail(IRIS_E_INVALID, "%s: event %d starts at %s %d, expected %lld", who, e, steps ? "row" : "segment", r[3], n_seg);
+        n_seg += r[2] / cut - r[1] / cut + 1;
+        if (n_seg > 0x7fffffffLL) return fail(IRIS_E_UNSUPPORTED, "%s: more than 2^31 - 1 %s", who, steps ? "rows" : "segments");
     }
     // (the plan is read only now: everything above is checked without it)
     if (p->channels != 2) return fail(IRIS_E_UNSUPPORTED, "%s: the plan has %d channel(s); the delay is that of a stereo pair", who, p->channels);
@@ -397,7 +402,7 @@ extern "C" int iris_locate_events(iris_plan* p, const float* spec, const float* 
     if (k_hi > p->n_bins) return fail(IRIS_E_INVALID, "%s: bins [%d, %d) leave [0, %d]", who, k_lo, k_hi, p->n_bins);
     if (n_events == 0) return IRIS_OK;  // nothing to do, no launch
     const int nk = k_hi - k_lo, lags = 2 * max_lag + 1;
-    const long long mom_waves = n_seg * nk, scan_waves = (long long)n_events * lags;
+    const long long mom_waves = n_seg * nk, scan_waves = (steps ? n_seg : (long long)n_events) * lags;
     if (workspace_bytes / 32 < (size_t)mom_waves)
         return fail(IRIS_E_CAPACITY, "%s: workspace of %zu bytes, %lld needed", who, workspace_bytes, 32 * mom_waves);
     if ((mom_waves + 3) / 4 > 0x7fffffffLL || (scan_waves + 3) / 4 > 0x7fffffffLL)
@@ -423,19 +428,96 @@ extern "C" int iris_locate_events(iris_plan* p, const float* spec, const float* 
     a.q = q;
     a.L = lags;
     a.period = 2LL * (p->n_bins - 1) * q;  // n_fft q (a mel-only plan carries no n_fft)
-    k_locate_moments<<<dim3((unsigned)((mom_waves + 3) / 4)), 256, 0, (hipStream_t)stream>>>(a);
+    a.cut = cut;  // (K19's field: K16's kernels do not read it)
+    const dim3 mom_grid((unsigned)((mom_waves + 3) / 4)), scan_grid((unsigned)((scan_waves + 3) / 4));
+    if (steps) {
+        k_locate_moments<true><<<mom_grid, 256, 0, (hipStream_t)stream>>>(a);
+        HIP_TRY(hipGetLastError());
+        k_track_scan<<<scan_grid, 256, 0, (hipStream_t)stream>>>(a);
+    } else {
+        k_locate_moments<false><<<mom_grid, 256, 0, (hipStream_t)stream>>>(a);
+        HIP_TRY(hipGetLastError());
+        k_locate_scan<<<scan_grid, 256, 0, (hipStream_t)stream>>>(a);
+    }
     HIP_TRY(hipGetLastError());
-    k_locate_scan<<<dim3((unsigned)((scan_waves + 3) / 4)), 256, 0, (hipStream_t)stream>>>(a);
+    return IRIS_OK;
+}
+
+extern "C" int iris_locate_events(iris_plan* p, const float* spec, const float* factors, int n_blocks, const int32_t* events_dev,
+                                  const int32_t* events_host, int n_events, int batch, int n_frames, int block, int k_lo, int k_hi,
+                                  int max_lag, int q, double* workspace, size_t workspace_bytes, double* curve, int64_t* n_terms,
+                                  void* stream) {
+    return locate_impl("iris_locate_events", 0, p, spec, factors, n_blocks, events_dev, events_host, n_events, batch, n_frames, block,
+                       k_lo, k_hi, max_lag, q, workspace, workspace_bytes, curve, n_terms, stream);
+}
+
+// iris_locate_steps: the steered response of every STEP of `step` frames of E events (k_track.h, two launches): iris_locate_events'
+// arguments and checks with rows for segments; `response` [rows, 2 max_lag + 1] and n_terms [rows].
+extern "C" int iris_locate_steps(iris_plan* p, const float* spec, const float* factors, int n_blocks, const int32_t* events_dev,
+                                 const int32_t* events_host, int n_events, int batch, int n_frames, int block, int step, int k_lo,
+                                 int k_hi, int max_lag, int q, double* workspace, size_t workspace_bytes, double* response,
+                                 int64_t* n_terms, void* stream) {
+    const char* who = "iris_locate_steps";
+    if (step < 1) return fail(IRIS_E_INVALID, "%s: step=%d must be at least 1 frame", who, step);
+    return locate_impl(who, step, p, spec, factors, n_blocks, events_dev, events_host, n_events, batch, n_frames, block, k_lo, k_hi,
+                       max_lag, q, workspace, workspace_bytes, response, n_terms, stream);
+}
+
+// iris_track_lags: the best path through the lags of every event's step responses (k_track.h, one launch); every check happens
+// before the first HIP call.  offsets_host is the host's copy of the device table: what is checked here.
+extern "C" int iris_track_lags(iris_plan* p, const double* response, const int32_t* offsets_dev, const int32_t* offsets_host,
+                               int n_events, int n_rows, int max_lag, const double* penalty_dev, int n_penalty, int max_jump,
+                               int32_t* workspace, size_t workspace_bytes, int32_t* path, void* stream) {
+    const char* who = "iris_track_lags";
+    if (!p) return fail(IRIS_E_INVALID, "%s: NULL argument", who);
+    if (n_events < 0 || n_rows < 0 || max_lag < 0 || max_jump < 0)
+        return fail(IRIS_E_INVALID, "%s: n_events=%d n_rows=%d max_lag=%d max_jump=%d", who, n_events, n_rows, max_lag, max_jump);
+    if (2LL * max_lag + 1 > kTrackMaxLags)
+        return fail(IRIS_E_UNSUPPORTED, "%s: %lld lags exceed the limit of %d", who, 2LL * max_lag + 1, kTrackMaxLags);
+    const int lags = 2 * max_lag + 1, jump = std::min(max_jump, lags - 1);
+    if (n_penalty != jump + 1)
+        return fail(IRIS_E_INVALID, "%s: a penalty table of %d entries, min(max_jump, lags - 1) + 1 = %d expected", who, n_penalty, jump + 1);
+    if (n_events > 0 && (!response || !offsets_dev || !offsets_host || !penalty_dev || !workspace || !path))
+        return fail(IRIS_E_INVALID, "%s: NULL argument", who);
+    if ((reinterpret_cast<uintptr_t>(response) & 7) || (reinterpret_cast<uintptr_t>(penalty_dev) & 7) ||
+        (reinterpret_cast<uintptr_t>(offsets_dev) & 3) || (reinterpret_cast<uintptr_t>(workspace) & 3) || (reinterpret_cast<uintptr_t>(path) & 3))
+        return fail(IRIS_E_INVALID, "%s: response and the penalty table must be 8-byte, offsets, workspace and path 4-byte aligned", who);
+    if (n_events > 0 && offsets_host[0] != 0) return fail(IRIS_E_INVALID, "%s: the offsets start at %d, not 0", who, offsets_host[0]);
+    for (int e = 0; e < n_events; ++e)
+        if (offsets_host[e + 1] <= offsets_host[e])
+            return fail(IRIS_E_INVALID, "%s: event %d owns rows %d .. %d: every event has at least one step", who, e, offsets_host[e],
+                        offsets_host[e + 1] - 1);
+    if (n_events > 0 && offsets_host[n_events] != n_rows)
+        return fail(IRIS_E_INVALID, "%s: the offsets end at %d, but there are %d rows", who, offsets_host[n_events], n_rows);
+    if (n_events == 0) {
+        if (n_rows != 0) return fail(IRIS_E_INVALID, "%s: %d rows without an event", who, n_rows);
+        return IRIS_OK;  // nothing to do, no launch
+    }
+    if (workspace_bytes / 4 / (size_t)lags < (size_t)n_rows)
+        return fail(IRIS_E_CAPACITY, "%s: workspace of %zu bytes, %lld needed", who, workspace_bytes, 4LL * lags * n_rows);
+    DeviceGuard guard(p->device);
+    TrackArgs a;
+    a.R = response;
+    a.offsets = offsets_dev;
+    a.pen = penalty_dev;
+    a.back = workspace;
+    a.path = path;
+    a.E = n_events;
+    a.rows = n_rows;
+    a.L = lags;
+    a.J = jump;
+    k_track_viterbi<<<dim3((unsigned)n_events), 256, 0, (hipStream_t)stream>>>(a);
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
 }
 
 // iris_beamform_events: the MVDR beamformer of E events, one [F, T_e, 2] slab each (k_beamform.h, one launch); every check
 // happens before the first HIP call.  events_host is the host's copy of the device table: what is checked here.
-extern "C" int iris_beamform_events(iris_plan* p, const float* spec, const float* factors, int n_blocks, const int32_t* events_dev,
-                                    const int32_t* events_host, const double* tdoa_dev, int n_events, int batch, int n_frames,
-                                    int block, int k_lo, int k_hi, float* out, size_t out_floats, void* stream) {
-    const char* who = "iris_beamform_events";
+// n_tdoa < 0: K17, one delay per event.  n_tdoa >= 0: K19, one delay per output frame, n_tdoa of them.
+static int beamform_impl(const char* who, long long n_tdoa, iris_plan* p, const float* spec, const float* factors, int n_blocks,
+                         const int32_t* events_dev, const int32_t* events_host, const double* tdoa_dev, int n_events, int batch,
+                         int n_frames, int block, int k_lo, int k_hi, float* out, size_t out_floats, void* stream) {
+    const bool per_frame = n_tdoa >= 0;
     if (!p || !spec) return fail(IRIS_E_INVALID, "%s: NULL argument", who);
     if (batch <= 0 || n_frames <= 0 || n_events < 0)
         return fail(IRIS_E_INVALID, "%s: batch=%d n_frames=%d n_events=%d", who, batch, n_frames, n_events);
@@ -468,6 +550,7 @@ extern "C" int iris_beamform_events(iris_plan* p, const float* spec, const float
         longest = std::max(longest, r[2] - r[1] + 1);
         if (total > 0x7fffffffLL) return fail(IRIS_E_UNSUPPORTED, "%s: more than 2^31 - 1 output frames", who);
     }
+    if (per_frame && n_tdoa != total) return fail(IRIS_E_INVALID, "%s: %lld delays for %lld output frames", who, n_tdoa, total);
     // (the plan is read only now: everything above is checked without it)
     if (p->channels != 2) return fail(IRIS_E_UNSUPPORTED, "%s: the plan has %d channel(s); the delay is that of a stereo pair", who, p->channels);
     if (p->n_bins < 2) return fail(IRIS_E_UNSUPPORTED, "%s: a plan of %d bin(s)", who, p->n_bins);
@@ -475,8 +558,8 @@ extern "C" int iris_beamform_events(iris_plan* p, const float* spec, const float
     if (n_events == 0) return IRIS_OK;  // nothing to do, no launch
     if (out_floats / 2 / (size_t)p->n_bins < (size_t)total)
         return fail(IRIS_E_CAPACITY, "%s: out of %zu floats, %lld needed", who, out_floats, 2LL * p->n_bins * total);
-    const int groups = (p->n_bins + kBeamBins - 1) / kBeamBins;
-    const long long waves = (long long)groups * ((longest + kBeamChunk - 1) / kBeamChunk);
+    const int groups = (p->n_bins + kBeamBins - 1) / kBeamBins, chunks = (longest + 63) / 64;
+    const long long waves = per_frame ? (long long)p->n_bins * chunks : (long long)groups * ((longest + kBeamChunk - 1) / kBeamChunk);
     if ((waves + 3) / 4 > 65535 || n_events > (1 << 24))
         return fail(IRIS_E_UNSUPPORTED, "%s: %lld waves per event / %d events exceed the grid limit", who, waves, n_events);
     DeviceGuard guard(p->device);
@@ -497,9 +580,31 @@ extern "C" int iris_beamform_events(iris_plan* p, const float* spec, const float
     a.groups = groups;
     a.total = total;
     a.n_fft = 2.0 * (p->n_bins - 1);  // (a mel-only plan carries no n_fft)
-    k_beamform<<<dim3((unsigned)n_events, (unsigned)((waves + 3) / 4)), 256, 0, (hipStream_t)stream>>>(a);
+    const dim3 grid((unsigned)n_events, (unsigned)((waves + 3) / 4));
+    if (per_frame)
+        k_beamform_frames<<<grid, 256, 0, (hipStream_t)stream>>>(a, chunks);
+    else
+        k_beamform<<<grid, 256, 0, (hipStream_t)stream>>>(a);
     HIP_TRY(hipGetLastError());
     return IRIS_OK;
+}
+
+extern "C" int iris_beamform_events(iris_plan* p, const float* spec, const float* factors, int n_blocks, const int32_t* events_dev,
+                                    const int32_t* events_host, const double* tdoa_dev, int n_events, int batch, int n_frames,
+                                    int block, int k_lo, int k_hi, float* out, size_t out_floats, void* stream) {
+    return beamform_impl("iris_beamform_events", -1, p, spec, factors, n_blocks, events_dev, events_host, tdoa_dev, n_events, batch,
+                         n_frames, block, k_lo, k_hi, out, out_floats, stream);
+}
+
+// iris_beamform_frames: iris_beamform_events with one delay per OUTPUT FRAME (k_beamform.h, k_beamform_frames; one launch):
+// tdoa_dev [n_tdoa], n_tdoa the frames of all events.
+extern "C" int iris_beamform_frames(iris_plan* p, const float* spec, const float* factors, int n_blocks, const int32_t* events_dev,
+                                    const int32_t* events_host, const double* tdoa_dev, size_t n_tdoa, int n_events, int batch,
+                                    int n_frames, int block, int k_lo, int k_hi, float* out, size_t out_floats, void* stream) {
+    const char* who = "iris_beamform_frames";
+    if (n_tdoa > 0x7fffffffULL) return fail(IRIS_E_UNSUPPORTED, "%s: more than 2^31 - 1 delays", who);
+    return beamform_impl(who, (long long)n_tdoa, p, spec, factors, n_blocks, events_dev, events_host, tdoa_dev, n_events, batch,
+                         n_frames, block, k_lo, k_hi, out, out_floats, stream);
 }
 
 extern "C" size_t iris_minmax_log_workspace(int n_rows, size_t row_len) {

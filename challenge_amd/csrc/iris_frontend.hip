@@ -72,6 +72,7 @@
 #include "k_whiten.h"
 #include "k_locate.h"
 #include "k_beamform.h"
+#include "k_track.h"
 #include "k_elementwise.h"
 #include "host_plan.h"
 #include "k_ism.h"

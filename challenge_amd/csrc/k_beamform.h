@@ -53,6 +53,24 @@ struct BeamformArgs {
     double n_fft;         // 2 (F - 1)
 };
 
+// The two double-precision steps both kernels of this file share, so that they cannot drift apart: the phase e = cs - i sn of
+// bin k at a delay, and (g0, g1) of one (a, b, c), rounded ONCE to fp32.
+__device__ __forceinline__ void beam_phase(int k, double tdoa, double n_fft, double& sn, double& cs) {
+    double r = (double)k * tdoa / n_fft;
+    r -= rint(r);
+    sincospi(2.0 * r, &sn, &cs);  // e = cs - i sn
+}
+
+__device__ __forceinline__ void beam_weights(double fa, double fb, double cr, double ci, double sn, double cs, float& g0r,
+                                             float& g0i, float& g1r, float& g1i) {
+    const double s1r = fb * (cs - cr), s1i = fb * (-sn - ci), a2 = fa * fa;
+    const double den = a2 + (s1r * s1r + s1i * s1i);
+    const double h1r = fb * s1r / den, h1i = -(fb * s1i) / den;  // g1 = b conj(s1) / den
+    g1r = (float)h1r, g1i = (float)h1i;
+    g0r = (float)(a2 / den - (h1r * cr - h1i * ci));             // g0 = a^2 / den - g1 c
+    g0i = (float)(-(h1r * ci + h1i * cr));
+}
+
 __global__ __launch_bounds__(256) void k_beamform(const BeamformArgs a) {
     typedef float vec4 __attribute__((ext_vector_type(4)));
     typedef float vec2 __attribute__((ext_vector_type(2)));
@@ -74,11 +92,7 @@ __global__ __launch_bounds__(256) void k_beamform(const BeamformArgs a) {
     const int k = k0 + lane;
     const bool steer = lane < nkb && k >= a.k_lo && k < a.k_hi && isfinite(tdoa);
     double sn = 0., cs = 1.;
-    if (steer) {
-        double r = (double)k * tdoa / a.n_fft;
-        r -= rint(r);
-        sincospi(2.0 * r, &sn, &cs);  // e = cs - i sn
-    }
+    if (steer) beam_phase(k, tdoa, a.n_fft, sn, cs);
     const vec4* spec = reinterpret_cast<const vec4*>(a.spec) + ((size_t)b * a.F + k0) * a.T;
     vec2* slab = reinterpret_cast<vec2*>(a.out) + ((size_t)row0 * a.F + (size_t)k0 * te);
     for (int j = c0 / a.block; j <= c1 / a.block && j < a.J; ++j) {
@@ -94,12 +108,7 @@ __global__ __launch_bounds__(256) void k_beamform(const BeamformArgs a) {
             }
             if (fa != 0.) {
                 live = true;
-                const double s1r = fb * (cs - cr), s1i = fb * (-sn - ci), a2 = fa * fa;
-                const double den = a2 + (s1r * s1r + s1i * s1i);
-                const double h1r = fb * s1r / den, h1i = -(fb * s1i) / den;  // g1 = b conj(s1) / den
-                g1r = (float)h1r, g1i = (float)h1i;
-                g0r = (float)(a2 / den - (h1r * cr - h1i * ci));             // g0 = a^2 / den - g1 c
-                g0i = (float)(-(h1r * ci + h1i * cr));
+                beam_weights(fa, fb, cr, ci, sn, cs, g0r, g0i, g1r, g1i);
             }
         }
         const unsigned long long alive = __ballot(live);
@@ -130,4 +139,53 @@ __global__ __launch_bounds__(256) void k_beamform(const BeamformArgs a) {
             }
         }
     }
+}
+
+// ---------------------------------------------------------------------------
+// K19 (with k_track.h): the same beamformer with one delay PER OUTPUT FRAME - tdoa [total] double, frame t of event e reads
+// tdoa[row0 + (t - first)], row0 the event's first output frame - for an event whose delay moves (transforms.track_delays).
+// Everything else is K17's definition, read per frame: Y = 0 exactly where k is outside [k_lo, k_hi), a == 0 or the frame's
+// delay is not finite.  One thread per (bin, frame): a wave takes one bin and 64 consecutive frames of an event (16-byte loads
+// and 8-byte stores, both coalesced along t); the thread forms e, g0, g1 in double with beam_phase / beam_weights - the very
+// statements of k_beamform - rounds once, and runs the same product and three fmas.  So the 6 u A bound above holds unchanged,
+// a frame's value depends on its sample, frame, bin and delay only, and a delay that is constant over an event gives the bits
+// of k_beamform.  It pays one double sincospi per (bin, frame) where k_beamform pays one per (bin, chunk): a small launch,
+// deliberately not tuned further.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_beamform_frames(const BeamformArgs a, const int chunks) {
+    typedef float vec4 __attribute__((ext_vector_type(4)));
+    typedef float vec2 __attribute__((ext_vector_type(2)));
+    const int lane = threadIdx.x & 63;
+    const int e = blockIdx.x;
+    const long long w = (long long)blockIdx.y * 4 + (threadIdx.x >> 6);  // wave-uniform: (bin, chunk of 64 frames)
+    const int k = (int)(w / chunks), chunk = (int)(w % chunks);
+    if (e >= a.E || k >= a.F) return;
+    const int b = a.events[4 * e], first = a.events[4 * e + 1], last = a.events[4 * e + 2], row0 = a.events[4 * e + 3];
+    // (the host checked every record; a record that does not fit reads nothing and writes nothing)
+    const bool fits = b >= 0 && b < a.B && first >= 0 && first <= last && last < a.T && row0 >= 0 &&
+                      (long long)row0 + (last - first + 1) <= a.total;
+    if (!fits) return;
+    const int te = last - first + 1;
+    const long long tl = (long long)chunk * 64 + lane;  // the frame inside the event
+    if (tl >= te) return;
+    const int t = first + (int)tl, j = t / a.block;
+    const double tdoa = a.tdoa[(size_t)row0 + tl];
+    vec2 y = vec2{0.f, 0.f};  // exactly 0 unless the bin is steered, whatever the spectrum holds there
+    if (k >= a.k_lo && k < a.k_hi && isfinite(tdoa) && j < a.J) {
+        double fa = 1., fb = 1., cr = 0., ci = 0.;
+        if (a.fac) {
+            const vec4 q = reinterpret_cast<const vec4*>(a.fac)[((size_t)b * a.F + k) * a.J + j];
+            fa = q[0], fb = q[1], cr = q[2], ci = q[3];
+        }
+        if (fa != 0.) {
+            double sn, cs;
+            beam_phase(k, tdoa, a.n_fft, sn, cs);
+            float g0r, g0i, g1r, g1i;
+            beam_weights(fa, fb, cr, ci, sn, cs, g0r, g0i, g1r, g1i);
+            const vec4 v = reinterpret_cast<const vec4*>(a.spec)[((size_t)b * a.F + k) * a.T + t];  // (re0, re1, im0, im1)
+            y[0] = __builtin_fmaf(-g1i, v[3], __builtin_fmaf(g1r, v[1], __builtin_fmaf(-g0i, v[2], g0r * v[0])));
+            y[1] = __builtin_fmaf(g1i, v[1], __builtin_fmaf(g1r, v[3], __builtin_fmaf(g0i, v[0], g0r * v[2])));
+        }
+    }
+    reinterpret_cast<vec2*>(a.out)[(size_t)row0 * a.F + (size_t)k * te + tl] = y;
 }

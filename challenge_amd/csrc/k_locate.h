@@ -41,6 +41,7 @@ struct LocateArgs {
     int E, S, k_lo, nk;  // nk = k_hi - k_lo
     int N, q, L;         // L = 2 N + 1
     long long period;    // n_fft q
+    int cut;             // K19 (k_track.h): rows are cut at multiples of `cut` frames (block % cut == 0 unless J == 1); K16 does not read it
 };
 
 template <typename T>
@@ -49,6 +50,9 @@ __device__ __forceinline__ T locate_wave_sum(T v) {  // the fixed xor tree over 
     return v;
 }
 
+// kSteps (K19, k_track.h): a row is a STEP of a.cut frames instead of a block - events[.][3] then counts steps, the factors are
+// still those of the row's block t0 / block (block % cut == 0 unless there is one block: a step lies in one block).  false is K16's kernel, untouched.
+template <bool kSteps>
 __global__ __launch_bounds__(256) void k_locate_moments(const LocateArgs a) {
     typedef float vec4 __attribute__((ext_vector_type(4)));
     const int lane = threadIdx.x & 63;
@@ -61,8 +65,10 @@ __global__ __launch_bounds__(256) void k_locate_moments(const LocateArgs a) {
         if (a.events[4 * mid + 3] <= s) lo = mid; else hi = mid - 1;
     }
     const int b = a.events[4 * lo], first = a.events[4 * lo + 1], last = a.events[4 * lo + 2];
-    const int j = first / a.block + (s - a.events[4 * lo + 3]);
-    const int t0 = max(first, j * a.block), t1 = min(last, (j + 1) * a.block - 1);  // inclusive
+    const int cut = kSteps ? a.cut : a.block;
+    const int r = first / cut + (s - a.events[4 * lo + 3]);
+    const int t0 = max(first, r * cut), t1 = min(last, (r + 1) * cut - 1);  // inclusive
+    const int j = kSteps ? t0 / a.block : r;
     double* out = a.mom + 4 * wave;
     // (the host checked every record; a record that does not fit writes zeros and reads nothing)
     const bool fits = b >= 0 && b < a.B && first >= 0 && last < a.T && j >= 0 && j < a.J && t0 <= t1;

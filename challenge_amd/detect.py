@@ -4,6 +4,7 @@
                                    [--overlap_hop 512] [--score ANSWER.json]
                                    [--tune ANSWER.json --decoder_out decoder.json] [--decoder decoder.json]
                                    [--decoder_kind pool|hmm] [--locate [--mic_spacing M] --locate_out FILE.json]
+                                   [--locate_track [--track_step S] [--track_max_rate R] [--track_penalty P]]    (with --locate)
                                    [--extract DIR [--extract_context S]]    (with --locate)
 
 `detect` runs a trained model over wav files (or in-memory recordings) and returns, per file, the events it finds in the
@@ -837,6 +838,46 @@ class Detection:
                                                            # behind any noise-covariance block the event touches, 0 where a block
                                                            # fell back on its own frames (the event nulls itself there as under
                                                            # noise='block'); None unless locate.noise == 'quiet'
+    track: Optional[Tuple[List[np.ndarray], ...]] = None   # per class a list of [n_steps, 4] float64 (first frame of step, last
+                                                           # frame, tdoa, score), row for row with `events`: the delay as it moves
+                                                           # (`location` stays the static estimate); None unless locate.track
+
+
+@dataclass
+class TrackSettings:
+    """How `detect(..., locate=LocateSettings(track=TrackSettings()))` follows a delay that MOVES inside an event - the array
+    flying past a standing source (`transforms.track_events` states the definition): step_s, the seconds of one step, rounded
+    to frames of the spectrum's hop (at least 1; the noise block must be a multiple of it); max_rate, the fastest the delay
+    may move in samples of delay per second: the path's jump limit is ceil(max_rate x step seconds x q) lag steps per step;
+    penalty, the whitened energy per (bin, frame) that one sample of delay change between neighbouring steps must buy: pen =
+    penalty (k_hi - k_lo) step / q response units per lag step.  max_rate = 20 follows from the `flyby` augmentation's default
+    ranges (0.1 m spacing, up to 15 m/s, 3.5 m above the source: about 20 samples per second), penalty = 0.03 from a six-case
+    NumPy sweep over a synthetic scene (0.03 and 0.1 best, 0.01 and 0.3 worse): both are choices, not measurements on
+    recordings.  The penalty's unit presumes whitening: with noise='identity' tracking is refused."""
+    step_s: float = 0.25
+    max_rate: float = 20.0
+    penalty: float = 0.03
+
+    def __post_init__(self):
+        for name in ("step_s", "max_rate"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not (np.isfinite(v) and v > 0):
+                raise ValueError(f"TrackSettings: {name} = {v!r} must be a positive finite number")
+        v = self.penalty
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not (np.isfinite(v) and v >= 0):
+            raise ValueError(f"TrackSettings: penalty = {v!r} must be a finite number >= 0")
+
+    def step_frames(self, hop: int = HOP) -> int:
+        """step_s in frames of `hop` samples at 16 kHz, rounded to the nearest frame, at least 1."""
+        return max(int(round(self.step_s * SR / hop)), 1)
+
+    def max_jump(self, q: int, hop: int = HOP) -> int:
+        """The jump limit in lag steps (1 / q sample) per step."""
+        return int(np.ceil(self.max_rate * (self.step_frames(hop) * hop / SR) * q))
+
+    def pen(self, n_bins_steered: int, q: int, hop: int = HOP) -> float:
+        """The path penalty in response units per lag step: penalty x steered bins x frames per step / q."""
+        return float(self.penalty) * int(n_bins_steered) * self.step_frames(hop) / int(q)
 
 
 @dataclass
@@ -868,7 +909,9 @@ class LocateSettings:
     there are at least min_quiet of them, else those of itself and up to `reach` neighbours a side, else - a fallback that
     `Detection.noise_frames` reports as 0 - its own frames with the event in them; `transforms.quiet_ranges`.  guard_s = 0.1,
     min_quiet = 32 frames (0.5 s at load_wav's hop) and reach = 1 are choices, not measurements); sound_speed in m/s; max_lag:
-    lag steps either way (None: the array's aperture, ceil(mic_spacing / sound_speed * 16000 * q))."""
+    lag steps either way (None: the array's aperture, ceil(mic_spacing / sound_speed * 16000 * q)); track: a TrackSettings -
+    every event's delay is also followed step by step (`Detection.track`; `extract` then steers along it) - or None: not
+    tracked.  Tracking needs whitening (noise 'block' or 'quiet') and at most 2049 lags."""
     mic_spacing: float = 0.1
     block: Optional[int] = None
     loading: float = 1e-2
@@ -881,6 +924,7 @@ class LocateSettings:
     guard_s: float = 0.1
     min_quiet: int = 32
     reach: int = 1
+    track: Optional[TrackSettings] = None
 
     def guard_frames(self, hop: int = HOP) -> int:
         """guard_s in frames of `hop` samples at 16 kHz, rounded to the nearest frame (as `ExtractSettings.frames`)."""
@@ -913,6 +957,15 @@ class LocateSettings:
         if isinstance(self.max_lag, bool) or not isinstance(self.max_lag, (int, np.integer)) or not 0 <= 2 * self.max_lag + 1 <= LOCATE_MAX_LAGS:
             raise ValueError(f"LocateSettings: max_lag = {self.max_lag!r} must be an integer in 0 .. {(LOCATE_MAX_LAGS - 1) // 2} "
                              f"steps of 1 / q sample")
+        if self.track is not None:
+            from .frontend import TRACK_MAX_LAGS
+            if not isinstance(self.track, TrackSettings):
+                raise ValueError(f"LocateSettings: track must be a TrackSettings or None, got {type(self.track).__name__}")
+            if self.noise == "identity":
+                raise ValueError("LocateSettings: track needs noise 'block' or 'quiet': the path penalty is in whitened energy")
+            if 2 * self.max_lag + 1 > TRACK_MAX_LAGS:
+                raise ValueError(f"LocateSettings: track follows at most {TRACK_MAX_LAGS} lags; max_lag = {self.max_lag} makes "
+                                 f"{2 * self.max_lag + 1}")
 
     def bins(self, n_bins: int) -> Tuple[int, int]:
         """[k_lo, k_hi) of f_lo_hz .. f_hi_hz (inclusive) on a spectrum of n_bins bins at 16 kHz, n_fft = 2 (n_bins - 1)."""
@@ -1026,7 +1079,14 @@ def detect(model, wavs_or_paths: Sequence, config, overlap_hop: int = 512, batch
     beamformer steered at the event's own `location[:, 0]` with `locate`'s block, loading, noise and bins, then the inverse
     STFT (`transforms.extract_events`), on `load_wav`'s scale (wav / (10 rms)).  It reuses the group's spectra and factors: per
     group one `FrontendPlan.beamform` launch, one `iris_istft` launch and one copy back.  An event whose delay is NaN gives an
-    all-zero clip.  Without `extract` nothing changes and `audio` is None."""
+    all-zero clip.  Without `extract` nothing changes and `audio` is None.
+    `LocateSettings(track=TrackSettings())`: every event's delay is also followed as it MOVES (`Detection.track`: per class a
+    list of [n_steps, 4] float64 (first frame of step, last frame, tdoa, score), row for row with `events`;
+    `transforms.track_events` states the definition) - per group three more launches (`FrontendPlan.locate_steps`, `track`) and
+    one more copy back - and `extract` steers every frame along `transforms.track_delays` of its event's track
+    (`FrontendPlan.beamform_frames` in place of `beamform`).  `location` stays the static estimate.  The noise block
+    (locate.block, else config.n_frame) must be a multiple of the step (ValueError).  Without `track` nothing changes and
+    `track` is None."""
     if locate is not None and not isinstance(locate, LocateSettings):
         raise ValueError(f"detect: locate must be a LocateSettings, got {type(locate).__name__}")
     if extract is not None and not isinstance(extract, ExtractSettings):
@@ -1054,7 +1114,11 @@ def _locate_group(spectra, events, config, locate: LocateSettings, extract: Opti
     length; the lanes that share a range follow from the block length alone, so the rows still equal the file alone, bit for
     bit.  Blocks past a file's end read zero padding: zero factors.  `Detection.noise_frames` is then the fewest quiet frames
     behind any block an event touches (else None).
-    Returns (locations, audio, spans, noise_frames), one entry per file."""
+    With locate.track also `Detection.track` of every file (else None): `FrontendPlan.locate_steps` and `FrontendPlan.track`
+    over the same padded spectra and factors - three more launches and one more copy back per group - and `extract` then steers
+    every frame at `transforms.track_delays` of its event's track through `FrontendPlan.beamform_frames`.  Steps count from
+    frame 0 and a row depends on its own event only, so tracks and clips still equal the file alone, bit for bit.
+    Returns (locations, audio, spans, noise_frames, tracks), one entry per file."""
     from . import transforms as T
     rows = [(i, int(f0), int(f1)) for i, ev in enumerate(events) for cls in ev for f0, f1 in np.asarray(cls).reshape(-1, 2)]
     out = np.zeros((0, 4), np.float64)
@@ -1062,6 +1126,9 @@ def _locate_group(spectra, events, config, locate: LocateSettings, extract: Opti
         n, f, t_max = len(spectra), int(spectra[0].shape[0]), max(int(sp.shape[1]) for sp in spectra)
         block = config.n_frame if locate.block is None else int(locate.block)
         k_lo, k_hi = locate.bins(f)
+        if locate.track is not None:   # (refused before any device work: a step must lie in one noise block)
+            from .frontend import track_step
+            step = track_step(locate.track.step_frames(f - 1), block)
         spec = spectra[0].float().unsqueeze(0).contiguous() if n == 1 else torch.zeros((n, f, t_max, 4), dtype=torch.float32,
                                                                                        device=spectra[0].device)
         plan, fac = T._locate_plan(spec), None
@@ -1080,20 +1147,30 @@ def _locate_group(spectra, events, config, locate: LocateSettings, extract: Opti
             behind = T.quiet_frames(rows, quiet, max(min(block, t_max), 1))
         curve, n_terms = plan.locate(spec, np.asarray(rows, np.int32), fac, block, k_lo, k_hi, locate.max_lag, locate.q)
         out = T.locate_peak(curve, n_terms, locate.q, locate.mic_spacing, float(SR), locate.sound_speed)
+        if locate.track is not None:   # three launches and one copy back; a row depends on its own event only
+            tracks = T._track(plan, spec, np.asarray(rows, np.int32), fac, block, step, k_lo, k_hi, locate.max_lag, locate.q,
+                              locate.track.pen(k_hi - k_lo, locate.q, f - 1), locate.track.max_jump(locate.q, f - 1))
         if extract is not None:
             wide = T.widen_events(np.asarray(rows, np.int64), extract.frames(f - 1),
                                   np.asarray([int(spectra[i].shape[1]) for i, _, _ in rows], np.int64))
-            _, flat = T.clips_from_slabs(plan.beamform(spec, wide, out[:, 0], fac, block, k_lo, k_hi))
+            if locate.track is not None:   # steered along the track, the context frames at its nearest end value
+                along = np.concatenate([T.track_delays(tr, a, z) for tr, (_, a, z) in zip(tracks, wide)])
+                slabs = plan.beamform_frames(spec, wide, along, fac, block, k_lo, k_hi)
+            else:
+                slabs = plan.beamform(spec, wide, out[:, 0], fac, block, k_lo, k_hi)
+            _, flat = T.clips_from_slabs(slabs)
             samples = flat.cpu().numpy()                                   # the one copy back of the group
             spans = wide[:, 1:] * (f - 1)                                  # load_wav's hop: n_fft // 2 = F - 1
             ends = np.cumsum(spans[:, 1] - spans[:, 0])
             clips = [samples[z - n:z].copy() for z, n in zip(ends, spans[:, 1] - spans[:, 0])]
-    res, audio, where, noise, at = [], [], [], [], 0
+    res, audio, where, noise, moving, at = [], [], [], [], [], 0
     quiet_on = locate.noise == "quiet"
     for ev in events:
-        per_class, per_audio, per_span, per_noise = [], [], [], []
+        per_class, per_audio, per_span, per_noise, per_track = [], [], [], [], []
         for cls in ev:
             per_class.append(out[at:at + len(cls)].copy())
+            if locate.track is not None:
+                per_track.append(tracks[at:at + len(cls)] if rows else [])
             if quiet_on:
                 per_noise.append(behind[at:at + len(cls)].copy() if rows else np.zeros((0,), np.int64))
             if extract is not None:
@@ -1104,7 +1181,8 @@ def _locate_group(spectra, events, config, locate: LocateSettings, extract: Opti
         audio.append(tuple(per_audio) if extract is not None else None)
         where.append(tuple(per_span) if extract is not None else None)
         noise.append(tuple(per_noise) if quiet_on else None)
-    return res, audio, where, noise
+        moving.append(tuple(per_track) if locate.track is not None else None)
+    return res, audio, where, noise, moving
 
 
 def _detect_group(model, group, config, overlap_hop: int, batch_size: int, settings=None, locate=None,
@@ -1115,11 +1193,11 @@ def _detect_group(model, group, config, overlap_hop: int, batch_size: int, setti
     else:
         events = decode_events(preds, win_off, [t for _, t, _ in group], config.n_frame, overlap_hop, settings=settings)
     none = [None] * len(group)
-    where, audio, spans, noise = _locate_group(spectra, events, config, locate, extract) if locate is not None else (none,) * 4
+    where, audio, spans, noise, moving = _locate_group(spectra, events, config, locate, extract) if locate is not None else (none,) * 5
     out = []
-    for (name, t_len, _), ev, loc, clips, span, behind in zip(group, events, where, audio, spans, noise):
+    for (name, t_len, _), ev, loc, clips, span, behind, tracks in zip(group, events, where, audio, spans, noise, moving):
         metric = M.output_to_metric(HOP, SR)(*ev)
-        out.append(Detection(name, t_len, ev, metric, _FromEvents(ev).get_start_end_time(None), loc, clips, span, behind))
+        out.append(Detection(name, t_len, ev, metric, _FromEvents(ev).get_start_end_time(None), loc, clips, span, behind, tracks))
     return out
 
 
@@ -1213,10 +1291,15 @@ def location_rows(det: Detection) -> list:
 def write_locations(results: Sequence[Detection], path: str) -> dict:
     """{"task2_location": {name: [[class, first_frame, last_frame, tdoa, bearing, score, contrast], ...]}}: where every event
     of `detect(..., locate=)` comes from (NaN is written as null).  Under LocateSettings(noise='quiet') also "noise_frames":
-    {name: [n, ...]}, row for row with the recording's locations: `Detection.noise_frames`, 0 where the event may null itself."""
+    {name: [n, ...]}, row for row with the recording's locations: `Detection.noise_frames`, 0 where the event may null itself.
+    Under LocateSettings(track=...) also "track": {name: [[[first frame of step, last frame, tdoa, score], ...], ...]}, one entry
+    per event, row for row with the recording's locations: `Detection.track`."""
     where = {"task2_location": {d.name: location_rows(d) for d in results}}
     if results and all(d.noise_frames is not None for d in results):
         where["noise_frames"] = {d.name: [int(v) for cls in d.noise_frames for v in np.asarray(cls).reshape(-1)] for d in results}
+    if results and all(d.track is not None for d in results):
+        where["track"] = {d.name: [[[int(r[0]), int(r[1])] + [None if np.isnan(x) else float(x) for x in r[2:]] for r in tr]
+                                   for cls in d.track for tr in cls] for d in results}
     with open(path, 'w') as f:
         json.dump(where, f, indent=4, allow_nan=False)
     return where
@@ -1279,6 +1362,14 @@ def main(argv=None):
                              help='the fewest quiet frames a noise covariance is taken from (--locate_noise quiet)')
     config.args.add_argument('--locate_reach', type=int, default=1, metavar='R',
                              help='how many neighbouring blocks a side may lend their quiet frames (--locate_noise quiet)')
+    config.args.add_argument('--locate_track', action='store_true',
+                             help='with --locate: also follow the delay of every event as it moves, step by step (--locate_out '
+                                  'then also lists a track per event, and --extract steers along it); not with --locate_noise identity')
+    config.args.add_argument('--track_step', type=float, default=0.25, metavar='S', help='seconds per step (--locate_track)')
+    config.args.add_argument('--track_max_rate', type=float, default=20.0, metavar='R',
+                             help='the fastest the delay may move, in samples of delay per second (--locate_track)')
+    config.args.add_argument('--track_penalty', type=float, default=0.03, metavar='P',
+                             help='whitened energy per (bin, frame) that one sample of delay change between steps must buy (--locate_track)')
     config.args.add_argument('--extract', type=str, default=None, metavar='DIR',
                              help='with --locate: also write the beamformed sound of every detected event to '
                                   'DIR/<recording>_c<class>_<row>.wav (mono, float32, 16 kHz, on load_wav\'s scale: the recording '
@@ -1290,8 +1381,12 @@ def main(argv=None):
     if config.extract is not None and not config.locate:
         parser.error("--extract steers every event at its own delay: it needs --locate")
     # (the settings refuse bad values before the model is loaded)
+    if config.locate_track and not config.locate:
+        parser.error("--locate_track follows the delay of located events: it needs --locate")
+    track = TrackSettings(step_s=config.track_step, max_rate=config.track_max_rate,
+                          penalty=config.track_penalty) if config.locate_track else None
     locate = LocateSettings(mic_spacing=config.mic_spacing, noise=config.locate_noise, guard_s=config.locate_guard,
-                            min_quiet=config.locate_min_quiet, reach=config.locate_reach) if config.locate else None
+                            min_quiet=config.locate_min_quiet, reach=config.locate_reach, track=track) if config.locate else None
     extract = ExtractSettings(context_s=config.extract_context) if config.extract is not None else None
     if config.p:
         parse_name(config)

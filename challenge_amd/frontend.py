@@ -496,8 +496,111 @@ class FrontendPlan:
             x.record_stream(torch.cuda.current_stream(self.device))
         return curve, n_terms
 
+    def locate_steps(self, spec: torch.Tensor, events, fac: Optional[torch.Tensor] = None, block: Optional[int] = None,
+                     step: int = 16, k_lo: int = 0, k_hi: Optional[int] = None, max_lag: int = 40, q: int = 8, out=None):
+        """`locate` per STEP of `step` frames (counted from frame 0) instead of per event, for events whose delay moves: -> (R
+        [rows, 2 max_lag + 1] float64, n_terms [rows] int64, both on the device, row_offsets int32 [E + 1] on the host): event e
+        owns the rows row_offsets[e] .. row_offsets[e + 1] - 1, one per step first // step .. last // step, and R[row] is
+        `locate`'s term sum over the step's frames with the factors of the step's block (`iris_locate_steps`, two launches;
+        `transforms.track_events` states the definition).  With factors `block % step == 0` is required, so a step lies in one
+        block.  out: (R, n_terms) preallocated (`track_buffers`).  Every check happens before a launch: ValueError."""
+        spec = _require_device_f32(spec, "spec")
+        if self.channels != 2:
+            raise ValueError(f"locate_steps: the plan has {self.channels} channel(s); the delay is that of a stereo pair")
+        if spec.dim() != 4 or spec.shape[1] != self.n_bins or spec.shape[3] != 4:
+            raise ValueError(f"spec must be [B, {self.n_bins}, T, 4], got {tuple(spec.shape)}")
+        if spec.data_ptr() % 16:
+            spec = spec.clone()   # (a view at an odd offset: the kernels load 16 bytes per bin)
+        b, t = int(spec.shape[0]), int(spec.shape[2])
+        k_hi = self.n_bins if k_hi is None else int(k_hi)
+        k_lo, max_lag, q = int(k_lo), int(max_lag), int(q)
+        if not 0 <= k_lo < k_hi <= self.n_bins:
+            raise ValueError(f"locate_steps: bins [{k_lo}, {k_hi}) must be a non-empty range inside [0, {self.n_bins}]")
+        if q < 1 or max_lag < 0 or 2 * max_lag + 1 > LOCATE_MAX_LAGS:
+            raise ValueError(f"locate_steps: q = {q} must be >= 1 and max_lag = {max_lag} in 0 .. {(LOCATE_MAX_LAGS - 1) // 2}")
+        if fac is not None and block is not None and int(block) < 1:
+            raise ValueError(f"locate_steps: block = {block} must be at least 1 frame")
+        step = track_step(step, None if fac is None or block is None else int(block))   # (None: one block holds every step)
+        if fac is None:
+            block, j = max(t, 1), 1
+        else:
+            fac = _require_device_f32(fac, "fac")
+            block = max(min(t if block is None else int(block), t), 1)
+            j = (t + block - 1) // block
+            if tuple(fac.shape) != (b, self.n_bins, j, 4) or fac.device != spec.device:
+                raise ValueError(f"locate_steps: fac must be [{b}, {self.n_bins}, {j}, 4] on {spec.device} for blocks of {block} "
+                                 f"frames, got {tuple(fac.shape)} on {fac.device}")
+            if fac.data_ptr() % 16:
+                fac = fac.clone()
+        table = locate_table(events, step, t, b)   # (the same table with steps for blocks: column 3 counts rows)
+        e, lags = int(table.shape[0]), 2 * max_lag + 1
+        offsets = np.zeros(e + 1, np.int32)
+        if e:
+            offsets[:-1] = table[:, 3]
+            offsets[-1] = int(table[-1, 3]) + int(table[-1, 2]) // step - int(table[-1, 1]) // step + 1
+        rows = int(offsets[-1])
+        if out is None:
+            out = track_buffers(rows, lags, spec.device)[1:3]
+        resp, n_terms = out
+        if not (torch.is_tensor(resp) and resp.dtype == torch.float64 and tuple(resp.shape) == (rows, lags) and resp.is_contiguous()
+                and torch.is_tensor(n_terms) and n_terms.dtype == torch.int64 and tuple(n_terms.shape) == (rows,)
+                and n_terms.is_contiguous() and resp.device == spec.device == n_terms.device):
+            raise ValueError(f"locate_steps: out must be (float64 [{rows}, {lags}], int64 [{rows}]) on {spec.device}")
+        if e == 0:
+            return resp, n_terms, offsets
+        work = torch.empty((rows, k_hi - k_lo, 4), dtype=torch.float64, device=spec.device)
+        table_dev = torch.from_numpy(table).to(spec.device, non_blocking=True)
+        with self._lock, torch.cuda.device(self.device):
+            rc = N.lib().iris_locate_steps(self._handle, spec.data_ptr(), None if fac is None else fac.data_ptr(), j,
+                                           table_dev.data_ptr(), table.ctypes.data, e, b, t, block, step, k_lo, k_hi, max_lag, q,
+                                           work.data_ptr(), work.numel() * 8, resp.data_ptr(), n_terms.data_ptr(),
+                                           _stream_ptr(self.device))
+        N.check(rc, "iris_locate_steps")
+        for x in (table_dev, work):   # (allocated here: they must outlive the kernels on this stream)
+            x.record_stream(torch.cuda.current_stream(self.device))
+        return resp, n_terms, offsets
+
+    def track(self, resp: torch.Tensor, row_offsets, pen: float, max_jump: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The best path through the lags of every event's step responses: resp [rows, L] float64 on the device and row_offsets
+        [E + 1] (`locate_steps`) -> path int32 [rows] on the device, the lag index of every step (`iris_track_lags`, one launch,
+        one workgroup per event; `transforms.track_events` states the recurrence).  pen >= 0: response units per lag step
+        between neighbouring steps; max_jump >= 0: the most lag steps a path may move per step.  At most 2049 lags.  Every
+        check happens before the launch: ValueError."""
+        resp = torch.as_tensor(resp)
+        if not (resp.is_cuda and resp.dtype == torch.float64 and resp.dim() == 2 and resp.is_contiguous()):
+            raise ValueError(f"track: R must be a contiguous float64 [rows, L] on a ROCm device, got {resp.dtype} {tuple(resp.shape)} "
+                             f"on {resp.device}")
+        rows, lags = int(resp.shape[0]), int(resp.shape[1])
+        offsets, table = track_offsets(row_offsets, rows), track_penalties(pen, max_jump, lags)
+        if out is None:
+            out = torch.empty((rows,), dtype=torch.int32, device=resp.device)
+        if not (torch.is_tensor(out) and out.dtype == torch.int32 and tuple(out.shape) == (rows,) and out.is_contiguous()
+                and out.device == resp.device):
+            raise ValueError(f"track: out must be int32 [{rows}] on {resp.device}")
+        e = len(offsets) - 1
+        if e == 0:
+            return out
+        back = torch.empty((rows, lags), dtype=torch.int32, device=resp.device)
+        off_dev = torch.from_numpy(offsets).to(resp.device, non_blocking=True)
+        pen_dev = torch.from_numpy(table).to(resp.device, non_blocking=True)
+        with self._lock, torch.cuda.device(self.device):
+            rc = N.lib().iris_track_lags(self._handle, resp.data_ptr(), off_dev.data_ptr(), offsets.ctypes.data, e, rows,
+                                         (lags - 1) // 2, pen_dev.data_ptr(), int(table.shape[0]), min(int(max_jump), 2 ** 31 - 1),
+                                         back.data_ptr(), back.numel() * 4, out.data_ptr(), _stream_ptr(self.device))
+        N.check(rc, "iris_track_lags")
+        for x in (off_dev, pen_dev, back, resp):   # (they must outlive the kernel on this stream)
+            x.record_stream(torch.cuda.current_stream(self.device))
+        return out
+
+    def beamform_frames(self, spec: torch.Tensor, events, tdoa, fac: Optional[torch.Tensor] = None, block: Optional[int] = None,
+                        k_lo: int = 0, k_hi: Optional[int] = None) -> List[torch.Tensor]:
+        """`beamform` steered per FRAME: tdoa is flat, one delay per output frame - the frames of event 0, then those of event 1,
+        ... (`transforms.track_delays`) - and a frame whose delay is not finite is exactly 0 (`iris_beamform_frames`, one launch).
+        A delay that is constant over each event gives `beamform`'s bits."""
+        return self.beamform(spec, events, tdoa, fac, block, k_lo, k_hi, _frames=True)
+
     def beamform(self, spec: torch.Tensor, events, tdoa, fac: Optional[torch.Tensor] = None, block: Optional[int] = None,
-                 k_lo: int = 0, k_hi: Optional[int] = None) -> List[torch.Tensor]:
+                 k_lo: int = 0, k_hi: Optional[int] = None, _frames: bool = False) -> List[torch.Tensor]:
         """Stereo complex spec [B,F,T,4], events int [E,3] = (sample, first frame, last frame; frames inclusive) and their
         delays tdoa [E] (samples, float64; positive: channel 1 hears the event later - `locate_peak`'s sign) -> the list of the
         events' MVDR-beamformed spectra, [F, T_e, 2] = (Re Y, Im Y) float32 each (T_e = last - first + 1; `iris_istft`'s record
@@ -535,20 +638,27 @@ class FrontendPlan:
         table = beamform_table(events, t, b)
         e = int(table.shape[0])
         delays = np.ascontiguousarray(np.asarray(tdoa.cpu() if torch.is_tensor(tdoa) else tdoa, np.float64).reshape(-1))
-        if delays.shape[0] != e:
+        frames = (table[:, 2] - table[:, 1] + 1).astype(np.int64)
+        if _frames and delays.shape[0] != int(frames.sum()):
+            raise ValueError(f"beamform_frames: {delays.shape[0]} delay(s) for {int(frames.sum())} output frame(s)")
+        if not _frames and delays.shape[0] != e:
             raise ValueError(f"beamform: {delays.shape[0]} delay(s) for {e} event(s)")
         if e == 0:
             return []
-        frames = (table[:, 2] - table[:, 1] + 1).astype(np.int64)
         per = 2 * self.n_bins
         flat = torch.empty((per * int(frames.sum()),), dtype=torch.float32, device=spec.device)
         table_dev = torch.from_numpy(table).to(spec.device, non_blocking=True)
         tdoa_dev = torch.from_numpy(delays).to(spec.device, non_blocking=True)
         with self._lock, torch.cuda.device(self.device):
-            rc = N.lib().iris_beamform_events(self._handle, spec.data_ptr(), None if fac is None else fac.data_ptr(), j,
-                                              table_dev.data_ptr(), table.ctypes.data, tdoa_dev.data_ptr(), e, b, t, block, k_lo,
-                                              k_hi, flat.data_ptr(), flat.numel(), _stream_ptr(self.device))
-        N.check(rc, "iris_beamform_events")
+            if _frames:
+                rc = N.lib().iris_beamform_frames(self._handle, spec.data_ptr(), None if fac is None else fac.data_ptr(), j,
+                                                  table_dev.data_ptr(), table.ctypes.data, tdoa_dev.data_ptr(), delays.shape[0], e, b,
+                                                  t, block, k_lo, k_hi, flat.data_ptr(), flat.numel(), _stream_ptr(self.device))
+            else:
+                rc = N.lib().iris_beamform_events(self._handle, spec.data_ptr(), None if fac is None else fac.data_ptr(), j,
+                                                  table_dev.data_ptr(), table.ctypes.data, tdoa_dev.data_ptr(), e, b, t, block, k_lo,
+                                                  k_hi, flat.data_ptr(), flat.numel(), _stream_ptr(self.device))
+        N.check(rc, "iris_beamform_frames" if _frames else "iris_beamform_events")
         for x in (table_dev, tdoa_dev, spec) + (() if fac is None else (fac,)):   # (they must outlive the kernel on this stream)
             x.record_stream(torch.cuda.current_stream(self.device))
         return [flat[per * int(o):per * int(o + n)].view(self.n_bins, int(n), 2) for o, n in zip(table[:, 3], frames)]
@@ -1459,6 +1569,59 @@ def locate_table(events, block: int, n_frames: int, batch: int) -> np.ndarray:
     table[:, :3] = ev
     table[:, 3] = np.concatenate([[0], np.cumsum(n_seg)[:-1]])
     return table
+
+
+TRACK_MAX_LAGS = 2049     # the lag limit of iris_track_lags (include/iris_frontend.h): max_lag <= 1024
+
+
+def track_step(step, block=None) -> int:
+    """`step` as a frame count >= 1; with `block` (the frames per block of the factors) block % step == 0, so that a step lies
+    in one block.  ValueError otherwise."""
+    if isinstance(step, bool) or not isinstance(step, (int, np.integer)) or step < 1:
+        raise ValueError(f"track: step = {step!r} must be a number of frames >= 1")
+    if block is not None and int(block) % int(step):
+        raise ValueError(f"track: block = {block} is not a multiple of step = {step}: a step must lie in one block")
+    return int(step)
+
+
+def track_offsets(row_offsets, rows: int) -> np.ndarray:
+    """row_offsets as a contiguous int32 [E + 1] that starts at 0, strictly ascends (every event has a step) and ends at `rows`;
+    E = 0: [0] with rows == 0.  ValueError otherwise."""
+    off = np.asarray(row_offsets.cpu() if torch.is_tensor(row_offsets) else row_offsets)
+    if off.ndim != 1 or off.size < 1 or not np.issubdtype(off.dtype, np.integer):
+        raise ValueError(f"track: row_offsets must be integers [E + 1], got {off.dtype} {off.shape}")
+    off = off.astype(np.int64)
+    if off[0] != 0 or off[-1] != rows or (np.diff(off) < 1).any() or rows > 2 ** 31 - 1:
+        raise ValueError(f"track: row_offsets must start at 0, ascend strictly and end at the {rows} rows of R, got {off.tolist()[:8]}"
+                         f"{' ...' if off.size > 8 else ''}")
+    return np.ascontiguousarray(off, np.int32)
+
+
+def track_penalties(pen, max_jump, lags: int) -> np.ndarray:
+    """The table P[d] = d x pen of iris_track_lags, float64 [min(max_jump, lags - 1) + 1], formed once here.  ValueError: pen not
+    a finite number >= 0, max_jump not an integer >= 0, lags even, < 1 or above TRACK_MAX_LAGS."""
+    if isinstance(pen, bool) or not isinstance(pen, (int, float, np.integer, np.floating)) or not (np.isfinite(pen) and pen >= 0):
+        raise ValueError(f"track: pen = {pen!r} must be a finite number >= 0")
+    if isinstance(max_jump, bool) or not isinstance(max_jump, (int, np.integer)) or max_jump < 0:
+        raise ValueError(f"track: max_jump = {max_jump!r} must be an integer >= 0")
+    if lags < 1 or lags % 2 != 1 or lags > TRACK_MAX_LAGS:
+        raise ValueError(f"track: {lags} lags; an odd count 2 N + 1 of at most {TRACK_MAX_LAGS} is tracked")
+    return np.arange(min(int(max_jump), lags - 1) + 1, dtype=np.float64) * np.float64(pen)
+
+
+def track_buffers(rows: int, lags: int, device):
+    """(flat, R [rows, lags] float64, n_terms [rows] int64, path [rows] int32): the outputs of `locate_steps` and `track` as views
+    of ONE flat int64 device buffer, so that one copy brings all three back."""
+    flat = torch.empty((rows * lags + rows + (rows + 1) // 2,), dtype=torch.int64, device=device)
+    resp = flat[:rows * lags].view(torch.float64).view(rows, lags)
+    return flat, resp, flat[rows * lags:rows * lags + rows], flat[rows * lags + rows:].view(torch.int32)[:rows]
+
+
+def track_unpack(flat, rows: int, lags: int):
+    """(R, n_terms, path) as NumPy arrays from a host copy of `track_buffers`' flat buffer."""
+    a = np.ascontiguousarray(flat.cpu().numpy() if torch.is_tensor(flat) else flat)
+    return (a[:rows * lags].view(np.float64).reshape(rows, lags), a[rows * lags:rows * lags + rows],
+            a[rows * lags + rows:].view(np.int32)[:rows])
 
 
 def beamform_table(events, n_frames: int, batch: int) -> np.ndarray:

@@ -15,7 +15,7 @@ halves are what the parity tests pin (`mask_apply`, `random_shift_apply`)."""
 from __future__ import annotations
 
 from math import e, log
-from typing import Optional
+from typing import List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -595,6 +595,131 @@ def locate_events(spec: torch.Tensor, events, block=None, loading: float = WHITE
     return locate_peak(curve, n_terms, q, mic_spacing, sample_rate, sound_speed)
 
 
+def track_peak(resp, n_terms, path, q: int = 8) -> np.ndarray:
+    """The delay of every step on its path: step responses R [rows, 2 N + 1] (lags -N .. N in steps of 1 / q sample), their
+    n_terms [rows] and the path's lag index i per row -> float64 [rows, 2] = (tdoa, score), host arithmetic in float64 in
+    `locate_peak`'s style: for an interior i the parabola through R[row, i - 1 .. i + 1] gives the offset (y[i - 1] - y[i + 1]) /
+    (2 (y[i - 1] - 2 y[i] + y[i + 1])), clipped to +-0.5 (a zero denominator, or i at either end of the grid: 0);
+    tdoa = (i - N + offset) / q;  score = R[row, i] / n_terms[row].  n_terms == 0: tdoa NaN, score 0.  (On a path, unlike at
+    the argmax, i need not be a local maximum: the clip then holds the delay within half a lag step of the path.)"""
+    y = np.asarray(resp.cpu() if torch.is_tensor(resp) else resp, np.float64)
+    n_t = np.asarray(n_terms.cpu() if torch.is_tensor(n_terms) else n_terms, np.int64).reshape(-1)
+    idx = np.asarray(path.cpu() if torch.is_tensor(path) else path, np.int64).reshape(-1)
+    q = int(q)
+    if y.ndim != 2 or y.shape[1] % 2 != 1 or y.shape[0] != n_t.shape[0] or y.shape[0] != idx.shape[0]:
+        raise ValueError(f"track_peak: R must be [rows, 2 N + 1], n_terms and path [rows], got {y.shape}, {n_t.shape}, {idx.shape}")
+    if q < 1 or (idx.size and (idx.min() < 0 or idx.max() >= y.shape[1])):
+        raise ValueError(f"track_peak: q = {q} must be >= 1 and every path index inside [0, {y.shape[1]})")
+    rows, lags = y.shape
+    n = (lags - 1) // 2
+    out = np.zeros((rows, 2), np.float64)
+    for r in range(rows):
+        if n_t[r] == 0:
+            out[r, 0] = np.nan
+            continue
+        i, off = int(idx[r]), 0.0
+        if 0 < i < lags - 1:
+            den = 2.0 * (y[r, i - 1] - 2.0 * y[r, i] + y[r, i + 1])
+            if den != 0.0:
+                off = float(np.clip((y[r, i - 1] - y[r, i + 1]) / den, -0.5, 0.5))
+        out[r] = ((i - n + off) / q, y[r, i] / n_t[r])
+    return out
+
+
+def track_rows(events, row_offsets, step: int, peaks) -> List[np.ndarray]:
+    """Per event the float64 [n_steps, 4] = (first frame of step, last frame, tdoa, score) of `track_events` from the call's
+    events [E, 3], `FrontendPlan.locate_steps`' row_offsets [E + 1] and `track_peak`'s [rows, 2]."""
+    ev, off = np.asarray(events, np.int64).reshape(-1, 3), np.asarray(row_offsets, np.int64).reshape(-1)
+    peaks, step, out = np.asarray(peaks, np.float64).reshape(-1, 2), int(step), []
+    for (_, first, last), r0, r1 in zip(ev, off[:-1], off[1:]):
+        u = np.arange(first // step, last // step + 1, dtype=np.int64)
+        rows = np.empty((len(u), 4), np.float64)
+        rows[:, 0], rows[:, 1] = np.maximum(u * step, first), np.minimum((u + 1) * step - 1, last)
+        rows[:, 2:] = peaks[r0:r1]
+        out.append(rows)
+    return out
+
+
+def track_delays(track, first: int, last: int) -> np.ndarray:
+    """The delay of every frame first .. last (inclusive) from one event's track [n_steps, 4] = (first frame of step, last
+    frame, tdoa, score): float64 [last - first + 1], the linear interpolation of the FINITE step delays over the step centres
+    (t0 + t1) / 2, held constant before the first and after the last centre - so frames outside the event (`extract`'s context)
+    take the nearest end value - and NaN for every frame if no step is finite."""
+    tr = np.asarray(track, np.float64).reshape(-1, 4)
+    first, last = int(first), int(last)
+    if last < first:
+        raise ValueError(f"track_delays: frames {first} .. {last}")
+    frames = np.arange(first, last + 1, dtype=np.float64)
+    ok = np.isfinite(tr[:, 2])
+    if not ok.any():
+        return np.full(frames.shape, np.nan)
+    return np.interp(frames, (tr[ok, 0] + tr[ok, 1]) / 2.0, tr[ok, 2])
+
+
+def track_events(spec: torch.Tensor, events, block=None, loading: float = WHITEN_LOADING, noise: str = "block", k_lo: int = 0,
+                 k_hi=None, max_lag: int = 40, q: int = 8, step: int = 16, pen: float = 0.0, max_jump: int = 40, guard: int = 0,
+                 min_quiet: int = 32, reach: int = 1) -> List[np.ndarray]:
+    """The delay of each event as it MOVES: `locate_events`' response per step of frames, and the best path through its lags.
+    spec, events, block, loading, noise, bins, lags, guard, min_quiet and reach are `locate_events`'.  Returns per event a
+    float64 [n_steps, 4] = (first frame of step, last frame, tdoa in samples, score); `track_delays` turns it into a delay per
+    frame.  Definition, in float64 (`tests/track_ref.py` restates it in NumPy):
+      1. Steps.  Frames are grouped into steps of `step` frames counted from frame 0; block % step == 0 is required (ValueError),
+         so a step lies in one block.  An event (sample, first, last) is cut into the steps u = first // step .. last // step;
+         the first and the last may be short.
+      2. Step response.  R[u, n] is `locate_events`' term sum with "segment" read as "step": the moments p00, p11, p10 over the
+         step's frames, (a, b, c) those of the step's block, the lags n = -max_lag .. max_lag in steps of 1 / q sample and the bins
+         [k_lo, k_hi) unchanged; n_terms[u] = the step's frame count x its contributing bins.  A short step sums over fewer
+         frames and so weighs less by itself.
+      3. Path.  With pen >= 0 (response units per lag step), the jump limit J = max_jump >= 0 (lag steps per step), L = 2 max_lag
+         + 1 and P[d] = d pen (formed once, in float64): D[n] = R[first step, n]; every later step
+             D_u[n] = max over n' in [max(0, n - J), min(L - 1, n + J)] of (D_{u-1}[n'] - P[|n - n'|]) + R[u, n]
+         where the maximiser is the smallest such n'; the last step takes the smallest argmax of D, earlier steps follow the
+         back-pointers.  The recurrence holds only subtractions, additions and comparisons of doubles - nothing that could be
+         contracted into an fma - so a NumPy loop with the same two operations per candidate gives the same path exactly.
+      4. Refinement (`track_peak`, host float64): per step the parabola through R[u, i - 1 .. i + 1] around the path's i with
+         `locate_peak`'s clipping and edge rules, tdoa_u = (i - max_lag + offset) / q, score_u = R[u, i] / n_terms[u]; a step with
+         n_terms == 0 gets tdoa NaN and score 0.
+    The launches are the factors' (as in `locate_events`), `FrontendPlan.locate_steps` (two) and `FrontendPlan.track` (one), and
+    one copy back; there is no CPU fallback.  At most 2049 lags (max_lag <= 1024).  noise="identity" is allowed here - the path
+    does not care what the response's unit is - but `pen` is in that unit: `detect.TrackSettings` presumes whitening.
+    What it cannot do: follow a delay that moves by more than max_jump lag steps per step, or resolve motion inside one step."""
+    if noise not in NOISE_KINDS:
+        raise ValueError(f"track_events: noise = {noise!r} must be 'block', 'identity' or 'quiet'")
+    if not isinstance(spec, torch.Tensor):
+        raise TypeError(f"spec must be a torch.Tensor, got {type(spec).__name__}")
+    x = spec if spec.dim() == 4 else spec.unsqueeze(0)
+    if x.dim() != 4 or x.shape[-1] != 4 or x.shape[1] < 2:
+        raise ValueError(f"track_events: spec must be [B, F >= 2, T, 4] (a stereo complex spectrum), got {tuple(spec.shape)}")
+    lags = 2 * int(max_lag) + 1
+    _fe.track_step(step, None if noise == "identity" or block is None else block)
+    _fe.track_penalties(pen, max_jump, lags)   # (refuses pen, max_jump and more than 2049 lags before any device work)
+    if not x.is_cuda:
+        raise RuntimeError(f"track_events: spec is on {x.device}: the tracking runs only as HIP kernels on a ROCm device "
+                           "(there is no CPU fallback); move the tensor to 'cuda'")
+    x = x.float().contiguous()
+    plan = _locate_plan(x)
+    if noise == "quiet":
+        fac, _ = _quiet_factors(plan, x, events, block, loading, guard, min_quiet, reach)
+    else:
+        fac = plan.whiten_factors(x, block, loading) if noise == "block" else None
+    return _track(plan, x, events, fac, block, step, k_lo, k_hi, max_lag, q, pen, max_jump)
+
+
+def _track(plan, x: torch.Tensor, events, fac, block, step: int, k_lo: int, k_hi, max_lag: int, q: int, pen: float,
+           max_jump: int) -> List[np.ndarray]:
+    """`track_events` behind the factors: three launches and ONE copy back (R, n_terms and the path share a buffer)."""
+    table = _fe.locate_table(events, int(step), int(x.shape[2]), int(x.shape[0]))
+    if len(table) == 0:
+        return []
+    lags = 2 * int(max_lag) + 1
+    rows = int(table[-1, 3]) + int(table[-1, 2]) // int(step) - int(table[-1, 1]) // int(step) + 1
+    flat, resp, n_terms, path = _fe.track_buffers(rows, lags, x.device)
+    _, _, offsets = plan.locate_steps(x, table[:, :3], fac, block, step, k_lo, k_hi, max_lag, q, out=(resp, n_terms))
+    plan.track(resp, offsets, pen, max_jump, out=path)
+    host = _fe.track_unpack(flat, rows, lags)   # the one copy back
+    return track_rows(table[:, :3], offsets, step, track_peak(*host, q))
+
+
 def widen_events(events, context: int, n_frames) -> np.ndarray:
     """Events [E, 3] = (sample, first frame, last frame) widened by `context` frames a side and clipped to [0, n_frames) -
     n_frames one count or one per event.  int64 [E, 3]."""
@@ -614,6 +739,23 @@ def widen_events(events, context: int, n_frames) -> np.ndarray:
     ev[:, 1] = np.maximum(ev[:, 1] - int(context), 0)
     ev[:, 2] = np.minimum(ev[:, 2] + int(context), limit - 1)
     return ev
+
+
+def frame_delays(tdoa, wide) -> Tuple[np.ndarray, bool]:
+    """`extract_events`' tdoa as (flat float64 delays, per_frame): one delay per event - a flat sequence of E numbers - passes
+    through with per_frame False; a sequence of E arrays, the e-th with one delay per frame of the (widened) event wide[e] =
+    (sample, first, last) (`track_delays(track, first, last)`), is concatenated with per_frame True.  ValueError: a length that
+    fits neither."""
+    wide = np.asarray(wide, np.int64).reshape(-1, 3)
+    if torch.is_tensor(tdoa):
+        tdoa = tdoa.cpu().numpy()
+    if isinstance(tdoa, np.ndarray) and tdoa.ndim <= 1 or not len(tdoa) or all(np.ndim(d) == 0 for d in tdoa):
+        return np.asarray(tdoa, np.float64).reshape(-1), False
+    parts = [np.asarray(d.cpu() if torch.is_tensor(d) else d, np.float64).reshape(-1) for d in tdoa]
+    want = (wide[:, 2] - wide[:, 1] + 1).tolist()
+    if [len(p) for p in parts] != want:
+        raise ValueError(f"extract: per-frame delays of {[len(p) for p in parts][:8]} frames for events of {want[:8]} (widened) frames")
+    return np.concatenate(parts), True
 
 
 def clips_from_slabs(slabs, hop=None):
@@ -682,6 +824,7 @@ def extract_events(spec: torch.Tensor, events, tdoa, block=None, loading: float 
     if x.dim() != 4 or x.shape[-1] != 4 or x.shape[1] < 2:
         raise ValueError(f"extract_events: spec must be [B, F >= 2, T, 4] (a stereo complex spectrum), got {tuple(spec.shape)}")
     wide = widen_events(events, context, int(x.shape[2]))
+    delays, per_frame = frame_delays(tdoa, wide)
     if not x.is_cuda:
         raise RuntimeError(f"extract_events: spec is on {x.device}: the extraction runs only as HIP kernels on a ROCm device "
                            "(there is no CPU fallback); move the tensor to 'cuda'")
@@ -693,7 +836,7 @@ def extract_events(spec: torch.Tensor, events, tdoa, block=None, loading: float 
         fac, _ = _quiet_factors(plan, x, events, block, loading, guard, min_quiet, reach)
     else:
         fac = plan.whiten_factors(x, block, loading) if noise == "block" else None
-    slabs = plan.beamform(x, wide, tdoa, fac, block, k_lo, k_hi)
+    slabs = (plan.beamform_frames if per_frame else plan.beamform)(x, wide, delays, fac, block, k_lo, k_hi)
     clips, _ = clips_from_slabs(slabs, hop)
     return clips, wide[:, 1:] * hop
 

@@ -371,6 +371,50 @@ int iris_beamform_events(iris_plan* plan, const float* spec, const float* factor
                          int k_lo, int k_hi, float* out, size_t out_floats, void* stream);
 
 /*
+ * Tracking the delay of a moving event (k_track.h, K19): the steered response per STEP of frames, the best path through its
+ * lags, and the beamformer steered per frame.
+ *
+ * iris_locate_steps: iris_locate_events with "segment" read as "step".  Frames are grouped into steps of `step` frames counted
+ * from frame 0; with more than one block, block % step == 0 is required, so a step lies in one block.  Events: int32
+ * [n_events, 4] = (sample, first frame, last frame, first row): an event is cut into the steps first / step .. last / step (the
+ * first and last may be short), each one ROW, and `first row` is the running count of the rows of the events before it.
+ * response [rows, 2 max_lag + 1] double: per row iris_locate_events' term sum - the moments over the step's frames, the factors
+ * of the step's block t0 / block, the same lags and bins; n_terms [rows] int64: the step's frames x its contributing bins.
+ * |response - exact| <= (n_l + n_s + 72) 2^-53 sum A, n_l = ceil(step frames / 64), n_s = ceil((k_hi - k_lo) / 64).
+ * workspace: DEVICE scratch of 32 bytes x rows x (k_hi - k_lo), 8-byte aligned.  Refusals: those of iris_locate_events with
+ * rows for segments, and step < 1 or (n_blocks > 1 and block % step != 0) (IRIS_E_INVALID).  Two launches on `stream`, no
+ * atomics, fixed summation orders: bitwise reproducible, and a row depends on its own event only.
+ *
+ * iris_track_lags: response [n_rows, L] (L = 2 max_lag + 1), offsets int32 [n_events + 1] (event e owns the rows offsets[e] ..
+ * offsets[e + 1] - 1; once on the device, once on the host: what is checked here), penalty_dev: DEVICE double [n_penalty] =
+ * P[d] = d x pen for d = 0 .. min(max_jump, L - 1), formed on the host -> path int32 [n_rows]: per event
+ *     D_0[n] = R[0, n];   D_u[n] = max over n' in [max(0, n - max_jump), min(L - 1, n + max_jump)] of (D_{u-1}[n'] - P[|n - n'|]) + R[u, n]
+ * the maximiser the smallest such n'; the last row takes the smallest argmax of D, earlier rows follow the back-pointers.  Only
+ * subtractions, additions and comparisons of doubles: a host loop with the same operations gives the same integers.
+ * workspace: DEVICE scratch of 4 bytes x n_rows x L (the back-pointers).  Refused before any HIP call: a NULL plan, negative
+ * counts, n_penalty != min(max_jump, L - 1) + 1, NULL or misaligned arrays (8 bytes: response, penalty; 4: the rest), offsets
+ * that do not start at 0, do not strictly ascend or do not end at n_rows (IRIS_E_INVALID); more than 2049 lags (max_lag > 1024:
+ * two rows of doubles in LDS; IRIS_E_UNSUPPORTED); a workspace that is too small (IRIS_E_CAPACITY).  n_events == 0 returns
+ * IRIS_OK without a launch.  One launch on `stream`, one workgroup per event, no atomics.
+ *
+ * iris_beamform_frames: iris_beamform_events with one delay per OUTPUT FRAME: tdoa_dev [n_tdoa] double, frame t of event e
+ * reads tdoa_dev[first output frame + (t - first)]; a frame whose delay is not finite is exactly 0.  n_tdoa must be the frames
+ * of all events (IRIS_E_INVALID); the grid holds n_bins x ceil(longest event / 64) <= 262140 (IRIS_E_UNSUPPORTED); otherwise
+ * iris_beamform_events' checks, bound (6 x 2^-24 A) and properties.  A delay that is constant over an event gives the bits of
+ * iris_beamform_events.
+ */
+int iris_locate_steps(iris_plan* plan, const float* spec, const float* factors, int n_blocks, const int32_t* events_dev,
+                      const int32_t* events_host, int n_events, int batch, int n_frames, int block, int step, int k_lo, int k_hi,
+                      int max_lag, int q, double* workspace, size_t workspace_bytes, double* response, int64_t* n_terms,
+                      void* stream);
+int iris_track_lags(iris_plan* plan, const double* response, const int32_t* offsets_dev, const int32_t* offsets_host,
+                    int n_events, int n_rows, int max_lag, const double* penalty_dev, int n_penalty, int max_jump,
+                    int32_t* workspace, size_t workspace_bytes, int32_t* path, void* stream);
+int iris_beamform_frames(iris_plan* plan, const float* spec, const float* factors, int n_blocks, const int32_t* events_dev,
+                         const int32_t* events_host, const double* tdoa_dev, size_t n_tdoa, int n_events, int batch,
+                         int n_frames, int block, int k_lo, int k_hi, float* out, size_t out_floats, void* stream);
+
+/*
  * minmax + log_on_mel (data_utils.py:37-55; fused twin trainer.py:63-77),
  * in place on x[n_rows, row_len]: per row (x - min) / max(max - min, eps_div)
  * when do_minmax, then ln(x + eps_log) when do_log.  A batched [B,M,T,C] tensor
