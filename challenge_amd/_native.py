@@ -98,6 +98,8 @@ SIGNATURES = {
     "iris_locate_steps": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
     "iris_track_lags": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _sz, _vp, _vp]),
     "iris_beamform_frames": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "iris_postfilter_events": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _i, _vp, _vp, _i, _i, _i, _i, C.c_double, C.c_double, _i, _i,
+                                    _vp, _sz, _vp]),
     "iris_filter_draw": (_i, [_i, _i, _i, _i, _i, _i, _f, _f, C.c_uint64, _vp, _vp, _vp, _vp, _vp]),
     "iris_crop_windows": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "iris_crop_draw": (_i, [_vp, _i, _i, C.c_uint64, _vp, _vp, _vp]),

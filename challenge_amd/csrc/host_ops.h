@@ -607,6 +607,84 @@ extern "C" int iris_beamform_frames(iris_plan* p, const float* spec, const float
                          n_frames, block, k_lo, k_hi, out, out_floats, stream);
 }
 
+// iris_postfilter_events: the decision-directed Wiener post-filter over the slabs of iris_beamform_events / _frames
+// (k_postfilter.h, one launch); every check happens before the first HIP call.  events_host and gmin_host are the host's
+// copies of the device arrays: what is checked here.  per_frame: n_tdoa delays, one per output frame; else one per event.
+extern "C" int iris_postfilter_events(iris_plan* p, const float* slabs, const float* factors, int n_blocks, const int32_t* events_dev,
+                                      const int32_t* events_host, const double* tdoa_dev, size_t n_tdoa, int per_frame,
+                                      const double* gmin_dev, const double* gmin_host, int n_events, int batch, int n_frames,
+                                      int block, double loading, double alpha, int k_lo, int k_hi, float* out, size_t out_floats,
+                                      void* stream) {
+    const char* who = "iris_postfilter_events";
+    if (!p || !factors) return fail(IRIS_E_INVALID, "%s: NULL argument (the factors are the noise model: there is no identity)", who);
+    if (batch <= 0 || n_frames <= 0 || n_events < 0)
+        return fail(IRIS_E_INVALID, "%s: batch=%d n_frames=%d n_events=%d", who, batch, n_frames, n_events);
+    if (n_frames > (1 << 30)) return fail(IRIS_E_UNSUPPORTED, "%s: n_frames=%d > 2^30", who, n_frames);
+    if (k_lo < 0 || k_lo >= k_hi) return fail(IRIS_E_INVALID, "%s: bins [%d, %d) must be a non-empty range from 0 up", who, k_lo, k_hi);
+    if (!(alpha >= 0.0 && alpha < 1.0)) return fail(IRIS_E_INVALID, "%s: alpha=%g must lie in [0, 1)", who, alpha);
+    if (!(loading > 0.0 && std::isfinite(loading))) return fail(IRIS_E_INVALID, "%s: loading=%g must be positive and finite", who, loading);
+    if (block < 1) return fail(IRIS_E_INVALID, "%s: block=%d must be at least 1 frame", who, block);
+    if (reinterpret_cast<uintptr_t>(factors) & 15) return fail(IRIS_E_INVALID, "%s: factors must be 16-byte aligned", who);
+    block = std::min(block, n_frames);
+    if (n_blocks != (n_frames + block - 1) / block)
+        return fail(IRIS_E_INVALID, "%s: factors of %d block(s), but %d frames in blocks of %d make %d", who, n_blocks, n_frames, block,
+                    (n_frames + block - 1) / block);
+    if (n_events > 0 && (!slabs || !events_dev || !events_host || !tdoa_dev || !gmin_dev || !gmin_host || !out))
+        return fail(IRIS_E_INVALID, "%s: NULL argument", who);
+    if ((reinterpret_cast<uintptr_t>(events_dev) & 3) || (reinterpret_cast<uintptr_t>(tdoa_dev) & 7) ||
+        (reinterpret_cast<uintptr_t>(gmin_dev) & 7) || (reinterpret_cast<uintptr_t>(slabs) & 7) || (reinterpret_cast<uintptr_t>(out) & 7))
+        return fail(IRIS_E_INVALID, "%s: the event table must be 4-byte, tdoa, g_min, slabs and out 8-byte aligned", who);
+    long long total = 0;
+    for (int e = 0; e < n_events; ++e) {
+        const int32_t* r = events_host + 4 * (size_t)e;
+        if (r[0] < 0 || r[0] >= batch) return fail(IRIS_E_INVALID, "%s: event %d names sample %d of %d", who, e, r[0], batch);
+        if (r[1] < 0 || r[1] > r[2] || r[2] >= n_frames)
+            return fail(IRIS_E_INVALID, "%s: event %d spans frames %d .. %d of %d", who, e, r[1], r[2], n_frames);
+        if (r[3] != total) return fail(IRIS_E_INVALID, "%s: event %d starts at output frame %d, expected %lld", who, e, r[3], total);
+        total += r[2] - r[1] + 1;
+        if (total > 0x7fffffffLL) return fail(IRIS_E_UNSUPPORTED, "%s: more than 2^31 - 1 output frames", who);
+        if (!(gmin_host[e] > 0.0 && gmin_host[e] <= 1.0))
+            return fail(IRIS_E_INVALID, "%s: event %d has the gain floor %g outside (0, 1]", who, e, gmin_host[e]);
+    }
+    if (n_tdoa != (per_frame ? (size_t)total : (size_t)n_events))
+        return fail(IRIS_E_INVALID, "%s: %zu delays for %lld output frames of %d events (per_frame=%d)", who, n_tdoa, total, n_events,
+                    per_frame);
+    // (the plan is read only now: everything above is checked without it)
+    if (p->channels != 2) return fail(IRIS_E_UNSUPPORTED, "%s: the plan has %d channel(s); the delay is that of a stereo pair", who, p->channels);
+    if (p->n_bins < 2) return fail(IRIS_E_UNSUPPORTED, "%s: a plan of %d bin(s)", who, p->n_bins);
+    if (k_hi > p->n_bins) return fail(IRIS_E_INVALID, "%s: bins [%d, %d) leave [0, %d]", who, k_lo, k_hi, p->n_bins);
+    if (n_events == 0) return IRIS_OK;  // nothing to do, no launch
+    if (out_floats / 2 / (size_t)p->n_bins < (size_t)total)
+        return fail(IRIS_E_CAPACITY, "%s: out of %zu floats, %lld needed", who, out_floats, 2LL * p->n_bins * total);
+    const int groups = (p->n_bins + kPostBins - 1) / kPostBins;
+    if (groups > 65535 || n_events > (1 << 24))
+        return fail(IRIS_E_UNSUPPORTED, "%s: %d bin groups / %d events exceed the grid limit", who, groups, n_events);
+    DeviceGuard guard(p->device);
+    PostfilterArgs a;
+    a.in = slabs;
+    a.fac = factors;
+    a.events = events_dev;
+    a.tdoa = tdoa_dev;
+    a.gmin = gmin_dev;
+    a.out = out;
+    a.B = batch;
+    a.F = p->n_bins;
+    a.T = n_frames;
+    a.J = n_blocks;
+    a.block = block;
+    a.E = n_events;
+    a.k_lo = k_lo;
+    a.k_hi = k_hi;
+    a.per_frame = per_frame ? 1 : 0;
+    a.total = total;
+    a.n_fft = 2.0 * (p->n_bins - 1);  // (a mel-only plan carries no n_fft)
+    a.alpha = alpha;
+    a.loading = loading;
+    k_postfilter<<<dim3((unsigned)n_events, (unsigned)groups), 256, 0, (hipStream_t)stream>>>(a);
+    HIP_TRY(hipGetLastError());
+    return IRIS_OK;
+}
+
 extern "C" size_t iris_minmax_log_workspace(int n_rows, size_t row_len) {
     return n_rows > 0 ? 2 * (size_t)n_rows * n_chunks_of(row_len) : 0;
 }

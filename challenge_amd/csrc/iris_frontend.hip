@@ -18,6 +18,8 @@
 //                    inter-channel delay, hence bearing, fits each detected event (two launches, double)
 //   k_beamform.h    stereo spectrum + whitening factors + events + delays -> the MVDR-beamformed spectrum of each event, one
 //                    [F, T_e, 2] slab per event in iris_istft's record layout (one streaming launch)
+//   k_postfilter.h  those slabs + the factors of noise="quiet" -> the decision-directed Wiener post-filter's slabs: one sequential
+//                    chain per (event, bin), transposed through LDS (one launch, double)
 //   k_elementwise.h  min-max / log, normalize, magnitude-phase, mask, adaptive gradient clipping
 //   k_mix.h          batched sample synthesis (merge_complex_specs)
 //   k_draw.h         the random half of a batch drawn on the device (source table, SpecAugment bands)
@@ -72,6 +74,7 @@
 #include "k_whiten.h"
 #include "k_locate.h"
 #include "k_beamform.h"
+#include "k_postfilter.h"
 #include "k_track.h"
 #include "k_elementwise.h"
 #include "host_plan.h"

@@ -61,14 +61,22 @@ __device__ __forceinline__ void beam_phase(int k, double tdoa, double n_fft, dou
     sincospi(2.0 * r, &sn, &cs);  // e = cs - i sn
 }
 
+// (the double core is shared with k_postfilter.h, which needs den, g0 and g1 before the rounding)
+__device__ __forceinline__ void beam_weights_core(double fa, double fb, double cr, double ci, double sn, double cs, double& den,
+                                                  double& h0r, double& h0i, double& h1r, double& h1i) {
+    const double s1r = fb * (cs - cr), s1i = fb * (-sn - ci), a2 = fa * fa;
+    den = a2 + (s1r * s1r + s1i * s1i);
+    h1r = fb * s1r / den, h1i = -(fb * s1i) / den;  // g1 = b conj(s1) / den
+    h0r = a2 / den - (h1r * cr - h1i * ci);         // g0 = a^2 / den - g1 c
+    h0i = -(h1r * ci + h1i * cr);
+}
+
 __device__ __forceinline__ void beam_weights(double fa, double fb, double cr, double ci, double sn, double cs, float& g0r,
                                              float& g0i, float& g1r, float& g1i) {
-    const double s1r = fb * (cs - cr), s1i = fb * (-sn - ci), a2 = fa * fa;
-    const double den = a2 + (s1r * s1r + s1i * s1i);
-    const double h1r = fb * s1r / den, h1i = -(fb * s1i) / den;  // g1 = b conj(s1) / den
+    double den, h0r, h0i, h1r, h1i;
+    beam_weights_core(fa, fb, cr, ci, sn, cs, den, h0r, h0i, h1r, h1i);
     g1r = (float)h1r, g1i = (float)h1i;
-    g0r = (float)(a2 / den - (h1r * cr - h1i * ci));             // g0 = a^2 / den - g1 c
-    g0i = (float)(-(h1r * ci + h1i * cr));
+    g0r = (float)h0r, g0i = (float)h0i;
 }
 
 __global__ __launch_bounds__(256) void k_beamform(const BeamformArgs a) {

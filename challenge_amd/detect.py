@@ -6,6 +6,8 @@
                                    [--decoder_kind pool|hmm] [--locate [--mic_spacing M] --locate_out FILE.json]
                                    [--locate_track [--track_step S] [--track_max_rate R] [--track_penalty P]]    (with --locate)
                                    [--extract DIR [--extract_context S]]    (with --locate)
+                                   [--extract_postfilter [--postfilter_smoothing A] [--postfilter_floor_db D]]
+                                                                            (with --extract and --locate_noise quiet)
 
 `detect` runs a trained model over wav files (or in-memory recordings) and returns, per file, the events it finds in the
 forms of the reference's helpers: frame events (Challenge_Metric.get_start_end_frame), the (class, middle second) rows
@@ -841,6 +843,10 @@ class Detection:
     track: Optional[Tuple[List[np.ndarray], ...]] = None   # per class a list of [n_steps, 4] float64 (first frame of step, last
                                                            # frame, tdoa, score), row for row with `events`: the delay as it moves
                                                            # (`location` stays the static estimate); None unless locate.track
+    postfiltered: Optional[Tuple[np.ndarray, ...]] = None  # per class [n] bool, row for row with `events`: True where the clip
+                                                           # went through the Wiener post-filter, False where the event was
+                                                           # bypassed (a fallback block: `noise_frames` 0); None unless
+                                                           # extract.postfilter
 
 
 @dataclass
@@ -881,16 +887,44 @@ class TrackSettings:
 
 
 @dataclass
+class PostFilterSettings:
+    """How `detect(..., extract=ExtractSettings(postfilter=PostFilterSettings()))` cleans every clip of the noise the beamformer
+    leaves - the decision-directed Wiener gain `transforms.extract_events` defines: smoothing, the weight alpha in [0, 1) of
+    the previous frame's estimate in the a-priori SNR (0.98 is Ephraim & Malah's value; lower follows onsets faster and leaves
+    more musical noise); floor_db <= 0, the least gain in dB (-20: noise-only cells go down by at most 20 dB, so that what is
+    left of the noise stays even).  Both defaults are choices, not measurements on recordings.  Needs
+    LocateSettings(noise='quiet'); an event in a fallback block (`Detection.noise_frames` 0) is passed through untouched."""
+    smoothing: float = 0.98
+    floor_db: float = -20.0
+
+    def __post_init__(self):
+        v = self.smoothing
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 <= v < 1:
+            raise ValueError(f"PostFilterSettings: smoothing = {v!r} must be a number in [0, 1)")
+        v = self.floor_db
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not (np.isfinite(v) and v <= 0) or not 10.0 ** (v / 20.0) > 0:
+            raise ValueError(f"PostFilterSettings: floor_db = {v!r} must be a finite number of dB <= 0 whose gain is above 0")
+
+    def pair(self) -> Tuple[float, float]:
+        """(alpha, floor_db): `transforms.extract_events`' postfilter argument."""
+        return float(self.smoothing), float(self.floor_db)
+
+
+@dataclass
 class ExtractSettings:
     """How `detect(..., locate=, extract=)` extracts the sound of every detected event (`transforms.extract_events` states the
-    definition): context_s, the seconds of recording kept on either side of an event (clipped to the recording).  Block,
-    loading, noise and bins are `locate`'s."""
+    definition): context_s, the seconds of recording kept on either side of an event (clipped to the recording); postfilter:
+    a PostFilterSettings - the Wiener post-filter runs on every event before the inverse STFT (`Detection.postfiltered`; only
+    with LocateSettings(noise='quiet')) - or None: not filtered.  Block, loading, noise and bins are `locate`'s."""
     context_s: float = 0.25
+    postfilter: Optional[PostFilterSettings] = None
 
     def __post_init__(self):
         v = self.context_s
         if isinstance(v, bool) or not isinstance(v, (int, float)) or not (np.isfinite(v) and v >= 0):
             raise ValueError(f"ExtractSettings: context_s = {v!r} must be a finite number of seconds >= 0")
+        if self.postfilter is not None and not isinstance(self.postfilter, PostFilterSettings):
+            raise ValueError(f"ExtractSettings: postfilter must be a PostFilterSettings or None, got {type(self.postfilter).__name__}")
 
     def frames(self, hop: int = HOP) -> int:
         """The context in frames of `hop` samples at 16 kHz, rounded to the nearest frame."""
@@ -1080,6 +1114,10 @@ def detect(model, wavs_or_paths: Sequence, config, overlap_hop: int = 512, batch
     STFT (`transforms.extract_events`), on `load_wav`'s scale (wav / (10 rms)).  It reuses the group's spectra and factors: per
     group one `FrontendPlan.beamform` launch, one `iris_istft` launch and one copy back.  An event whose delay is NaN gives an
     all-zero clip.  Without `extract` nothing changes and `audio` is None.
+    `ExtractSettings(postfilter=PostFilterSettings())`, only with LocateSettings(noise='quiet') (ValueError otherwise, before
+    any device work): every event's beamformed spectrum goes through the decision-directed Wiener post-filter before the
+    inverse STFT - per group one more launch, `FrontendPlan.postfilter` - and `Detection.postfiltered` says, per class and
+    row for row with `events`, which clips it touched: an event with `noise_frames` 0 is bypassed, bit for bit.
     `LocateSettings(track=TrackSettings())`: every event's delay is also followed as it MOVES (`Detection.track`: per class a
     list of [n_steps, 4] float64 (first frame of step, last frame, tdoa, score), row for row with `events`;
     `transforms.track_events` states the definition) - per group three more launches (`FrontendPlan.locate_steps`, `track`) and
@@ -1093,6 +1131,8 @@ def detect(model, wavs_or_paths: Sequence, config, overlap_hop: int = 512, batch
         raise ValueError(f"detect: extract must be an ExtractSettings, got {type(extract).__name__}")
     if extract is not None and locate is None:
         raise ValueError("detect: extract= steers every event at its own delay: it needs locate=LocateSettings(...)")
+    if extract is not None and extract.postfilter is not None and locate.noise != "quiet":
+        raise ValueError(f"detect: extract.postfilter needs locate.noise = 'quiet' (a covariance free of the event), not {locate.noise!r}")
     results: List[Detection] = []
     spectra = [] if locate is not None else None
     for group in _groups(model, wavs_or_paths, config, overlap_hop, sample_rate, device, max_windows, spectra):
@@ -1118,7 +1158,10 @@ def _locate_group(spectra, events, config, locate: LocateSettings, extract: Opti
     over the same padded spectra and factors - three more launches and one more copy back per group - and `extract` then steers
     every frame at `transforms.track_delays` of its event's track through `FrontendPlan.beamform_frames`.  Steps count from
     frame 0 and a row depends on its own event only, so tracks and clips still equal the file alone, bit for bit.
-    Returns (locations, audio, spans, noise_frames, tracks), one entry per file."""
+    With extract.postfilter the slabs pass through ONE `FrontendPlan.postfilter` launch before the inverse STFT, with the
+    same delays (per event or per frame) and a gain floor per event: 1 - the bypass - where `noise_frames` is 0.  An event's
+    chain depends on its own slab only, so the clips still equal the file alone.  `Detection.postfiltered` (else None).
+    Returns (locations, audio, spans, noise_frames, tracks, postfiltered), one entry per file."""
     from . import transforms as T
     rows = [(i, int(f0), int(f1)) for i, ev in enumerate(events) for cls in ev for f0, f1 in np.asarray(cls).reshape(-1, 2)]
     out = np.zeros((0, 4), np.float64)
@@ -1158,15 +1201,21 @@ def _locate_group(spectra, events, config, locate: LocateSettings, extract: Opti
                 slabs = plan.beamform_frames(spec, wide, along, fac, block, k_lo, k_hi)
             else:
                 slabs = plan.beamform(spec, wide, out[:, 0], fac, block, k_lo, k_hi)
+            if extract.postfilter is not None:   # one more launch; the floors from the quiet frames behind each event
+                alpha, floors = T.postfilter_floors(extract.postfilter.pair(), behind)
+                slabs = plan.postfilter(slabs, wide, along if locate.track is not None else out[:, 0], fac,
+                                        max(min(block, t_max), 1), locate.loading, k_lo, k_hi, alpha, floors,
+                                        locate.track is not None)
             _, flat = T.clips_from_slabs(slabs)
             samples = flat.cpu().numpy()                                   # the one copy back of the group
             spans = wide[:, 1:] * (f - 1)                                  # load_wav's hop: n_fft // 2 = F - 1
             ends = np.cumsum(spans[:, 1] - spans[:, 0])
             clips = [samples[z - n:z].copy() for z, n in zip(ends, spans[:, 1] - spans[:, 0])]
-    res, audio, where, noise, moving, at = [], [], [], [], [], 0
+    res, audio, where, noise, moving, filtered, at = [], [], [], [], [], [], 0
     quiet_on = locate.noise == "quiet"
+    post_on = extract is not None and extract.postfilter is not None
     for ev in events:
-        per_class, per_audio, per_span, per_noise, per_track = [], [], [], [], []
+        per_class, per_audio, per_span, per_noise, per_track, per_post = [], [], [], [], [], []
         for cls in ev:
             per_class.append(out[at:at + len(cls)].copy())
             if locate.track is not None:
@@ -1176,13 +1225,16 @@ def _locate_group(spectra, events, config, locate: LocateSettings, extract: Opti
             if extract is not None:
                 per_audio.append(clips[at:at + len(cls)] if rows else [])
                 per_span.append(spans[at:at + len(cls)].copy() if rows else np.zeros((0, 2), np.int64))
+            if post_on:
+                per_post.append(behind[at:at + len(cls)] > 0 if rows else np.zeros((0,), bool))
             at += len(cls)
         res.append(tuple(per_class))
         audio.append(tuple(per_audio) if extract is not None else None)
         where.append(tuple(per_span) if extract is not None else None)
         noise.append(tuple(per_noise) if quiet_on else None)
         moving.append(tuple(per_track) if locate.track is not None else None)
-    return res, audio, where, noise, moving
+        filtered.append(tuple(per_post) if post_on else None)
+    return res, audio, where, noise, moving, filtered
 
 
 def _detect_group(model, group, config, overlap_hop: int, batch_size: int, settings=None, locate=None,
@@ -1193,11 +1245,12 @@ def _detect_group(model, group, config, overlap_hop: int, batch_size: int, setti
     else:
         events = decode_events(preds, win_off, [t for _, t, _ in group], config.n_frame, overlap_hop, settings=settings)
     none = [None] * len(group)
-    where, audio, spans, noise, moving = _locate_group(spectra, events, config, locate, extract) if locate is not None else (none,) * 5
+    where, audio, spans, noise, moving, filtered = _locate_group(spectra, events, config, locate, extract) if locate is not None \
+        else (none,) * 6
     out = []
-    for (name, t_len, _), ev, loc, clips, span, behind, tracks in zip(group, events, where, audio, spans, noise, moving):
+    for (name, t_len, _), ev, loc, clips, span, behind, tracks, post in zip(group, events, where, audio, spans, noise, moving, filtered):
         metric = M.output_to_metric(HOP, SR)(*ev)
-        out.append(Detection(name, t_len, ev, metric, _FromEvents(ev).get_start_end_time(None), loc, clips, span, behind, tracks))
+        out.append(Detection(name, t_len, ev, metric, _FromEvents(ev).get_start_end_time(None), loc, clips, span, behind, tracks, post))
     return out
 
 
@@ -1305,10 +1358,12 @@ def write_locations(results: Sequence[Detection], path: str) -> dict:
     return where
 
 
-def write_extracts(results: Sequence[Detection], out_dir: str) -> dict:
+def write_extracts(results: Sequence[Detection], out_dir: str, postfilter: Optional[PostFilterSettings] = None) -> dict:
     """Every clip of `detect(..., locate=, extract=)` as out_dir/<recording>_c<class>_<row>.wav - mono, float32, 16 kHz, on
     load_wav's scale (the recording divided by 10 times its rms) - and out_dir/extract.json = {"task2_extract": {name: [[class,
-    row, file, start sample, end sample, tdoa, bearing], ...]}} (NaN is written as null)."""
+    row, file, start sample, end sample, tdoa, bearing], ...]}} (NaN is written as null).  With `postfilter`, the settings the
+    clips were made with (`Detection.postfiltered` must be there: ValueError), also "postfilter": {"smoothing", "floor_db",
+    "applied": {name: [true | false, ...]}}, row for row with the recording's clips: false where the event was bypassed."""
     from scipy.io import wavfile
     os.makedirs(out_dir, exist_ok=True)
     index = {}
@@ -1323,6 +1378,13 @@ def write_extracts(results: Sequence[Detection], out_dir: str) -> dict:
                 rows.append([c, r, name, int(span[0]), int(span[1])] + [None if np.isnan(x) else float(x) for x in v[:2]])
         index[d.name] = rows
     index = {"task2_extract": index}
+    if postfilter is not None:
+        if any(d.postfiltered is None for d in results):
+            raise ValueError("write_extracts: postfilter settings, but the results carry no `postfiltered` - run detect(..., "
+                             "extract=ExtractSettings(postfilter=PostFilterSettings()))")
+        index["postfilter"] = {"smoothing": float(postfilter.smoothing), "floor_db": float(postfilter.floor_db),
+                               "applied": {d.name: [bool(v) for cls in d.postfiltered for v in np.asarray(cls).reshape(-1)]
+                                           for d in results}}
     with open(os.path.join(out_dir, "extract.json"), 'w') as f:
         json.dump(index, f, indent=4, allow_nan=False)
     return index
@@ -1376,6 +1438,14 @@ def main(argv=None):
                                   'divided by 10 times its rms) and DIR/extract.json')
     config.args.add_argument('--extract_context', type=float, default=0.25, metavar='S',
                              help='seconds of recording kept on either side of an event (--extract)')
+    config.args.add_argument('--extract_postfilter', action='store_true',
+                             help='with --extract and --locate_noise quiet: pass every event through the decision-directed Wiener '
+                                  'post-filter before the inverse STFT (extract.json then also lists the settings and which clips it '
+                                  'touched)')
+    config.args.add_argument('--postfilter_smoothing', type=float, default=0.98, metavar='A',
+                             help='the weight in [0, 1) of the previous frame in the a-priori SNR (--extract_postfilter)')
+    config.args.add_argument('--postfilter_floor_db', type=float, default=-20.0, metavar='D',
+                             help='the least gain in dB, <= 0 (--extract_postfilter)')
     parser = config.args
     config = config.get(argv)
     if config.extract is not None and not config.locate:
@@ -1387,7 +1457,13 @@ def main(argv=None):
                           penalty=config.track_penalty) if config.locate_track else None
     locate = LocateSettings(mic_spacing=config.mic_spacing, noise=config.locate_noise, guard_s=config.locate_guard,
                             min_quiet=config.locate_min_quiet, reach=config.locate_reach, track=track) if config.locate else None
-    extract = ExtractSettings(context_s=config.extract_context) if config.extract is not None else None
+    if config.extract_postfilter and config.extract is None:
+        parser.error("--extract_postfilter filters the extracted clips: it needs --extract")
+    if config.extract_postfilter and config.locate_noise != 'quiet':
+        parser.error("--extract_postfilter needs --locate_noise quiet: a noise covariance that is free of the event")
+    post = PostFilterSettings(smoothing=config.postfilter_smoothing, floor_db=config.postfilter_floor_db) if config.extract_postfilter \
+        else None
+    extract = ExtractSettings(context_s=config.extract_context, postfilter=post) if config.extract is not None else None
     if config.p:
         parse_name(config)
     if config.tune and config.decoder:
@@ -1416,7 +1492,7 @@ def main(argv=None):
         write_locations(results, config.locate_out)
         print(f"locations (tdoa in samples, bearing in degrees, score, contrast) -> {config.locate_out}")
     if extract is not None:
-        write_extracts(results, config.extract)
+        write_extracts(results, config.extract, extract.postfilter)
         print(f"{sum(len(c) for d in results for c in d.audio)} clips (mono float32, load_wav's scale) and extract.json -> {config.extract}")
     if config.score:
         with open(config.score) as f:

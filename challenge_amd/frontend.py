@@ -663,6 +663,87 @@ class FrontendPlan:
             x.record_stream(torch.cuda.current_stream(self.device))
         return [flat[per * int(o):per * int(o + n)].view(self.n_bins, int(n), 2) for o, n in zip(table[:, 3], frames)]
 
+    def postfilter(self, slabs, events, tdoa, fac: torch.Tensor, block: Optional[int], loading: float, k_lo: int, k_hi: Optional[int],
+                   alpha: float, g_min, per_frame: bool = False) -> List[torch.Tensor]:
+        """The decision-directed Wiener post-filter over the slabs `beamform` (or, per_frame=True, `beamform_frames`) returned
+        for the SAME events, tdoa, fac, block and bins: new slabs [F, T_e, 2] float32, views of ONE flat device buffer
+        (`iris_postfilter_events`, one launch; `transforms.extract_events` states the definition).  fac must be the factors of
+        a covariance that does not contain the events (`whiten_factors_ranges`: noise="quiet") made with `loading`; fac=None
+        is refused - there is no noise model.  alpha in [0, 1): the smoothing of the a-priori SNR; g_min: one gain floor in
+        (0, 1] per event (a number: the same for all); g_min = 1 returns that event's slab bit for bit.  Bins outside
+        [k_lo, k_hi) (None: F) are exactly 0.  Every check happens before a launch: ValueError."""
+        if self.channels != 2:
+            raise ValueError(f"postfilter: the plan has {self.channels} channel(s); the delay is that of a stereo pair")
+        if fac is None:
+            raise ValueError("postfilter: fac=None - there is no noise model without the factors of noise='quiet'")
+        fac = _require_device_f32(fac, "fac")
+        if fac.dim() != 4 or fac.shape[1] != self.n_bins or fac.shape[3] != 4:
+            raise ValueError(f"postfilter: fac must be [B, {self.n_bins}, J, 4], got {tuple(fac.shape)}")
+        b, j = int(fac.shape[0]), int(fac.shape[2])
+        if block is None and j == 1:
+            block = 1 << 30                               # one block over all frames, however many there were
+        if isinstance(block, bool) or not isinstance(block, (int, np.integer)) or block < 1:
+            raise ValueError(f"postfilter: block = {block!r} must be the frames per block of fac {tuple(fac.shape)}, at least 1 "
+                             "(None: fac holds one block)")
+        block = min(int(block), 1 << 30) if j == 1 else int(block)   # (the entry point takes at most 2^30 frames)
+        if j < 1 or j * block > 1 << 30:
+            raise ValueError(f"postfilter: fac {tuple(fac.shape)} in blocks of {block} frames: between 1 and 2^30 frames in all")
+        for name, v, ok in (("alpha", alpha, lambda v: 0.0 <= v < 1.0), ("loading", loading, lambda v: v > 0.0 and np.isfinite(v))):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating)) or not ok(float(v)):
+                raise ValueError(f"postfilter: {name} = {v!r} must be " + ("in [0, 1)" if name == "alpha" else "positive and finite"))
+        k_hi = self.n_bins if k_hi is None else int(k_hi)
+        k_lo = int(k_lo)
+        if not 0 <= k_lo < k_hi <= self.n_bins:
+            raise ValueError(f"postfilter: bins [{k_lo}, {k_hi}) must be a non-empty range inside [0, {self.n_bins}]")
+        # (the spectrum is not an argument: any frame count whose blocks make J fits; the records are checked against the largest)
+        t = j * block
+        table = beamform_table(events, t, b)
+        e = int(table.shape[0])
+        frames = (table[:, 2] - table[:, 1] + 1).astype(np.int64)
+        delays = np.ascontiguousarray(np.asarray(tdoa.cpu() if torch.is_tensor(tdoa) else tdoa, np.float64).reshape(-1))
+        if delays.shape[0] != (int(frames.sum()) if per_frame else e):
+            raise ValueError(f"postfilter: {delays.shape[0]} delay(s) for {e} event(s) of {int(frames.sum())} output frame(s), "
+                             f"per_frame={bool(per_frame)}")
+        floors = np.asarray(g_min.cpu() if torch.is_tensor(g_min) else g_min, np.float64)
+        floors = np.full((e,), floors) if floors.ndim == 0 else np.ascontiguousarray(floors.reshape(-1))
+        if floors.shape[0] != e or not np.all((floors > 0.0) & (floors <= 1.0)):
+            raise ValueError(f"postfilter: g_min must be one gain floor in (0, 1] per event ({e}), got {floors[:8].tolist()}")
+        slabs = list(slabs)
+        if len(slabs) != e:
+            raise ValueError(f"postfilter: {len(slabs)} slab(s) for {e} event(s)")
+        for i, (s, n) in enumerate(zip(slabs, frames)):
+            if not torch.is_tensor(s) or not s.is_cuda:
+                raise RuntimeError(f"postfilter: slab {i} is not on a ROCm device: the post-filter runs only as a HIP kernel "
+                                   "(there is no CPU fallback)")
+            if tuple(s.shape) != (self.n_bins, int(n), 2) or s.dtype != torch.float32 or not s.is_contiguous() or s.device != fac.device:
+                raise ValueError(f"postfilter: slab {i} must be a contiguous float32 [{self.n_bins}, {int(n)}, 2] on {fac.device}, "
+                                 f"got {s.dtype} {tuple(s.shape)} on {s.device}")
+        if e == 0:
+            return []
+        per = 2 * self.n_bins
+        base = slabs[0].data_ptr()
+        if base % 8 == 0 and all(s.data_ptr() == base + 4 * per * int(o) for s, o in zip(slabs, table[:, 3])) and \
+                all(s.untyped_storage().data_ptr() == slabs[0].untyped_storage().data_ptr() for s in slabs):
+            src, keep = base, slabs                      # `beamform`'s own flat buffer, in place
+        else:
+            keep = [torch.cat([s.reshape(-1) for s in slabs])]
+            src = keep[0].data_ptr()
+        if fac.data_ptr() % 16:
+            fac = fac.clone()
+        flat = torch.empty((per * int(frames.sum()),), dtype=torch.float32, device=fac.device)
+        table_dev = torch.from_numpy(table).to(fac.device, non_blocking=True)
+        tdoa_dev = torch.from_numpy(delays).to(fac.device, non_blocking=True)
+        floors_dev = torch.from_numpy(floors).to(fac.device, non_blocking=True)
+        with self._lock, torch.cuda.device(self.device):
+            rc = N.lib().iris_postfilter_events(self._handle, src, fac.data_ptr(), j, table_dev.data_ptr(), table.ctypes.data,
+                                                tdoa_dev.data_ptr(), delays.shape[0], int(bool(per_frame)), floors_dev.data_ptr(),
+                                                floors.ctypes.data, e, b, t, block, float(loading), float(alpha), k_lo, k_hi,
+                                                flat.data_ptr(), flat.numel(), _stream_ptr(self.device))
+        N.check(rc, "iris_postfilter_events")
+        for x in [table_dev, tdoa_dev, floors_dev, fac] + list(keep):   # (they must outlive the kernel on this stream)
+            x.record_stream(torch.cuda.current_stream(self.device))
+        return [flat[per * int(o):per * int(o + n)].view(self.n_bins, int(n), 2) for o, n in zip(table[:, 3], frames)]
+
     def wav_to_logmel(self, wav: torch.Tensor, minmax: bool = True, log: bool = True,
                       normalize: bool = False, t_bands=None, f_bands=None,
                       out: Optional[torch.Tensor] = None, mel_gain=None) -> torch.Tensor:

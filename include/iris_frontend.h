@@ -415,6 +415,35 @@ int iris_beamform_frames(iris_plan* plan, const float* spec, const float* factor
                          int n_frames, int block, int k_lo, int k_hi, float* out, size_t out_floats, void* stream);
 
 /*
+ * The Wiener post-filter of event extraction (k_postfilter.h): a decision-directed single-channel gain on the beamformer's
+ * output, its noise power taken in closed form from the factors of a covariance that is free of the event (noise="quiet").
+ * slabs: the device buffer iris_beamform_events / iris_beamform_frames wrote for the SAME events table, delays, factors,
+ * block, bins and plan; out: a buffer of the same layout, at least 2 n_bins x (frames of all events) floats.  per_frame != 0:
+ * tdoa_dev holds n_tdoa = the frames of all events delays, one per output frame; else n_tdoa = n_events.  gmin_dev /
+ * gmin_host: one gain floor per event, double, in (0, 1], on the device and the host's copy that is checked here.
+ * For bin k in [k_lo, k_hi), frame t of event e, block j = t / block, (a, b, c) = factors[sample, k, j], and e_k, s1, den, g0, g1
+ * as iris_beamform_events defines them, kept in double:
+ *     S = 1/a^2 + |c|^2/a^2 + 1/b^2,  d = loading S / (2 (1 + loading)),  phi = max(1/den - d (|g0|^2 + |g1|^2), 1e-3 / den)
+ *     gamma = |Y|^2 / phi;  gamma = 0 where a == 0 or the delay is not finite
+ * and along the event's frames, p = 1 before the first:
+ *     xi = alpha p + (1 - alpha) max(gamma - 1, 0),  G = max(xi / (1 + xi), g_min[e]),  p = G^2 gamma,  Z = fl32(G) Y
+ * Bins outside [k_lo, k_hi) are written as exact zeros and not read; g_min = 1 returns Y bit for bit.  Per real component
+ * |Z - exact| <= 3 x 2^-24 |G| |Y| against the float64 definition from the same fp32 inputs.  The same inputs give the same
+ * bits; an event's result depends on its own slab, record, delays and floor only.  One launch on `stream` (a workgroup per
+ * (event, 64 bins), 33 280 bytes of LDS), no atomics, no workspace.
+ * Refused before any launch: NULL plan or factors (there is no identity noise model), batch or n_frames < 1, n_events < 0, an
+ * empty bin range or one outside [0, n_bins], alpha outside [0, 1), a loading that is not positive and finite, block < 1,
+ * n_blocks != ceil(n_frames / min(block, n_frames)), NULL or misaligned arrays (16 bytes: factors; 8: slabs, out, tdoa, g_min;
+ * 4: events), a record that does not fit or does not start at the running frame count, a floor outside (0, 1], a delay count
+ * that fits neither form (IRIS_E_INVALID); a plan of other than 2 channels, more than 2^31 - 1 output frames, 2^24 events
+ * (IRIS_E_UNSUPPORTED); an `out` that is too small (IRIS_E_CAPACITY).  n_events == 0 returns IRIS_OK without a launch.
+ */
+int iris_postfilter_events(iris_plan* plan, const float* slabs, const float* factors, int n_blocks, const int32_t* events_dev,
+                           const int32_t* events_host, const double* tdoa_dev, size_t n_tdoa, int per_frame,
+                           const double* gmin_dev, const double* gmin_host, int n_events, int batch, int n_frames, int block,
+                           double loading, double alpha, int k_lo, int k_hi, float* out, size_t out_floats, void* stream);
+
+/*
  * minmax + log_on_mel (data_utils.py:37-55; fused twin trainer.py:63-77),
  * in place on x[n_rows, row_len]: per row (x - min) / max(max - min, eps_div)
  * when do_minmax, then ln(x + eps_log) when do_log.  A batched [B,M,T,C] tensor
