@@ -34,10 +34,63 @@ static hipError_t launch_stft(const StftArgs& a, int grid, size_t lds, hipStream
     return hipGetLastError();
 }
 
+// Geometry of iris_stft for (plan, batch, len): the LDS tile, K1's balanced chunks and the grid.  Host arithmetic only - iris_stft
+// launches with exactly these numbers, iris_stft_geometry reports them.
+struct StftGeom {
+    int tile_frames, chunks_per_clip, n_chunks, grid, waves;
+    size_t lds;
+};
+static int stft_geometry(const iris_plan* p, int batch, int len, StftGeom* g, const char* who) {
+    const int T = 1 + len / p->hop;
+    const int NC = p->n_fft / 2, F = NC + 1, waves = stft_waves(p->log2n), C2 = 2 * p->channels;
+    // tile = as many frames as the LDS left by the waves' exchange buffers holds (one workgroup per
+    // CU owns the whole 160 KiB); at least the constant block must fit (it is staged through the tile)
+    const size_t xbufs = (size_t)waves * ((wave_buf_bytes(p->log2n) + 15) & ~(size_t)15);
+    const int wgs = stft_wgs(p->log2n);  // workgroups per CU
+    const size_t room = (160 * 1024 - 1024) / wgs - xbufs;
+    auto tile_bytes = [&](int t) { return (size_t)F * ((size_t)t * C2 + 1) * 4; };
+    int tf = 1;
+    while (tf < 256 && tile_bytes(tf + 1) <= room) ++tf;
+    if (tile_bytes(tf) > room) return fail(IRIS_E_UNSUPPORTED, "%s: channels=%d too large", who, p->channels);
+    // a whole number of rounds of the workgroup's waves
+    const int per_round = std::max(1, waves / std::max(1, p->channels));
+    if (tf > per_round) tf -= tf % per_round;
+    g->tile_frames = tf;
+    g->waves = waves;
+    int chunk_frames = 0;
+    fused_geometry(p, batch, T, wgs, &chunk_frames, &g->chunks_per_clip);  // K1's balanced chunks, one per workgroup
+    g->n_chunks = batch * g->chunks_per_clip;
+    g->lds = xbufs + std::max(tile_bytes(tf), (size_t)const_nv4(p->log2n) * 64 * 16);
+    if (g->lds > 160 * 1024) return fail(IRIS_E_UNSUPPORTED, "%s: %zu B of LDS", who, g->lds);
+    g->grid = std::min(g->n_chunks, p->num_cu * wgs);
+    return IRIS_OK;
+}
+
+extern "C" int iris_stft_geometry(const iris_plan* p, int batch, int len, int out[5]) {
+    const char* who = "iris_stft_geometry";
+    if (!p || !out) return fail(IRIS_E_INVALID, "%s: NULL argument", who);
+    if (p->mel_only) return fail(IRIS_E_UNSUPPORTED, "%s: plan was created mel-only (n_fft = 0)", who);
+    if (batch <= 0 || len <= 0) return fail(IRIS_E_INVALID, "%s: batch=%d len=%d must be positive", who, batch, len);
+    if (batch > p->max_batch || len > p->max_len)
+        return fail(IRIS_E_CAPACITY, "%s: batch=%d len=%d exceed plan capacity (%d, %d)", who, batch, len, p->max_batch, p->max_len);
+    if (len <= p->n_fft / 2) return fail(IRIS_E_INVALID, "%s: len=%d must exceed n_fft/2=%d (reflect padding)", who, len, p->n_fft / 2);
+    StftGeom g;
+    const int rc = stft_geometry(p, batch, len, &g, who);
+    if (rc) return rc;
+    out[0] = g.tile_frames;
+    out[1] = g.chunks_per_clip;
+    out[2] = g.n_chunks;
+    out[3] = g.grid;
+    out[4] = g.waves;
+    return IRIS_OK;
+}
+
 extern "C" int iris_stft(iris_plan* p, const float* wav, float* spec, int batch, int len, int flags, void* stream) {
     int rc = check_wav_args(p, wav, spec, batch, len, "iris_stft");
     if (rc) return rc;
     if (flags & ~IRIS_F_NORMALIZE) return fail(IRIS_E_INVALID, "iris_stft: flags 0x%x (only IRIS_F_NORMALIZE applies)", flags);
+    StftGeom g;
+    if ((rc = stft_geometry(p, batch, len, &g, "iris_stft"))) return rc;
     DeviceGuard guard(p->device);
     StftArgs a;
     a.wav = wav;
@@ -48,28 +101,13 @@ extern "C" int iris_stft(iris_plan* p, const float* wav, float* spec, int batch,
     a.L = len;
     a.T = 1 + len / p->hop;
     a.hop = p->hop;
-    const int NC = p->n_fft / 2, F = NC + 1, waves = stft_waves(p->log2n), C2 = 2 * p->channels;
-    // tile = as many frames as the LDS left by the waves' exchange buffers holds (one workgroup per
-    // CU owns the whole 160 KiB); at least the constant block must fit (it is staged through the tile)
-    const size_t xbufs = (size_t)waves * ((wave_buf_bytes(p->log2n) + 15) & ~(size_t)15);
-    const int wgs = stft_wgs(p->log2n);  // workgroups per CU
-    const size_t room = (160 * 1024 - 1024) / wgs - xbufs;
-    auto tile_bytes = [&](int t) { return (size_t)F * ((size_t)t * C2 + 1) * 4; };
-    int tf = 1;
-    while (tf < 256 && tile_bytes(tf + 1) <= room) ++tf;
-    if (tile_bytes(tf) > room) return fail(IRIS_E_UNSUPPORTED, "iris_stft: channels=%d too large", p->channels);
-    // a whole number of rounds of the workgroup's waves
-    const int per_round = std::max(1, waves / std::max(1, p->channels));
-    if (tf > per_round) tf -= tf % per_round;
-    a.tile_frames = tf;
-    int chunk_frames = 0;
-    fused_geometry(p, batch, a.T, wgs, &chunk_frames, &a.chunks_per_clip);  // K1's balanced chunks, one per workgroup
+    a.tile_frames = g.tile_frames;
+    a.chunks_per_clip = g.chunks_per_clip;
     a.chunk_base = a.T / a.chunks_per_clip;
     a.chunk_rem = a.T % a.chunks_per_clip;
-    a.n_chunks = batch * a.chunks_per_clip;
-    const size_t lds = xbufs + std::max(tile_bytes(tf), (size_t)const_nv4(p->log2n) * 64 * 16);
-    if (lds > 160 * 1024) return fail(IRIS_E_UNSUPPORTED, "iris_stft: %zu B of LDS", lds);
-    const int grid = std::min(a.n_chunks, p->num_cu * wgs);
+    a.n_chunks = g.n_chunks;
+    const size_t lds = g.lds;
+    const int grid = g.grid;
     hipStream_t s = (hipStream_t)stream;
     a.sumsq = nullptr;
     a.n_sq = 0;

@@ -134,7 +134,11 @@ __global__ __launch_bounds__(64 * stft_waves(LOG2N), stft_waves(LOG2N) * stft_wg
             fft_frame<LOG2N>(x, tw, lds, lane);
             cf xlo[P / 2], xhi[P / 2];
             untangle<LOG2N, true, true>(x, post, lds, lane, xlo, xhi);
-            const cf mid = mk(x[P / 2].x, -x[P / 2].y);  // X[NC/2] = conj(Z[NC/2]) (lane 0)
+            // X[NC/2] = conj(Z[NC/2]) (lane 0).  The definition's coefficient of a sample in the other part is an exact zero that
+            // no step of the transform ever multiplies by (lane 0's points reach Z[NC/2] through additions and +-j swaps only), so a
+            // non-finite sample would leave this one word of its frame finite: 0 * the other part makes the frame non-finite in
+            // every bin and changes no finite value
+            const cf mid = mk(x[P / 2].x + 0.f * x[P / 2].y, -(x[P / 2].y + 0.f * x[P / 2].x));
             // x is dead: the next frame (of this tile, or the first of the chunk's next tile) loads
             // behind the tile writes and the write-out
             if (f + W < nwf) {

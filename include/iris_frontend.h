@@ -199,6 +199,14 @@ int iris_normalize(const float* wav, float* out, int n_rows, size_t row_len, flo
  */
 int iris_stft(iris_plan* plan, const float* wav, float* spec, int batch, int len, int flags,
               void* stream);
+/*
+ * The geometry iris_stft launches with for (plan, batch, len), host arithmetic only (no launch, no HIP call):
+ * out = { tile_frames (frames of the LDS tile), chunks_per_clip, n_chunks = batch * chunks_per_clip, grid (workgroups),
+ * waves per workgroup }.  A clip's 1 + len / hop frames are split into chunks_per_clip chunks whose sizes differ by at
+ * most one; a workgroup walks a chunk in tiles of tile_frames frames and takes chunks grid apart.  Same argument checks
+ * as iris_stft (NULL: IRIS_E_INVALID; beyond the plan's capacity: IRIS_E_CAPACITY; len <= n_fft / 2: IRIS_E_INVALID).
+ */
+int iris_stft_geometry(const iris_plan* plan, int batch, int len, int out[5]);
 
 /*
  * complex_to_magphase (transforms.py:111-123) on n_outer rows of 2C floats:

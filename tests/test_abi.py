@@ -64,6 +64,11 @@ def test_argument_validation_without_gpu():
     assert lib.iris_wav_to_logmel(None, None, None, 1, 1, 3, None, 0, None, 0, None) == -1
     assert lib.iris_minmax_log_workspace(32, 40064) == 2 * 32 * 10
     assert lib.iris_normalize_workspace(32, 160000) == 32 * 40
+    # the STFT's geometry query: host arithmetic only, refuses NULL before it reads the plan
+    geom = (C.c_int * 5)(7, 7, 7, 7, 7)
+    assert lib.iris_stft_geometry(None, 1, 1000, geom) == -1 and lib.iris_last_error().startswith(b"iris_stft_geometry:")
+    assert lib.iris_stft_geometry(None, 1, 1000, None) == -1
+    assert list(geom) == [7] * 5
     assert lib.iris_mask_apply(None, 1, 1, 1, 4, None, 0, 1, None) == -1
     assert lib.iris_mask_apply(C.c_void_p(8), 1, 1, 1, 2, None, 0, 1, None) == -2
     # batched synthesis, spectrum and waveform domain: NULL / inconsistent sizes are rejected before any launch

@@ -50,6 +50,18 @@ def assert_mel(mel, wav, n_fft, hop, n_mel, sr=16000, **kw):
     return ratio
 
 
+def assert_stft_rule(spec, wav, n_fft, hop, normalize=False):
+    """The per-frame rule of tests/stft_ref.py on one clip: spec [F, T, 2C] against the float64 definition of wav [C, L],
+    |dX| <= K u (||w x_t||_2 + max_k |X_ref|) for every bin of every frame and channel; returns the worst ratio."""
+    import stft_ref as S
+    x, s = (S.stft_ref_normalized if normalize else S.stft_ref)(np.ascontiguousarray(wav, np.float32), n_fft, hop)
+    ratio, at = S.rule_ratio(spec, x, s)
+    k = S.K_NORMALIZED if normalize else S.K
+    print(f"stft n_fft {n_fft} hop {hop} {spec.shape}{' normalize' if normalize else ''}: worst |dX| / (u S) {ratio:.3f} at {at} (K = {k})")
+    assert ratio <= k, (ratio, at)
+    return ratio
+
+
 # the bound the committed golden mel vectors were accepted under (SURVEY 8(d): max |d| / max(|ref|, 1e-3)); the reference's
 # default shape (80 mel over 257 bins: one-bin bands) reads up to 2e-5 under it for every fp32 engine, the others 1e-5
 GOLDEN_MEL_BOUND = {"refdefault_stereo": 2e-5}
@@ -77,6 +89,7 @@ def test_stft_matches_golden(golden_dir, dev, name):
         assert np.abs(spec[:, fr, c + ch] - g["spec_im"][ch]).max() <= 2e-6 * scale
     full = R.to_ref_layout(R.stft(g["wav"], int(g["n_fft"]), int(g["hop"])))
     assert np.abs(spec - full).max() <= 3e-6 * scale
+    assert_stft_rule(spec, g["wav"], int(g["n_fft"]), int(g["hop"]))
 
 
 @pytest.mark.parametrize("name", CASES)
@@ -225,6 +238,7 @@ def test_normalize_flag_and_op(dev):
     for i in range(3):
         peak = np.abs(oracle[i]).max()
         assert np.abs(folded[i] - first[i]).max() <= 2e-6 * peak and np.abs(folded[i] - oracle[i]).max() <= 3e-6 * peak
+        assert_stft_rule(folded[i], raw[i], 512, 256, normalize=True)
     with pytest.raises(ValueError):
         FE().N.check(FE().N.lib().iris_stft(plan._handle, x.data_ptr(), x.data_ptr(), 3, 7000, 1, None), "iris_stft")  # IRIS_F_MINMAX
 
@@ -391,6 +405,8 @@ def test_minimal_and_odd_shapes(dev):
         spec = plan.stft(torch.from_numpy(wav).to(dev)).cpu().numpy()
         full = np.stack([R.to_ref_layout(R.stft(wav[i], n_fft, hop)) for i in range(b)])
         assert np.abs(spec - full).max() <= 3e-6 * np.abs(full).max()
+        for i in range(b):
+            assert_stft_rule(spec[i], wav[i], n_fft, hop)
 
 
 def test_side_stream_and_graph_capture(dev):
